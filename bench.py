@@ -10,11 +10,13 @@ N > 1 (launched by torch.distributed.run, one rank per GPU): every rank renders 
 of the same Gaussian set and the per-Gaussian gradients are summed with one bucketed all-reduce over
 RCCL — the keyframe-parallel mapping step of SURVEY.md §8e.  value = renders of all ranks / max time.
 
-Prints ONE JSON line (rank 0) carrying `roofline` (dominant kernel, timed live with HIP events on the
-launch stream through the library's hsr_profile hooks), `cpu_baseline` (the oracle on the host cores) and
-`parity` — the metric's second half, "grad max-abs-err vs ref": one more GPU step compared with the oracle
-render of the SAME workload that the cpu_baseline leg computes anyway (bit-equality of the integer state,
-image and gradient errors).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps, optionally writes the last
+timed step's outputs (--dump-outputs DIR) and prints the line: `value` (renders/s) and `ms_per_step`.
+With --full the line also carries `roofline` and `stages_ms` (dominant kernel, timed live with HIP events on
+the launch stream through the library's hsr_profile hooks), `workloads` (the rest of the north star's list),
+`cpu_baseline` (the oracle on the host cores) and `parity` — the metric's second half, "grad max-abs-err vs
+ref": one more GPU step compared with the oracle render of the SAME workload that the cpu_baseline leg
+computes anyway (bit-equality of the integer state, image and gradient errors).
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (a child `python -m
 torch.distributed.run`, before this process has touched the GPU) and relays rank 0's line.
@@ -333,10 +335,11 @@ class Workload:
         self.leaf = self.upd = self.renderer = None
         torch.cuda.empty_cache()
 
-    def step(self):
+    def step(self, keep=False):
         """N = 1: one render (forward + backward).  N > 1: one optimizer step's worth of the mapping loop (scripts/hierslam.py:1966-2057) —
         this rank's G keyframes rendered one after the other, their gradients accumulated in the exchange bucket, ONE exchange, and
-        (unless --stale-gradients) the wait for the sum: the point at which an Adam step could run."""
+        (unless --stale-gradients) the wait for the sum: the point at which an Adam step could run.
+        keep: hold on to the first keyframe's forward outputs and means2D (for --dump-outputs)."""
         leaf, dev = self.leaf, self.dev
         if self.exchange is not None:
             self.exchange.begin_step()   # the backwards write / accumulate their gradient outputs into the bucket
@@ -352,6 +355,9 @@ class Workload:
             if g == 0:
                 self.info["node"] = color.grad_fn
                 self.info["radii"] = radii
+                if keep:
+                    self.info["outputs"] = {"color": color, "radii": radii, "semantic": sem, "depth": depth, "median_depth": median,
+                                            "opacity": opac, "means2D": means2D}
             if self.exchange is not None:
                 self.exchange.add_keyframe(radii)
             torch.autograd.backward([color, sem, depth, median, opac], upd)
@@ -369,7 +375,7 @@ class Workload:
             dist.barrier()
             torch.cuda.synchronize(self.dev)
 
-    def run(self, steps, warmup, profile=True, lib=None):
+    def run(self, steps, warmup, profile=True, lib=None, keep_last=False):
         for _ in range(warmup):
             self.step()
         self.sync()
@@ -392,8 +398,8 @@ class Workload:
             lib.hsr_profile_select(1 << dom_stage)
         lib.hsr_profile_host_wait_ms(1)
         t0 = time.perf_counter()
-        for _ in range(steps):
-            self.step()
+        for i in range(steps):
+            self.step(keep=keep_last and i == steps - 1)
         host_wait_ms = float(lib.hsr_profile_host_wait_ms(1)) / steps
         self.sync()
         t1 = time.perf_counter()
@@ -445,6 +451,53 @@ def roofline_block(stages, dom, P, W, H, K, kind):
     return rl
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6   # --dump-outputs: at most this much array data in all (under 64 MB with the .npy headers)
+DUMP_SEED = 20240601
+
+
+def _sample_index(n, k, seed, dev):
+    """k of n indices, sorted, from a fixed seed (None: k >= n, keep everything)"""
+    if k >= n:
+        return None
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    return torch.from_numpy(idx).to(dev)
+
+
+def dump_outputs(wl, out_dir, budget=DUMP_BUDGET_BYTES):
+    """What the timed path handed its caller in its last step, as <out_dir>/<name>.npy (float32): the first keyframe's forward
+    outputs (images [C, pixels]) and the gradients of the leaves and of means2D ([Gaussians, ...]).  When the whole set is over `budget`
+    bytes, a fixed, seeded sample of pixels (every image output) and of Gaussians (every per-Gaussian array) is kept instead, half
+    the budget each; the indices depend only on the workload's size.  Returns a summary for the result line."""
+    o = wl.info.pop("outputs")
+    # flatten(1), not reshape(n, -1): K = 0 gives empty semantic tensors
+    imgs = {n: o[n].detach().flatten(1) for n in ("color", "semantic", "depth", "median_depth", "opacity")}
+    per_g = {"radii": o["radii"].unsqueeze(1), "grad_means2D": o["means2D"].grad}
+    for n in wl.names:
+        per_g["grad_" + n] = wl.leaf[n].grad
+    per_g = {n: v.detach().flatten(1) for n, v in per_g.items() if v is not None}   # --geo: no gradient for the other leaves
+    n_pix = wl.W * wl.H
+    pix_cols = sum(v.shape[0] for v in imgs.values())
+    g_cols = sum(v.shape[1] for v in per_g.values())
+    if 4 * (n_pix * pix_cols + wl.P * g_cols) <= budget:
+        pix = gau = None
+    else:
+        pix = _sample_index(n_pix, budget // 2 // (4 * pix_cols), DUMP_SEED, wl.dev)
+        gau = _sample_index(wl.P, budget // 2 // (4 * g_cols), DUMP_SEED + 1, wl.dev)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, v in list(imgs.items()) + list(per_g.items()):
+        if name in imgs and pix is not None:
+            v = v.index_select(1, pix)
+        elif name in per_g and gau is not None:
+            v = v.index_select(0, gau)
+        a = v.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return {"dir": out_dir, "files": len(imgs) + len(per_g), "bytes": total,
+            "pixels_kept": n_pix if pix is None else int(pix.numel()), "pixels": n_pix,
+            "gaussians_kept": wl.P if gau is None else int(gau.numel()), "gaussians": wl.P, "sample_seeds": [DUMP_SEED, DUMP_SEED + 1]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -472,7 +525,16 @@ def main():
                     help="N > 1: two buckets, the exchange of step i overlaps the renders of step i + 1 — only valid for a caller that applies "
                          "step i's gradients after rendering step i + 1 (the reference's loop does not: an Adam step sits between iterations)")
     ap.add_argument("--async-forward", action="store_true", help="opt-in non-blocking forward for the main workload too (diff_gaussian_rasterization.set_async_forward)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-stage timers and the roofline block, the rest of the workload list, "
+                         "the CPU baseline and the parity check against the oracle (each can still be switched off with its --no-* option). "
+                         "Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (forward outputs, gradients) as DIR/<name>.npy, "
+                         "float32; a fixed, seeded sample of pixels / Gaussians when the whole set is over 60 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
     # Keep the process — main thread, autograd engine thread, HIP runtime threads — on the CPUs that share an L3 with the one
@@ -539,7 +601,7 @@ def main():
     if args.async_forward:
         import diff_gaussian_rasterization as dgr
         dgr.set_async_forward(True)
-    res = wl.run(args.steps, args.warmup, profile=not args.no_profile, lib=_C._lib)
+    res = wl.run(args.steps, args.warmup, profile=args.full and not args.no_profile, lib=_C._lib, keep_last=bool(args.dump_outputs))
     if args.async_forward:
         dgr.set_async_forward(False)
     elapsed = res["elapsed"]
@@ -591,9 +653,11 @@ def main():
                        "note": "ms_per_step - blocked = host-side work per step (Python glue + launches)"}
         if rank_cpus is not None:
             out["host"]["rank_cpus"] = rank_cpus
-        # ---- the rest of the north star's workload list, GPU only (no oracle), through the same step ----
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(wl, args.dump_outputs)
+        # ---- --full: the rest of the north star's workload list, GPU only (no oracle), through the same step ----
         stress = None
-        if world == 1 and not args.no_workloads:
+        if world == 1 and args.full and not args.no_workloads:
             out["workloads"] = []
             import diff_gaussian_rasterization as dgr
             for (w_, h_, p_, k_, kind_, tag) in EXTRA_WORKLOADS:
@@ -623,7 +687,7 @@ def main():
                 out["workloads"].append(e)
                 if tag == "stress":
                     stress = (wl, e)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if full_affinity:
                 os.sched_setaffinity(0, full_affinity)   # the oracle gets every host thread it is allowed
             # the stress configuration's comparison with the oracle at its own size (one oracle render is several seconds of CPU)

@@ -3,6 +3,7 @@
 # (the matrix-core forward lives in the ablate build: make -C hier-slam_amd/csrc ablate)
 export HSR_RAST_LIB=${HSR_RAST_LIB:-$PWD/hier-slam_amd/libhsr_rast_ablate.so} HSR_GLUE=ctypes
 set -e
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 HSR_FWD_IMPL=mma python - <<'PY'
 import sys; sys.path[:0]=['hier-slam_amd','tests']
 import scenes
@@ -16,9 +17,9 @@ for n in ('replica_tree_k26','scannet_tree_k16','generic_k5_white_bg','generic_k
 PY
 run() {  # $1 tag, $2 impl ("" = default), rest: bench flags
     tag=$1; impl=$2; shift 2
-    HSR_FWD_IMPL=$impl python bench.py --no-workloads --no-cpu-baseline --steps 40 --warmup 8 "$@" > gpurun_out/mma_$tag.json
+    HSR_FWD_IMPL=$impl python bench.py --full --no-workloads --no-cpu-baseline --steps 40 --warmup 8 "$@" > $OUT/mma_$tag.json
     python -c "
-import json;d=json.load(open('gpurun_out/mma_$tag.json'));print('$tag', round(d['value'],1), 'fwd_render', round(d['stages_ms']['fwd_render'],4))"
+import json;d=json.load(open('$OUT/mma_$tag.json'));print('$tag', round(d['value'],1), 'fwd_render', round(d['stages_ms']['fwd_render'],4))"
 }
 for cfg in "head" "k16 --K 16" "k74 --K 74" "k102 --K 102" "k48 --K 48" "p100k --P 100000" "p2m --P 2000000 --width 1920 --height 1080" "stress --P 2000000 --width 1920 --height 1080 --K 74" "aniso --kind aniso"; do
     set -- $cfg; tag=$1; shift

@@ -2,13 +2,14 @@
 # `git archive`) against the tree's libhsr_rast.so, alternating, through the ctypes glue (HSR_RAST_LIB selects the library).
 # usage: bash tools/lib_ab.sh [rounds]
 set -e
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
 R=${1:-2}
 export HSR_GLUE=ctypes
 run() {  # $1 tag, $2 lib, rest: bench flags
     tag=$1; lib=$2; shift 2
-    HSR_RAST_LIB=$PWD/hier-slam_amd/$lib python bench.py --no-workloads --no-cpu-baseline --steps 40 --warmup 8 "$@" > gpurun_out/ab_$tag.json
+    HSR_RAST_LIB=$PWD/hier-slam_amd/$lib python bench.py --full --no-workloads --no-cpu-baseline --steps 40 --warmup 8 "$@" > $OUT/ab_$tag.json
     python -c "
-import json,sys;d=json.load(open('gpurun_out/ab_$tag.json'));print('$tag', round(d['value'],1), {a:round(b,4) for a,b in d['stages_ms'].items() if b>0.004})"
+import json,sys;d=json.load(open('$OUT/ab_$tag.json'));print('$tag', round(d['value'],1), {a:round(b,4) for a,b in d['stages_ms'].items() if b>0.004})"
 }
 for r in $(seq 1 $R); do
     run prev_head_$r libhsr_rast_prev.so

@@ -5,7 +5,7 @@ export HSR_GLUE=ctypes
 HSR_RAST_LIB=$PWD/hier-slam_amd/libhsr_rast_map2d.so python -m pytest tests/test_gpu_parity.py -x -q -k "test_parity" 2>&1 | tail -1
 run() {
     tag=$1; lib=$2; shift 2
-    HSR_RAST_LIB=$PWD/hier-slam_amd/$lib python bench.py --no-workloads --no-cpu-baseline --steps 40 --warmup 8 "$@" 2>/dev/null | python -c "
+    HSR_RAST_LIB=$PWD/hier-slam_amd/$lib python bench.py --full --no-workloads --no-cpu-baseline --steps 40 --warmup 8 "$@" 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$tag', round(d['value'],1), {a:round(b,4) for a,b in d['stages_ms'].items() if 'render' in a})"
 }
 for r in 1 2 3; do

@@ -4,7 +4,7 @@ python -m pytest tests/test_gpu_parity.py tests/test_gpu_truth.py tests/test_gpu
 tail -4 gpurun_out/r04_t6.log
 for cfg in "--K 26" "--K 16" "--K 0" "--geo"; do
   for impl in sub ""; do
-      HSR_BWD_IMPL=$impl python bench.py --no-workloads --no-cpu-baseline --steps 40 --warmup 8 $cfg 2>/dev/null | python -c "
+      HSR_BWD_IMPL=$impl python bench.py --full --no-workloads --no-cpu-baseline --steps 40 --warmup 8 $cfg 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$cfg', 'impl=${impl:-q}', 'bwd_render %.4f ms' % d['stages_ms']['bwd_render'], 'bwd_zero %.4f' % d['stages_ms']['bwd_zero'], 'bwd_pre %.4f' % d['stages_ms']['bwd_preprocess'], 'step %.3f ms' % d['ms_per_step'])"
   done
 done

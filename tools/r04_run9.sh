@@ -3,7 +3,7 @@ python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py -x -q > gpurun_
 tail -2 gpurun_out/r04_t9.log
 for cfg in "--K 0" "--K 16" "--geo" "--K 26"; do
   for impl in ""; do
-      HSR_BWD_IMPL=$impl python bench.py --no-workloads --no-cpu-baseline --steps 40 --warmup 8 $cfg 2>/dev/null | python -c "
+      HSR_BWD_IMPL=$impl python bench.py --full --no-workloads --no-cpu-baseline --steps 40 --warmup 8 $cfg 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print('$cfg', 'impl=${impl:-q}', 'bwd_render %.4f ms' % d['stages_ms']['bwd_render'], 'step %.3f ms' % d['ms_per_step'])"
   done
 done
