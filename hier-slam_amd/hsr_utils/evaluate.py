@@ -1,0 +1,298 @@
+"""Per-frame evaluation of a finished map with the reference's metrics, on the GPU (include/hsr_eval.h); the trajectory error on the host.
+
+    frame_metrics(im, gt_im, depth, gt_depth, final_opacity=None, sil_thres=None)   psnr, depth L1, "depth RMSE"
+                                                                                    utils/eval_helpers.py:1258-1295
+    semantic_labels(im_semantic, mode, level_sizes=, tree_table=, mlp=)            argmax(softmax): flat :974-983, tree :187-204 +
+                                                                                    :135-156, leaf MLP :1251-1255
+    tree_lookup_table(label_mapping_tree, level_sizes)                             the dict of transfer_tree_2_label as a dense table
+    iou_counts(pred, gt, num_classes=, class_ids=, dilation_ratio=0.02)            calculate_iou :83-90, boundary_iou :37-81, per class
+    frame_miou(counts)                                                             mean IoU / boundary IoU of a frame :1487-1498
+    evaluate_frame(...)                                                            the per-frame body of eval_semantic_tree_newrender
+    trajectory_ate(gt_w2c_list, est_w2c_list)                                      evaluate_ate + align :218-275, :1555-1577 (numpy)
+
+Every per-frame call runs on the current stream and returns device tensors without a host synchronisation: score all frames, read
+the numbers once at the end.  Frame averages are plain means over frames (:1590-1600).  There is no CPU path.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from diff_gaussian_rasterization import _C as _glue
+
+_lib = _glue._lib
+_vp, _ci, _sz = C.c_void_p, C.c_int, C.c_size_t
+_lib.hsr_eval_metrics_scratch_bytes.restype = _sz
+_lib.hsr_eval_metrics_scratch_bytes.argtypes = [_ci, _ci]
+_lib.hsr_eval_frame_metrics.restype = _ci
+_lib.hsr_eval_frame_metrics.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _sz, _vp]
+_lib.hsr_eval_labels_flat.restype = _ci
+_lib.hsr_eval_labels_flat.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp]
+_lib.hsr_eval_labels_tree.restype = _ci
+_lib.hsr_eval_labels_tree.argtypes = [_ci, _ci, _ci, _ci, C.POINTER(_ci), _vp, _vp, _vp, _vp, _vp]
+_lib.hsr_eval_leaf_scratch_bytes.restype = _sz
+_lib.hsr_eval_leaf_scratch_bytes.argtypes = [_ci]
+_lib.hsr_eval_labels_leaf.restype = _ci
+_lib.hsr_eval_labels_leaf.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
+_lib.hsr_eval_iou_scratch_bytes.restype = _sz
+_lib.hsr_eval_iou_scratch_bytes.argtypes = [_ci, _ci]
+_lib.hsr_eval_iou_counts.restype = _ci
+_lib.hsr_eval_iou_counts.argtypes = [_ci, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _sz, _vp]
+_lib.hsr_eval_frame_miou.restype = _ci
+_lib.hsr_eval_frame_miou.argtypes = [_ci, _vp, _vp, _vp]
+
+MAX_CLASSES, MAX_LEVELS, LEAF_MAX_K, LEAF_MAX_C, MAX_DILATION = 4096, 16, 32, 256, 1024
+_class_cache = {}
+
+
+def _dev(t, what, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError("hsr_utils.evaluate: %s must be a torch tensor" % what)
+    if not t.is_cuda:
+        raise RuntimeError("hsr_utils.evaluate: %s must live on a HIP device (got %s); there is no CPU path" % (what, t.device))
+    if t.dtype != dtype:
+        raise RuntimeError("hsr_utils.evaluate: %s must be %s (got %s)" % (what, dtype, t.dtype))
+    return t.contiguous()
+
+
+def _plane(t, what, H, W, dtype=torch.float32):
+    t = _dev(t, what, dtype)
+    if t.numel() != H * W or t.shape[-2:] != (H, W):
+        raise RuntimeError("hsr_utils.evaluate: %s must be [H,W] or [1,H,W] with H=%d W=%d (got %s)" % (what, H, W, tuple(t.shape)))
+    return t
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _call(fn, name, dev, *args):
+    with torch.cuda.device(dev):
+        rc = fn(*args, _stream(dev))
+    if rc < 0:
+        _glue._fail(rc, name)
+
+
+def frame_metrics(im, gt_im, depth, gt_depth, final_opacity=None, sil_thres=None):
+    """float64 [3] on the device: psnr, depth_l1, depth_rmse of one frame (utils/eval_helpers.py:1258-1295).  im / gt_im: [3,H,W];
+    depth / gt_depth / final_opacity: [1,H,W] or [H,W], all float32.  With final_opacity and sil_thres (the reference's
+    `mapping_iters == 0 and not add_new_gaussians` branch) the silhouette mask multiplies the image and depth terms; otherwise only
+    gt_depth > 0 does.  PSNR is calc_psnr over all H*W pixels (masked ones as zeros), averaged over the channels; the "RMSE" is the
+    reference's mean of sqrt(e^2).  An exact image gives +inf, a frame without valid depth NaN."""
+    a = _dev(im, "im")
+    if a.dim() != 3 or a.shape[0] != 3:
+        raise RuntimeError("hsr_utils.evaluate: im must be [3,H,W] (got %s)" % (tuple(im.shape),))
+    H, W = a.shape[1:]
+    b = _dev(gt_im, "gt_im")
+    if b.shape != a.shape:
+        raise RuntimeError("hsr_utils.evaluate: gt_im %s differs from im %s" % (tuple(b.shape), tuple(a.shape)))
+    d, gd = _plane(depth, "depth", H, W), _plane(gt_depth, "gt_depth", H, W)
+    if (final_opacity is None) != (sil_thres is None):
+        raise RuntimeError("hsr_utils.evaluate: final_opacity and sil_thres go together")
+    op = None if final_opacity is None else _plane(final_opacity, "final_opacity", H, W)
+    dev = a.device
+    out = torch.empty(3, dtype=torch.float64, device=dev)
+    sc = torch.empty(int(_lib.hsr_eval_metrics_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _call(_lib.hsr_eval_frame_metrics, "hsr_eval_frame_metrics", dev, H, W, a.data_ptr(), b.data_ptr(), d.data_ptr(), gd.data_ptr(),
+          None if op is None else op.data_ptr(), 0.0 if sil_thres is None else float(sil_thres), out.data_ptr(), sc.data_ptr(), sc.numel())
+    return out
+
+
+def tree_lookup_table(label_mapping_tree, level_sizes, device="cuda"):
+    """The dataset's label_mapping_tree ({leaf id (int or str): tuple of per-level labels}) as a dense int32 table over the mixed-radix
+    index of the level labels (level 0 most significant), for the levels level_sizes[:-1] (the dataset's num_semantic, whose last
+    entry is the leaf count; datasets/gradslam_datasets/replica.py:144-147).  A tuple not in the dict maps to -1; of two keys with one
+    tuple the later entry wins, as transfer_tree_2_label's loop of masked assignments does (utils/eval_helpers.py:135-156).  Tuples
+    with a label outside its level's range are never produced by the argmax and are left out.  Built once on the host."""
+    sizes = [int(s) for s in level_sizes][:-1]
+    if not 1 <= len(sizes) <= MAX_LEVELS or min(sizes) < 1:
+        raise RuntimeError("hsr_utils.evaluate: level_sizes must list 1..%d level sizes >= 1 plus the leaf count" % MAX_LEVELS)
+    n = int(np.prod(sizes))
+    if n > 1 << 26:
+        raise RuntimeError("hsr_utils.evaluate: a %d-entry tree table is too large" % n)
+    table = np.full(n, -1, dtype=np.int64)
+    for key, value in label_mapping_tree.items():
+        value = [int(v) for v in value]
+        if len(value) != len(sizes):
+            raise RuntimeError("hsr_utils.evaluate: tree entry %r has %d levels, level_sizes %d" % (key, len(value), len(sizes)))
+        if any(v < 0 or v >= s for v, s in zip(value, sizes)):
+            continue
+        idx = 0
+        for v, s in zip(value, sizes):
+            idx = idx * s + v
+        table[idx] = int(key)
+    if table.min() < -(1 << 31) or table.max() >= 1 << 31:
+        raise RuntimeError("hsr_utils.evaluate: leaf ids must fit in int32")
+    return torch.tensor(table.astype(np.int32), device=device)
+
+
+def semantic_labels(im_semantic, mode, *, level_sizes=None, tree_table=None, mlp=None):
+    """int32 [H,W] labels argmax(softmax(.)) of the rendered semantic map im_semantic ([K,H,W] float32).
+      mode "flat": over all K planes (utils/eval_helpers.py:974-983);
+      mode "tree": per level over the channel ranges level_sizes[:-1] (transfer_tree_label, :187-204), then the leaf id of the tuple of
+                   level labels from tree_table (tree_lookup_table; -1 where the tuple names no leaf).  Returns (labels, level labels
+                   int32 [L,H,W]);
+      mode "leaf": over the C logits of the 1x1-conv leaf head `mlp` (a Conv2d(K, C, 1) or a (weight, bias) pair; :1251-1255), which
+                   are never materialised.
+    Ties are among the fp32 probabilities expf(x_i - max) / sum and go to the lowest index, like torch.argmax."""
+    z = _dev(im_semantic, "im_semantic")
+    if z.dim() == 4 and z.shape[0] == 1:
+        z = z[0]
+    if z.dim() != 3:
+        raise RuntimeError("hsr_utils.evaluate: im_semantic must be [K,H,W] (got %s)" % (tuple(im_semantic.shape),))
+    K, H, W = z.shape
+    dev = z.device
+    out = torch.empty((H, W), dtype=torch.int32, device=dev)
+    if mode == "flat":
+        _call(_lib.hsr_eval_labels_flat, "hsr_eval_labels_flat", dev, K, H, W, z.data_ptr(), out.data_ptr())
+        return out
+    if mode == "tree":
+        if level_sizes is None or tree_table is None:
+            raise RuntimeError("hsr_utils.evaluate: mode 'tree' needs level_sizes and tree_table")
+        sizes = [int(s) for s in level_sizes][:-1]
+        L = len(sizes)
+        if not 1 <= L <= MAX_LEVELS or sum(sizes) > K or min(sizes) < 1:
+            raise RuntimeError("hsr_utils.evaluate: level_sizes %s (levels + leaf count) do not fit %d planes" % (list(level_sizes), K))
+        table = _dev(tree_table, "tree_table", torch.int32)
+        if table.numel() != int(np.prod(sizes)):
+            raise RuntimeError("hsr_utils.evaluate: tree_table has %d entries, the levels %s need %d" % (table.numel(), sizes, int(np.prod(sizes))))
+        levels = torch.empty((L, H, W), dtype=torch.int32, device=dev)
+        _call(_lib.hsr_eval_labels_tree, "hsr_eval_labels_tree", dev, K, H, W, L, (_ci * L)(*sizes), z.data_ptr(), table.data_ptr(),
+              out.data_ptr(), levels.data_ptr())
+        return out, levels
+    if mode == "leaf":
+        if mlp is None:
+            raise RuntimeError("hsr_utils.evaluate: mode 'leaf' needs mlp")
+        weight, bias = (mlp.weight, mlp.bias) if hasattr(mlp, "weight") else mlp
+        w = _dev(weight.detach(), "mlp weight").reshape(weight.shape[0], -1)
+        b = _dev(bias.detach(), "mlp bias").reshape(-1)
+        Cc = w.shape[0]
+        if w.shape[1] != K or b.numel() != Cc:
+            raise RuntimeError("hsr_utils.evaluate: mlp weight %s / bias %s do not match %d planes" % (tuple(weight.shape), tuple(bias.shape), K))
+        if K > LEAF_MAX_K or Cc > LEAF_MAX_C:
+            raise RuntimeError("hsr_utils.evaluate: the leaf head takes K <= %d planes and C <= %d classes (got K=%d C=%d)"
+                               % (LEAF_MAX_K, LEAF_MAX_C, K, Cc))
+        sc = torch.empty(int(_lib.hsr_eval_leaf_scratch_bytes(Cc)), dtype=torch.uint8, device=dev)
+        _call(_lib.hsr_eval_labels_leaf, "hsr_eval_labels_leaf", dev, K, Cc, H, W, z.data_ptr(), w.contiguous().data_ptr(), b.data_ptr(),
+              out.data_ptr(), sc.data_ptr(), sc.numel())
+        return out
+    raise RuntimeError("hsr_utils.evaluate: mode must be 'flat', 'tree' or 'leaf' (got %r)" % (mode,))
+
+
+def dilation_pixels(H, W, dilation_ratio=0.02):
+    """mask_to_boundary's erosion count: max(1, int(round(ratio * sqrt(H^2 + W^2)))), round half to even (utils/eval_helpers.py:44-48)."""
+    return max(1, int(round(dilation_ratio * float(np.sqrt(H ** 2 + W ** 2)))))
+
+
+def _classes(class_ids, dev):
+    key = (tuple(int(c) for c in class_ids), dev)
+    if key not in _class_cache:
+        ids = np.asarray(key[0], dtype=np.int64)
+        if len(np.unique(ids)) != len(ids):
+            raise RuntimeError("hsr_utils.evaluate: class_ids must be distinct")
+        if ids.size and (ids.min() < -(1 << 31) or ids.max() >= 1 << 31):
+            raise RuntimeError("hsr_utils.evaluate: class_ids must fit in int32")
+        order = np.argsort(ids, kind="stable")
+        _class_cache[key] = (torch.tensor(ids[order].astype(np.int32), device=dev), torch.tensor(order.astype(np.int32), device=dev))
+    return _class_cache[key]
+
+
+def iou_counts(pred, gt, num_classes=None, class_ids=None, dilation_ratio=0.02):
+    """int64 [C,6] on the device, per class c: [G, P, I, G_b, P_b, I_b] with G = |gt == c|, P = |pred == c|, I = |both|, and the same
+    over the boundary pixels of mask_to_boundary (utils/eval_helpers.py:37-90); the union is G + P - I.  pred / gt: int32 label maps
+    [H,W].  Classes: range(num_classes), or the labels of class_ids (distinct ints, any order; rows follow it) as the ScanNet
+    tree_large branch iterates dataset.semantic_id (:1407).  A label in neither set counts for no class.  C <= 4096."""
+    p = _dev(pred, "pred", torch.int32)
+    H, W = p.shape[-2:]
+    p = _plane(p, "pred", H, W, torch.int32)
+    g = _plane(gt, "gt", H, W, torch.int32)
+    if (num_classes is None) == (class_ids is None):
+        raise RuntimeError("hsr_utils.evaluate: give exactly one of num_classes and class_ids")
+    Cc = int(num_classes) if class_ids is None else len(class_ids)
+    if not 1 <= Cc <= MAX_CLASSES:
+        raise RuntimeError("hsr_utils.evaluate: %d classes; 1..%d are supported" % (Cc, MAX_CLASSES))
+    d = dilation_pixels(H, W, dilation_ratio)
+    if d > MAX_DILATION:
+        raise RuntimeError("hsr_utils.evaluate: a boundary width of %d pixels exceeds %d" % (d, MAX_DILATION))
+    dev = p.device
+    ids = rows = None
+    if class_ids is not None:
+        ids, rows = _classes(class_ids, dev)
+    out = torch.empty((Cc, 6), dtype=torch.int64, device=dev)
+    sc = torch.empty(int(_lib.hsr_eval_iou_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _call(_lib.hsr_eval_iou_counts, "hsr_eval_iou_counts", dev, H, W, p.data_ptr(), g.data_ptr(), Cc,
+          None if ids is None else ids.data_ptr(), None if rows is None else rows.data_ptr(), d, out.data_ptr(), sc.data_ptr(), sc.numel())
+    return out
+
+
+def frame_miou(counts):
+    """float64 [2] on the device: the frame's mean IoU and mean boundary IoU over the classes with G + P > 0
+    (utils/eval_helpers.py:1487-1498); NaN when no class is present, like np.mean([])."""
+    q = _dev(counts, "counts", torch.int64)
+    if q.dim() != 2 or q.shape[1] != 6:
+        raise RuntimeError("hsr_utils.evaluate: counts must be [C,6] (got %s)" % (tuple(q.shape),))
+    out = torch.empty(2, dtype=torch.float64, device=q.device)
+    _call(_lib.hsr_eval_frame_miou, "hsr_eval_frame_miou", q.device, q.shape[0], q.data_ptr(), out.data_ptr())
+    return out
+
+
+def evaluate_frame(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, *, final_opacity=None, sil_thres=None, level_sizes=None,
+                   tree_table=None, mlp=None, num_classes=None, class_ids=None, dilation_ratio=0.02):
+    """The per-frame scores of eval_semantic_tree_newrender (utils/eval_helpers.py:1258-1498) without MS-SSIM and LPIPS: a dict of
+    0-dim device tensors psnr, depth_l1, depth_rmse (float64), miou, mbiou (float64).  im / im_semantic / depth / final_opacity as the
+    semantic rasterizer returns them; gt_labels: the leaf label map ([H,W], int; label_gt[-1] for tree datasets).  `mode` and its
+    arguments as semantic_labels; num_classes / class_ids as iou_counts.  No host synchronisation."""
+    m = frame_metrics(im, gt_im, depth, gt_depth, final_opacity, sil_thres)
+    lab = semantic_labels(im_semantic, mode, level_sizes=level_sizes, tree_table=tree_table, mlp=mlp)
+    if mode == "tree":
+        lab = lab[0]
+    H, W = lab.shape
+    g = gt_labels.reshape(H, W)
+    if g.dtype != torch.int32:
+        g = g.to(torch.int32)
+    s = frame_miou(iou_counts(lab, g, num_classes=num_classes, class_ids=class_ids, dilation_ratio=dilation_ratio))
+    return {"psnr": m[0], "depth_l1": m[1], "depth_rmse": m[2], "miou": s[0], "mbiou": s[1]}
+
+
+def _align(model, data):
+    """align() of utils/eval_helpers.py:218-256 (Horn, closed form) without np.matrix: model, data 3 x n; returns rot, trans, errors."""
+    mu_m, mu_d = model.mean(1).reshape(3, 1), data.mean(1).reshape(3, 1)
+    Wm = (model - mu_m) @ (data - mu_d).T
+    U, _d, Vh = np.linalg.svd(Wm.T)
+    S = np.eye(3)
+    if np.linalg.det(U) * np.linalg.det(Vh) < 0:
+        S[2, 2] = -1
+    rot = U @ S @ Vh
+    trans = mu_d - rot @ mu_m
+    err = rot @ model + trans - data
+    return rot, trans, np.sqrt(np.sum(err * err, 0))
+
+
+def _np(m):
+    return m.detach().cpu().double().numpy() if isinstance(m, torch.Tensor) else np.asarray(m, dtype=np.float64)
+
+
+def trajectory_ate(gt_w2c_list, est_w2c_list, first_frame_w2c=None):
+    """Average translational error after Horn alignment, as eval_semantic_tree_newrender computes it (utils/eval_helpers.py:1555-1577
+    with evaluate_ate / align, :218-275): the [:3,3] columns of the world-to-camera matrices are aligned (not camera centres), frames
+    whose gt pose holds a NaN are skipped, and frame 0's estimate is first_frame_w2c (default: gt_w2c_list[0], which is what the
+    reference's first_frame_w2c = inv(pose_0) equals).  Lists of 4x4 tensors or arrays, one per frame of the estimate.  Host numpy."""
+    n = len(est_w2c_list)
+    if n < 1 or len(gt_w2c_list) < n:
+        raise RuntimeError("hsr_utils.evaluate: %d estimated poses for %d gt poses" % (n, len(gt_w2c_list)))
+    gts = [_np(gt_w2c_list[0])]
+    ests = [_np(gt_w2c_list[0] if first_frame_w2c is None else first_frame_w2c)]
+    for i in range(1, n):
+        g = _np(gt_w2c_list[i])
+        if np.isnan(g).any():
+            continue
+        gts.append(g)
+        ests.append(_np(est_w2c_list[i]))
+    gt_pts = np.stack([m[:3, 3] for m in gts]).T
+    est_pts = np.stack([m[:3, 3] for m in ests]).T
+    _rot, _trans, err = _align(gt_pts, est_pts)
+    return float(err.mean())
+
+
+__all__ = ["frame_metrics", "semantic_labels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
+           "dilation_pixels"]
