@@ -47,21 +47,17 @@ uint32_t higher_msb(uint32_t n)  // reference getHigherMsb, rasterizer_impl.cu:3
     return msb;
 }
 
-// backward accumulation mode: 0 packed per-Gaussian rows (default), 1 per-instance rows (experiment: ablate build only),
-// 2 legacy separate arrays.  Initialised from HSR_BWD_IMPL=legacy (rows: ablate build), changed with hsr_set_backward_mode().
+// backward accumulation mode: 0 packed per-Gaussian rows (default), 2 legacy separate arrays (1, per-instance rows, was an
+// experiment and is refused).  Initialised from HSR_BWD_IMPL=legacy, changed with hsr_set_backward_mode().
 int g_bwd_mode = -1;
 int backward_mode()
 {
     if (g_bwd_mode < 0) {
         const char* e = getenv("HSR_BWD_IMPL");
         g_bwd_mode = (e && !strcmp(e, "legacy")) ? 2 : 0;
-#ifdef HSR_ABLATE
-        if (e && !strcmp(e, "rows")) g_bwd_mode = 1;
-#endif
     }
     return g_bwd_mode;
 }
-bool rows_mode_requested() { return backward_mode() == 1; }
 
 // semantic -> alpha gradient: 0 as the reference computes it (none: backward.cu:834-845 reads a scratch nothing wrote), 1 exact
 // (opt-in; HSR_SEMANTIC_ALPHA=exact or hsr_set_semantic_alpha_mode)
@@ -406,8 +402,7 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
     HsrBinPlan plan{0, 0};
     uint32_t* bin_scratch = reinterpret_cast<uint32_t*>(im.final_T);   // free until the render kernel writes it
     const bool binned = !force_radix && hsr_bin_plan(P, T, (size_t)W * H, &plan);
-    static const bool no_speculation = hsr_ablate_env("HSR_NO_SPECULATION") != nullptr;
-    const bool will_speculate = binned && !no_speculation && !in.debug && binning && binning->ptr && binning->capacity >= 4096;
+    const bool will_speculate = binned && !in.debug && binning && binning->ptr && binning->capacity >= 4096;
     const bool go_async = ticket != nullptr && will_speculate;
     uint32_t seq = 0;
     volatile uint32_t* slot_host = nullptr;   // non-blocking forward: this call's slot of the device's ring
@@ -440,10 +435,6 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
     ra.final_T = im.final_T; ra.n_contrib = im.n_contrib; ra.median_pos = im.median_pos;
     ra.out_color = in.out_color; ra.out_semantic = in.out_semantic; ra.out_depth = in.out_depth;
     ra.out_median_depth = in.out_median; ra.out_opacity = in.out_opacity; ra.out_mask = in.out_mask;
-    {
-        static const int dbg = hsr_ablate_env("HSR_DEBUG_FLAGS") ? atoi(hsr_ablate_env("HSR_DEBUG_FLAGS")) : 0;
-        ra.debug_flags = dbg & 16;   // 0 in the product build; ablate build: bit 4 = no sub-block culling
-    }
     ra.bin = BinDevRef{nullptr, nullptr, 0};
     if (!in.semantic && !in.out_mask) {
         hsr_set_error("out_mask is NULL");
@@ -631,26 +622,18 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     // Accumulation modes (hsr_backward_scratch_bytes() sizes the scratch for the one in force):
     //   packed (default with scratch): fp32 atomics into ONE 64-byte-aligned row per Gaussian, unpacked by
     //       the per-Gaussian kernel — half the atomic requests of the reference's six separate arrays;
-    //   rows (HSR_BWD_IMPL=rows, K <= 27): per-instance rows, no global atomics (experimental);
     //   legacy (no scratch): atomics straight into the six output arrays.
-#ifdef HSR_ABLATE
-    const bool want_rows = rows_mode_requested();
-    const bool use_rows = want_rows && in.scratch && hsr_rows_supported(K) && in.R > 0 &&
-                          in.scratch_bytes >= hsr_backward_scratch_bytes(P, K, in.R);
-#else
-    const bool use_rows = false;
-#endif
     int glayout = 0;   // set below once the accumulation mode is known
     int gstride = hsr_grow_stride(K);
-    const bool use_packed = !use_rows && backward_mode() != 2 && in.scratch &&
+    const bool use_packed = backward_mode() != 2 && in.scratch &&
                             in.scratch_bytes >= (size_t)P * gstride * sizeof(float) + 256;
     const bool geo = geo_request && use_packed && (size_t)P * 16 < ((size_t)1 << 30);
     if (geo_request && !geo) {
         hsr_set_error("dL_dcolor / dL_dopacity / dL_dsemantics may only all be NULL (geometry-only gradients) in the packed accumulation mode");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    if (!use_rows && !use_packed && (!in.dL_dconic || !in.dL_ddepth)) {
-        hsr_set_error("dL_dconic and dL_ddepth may only be NULL when a scratch buffer carries the accumulation (packed / rows mode)");
+    if (!use_packed && (!in.dL_dconic || !in.dL_ddepth)) {
+        hsr_set_error("dL_dconic and dL_ddepth may only be NULL when a scratch buffer carries the accumulation (packed mode)");
         return HSR_ERR_INVALID_ARGUMENT;
     }
     // opt-in exact semantic -> alpha term: extra passes over the packed rows (a geometry-only caller that passes no dL_dpix_sem has no
@@ -667,19 +650,6 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
         }
     }
     float* grow = nullptr;
-    int rows_kc = 0;
-    float* rows = nullptr;
-    uint32_t* inv = nullptr;
-#ifdef HSR_ABLATE
-    if (use_rows) {
-        char* sp = in.scratch;
-        take(sp, rows, (size_t)in.R * (size_t)hsr_rows_row_floats(K));
-        take(sp, inv, (size_t)in.R);
-        // SH coefficients above the active degree (and those of culled Gaussians) receive no gradient
-        if (!in.colors_precomp && in.shs && in.dL_dsh && in.M > 0)
-            HSR_HIP_CHECK(hipMemsetAsync(in.dL_dsh, 0, sizeof(float) * 3 * (size_t)in.M * (size_t)P, stream));
-    } else
-#endif
     if (use_packed) {
         if (geo) gstride = 16;   // one 64-byte line per Gaussian: columns 0..6
         else {
@@ -700,10 +670,6 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     if (in.R > 0) {
         RenderBwdArgs ra;
         ra.W = W; ra.H = H; ra.K = K; ra.semantic = in.semantic; ra.P = P;
-        {
-            static const int dbg = hsr_ablate_env("HSR_DEBUG_FLAGS") ? atoi(hsr_ablate_env("HSR_DEBUG_FLAGS")) : 0;
-            ra.debug_flags = dbg;   // 0 in the product build
-        }
         ra.bg = in.background; ra.ranges = im.ranges; ra.point_list = b.vals; ra.masks = b.vals_unsorted; ra.means2D = g.means2D;
         ra.conic_opacity = g.conic_opacity; ra.depths = g.depths; ra.colors = in.colors_precomp ? in.colors_precomp : g.rgb;
         ra.rec = g.rec;
@@ -712,23 +678,12 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
         ra.dL_dpix_median = in.dL_dpix_median; ra.dL_dpix_opacity = in.dL_dpix_opacity;
         ra.dL_dmean2D = in.dL_dmean2D; ra.dL_dconic = in.dL_dconic; ra.dL_dopacity = in.dL_dopacity;
         ra.dL_dcolor = in.dL_dcolor; ra.dL_dsemantics = in.dL_dsemantics; ra.dL_ddepth = in.dL_ddepth;
-        ra.rows = rows;
         ra.grow = grow;
         ra.grow_stride = gstride;
         ra.grow_layout = glayout;
         StageTimer tm(HSR_STAGE_BWD_RENDER, stream);
-#ifdef HSR_ABLATE
-        if (use_rows) {
-            const int tiles_x = (W + HSR_TILE_X - 1) / HSR_TILE_X, tiles_y = (H + HSR_TILE_Y - 1) / HSR_TILE_Y;
-            hsr_launch_inverse_map(in.R, tiles_x, tiles_y, b.keys, b.vals, g.means2D, radii, g.point_offsets, inv, stream);
-            rows_kc = hsr_launch_render_backward_rows(ra, stream);
-        } else
-#endif
         if (geo) {
-            static const char* e_impl = getenv("HSR_BWD_IMPL");
-            static const bool old_sub = e_impl && !strcmp(e_impl, "sub");   // round 3's butterfly kernel (A/B timing, parity-tested)
-            if (old_sub) hsr_launch_render_backward_geo(ra, stream);
-            else hsr_launch_render_backward_qgeo(ra, stream);
+            hsr_launch_render_backward_qgeo(ra, stream);
         } else {
             hsr_launch_render_backward(ra, stream);
         }
@@ -749,7 +704,7 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     pb.dL_dmean2D = in.dL_dmean2D; pb.dL_dconic = in.dL_dconic; pb.dL_dmean3D = in.dL_dmean3D; pb.dL_dcolor = in.dL_dcolor;
     pb.dL_ddepth = in.dL_ddepth; pb.dL_dcov3D = in.dL_dcov3D; pb.dL_dsh = in.dL_dsh; pb.dL_dscale = in.dL_dscale;
     pb.dL_drot = in.dL_drot;
-    pb.rows_kc = rows_kc; pb.K = K; pb.rows = rows; pb.inv = inv; pb.point_offsets = g.point_offsets;
+    pb.K = K;
     pb.out_mean2D = in.dL_dmean2D; pb.out_conic = in.dL_dconic; pb.out_opacity = in.dL_dopacity; pb.out_color = in.dL_dcolor;
     pb.out_semantics = in.dL_dsemantics; pb.out_depth = in.dL_ddepth;
     pb.grow = grow; pb.grow_stride = gstride; pb.grow_layout = glayout; pb.geo = geo ? 1 : 0;
@@ -834,10 +789,6 @@ size_t hsr_required_binning_bytes(int num_rendered) { return hsr_carve_bin(nullp
 size_t hsr_backward_scratch_bytes(int P, int K, int num_rendered)
 {
     if (P <= 0 || K < 0 || backward_mode() == 2) return 0;
-#ifdef HSR_ABLATE
-    if (rows_mode_requested() && hsr_rows_supported(K) && num_rendered > 0)
-        return (size_t)num_rendered * ((size_t)hsr_rows_row_floats(K) * 4 + 4) + 1024;
-#endif
     return (size_t)P * hsr_grow_stride(K) * sizeof(float) + 512;  // packed per-Gaussian rows
 }
 
@@ -851,12 +802,10 @@ int hsr_set_backward_mode(int mode)
         hsr_set_error("backward mode must be 0 (packed), 1 (rows) or 2 (legacy)");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-#ifndef HSR_ABLATE
     if (mode == 1) {
-        hsr_set_error("the per-instance rows mode is an experiment (measured slower): it exists in the ablate build only");
+        hsr_set_error("the per-instance rows mode was an experiment (measured slower) and has been removed");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-#endif
     g_bwd_mode = mode;
     return HSR_OK;
 }

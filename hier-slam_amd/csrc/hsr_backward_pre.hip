@@ -131,22 +131,18 @@ __global__ void __launch_bounds__(256) zero_visible_rows_kernel(int P, const int
     }
 }
 
-// KC < 0: legacy mode (sums already accumulated atomically in dL_dmean2D / dL_dconic / dL_ddepth).
-// KC >= 0 (ablate build only): rows mode — this thread first sums the rows of its Gaussian's instances (emission order = ascending
-// tile id inside its rect, a FIXED order: gradients are bit-reproducible), writes the six per-Gaussian sums
-// the tile kernel used to add atomically, and continues with them in registers.
-template <int KC>
+// packed mode (a.grow): unpacks each Gaussian's accumulated row; legacy mode: the sums are already in dL_dmean2D / dL_dconic / dL_ddepth.
 __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdArgs a)
 {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     // packed mode: rows of culled Gaussians (radii <= 0) were neither zero-filled nor added into (zero_visible_rows_kernel): they
     // are not read either — their gradients are the zeros written below
     __shared__ uint8_t s_vis[256];
-    if (KC < 0 && a.grow) {
+    if (a.grow) {
         s_vis[threadIdx.x] = idx < a.P && a.radii[idx] > 0;
         __syncthreads();
     }
-    if (KC < 0 && a.grow && a.K > 0 && a.out_semantics) {
+    if (a.grow && a.K > 0 && a.out_semantics) {
         // packed mode: the block unpacks the semantic columns of its 256 rows cooperatively — consecutive
         // lanes read consecutive floats of a row and write one contiguous [256, K] slab of dL_dsemantics
         // (row, column) of element e advance incrementally — no division in the loop — and four loads are in flight per lane
@@ -183,33 +179,7 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdArgs a)
     }
     if (idx >= a.P) return;
     float g_m2x = 0, g_m2y = 0, g_cx = 0, g_cy = 0, g_cw = 0, g_depth = 0;
-    if (KC >= 0) {
-        constexpr int NCHP = 16 * ((KC + 5 + 15) / 16);
-        constexpr int ROW = 8 + NCHP;
-        float racc[ROW];
-#pragma unroll
-        for (int c = 0; c < ROW; c++) racc[c] = 0.f;
-        const uint32_t beg = idx == 0 ? 0u : a.point_offsets[idx - 1], end = a.point_offsets[idx];
-        for (uint32_t u = beg; u < end; u++) {
-            const float4* r = reinterpret_cast<const float4*>(a.rows + (size_t)a.inv[u] * ROW);
-#pragma unroll
-            for (int q = 0; q < ROW / 4; q++) {
-                const float4 v = r[q];
-                racc[4 * q] += v.x; racc[4 * q + 1] += v.y; racc[4 * q + 2] += v.z; racc[4 * q + 3] += v.w;
-            }
-        }
-        constexpr int KCC = KC < 0 ? 0 : KC;
-        g_m2x = racc[0]; g_m2y = racc[1]; g_cx = racc[2]; g_cy = racc[3]; g_cw = racc[4];
-        g_depth = racc[6] + racc[8 + KCC + 3];
-        a.out_mean2D[3 * idx] = g_m2x; a.out_mean2D[3 * idx + 1] = g_m2y; a.out_mean2D[3 * idx + 2] = 0.f;
-        if (a.out_conic) reinterpret_cast<float4*>(a.out_conic)[idx] = make_float4(g_cx, g_cy, 0.f, g_cw);
-        a.out_opacity[idx] = racc[5] + racc[8 + KCC + 4];
-        a.out_color[3 * idx] = racc[8 + KCC]; a.out_color[3 * idx + 1] = racc[8 + KCC + 1]; a.out_color[3 * idx + 2] = racc[8 + KCC + 2];
-        if (a.out_depth) a.out_depth[idx] = g_depth;
-#pragma unroll
-        for (int c = 0; c < KCC; c++)
-            if (c < a.K) a.out_semantics[(size_t)idx * a.K + c] = racc[8 + c];
-    } else if (a.grow) {
+    if (a.grow) {
         // packed mode: unpack this Gaussian's atomically accumulated row into the reference's arrays
         // a culled Gaussian's lane re-reads the first row of the block's slab (unconditional loads, values discarded)
         const bool vis = s_vis[threadIdx.x];
@@ -393,15 +363,6 @@ int hsr_launch_preprocess_backward(const PreBwdArgs& a, hipStream_t stream)
 {
     if (a.P <= 0) return HSR_OK;
     const dim3 grid((a.P + 255) / 256), block(256);
-    switch (a.rows_kc) {
-    case 0: preprocess_backward_kernel<-1><<<grid, block, 0, stream>>>(a); break;
-#ifdef HSR_ABLATE   // per-instance rows experiment (experiments/hsr_render_bwd_rows.hip)
-    case 11: preprocess_backward_kernel<11><<<grid, block, 0, stream>>>(a); break;
-    case 16: preprocess_backward_kernel<16><<<grid, block, 0, stream>>>(a); break;
-    case 26: preprocess_backward_kernel<26><<<grid, block, 0, stream>>>(a); break;
-    case 27: preprocess_backward_kernel<27><<<grid, block, 0, stream>>>(a); break;
-#endif
-    default: hsr_set_error("unsupported rows_kc %d", a.rows_kc); return HSR_ERR_INVALID_ARGUMENT;
-    }
+    preprocess_backward_kernel<<<grid, block, 0, stream>>>(a);
     return HSR_OK;
 }

@@ -80,18 +80,9 @@ uint32_t hsr_sort_hist_entries(int R);
 
 void hsr_set_error(const char* fmt, ...);
 
-// Ablation switches (HSR_DEBUG_FLAGS, HSR_FWD_DEBUG, HSR_NO_SPECULATION) and the measured-slower experimental kernel
-// families (csrc/experiments/: moments backward, per-instance rows backward, pair-pipelined forward) exist only in the
-// diagnostic build (`make ablate` -> libhsr_rast_ablate.so, -DHSR_ABLATE).  The product library reads none of them: a
-// stray environment variable cannot change its results.  What the product still reads are the parity-tested kernel-family
-// selectors HSR_FWD_IMPL=valu, HSR_BWD_IMPL=valu|mfma|legacy and HSR_SORT_IMPL=radix|block (every choice gives the same
-// results; tests/test_gpu_golden_and_scale.py runs the parity cases under each).
-#ifdef HSR_ABLATE
-#include <stdlib.h>
-static inline const char* hsr_ablate_env(const char* name) { return getenv(name); }
-#else
-static inline const char* hsr_ablate_env(const char*) { return nullptr; }
-#endif
+// Environment selectors the library reads, each once per process: HSR_BWD_IMPL=valu (the all-VALU backward) | legacy (accumulation
+// mode 2), HSR_BWD_WIDE_PASS=split and HSR_SORT_IMPL=radix|block|wave pick kernel families that give the same results
+// (tests/test_gpu_golden_and_scale.py runs the parity cases under each); HSR_SEMANTIC_ALPHA=exact opts in to the semantic -> alpha term.
 
 #define HSR_HIP_CHECK(expr)                                                                     \
     do {                                                                                        \
@@ -173,16 +164,12 @@ struct RenderFwdArgs {
     float* out_median_depth;
     float* out_opacity;
     float* out_mask;  // non-semantic variant only
-    int debug_flags;  // ablation switches for tools/ablate.sh (wide kernel: 1 no MFMA, 2 no row gather, 4 no blend loop); 0 in production
     BinDevRef bin;    // base != NULL: point_list is resolved on the device (speculative forward)
 };
 int hsr_launch_render_forward(const RenderFwdArgs& a, hipStream_t stream);
-bool hsr_launch_render_forward_mma(const RenderFwdArgs& a, hipStream_t stream);   // experiments/ (ablate build): semantic, K <= 140, channel sums on the fp32 matrix cores
-bool hsr_launch_render_forward_wide(const RenderFwdArgs& a, hipStream_t stream);  // experiments/ (ablate build): semantic, 29 <= K <= 124; false otherwise
 
 struct RenderBwdArgs {
     int W, H, K, semantic, P;
-    int debug_flags;  // HSR_DEBUG_FLAGS env (timing experiments only): bit0 = drop the gradient atomics
     const float* bg;  // device [3]
     const uint2* ranges;
     const uint32_t* point_list;
@@ -206,7 +193,6 @@ struct RenderBwdArgs {
     float* dL_dcolor;     // [P,3]
     float* dL_dsemantics; // [P,K]
     float* dL_ddepth;     // [P]
-    float* rows;          // rows mode: [R][ROW] per-instance sums (scratch)
     float* grow;          // packed mode: [P][grow_stride] one gradient row per Gaussian (scratch), else NULL
     int grow_stride;
     int grow_layout;      // 0: classic packed row; 1: compact (hsr_tile_common.h, hsr_grow_col) — hsr_render_bwd_q.hip only
@@ -214,21 +200,11 @@ struct RenderBwdArgs {
     int sem_c0 = 0;                      // ... first channel of the pass
 };
 int hsr_launch_render_backward(const RenderBwdArgs& a, hipStream_t stream);
-int hsr_launch_render_backward_mfma(const RenderBwdArgs& a, hipStream_t stream);
-int hsr_launch_render_backward_mom(const RenderBwdArgs& a, hipStream_t stream);   // K <= 27, packed mode: all sums on MFMA
-int hsr_launch_render_backward_sub(const RenderBwdArgs& a, hipStream_t stream);   // K <= 27, packed mode: 4x4 sub-block lists, rows merged per tile in LDS
-int hsr_launch_render_backward_geo(const RenderBwdArgs& a, hipStream_t stream);   // packed mode, geometry gradients only (grow_stride 16)
 int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream);     // K <= 27, packed mode: round 4, both per-pixel factors in LDS panels, moments per chunk
 int hsr_launch_render_backward_qgeo(const RenderBwdArgs& a, hipStream_t stream);  // geometry gradients only, same scheme
 int hsr_launch_render_backward_qsema(const RenderBwdArgs& a, hipStream_t stream); // packed rows: + the exact semantic -> alpha term into columns 0..5 (opt-in)
 int hsr_backward_row_layout(int K_semantic, bool packed, int P);   // layout hsr_launch_render_backward will expect for this K (0 unless it takes the Q-panel kernel and the compact row saves a line)
 int hsr_launch_render_backward_subw(const RenderBwdArgs& a, hipStream_t stream);  // K > 27, packed mode: sub-block masks, channel passes
-int hsr_launch_render_backward_wide(const RenderBwdArgs& a, hipStream_t stream);  // semantic, K > 27: matrix-core channel passes
-int hsr_launch_render_backward_rows(const RenderBwdArgs& a, hipStream_t stream);  // returns the kernel's KC
-int hsr_rows_row_floats(int K);
-bool hsr_rows_supported(int K);
-int hsr_launch_inverse_map(int R, int tiles_x, int tiles_y, const uint64_t* keys, const uint32_t* vals, const float2* means2D,
-                           const int* radii, const uint32_t* offsets, uint32_t* inv, hipStream_t stream);
 
 struct PreBwdArgs {
     int P, D, M;
@@ -253,15 +229,9 @@ struct PreBwdArgs {
     float* dL_dsh;
     float* dL_dscale;
     float* dL_drot;
-    // rows mode (deterministic backward): per-instance rows are summed per Gaussian here, and the sums are
-    // written to the out_* arrays (then used in place of the dL_dmean2D / dL_dconic / dL_ddepth inputs)
-    int rows_kc;             // 0 = legacy (atomic) mode; else the KC the rows kernel was instantiated for
+    // packed mode: one atomically accumulated row per Gaussian (see hsr_grow_* in hsr_tile_common.h), unpacked into the out_* arrays
     int K;
-    const float* rows;       // [R][8 + 16*NG]
-    const uint32_t* inv;     // emission index -> sorted position
-    const uint32_t* point_offsets;
     float *out_mean2D, *out_conic, *out_opacity, *out_color, *out_semantics, *out_depth;
-    // packed mode: one atomically accumulated row per Gaussian (see hsr_grow_* in hsr_tile_common.h)
     const float* grow;
     int grow_stride;
     int grow_layout;         // layout of the packed rows (RenderBwdArgs::grow_layout)

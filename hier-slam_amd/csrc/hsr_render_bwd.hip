@@ -250,11 +250,7 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a, int c0
                 if (active) T = test_T;
 
                 const float total = wave_reduce_transpose<NV>(v, lane);
-                if (a.debug_flags & 1) {
-                    asm volatile("" ::"v"(total));  // timing experiment: keep the sum alive, drop the atomic
-                } else if (tgt_base) {
-                    atomicAdd(tgt_base + (size_t)s_id[j] * tgt_stride, total);
-                }
+                if (tgt_base) atomicAdd(tgt_base + (size_t)s_id[j] * tgt_stride, total);
             }
         }
     }
@@ -267,8 +263,8 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a, int c0
 static bool backward_takes_q(int Ksem)
 {
     static const char* impl = getenv("HSR_BWD_IMPL");
-    static const bool other = impl && (!strcmp(impl, "valu") || !strcmp(impl, "sub") || !strcmp(impl, "mfma") || !strcmp(impl, "mom"));
-    return !other && Ksem <= 27;
+    static const bool valu = impl && !strcmp(impl, "valu");
+    return !valu && Ksem <= 27;
 }
 int hsr_backward_row_layout(int K_semantic, bool packed, int P)
 {
@@ -281,28 +277,17 @@ int hsr_launch_render_backward(const RenderBwdArgs& a, hipStream_t stream)
 {
     const int tiles = ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
     const dim3 grid(hsr_tile_grid(tiles)), block(256);
-    // Default (packed accumulation rows, a.grow): the matrix-core kernels on 4x4 sub-block lists (hsr_render_bwd_sub.hip) — `sub` for
-    // K <= 27, one-pass `subw` beyond.  They address the packed rows with 32-bit element indices; beyond 2^30 row elements (P > 22 M
-    // Gaussians at K = 26), in the legacy accumulation mode (no scratch: atomics straight into the six output arrays, like the
-    // reference) and under HSR_BWD_IMPL=valu (A/B timing, tests) the all-VALU kernel of this file takes over: 64-bit addressing, any K.
-    // Round 1's quadrant-list matrix-core kernels live in experiments/ (HSR_BWD_IMPL=mfma in the ablate build).
+    // Default (packed accumulation rows, a.grow): the matrix-core kernels on 4x4 sub-block lists — the Q-panel kernel for K <= 27
+    // (hsr_render_bwd_q.hip), one-pass `subw` beyond (hsr_render_bwd_sub.hip).  They address the packed rows with 32-bit element
+    // indices; beyond 2^30 row elements (P > 22 M Gaussians at K = 26), in the legacy accumulation mode (no scratch: atomics straight
+    // into the six output arrays, like the reference) and under HSR_BWD_IMPL=valu (A/B timing, tests) the all-VALU kernel of this file
+    // takes over: 64-bit addressing, any K.
     const bool rows_fit_32bit = !a.grow || (size_t)a.P * (size_t)a.grow_stride < ((size_t)1 << 30);
     static const char* impl = getenv("HSR_BWD_IMPL");
     static const bool force_valu = impl && !strcmp(impl, "valu");
     const int Ksem = a.semantic ? a.K : 0;
-#ifdef HSR_ABLATE
-    static const bool use_quad = impl && !strcmp(impl, "mfma");
-    static const bool use_mom = impl && !strcmp(impl, "mom");
-    if (!force_valu && rows_fit_32bit) {
-        if (use_mom && a.grow && Ksem <= 27) return hsr_launch_render_backward_mom(a, stream);
-        if (use_quad) return Ksem <= 27 ? hsr_launch_render_backward_mfma(a, stream) : hsr_launch_render_backward_wide(a, stream);
-    }
-#endif
-    static const bool old_sub = impl && !strcmp(impl, "sub");   // round 3's butterfly kernel (A/B timing, parity-tested)
-    if (!force_valu && rows_fit_32bit && a.grow) {
-        if (Ksem > 27) return hsr_launch_render_backward_subw(a, stream);
-        return old_sub ? hsr_launch_render_backward_sub(a, stream) : hsr_launch_render_backward_q(a, stream);
-    }
+    if (!force_valu && rows_fit_32bit && a.grow)
+        return Ksem > 27 ? hsr_launch_render_backward_subw(a, stream) : hsr_launch_render_backward_q(a, stream);
     if (!a.semantic || a.K == 0) {
         render_bwd_kernel<0, true><<<grid, block, 0, stream>>>(a, 0);
         return HSR_OK;

@@ -40,8 +40,6 @@
 //     What helps there is fewer LINES: compact rows (hsr_tile_common.h) make K = 0 one line instead of two and 12 <= K <= 20 two
 //     instead of three; K = 26 needs 36 floats and stays at three.
 #include "hsr_tile_common.h"
-#include <stdlib.h>
-#include <string.h>
 
 #ifdef HSR_TRACE
 // Diagnostic build only (make -C hier-slam_amd/csrc trace -> libhsr_rast_trace.so, tools/trace_bwd.py): per-wave cycle counts of
@@ -67,16 +65,6 @@ namespace {
                  "v"(p_b), "v"(p_d), "v"(p_mask))
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Timing ablations (diagnostic build only; results are WRONG with any of them set): HSR_DEBUG_FLAGS bit 1 (2) no panel stores, bit 2 (4) no
-// median add, bit 3 (8) no flush at all, bit 5 (32) no moments / emission table in the flush, bit 6 (64) no matrix instructions, bit 7 (128) no
-// panel clear, bit 8 (256) no visit loop, bit 9 (512) the visit's record is not read (the chunk's first one is reused), bit 10 (1024) no
-// v_exp_f32 / v_rcp_f32, bit 11 (2048) no list-element reads.  tools/r04_ablate_q.sh
-#ifdef HSR_ABLATE
-#define QAB(a, bit) ((a).debug_flags & (bit))
-#else
-#define QAB(a, bit) 0
-#endif
 
 // orders the LDS accesses of ONE wave (stores before it are visible to the wave's loads after it); no workgroup barrier
 __device__ __forceinline__ void wave_lds_fence()
@@ -139,7 +127,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
     __shared__ float s_medj[BATCH];                    // median-depth gradient of each staged splat: see "median" below
     __shared__ uint8_t s_segtab[4][Q_ROWS][4];         // segment of each (row, group) pair of the chunk, Q_SEG_ZERO where the group does not visit the row
 
-    const int tile = HSR_TILE_OF_BLOCK(blockIdx.x, (a.W + HSR_TILE_X - 1) / HSR_TILE_X, (a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
+    const int tile = hsr_block_tile(blockIdx.x, ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y));
     if (tile >= ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)) return;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, gq = lane >> 4, l16 = lane & 15;
     const TileGeom tg = tile_geom_sub(tile, a.W, a.H, t);
@@ -312,76 +300,73 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
                 for (int m = 0; m < 16; m++)
 #pragma unroll
                     for (int g = 0; g < NG; g++)
-                        if (!QAB(a, 64)) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], Breg[g][m], acc[g], 0, 0, 0);
-                        else acc[g][0] += av[m] * Breg[g][m];
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], Breg[g][m], acc[g], 0, 0, 0);
             }
         }
         // (2) lane (row l16, group gq): the six moments of the group's 16 gda values of that row about the sub-block centre.
         //     pixel 4 yy + xx of the group sits at (u, v) = (xx - 1.5, yy - 1.5)
-        float o[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (!QAB(a, 32)) {
-            const uint32_t myseg = (st >> (8 * gq)) & 0xFFu;
-            float qv[16], wd[GEO ? 16 : 1], medsum;
-            if (GEO) {
-                const float2* qp = reinterpret_cast<const float2*>(pw) + myseg * Q_SEGW;
+        float o[7];
+        const uint32_t myseg = (st >> (8 * gq)) & 0xFFu;
+        float qv[16], wd[GEO ? 16 : 1], medsum;
+        if (GEO) {
+            const float2* qp = reinterpret_cast<const float2*>(pw) + myseg * Q_SEGW;
 #pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    const float2 v = qp[i];
-                    qv[i] = v.x;
-                    wd[GEO ? i : 0] = v.y;
-                }
-                medsum = 0.f;
-            } else {
-                const float* qp = pq + myseg * Q_SEGW;
-#pragma unroll
-                for (int i = 0; i < 16; i++) qv[i] = qp[i];
-                medsum = 0.f;
+            for (int i = 0; i < 16; i++) {
+                const float2 v = qp[i];
+                qv[i] = v.x;
+                wd[GEO ? i : 0] = v.y;
             }
-            const uint32_t eo = s_rowent[wv][l16];
-            // median: whatever has been added for this row's splat so far, by any wave — taken (exchanged with zero), so that it is emitted once
-            if (!SEMA && gq == 0 && eo < (uint32_t)(BATCH * ENTB)) medsum = atomicExch(&s_medj[eo / ENTB], 0.f);
-            const float4* ent = reinterpret_cast<const float4*>(entb + eo);
-            const float4 e0 = ent[0], e2 = ent[2];
-            float s0[4], s1[4], s2[4];
+            medsum = 0.f;
+        } else {
+            const float* qp = pq + myseg * Q_SEGW;
 #pragma unroll
-            for (int yy = 0; yy < 4; yy++) {
-                const float qa = qv[4 * yy], qb = qv[4 * yy + 1], qc = qv[4 * yy + 2], qd = qv[4 * yy + 3];
-                const float ad = qa + qd, bc = qb + qc;
-                s0[yy] = ad + bc;
-                s1[yy] = fmaf(1.5f, qd - qa, 0.5f * (qc - qb));
-                s2[yy] = fmaf(2.25f, ad, 0.25f * bc);
-            }
-            const float M0 = (s0[0] + s0[3]) + (s0[1] + s0[2]);
-            const float Mu = (s1[0] + s1[3]) + (s1[1] + s1[2]);
-            const float Muu = (s2[0] + s2[3]) + (s2[1] + s2[2]);
-            const float Mv = fmaf(1.5f, s0[3] - s0[0], 0.5f * (s0[2] - s0[1]));
-            const float Mvv = fmaf(2.25f, s0[0] + s0[3], 0.25f * (s0[1] + s0[2]));
-            const float Muv = fmaf(1.5f, s1[3] - s1[0], 0.5f * (s1[2] - s1[1]));
-            // shift to the splat's centre: dx = ex - u, dy = ey - v (reference backward.cu:881-896 sums these per pixel)
-            const float ex = e0.x - cxg, ey = e0.y - cyg;
-            const float Ap = e0.z, Cp = e2.x, op = e2.y, hB = e2.z;
-            const float Sx = fmaf(fmaf(Ap, ex, hB * ey), M0, -fmaf(Ap, Mu, hB * Mv));     // sum gda (A' dx + B'/2 dy)
-            const float Sy = fmaf(fmaf(Cp, ey, hB * ex), M0, -fmaf(Cp, Mv, hB * Mu));     // sum gda (C' dy + B'/2 dx)
-            const float Sxx = fmaf(ex, fmaf(ex, M0, -2.0f * Mu), Muu);                     // sum gda dx^2
-            const float Sxy = fmaf(ex, fmaf(ey, M0, -Mv), fmaf(-ey, Mu, Muv));             // sum gda dx dy
-            const float Syy = fmaf(ey, fmaf(ey, M0, -2.0f * Mv), Mvv);                     // sum gda dy^2
-            const float mh = -0.5f * op;
-            o[0] = (kx2 * op) * Sx;   // dL_dmean2D.x
-            o[1] = (ky2 * op) * Sy;   // dL_dmean2D.y
-            o[2] = mh * Sxx;          // dL_dconic.x
-            o[3] = mh * Sxy;          // dL_dconic.y
-            o[4] = mh * Syy;          // dL_dconic.w
-            o[5] = M0;                // dL_dopacity, alpha path
-            // column 6: the median-depth sum taken above (group 0); GEO: + the segment's depth sum (the panel's .y holds w * dL_ddepth)
-            float s6 = medsum;
-            if (GEO) {
-                float wsum[4];
-#pragma unroll
-                for (int yy = 0; yy < 4; yy++) wsum[yy] = (wd[GEO ? 4 * yy : 0] + wd[GEO ? 4 * yy + 1 : 0]) + (wd[GEO ? 4 * yy + 2 : 0] + wd[GEO ? 4 * yy + 3 : 0]);
-                s6 += (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-            }
-            o[6] = s6;
+            for (int i = 0; i < 16; i++) qv[i] = qp[i];
+            medsum = 0.f;
         }
+        const uint32_t eo = s_rowent[wv][l16];
+        // median: whatever has been added for this row's splat so far, by any wave — taken (exchanged with zero), so that it is emitted once
+        if (!SEMA && gq == 0 && eo < (uint32_t)(BATCH * ENTB)) medsum = atomicExch(&s_medj[eo / ENTB], 0.f);
+        const float4* ent = reinterpret_cast<const float4*>(entb + eo);
+        const float4 e0 = ent[0], e2 = ent[2];
+        float s0[4], s1[4], s2[4];
+#pragma unroll
+        for (int yy = 0; yy < 4; yy++) {
+            const float qa = qv[4 * yy], qb = qv[4 * yy + 1], qc = qv[4 * yy + 2], qd = qv[4 * yy + 3];
+            const float ad = qa + qd, bc = qb + qc;
+            s0[yy] = ad + bc;
+            s1[yy] = fmaf(1.5f, qd - qa, 0.5f * (qc - qb));
+            s2[yy] = fmaf(2.25f, ad, 0.25f * bc);
+        }
+        const float M0 = (s0[0] + s0[3]) + (s0[1] + s0[2]);
+        const float Mu = (s1[0] + s1[3]) + (s1[1] + s1[2]);
+        const float Muu = (s2[0] + s2[3]) + (s2[1] + s2[2]);
+        const float Mv = fmaf(1.5f, s0[3] - s0[0], 0.5f * (s0[2] - s0[1]));
+        const float Mvv = fmaf(2.25f, s0[0] + s0[3], 0.25f * (s0[1] + s0[2]));
+        const float Muv = fmaf(1.5f, s1[3] - s1[0], 0.5f * (s1[2] - s1[1]));
+        // shift to the splat's centre: dx = ex - u, dy = ey - v (reference backward.cu:881-896 sums these per pixel)
+        const float ex = e0.x - cxg, ey = e0.y - cyg;
+        const float Ap = e0.z, Cp = e2.x, op = e2.y, hB = e2.z;
+        const float Sx = fmaf(fmaf(Ap, ex, hB * ey), M0, -fmaf(Ap, Mu, hB * Mv));     // sum gda (A' dx + B'/2 dy)
+        const float Sy = fmaf(fmaf(Cp, ey, hB * ex), M0, -fmaf(Cp, Mv, hB * Mu));     // sum gda (C' dy + B'/2 dx)
+        const float Sxx = fmaf(ex, fmaf(ex, M0, -2.0f * Mu), Muu);                     // sum gda dx^2
+        const float Sxy = fmaf(ex, fmaf(ey, M0, -Mv), fmaf(-ey, Mu, Muv));             // sum gda dx dy
+        const float Syy = fmaf(ey, fmaf(ey, M0, -2.0f * Mv), Mvv);                     // sum gda dy^2
+        const float mh = -0.5f * op;
+        o[0] = (kx2 * op) * Sx;   // dL_dmean2D.x
+        o[1] = (ky2 * op) * Sy;   // dL_dmean2D.y
+        o[2] = mh * Sxx;          // dL_dconic.x
+        o[3] = mh * Sxy;          // dL_dconic.y
+        o[4] = mh * Syy;          // dL_dconic.w
+        o[5] = M0;                // dL_dopacity, alpha path
+        // column 6: the median-depth sum taken above (group 0); GEO: + the segment's depth sum (the panel's .y holds w * dL_ddepth)
+        float s6 = medsum;
+        if (GEO) {
+            float wsum[4];
+#pragma unroll
+            for (int yy = 0; yy < 4; yy++) wsum[yy] = (wd[GEO ? 4 * yy : 0] + wd[GEO ? 4 * yy + 1 : 0]) + (wd[GEO ? 4 * yy + 2 : 0] + wd[GEO ? 4 * yy + 3 : 0]);
+            s6 += (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        }
+        o[6] = s6;
         // D[row = 4*(lane>>4) + r][col = lane&15]: one atomic wave-instruction per register = 4 rows x 64 bytes
         if (!GEO && !ALL_IN_LINE0) {
             const uint4 b4 = *reinterpret_cast<const uint4*>(&s_cid[wv][4 * (lane >> 4)]);   // the four row offsets in one LDS read
@@ -391,7 +376,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             for (int r = 0; r < 4; r++)
 #pragma unroll
                 for (int g = 0; g < NG; g++)
-                    if (r < nr && colg[g] >= 0 && !(a.debug_flags & 1))
+                    if (r < nr && colg[g] >= 0)
                         atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(a.grow) + 4u * (bb[r] + (uint32_t)colg[g])), acc[g][r]);
         }
         if (CL && !GEO) {
@@ -405,7 +390,6 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
                 }
         }
         // (3) the four groups' contributions of a row meet in the emission table (it overlays the W panel, which is dead now)
-        if (QAB(a, 32)) return;
         wave_lds_fence();
         float* tb = pw;
 #pragma unroll
@@ -434,7 +418,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             for (int pass = 0; pass < 4; pass++) {
                 const int row = (lane >> 4) + 4 * pass;
                 const float val = vi < 7 ? (sa[pass].x + sa[pass].y) + (sa[pass].z + sa[pass].w) : ta[pass];
-                if (vi < 7 + nl0 && row < nrows && val != 0.f && !(a.debug_flags & 1))
+                if (vi < 7 + nl0 && row < nrows && val != 0.f)
                     atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(a.grow) + 4u * (cid[pass] + (uint32_t)vi)), val);
             }
         } else {
@@ -453,7 +437,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             for (int pass = 0; pass < 2; pass++) {
                 const int row = (lane >> 3) + 8 * pass;
                 const float val = (sa[pass].x + sa[pass].y) + (sa[pass].z + sa[pass].w);
-                if (vi < 7 && row < nrows && val != 0.f && !(a.debug_flags & 1))
+                if (vi < 7 && row < nrows && val != 0.f)
                     atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(a.grow) + 4u * (cid[pass] + (uint32_t)vi)), val);
             }
         }
@@ -564,7 +548,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
                 const float dx = ra.x - pfx, dy = ra.y - pfy;
                 const float dxx = dx * dx, dxy = dx * dy, dyy = dy * dy;
                 const float power2 = fmaf(rc.x, dyy, fmaf(ra.w, dxy, ra.z * dxx));
-                const float G = QAB(a, 1024) ? power2 + 1.0f : __builtin_amdgcn_exp2f(power2);
+                const float G = __builtin_amdgcn_exp2f(power2);
                 const float alpha = fminf(0.99f, rc.y * G);
                 const bool active = eo >= jf_off && power2 <= 0.0f && alpha >= 1.0f / 255.0f;
 #ifdef HSR_TRACE
@@ -577,7 +561,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
 #endif
                 o.am = active ? alpha : 0.f;
                 o.Gm = active ? G : 0.f;
-                o.inv = QAB(a, 1024) ? 1.0f + o.am : __builtin_amdgcn_rcpf(1.0f - o.am);   // 1 where the pixel skips the splat: T * 1 = T
+                o.inv = __builtin_amdgcn_rcpf(1.0f - o.am);   // 1 where the pixel skips the splat: T * 1 = T
                 o.nb = ntfbg * o.inv;
                 if (SEMA) {
                     const float4* f = reinterpret_cast<const float4*>(entb + e.x + Q_ENTB);
@@ -600,15 +584,11 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
                 const float d = c.h - Racc;
                 const float dL_dalpha = fmaf(d, test_T, c.nb);
                 const float gda = c.Gm * dL_dalpha;
-                if (!QAB(a, 2)) {
-                    if (GEO) {
-                        *reinterpret_cast<float2*>(panb + c.ro) = make_float2(gda, w * dpd);
-                    } else {
-                        *reinterpret_cast<float*>(panb + c.ro) = w;
-                        *reinterpret_cast<float*>(panb + c.ro + Q_PANEL * 4) = gda;
-                    }
+                if (GEO) {
+                    *reinterpret_cast<float2*>(panb + c.ro) = make_float2(gda, w * dpd);
                 } else {
-                    asm volatile("" ::"v"(w), "v"(gda));
+                    *reinterpret_cast<float*>(panb + c.ro) = w;
+                    *reinterpret_cast<float*>(panb + c.ro + Q_PANEL * 4) = gda;
                 }
                 Racc = fmaf(c.am, d, Racc);
                 T = test_T;
@@ -635,18 +615,17 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             asm volatile("" ::"v"(cur.am), "v"(cur.h), "v"(ra1.x), "v"(rb1.x));   // the pipeline's first stage has landed
 #endif
             TR_ADD(tr_setup, tsu);
-            for (int it = 0; it < (QAB(a, 256) ? 0 : iters); it += 2) {
+            for (int it = 0; it < iters; it += 2) {
                 // first half: visit it + 2's record and the list element after it in flight; A of visit it + 1; B of visit it
-                const uint2 e3 = QAB(a, 2048) ? e1 : ordp[it + 3];
+                const uint2 e3 = ordp[it + 3];
                 float4 ra2, rb2;
                 float2 rc2;
-                if (QAB(a, 512)) { ra2 = ra1; rb2 = rb1; rc2 = rc1; }
-                else load_rec(e2, ra2, rb2, rc2);
+                load_rec(e2, ra2, rb2, rc2);
                 const StageA nxt = stage_a(ra1, rb1, rc1, e1);
                 stage_b(cur);
                 // second half (an odd list ends on the dummy entry: weight 0 into the dummy segment)
-                const uint2 e4 = QAB(a, 2048) ? e2 : ordp[it + 4];
-                if (!QAB(a, 512)) load_rec(e3, ra1, rb1, rc1);
+                const uint2 e4 = ordp[it + 4];
+                load_rec(e3, ra1, rb1, rc1);
                 cur = stage_a(ra2, rb2, rc2, e2);
                 stage_b(nxt);
                 e1 = e3; e2 = e4;
@@ -655,7 +634,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
                 const long long tf = TR_NOW();
                 (void)tf;
                 if (c0 == 0) HSR_SETTLE_STAGING();
-                if (!QAB(a, 8)) flush(nrows);
+                flush(nrows);
                 TR_ADD(tr_flush, tf);
 #ifdef HSR_TRACE
                 tr_chunks++;
@@ -671,7 +650,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             unsigned long long* o = g_hsr_trace_q + (size_t)wid * HSR_TRACE_SLOTS;
             o[0] = (unsigned long long)(clock64() - tr_t0);
             o[1] = (unsigned long long)(tr_t1 - tr_t0);
-            o[2] = tr_stage; o[3] = tr_loop; o[4] = tr_flush; o[5] = tr_chunks; o[6] = tr_iters; o[7] = tr_setup;   // slot 7: chunk set-up (round 3's kernel: accepting visits)
+            o[2] = tr_stage; o[3] = tr_loop; o[4] = tr_flush; o[5] = tr_chunks; o[6] = tr_iters; o[7] = tr_setup;   // slot 7: chunk set-up
         }
     }
 #endif
@@ -682,7 +661,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
 // packed mode, K <= 27, P * grow_stride < 2^30 (32-bit row addressing): the caller checks.  a.grow_layout: hsr_backward_row_layout.
 int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream)
 {
-    const dim3 grid(HSR_GRID_OF_TILES((a.W + HSR_TILE_X - 1) / HSR_TILE_X, (a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)), block(256);
+    const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
     const int K = a.semantic ? a.K : 0;
     const bool cl = a.grow_layout == 1;
     if (K == 0) {
@@ -703,7 +682,7 @@ int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream)
 int hsr_launch_render_backward_qsema(const RenderBwdArgs& a0, hipStream_t stream)
 {
     RenderBwdArgs a = a0;
-    const dim3 grid(HSR_GRID_OF_TILES((a.W + HSR_TILE_X - 1) / HSR_TILE_X, (a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)), block(256);
+    const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
     for (int c0 = 0; c0 < a.K; c0 += 16) {
         a.sem_c0 = c0;
         render_bwd_q_kernel<16, 208, true, false, true><<<grid, block, 0, stream>>>(a);
@@ -714,6 +693,6 @@ int hsr_launch_render_backward_qsema(const RenderBwdArgs& a0, hipStream_t stream
 // geometry-only gradients (a.grow_stride == 16): any K
 int hsr_launch_render_backward_qgeo(const RenderBwdArgs& a, hipStream_t stream)
 {
-    render_bwd_q_kernel<0, 208, true><<<dim3(HSR_GRID_OF_TILES((a.W + HSR_TILE_X - 1) / HSR_TILE_X, (a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)), dim3(256), 0, stream>>>(a);
+    render_bwd_q_kernel<0, 208, true><<<dim3(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), dim3(256), 0, stream>>>(a);
     return HSR_OK;
 }

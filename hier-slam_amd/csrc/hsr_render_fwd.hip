@@ -22,8 +22,6 @@
 //     v_exp_f32 and a handful of FMAs: the kernel is VALU-issue bound, not HBM bound.
 //   * K is a template parameter of the kernel but a run-time argument of the library: known tree
 //     sizes get one fused launch, any other K is rendered in 32-channel chunks.
-#include <stdlib.h>
-#include <string.h>
 
 #include "hsr_tile_common.h"
 
@@ -167,7 +165,7 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
     __shared__ uint8_t s_subcnt[4][16];
     __shared__ int s_wdone[4];
 
-    const int tile = HSR_TILE_OF_BLOCK(blockIdx.x, (a.W + HSR_TILE_X - 1) / HSR_TILE_X, (a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
+    const int tile = hsr_block_tile(blockIdx.x, ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y));
     if (tile >= ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)) return;
     const int t = threadIdx.x, wv = t >> 6;
     if (a.bin.base) {   // speculative forward: the list lives where num_rendered says
@@ -295,7 +293,7 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
         const int cnt = min(BATCH, n - start);
         uint32_t qmask = 0u;
         if (t < cnt) {
-            const uint32_t mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0, !(a.debug_flags & 16));
+            const uint32_t mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0);
             qmask = SUB ? mask16 : quadrant_bits(mask16);
             a.masks[range.x + start + t] = mask16;   // the backward stages the same entries: it reads the mask instead of deriving it again
             s_rec[2 * t] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);
@@ -616,46 +614,22 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
 
 int hsr_launch_render_forward(const RenderFwdArgs& a, hipStream_t stream)
 {
-    const dim3 grid(HSR_GRID_OF_TILES((a.W + HSR_TILE_X - 1) / HSR_TILE_X, (a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)), block(256);
+    const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
     // Default for K <= 28: the per-lane kernel on 4x4 sub-block lists (SUB).  Measured at the headline workload (500k
-    // Gaussians, 1200x680, K = 26): 0.18 ms against 0.22 ms for the same kernel on quadrant lists (HSR_FWD_IMPL=valu, kept
-    // in the ablate build for A/B timing) and 0.27 ms for round 1's pair-pipelined matrix-core kernel (EXPERIMENTS.md §4: the ~25 VALU
-    // instructions that evaluate alpha per list entry dominate, the matrix cores only take the 15 packed FMAs behind them, and every list
-    // entry has to go through the pair; removed in round 3 — it predates the saved sub-block masks and median positions the backward reads).
-#ifdef HSR_ABLATE
-    static const char* impl = getenv("HSR_FWD_IMPL");
-    static const bool force_valu = impl && !strcmp(impl, "valu");   // quadrant lists, per-lane accumulators for every K: ablate build only
-#else
-    constexpr bool force_valu = false;   // the product renders on sub-block lists; HSR_FWD_IMPL selects nothing here
-#endif
-#ifdef HSR_ABLATE
-    // round 3's sub-block forward with the channel sums on the fp32 matrix cores (experiments/hsr_render_fwd_mma.hip): parity-green and
-    // slower at every width — fp32 MFMA and plain VALU FMA both run ~34 MAC per cycle and SIMD (EXPERIMENTS.md §9b)
-    static const bool use_mma = impl && !strcmp(impl, "mma");
-    if (use_mma && hsr_launch_render_forward_mma(a, stream)) return HSR_OK;
-#endif
+    // Gaussians, 1200x680, K = 26): 0.18 ms against 0.22 ms for the same kernel on quadrant lists and 0.27 ms for round 1's
+    // pair-pipelined matrix-core kernel (EXPERIMENTS.md §4: the ~25 VALU instructions that evaluate alpha per list entry dominate, the
+    // matrix cores only take the 15 packed FMAs behind them, and every list entry has to go through the pair).
     if (!a.semantic) {
-#ifdef HSR_ABLATE
-        if (force_valu) {
-            render_fwd_kernel<0, true, true, false, false><<<grid, block, 0, stream>>>(a, 0);
-            return HSR_OK;
-        }
-#endif
         render_fwd_kernel<0, true, true, false, true><<<grid, block, 0, stream>>>(a, 0);
         return HSR_OK;
     }
-    // Wide trees.  Round 1 accumulated 29 <= K <= 124 on the matrix cores (experiments/hsr_render_fwd_wide.hip; HSR_FWD_IMPL=wide in the
-    // ablate build still selects it).  Since round 2 the per-lane kernel on sub-block lists takes every K: with the rows of the next batch
-    // touched into L2 instead of parked in registers (PF) it runs at three or four waves per SIMD up to 80 channels, and with quad-shared
-    // rows it also wins beyond (tools/fwd_pf_max.sh, 500k Gaussians, matrix-core -> per-lane: K = 90 0.644 -> 0.557 ms, K = 102
-    // 0.712 -> 0.617, K = 124 0.732 -> 0.695; profiles/r02_fwd_generic_k.log for the narrower ones).
+    // Wide trees.  Round 1 accumulated 29 <= K <= 124 on the matrix cores.  Since round 2 the per-lane kernel on sub-block lists takes
+    // every K: with the rows of the next batch touched into L2 instead of parked in registers (PF) it runs at three or four waves per SIMD
+    // up to 80 channels, and with quad-shared rows it also wins beyond (500k Gaussians, matrix-core -> per-lane: K = 90 0.644 -> 0.557 ms,
+    // K = 102 0.712 -> 0.617, K = 124 0.732 -> 0.695; profiles/r02_fwd_generic_k.log for the narrower ones).
     // (K = 74 and K = 102 — the reference's large ScanNet tree and its flat Replica label set — have instantiations of their exact width
     // below: rows fetched as aligned float2, no padding channels: K = 74 0.371 vs 0.430 ms through the 80-channel kernel)
-#ifdef HSR_ABLATE
-    static const bool prefer_wide = impl && !strcmp(impl, "wide");
-    if (prefer_wide && hsr_launch_render_forward_wide(a, stream)) return HSR_OK;
-#endif
-    if (!force_valu && a.K >= 27 && a.K <= 128 && a.K != 74 && a.K != 102) {
+    if (a.K >= 27 && a.K <= 128 && a.K != 74 && a.K != 102) {
         if (a.K <= 32) render_fwd_kernel<32, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
         else if (a.K <= 48) render_fwd_kernel<48, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
         else if (a.K <= 64) render_fwd_kernel<64, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
@@ -665,45 +639,15 @@ int hsr_launch_render_forward(const RenderFwdArgs& a, hipStream_t stream)
         else render_fwd_kernel<128, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
         return HSR_OK;
     }
-    if (!force_valu) {
-        switch (a.K) {
-        case 0: render_fwd_kernel<0, true, false, false, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;
-        case 16: render_fwd_kernel<16, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // ScanNet tree
-        case 26: render_fwd_kernel<26, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica tree
-        case 74: {   // ScanNet large tree
-#ifdef HSR_ABLATE
-            static const bool no_pf = getenv("HSR_FWD_PF") && !strcmp(getenv("HSR_FWD_PF"), "0");   // A/B selector, ablate build only: rows parked in registers
-            if (no_pf) {
-                render_fwd_kernel<74, true, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-                return HSR_OK;
-            }
-#endif
-            render_fwd_kernel<74, true, false, true, true, true><<<grid, block, 0, stream>>>(a, 0);
-            return HSR_OK;
-        }
-        case 102:   // Replica flat label set
-            render_fwd_kernel<102, true, false, true, true, true><<<grid, block, 0, stream>>>(a, 0);
-            return HSR_OK;
-        default:   // K <= 26 or K > 128: 32-channel chunks; the first chunk also produces the base outputs
-            render_fwd_kernel<32, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
-            for (int c0 = 32; c0 < a.K; c0 += 32) render_fwd_kernel<32, false, false, false, true><<<grid, block, 0, stream>>>(a, c0);
-            return HSR_OK;
-        }
-    }
-#ifdef HSR_ABLATE
-    // HSR_FWD_IMPL=valu: quadrant lists, per-lane accumulators
     switch (a.K) {
-    case 0: render_fwd_kernel<0, true, false, false><<<grid, block, 0, stream>>>(a, 0); break;
-    case 16: render_fwd_kernel<16, true, false, true><<<grid, block, 0, stream>>>(a, 0); break;   // ScanNet tree
-    case 26: render_fwd_kernel<26, true, false, true><<<grid, block, 0, stream>>>(a, 0); break;   // Replica tree
-    case 74: render_fwd_kernel<74, true, false, true><<<grid, block, 0, stream>>>(a, 0); break;   // ScanNet large tree
-    case 102: render_fwd_kernel<102, true, false, true><<<grid, block, 0, stream>>>(a, 0); break; // Replica flat
-    default:
-        // any other K: 32-channel chunks; the first chunk also produces the base outputs
-        render_fwd_kernel<32, true, false, false><<<grid, block, 0, stream>>>(a, 0);
-        for (int c0 = 32; c0 < a.K; c0 += 32) render_fwd_kernel<32, false, false, false><<<grid, block, 0, stream>>>(a, c0);
-        break;
+    case 0: render_fwd_kernel<0, true, false, false, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;
+    case 16: render_fwd_kernel<16, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // ScanNet tree
+    case 26: render_fwd_kernel<26, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica tree
+    case 74: render_fwd_kernel<74, true, false, true, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;     // ScanNet large tree
+    case 102: render_fwd_kernel<102, true, false, true, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica flat label set
+    default:   // K <= 26 or K > 128: 32-channel chunks; the first chunk also produces the base outputs
+        render_fwd_kernel<32, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        for (int c0 = 32; c0 < a.K; c0 += 32) render_fwd_kernel<32, false, false, false, true><<<grid, block, 0, stream>>>(a, c0);
+        return HSR_OK;
     }
-#endif
-    return HSR_OK;
 }

@@ -329,8 +329,8 @@ def _rows_or_legacy():
 
 
 def set_backward_mode(mode):
-    """'packed' (default: one gradient row per Gaussian) or 'legacy' (atomics into the reference's six arrays); 'rows' exists in
-    the ablate build of the library only and is refused by the product."""
+    """'packed' (default: one gradient row per Gaussian) or 'legacy' (atomics into the reference's six arrays); 'rows' (a removed
+    experiment) is refused."""
     rc = _lib.hsr_set_backward_mode({"packed": 0, "rows": 1, "legacy": 2}[mode])
     if rc < 0:
         _fail(rc, "hsr_set_backward_mode")

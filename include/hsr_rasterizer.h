@@ -69,8 +69,7 @@ size_t hsr_backward_scratch_bytes(int P, int K, int num_rendered);
 /* How the backward accumulates per-Gaussian sums (process-wide; default 0, or HSR_BWD_IMPL=legacy):
  *   0 packed : fp32 atomics into one 64-byte-aligned scratch row per Gaussian, unpacked by the per-Gaussian
  *              kernel — about half the atomic requests of the reference's six separate arrays (default);
- *   1        : refused by this library (HSR_ERR_INVALID_ARGUMENT): the per-instance-rows experiment lives in the
- *              diagnostic build `make ablate` only;
+ *   1        : refused (HSR_ERR_INVALID_ARGUMENT): the per-instance-rows experiment was measured slower and removed;
  *   2 legacy : atomics straight into the six output arrays, as the reference does; needs no scratch. */
 int hsr_set_backward_mode(int mode);
 int hsr_get_backward_mode(void);   /* 0 packed, 2 legacy */

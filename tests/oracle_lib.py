@@ -170,7 +170,7 @@ def forward(cam, means3D, opacities, colors_precomp=None, shs=None, semantics_pr
 
 
 # HSR_TEST_SEM_ALPHA=exact: every oracle backward that does not say otherwise runs the exact semantic -> alpha mode, and tests/conftest.py
-# switches the library to it — the parity and fuzz tests then exercise the opt-in mode end to end (tools/r04_exact_fuzz.sh)
+# switches the library to it — the parity and fuzz tests then exercise the opt-in mode end to end
 DEFAULT_SEM_ALPHA_EXACT = os.environ.get("HSR_TEST_SEM_ALPHA", "") == "exact"
 
 

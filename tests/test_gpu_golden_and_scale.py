@@ -139,11 +139,10 @@ def test_forward_is_deterministic_and_backward_reproducible_within_fp32_noise():
         assert_close("grad " + n, g1[n], g2[n], rtol=1e-5, atol=1e-6)  # fp32 atomics: order-dependent last bits
 
 
-def test_experimental_modes_are_not_in_the_product_library():
-    """the per-instance rows accumulation (and the moments kernels) were measured slower and live in the
-    ablate build only (csrc/experiments/, `make -C hier-slam_amd/csrc ablate`): the product refuses the mode"""
+def test_removed_rows_mode_is_refused():
+    """the per-instance rows accumulation was measured slower and removed: the library refuses the mode"""
     from diff_gaussian_rasterization import _C
-    with pytest.raises(RuntimeError, match="ablate build"):
+    with pytest.raises(RuntimeError, match="has been removed"):
         _C.set_backward_mode("rows")
     assert int(_C._lib.hsr_get_backward_mode()) == 0
 
@@ -164,24 +163,12 @@ def test_parity_other_accumulation_modes(name, mode):
         _C.set_backward_mode("packed")
 
 
-ABLATE_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hier-slam_amd", "libhsr_rast_ablate.so")
-
-
-def _ablate_env(**extra):
-    """environment of a child process that runs the diagnostic library (`make -C hier-slam_amd/csrc ablate`: csrc/experiments/ linked
-    in, ablation switches live) through the ctypes glue; skips the test when that library was not built"""
-    if not os.path.exists(ABLATE_LIB):
-        pytest.skip("libhsr_rast_ablate.so not built (make -C hier-slam_amd/csrc ablate): experimental kernel families are not in the product")
-    return dict(os.environ, HSR_RAST_LIB=ABLATE_LIB, HSR_GLUE="ctypes", **extra)
-
-
-@pytest.mark.parametrize("impl", ["mfma", "valu", "sub"])
+@pytest.mark.parametrize("impl", ["valu"])
 def test_parity_alternate_kernels(impl):
-    """kernel families are selected per process (HSR_FWD_IMPL / HSR_BWD_IMPL; defaults: per-lane forward and matrix-core backward
-    on 4x4 sub-block lists — since round 4 the Q-panel kernels of hsr_render_bwd_q.hip for K <= 27 and the geometry-only path; "sub" =
-    round 3's butterfly kernels, kept in the product library for A/B timing).  "valu" = quadrant-list per-lane kernels both ways — the product's fallback for the legacy accumulation
-    mode and beyond 2^30 row elements; "mfma" = round 1's quadrant-list matrix-core backward, since round 3 in the ablate build only
-    (csrc/experiments/).  Parity cases, each family in a child process"""
+    """backward kernel families are selected per process (HSR_BWD_IMPL; default: the matrix-core backward on 4x4 sub-block lists —
+    the Q-panel kernels of hsr_render_bwd_q.hip for K <= 27 and the geometry-only path).  "valu" = the quadrant-list all-VALU
+    backward — the fallback for the legacy accumulation mode and beyond 2^30 row elements.  Parity cases, each family in a child
+    process"""
     import subprocess
     import sys
     code = ("import sys; sys.path[:0]=['hier-slam_amd','tests'];import scenes;from test_gpu_parity import CASES,_compare;"
@@ -189,9 +176,7 @@ def test_parity_alternate_kernels(impl):
             "_compare(cam,sc,up,sem,var,None);"
             "[_compare(*((lambda W,H,P,K,kind,sm,sem,var,bg,beh: (lambda csu: (csu[0],csu[1],csu[2],sem,var,None))(scenes.build(W,H,P,K,seed=11,kind=kind,scale_mult=sm,bg=bg,behind_frac=beh)))(*CASES[n]))) "
             "for n in ('scannet_tree_k16','generic_k5_white_bg','plain_mask','huge_splats','deep_tiles_3000','large_tree_k74')];print('ok')")
-    # "valu": the all-VALU backward in the PRODUCT library (its fallback kernel); the quadrant-list forward of the same name exists in
-    # the ablate build only and is covered by test_parity_round1_wide_kernels_in_the_ablate_build
-    env = _ablate_env(HSR_BWD_IMPL=impl) if impl == "mfma" else dict(os.environ, HSR_BWD_IMPL=impl)
+    env = dict(os.environ, HSR_BWD_IMPL=impl)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
@@ -199,9 +184,7 @@ def test_parity_alternate_kernels(impl):
 
 def test_parity_wide_tree_kernel_selectors():
     """wide trees (K > 27) default to ONE backward pass of up to 112 columns at two waves per SIMD; HSR_BWD_WIDE_PASS=split
-    selects the earlier 64-column passes (what K + 5 > 112 still takes); 49..80 columns contract their panels on the bf16 matrix
-    cores (exact three-way split of the fp32 operands), HSR_BWD_WIDE_MMA=f32 keeps them on the fp32 matrix instructions:
-    same results, parity cases in a child process"""
+    selects the earlier 64-column passes (what K + 5 > 112 still takes): same results, parity cases in a child process"""
     import subprocess
     import sys
     code = ("import sys; sys.path[:0]=['hier-slam_amd','tests'];import scenes;from test_gpu_parity import CASES,_compare;"
@@ -210,26 +193,6 @@ def test_parity_wide_tree_kernel_selectors():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, HSR_BWD_WIDE_PASS="split"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-    # the fp32-matrix-instruction variants of the 4- and 5-group passes and the K = 74 forward with its rows parked in registers are
-    # A/B selectors of the ablate build
-    if os.path.exists(ABLATE_LIB):
-        for extra in (dict(HSR_BWD_WIDE_MMA="f32"), dict(HSR_FWD_PF="0")):
-            r = subprocess.run([sys.executable, "-c", code], cwd=root, env=_ablate_env(**extra), capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0 and "ok" in r.stdout, str(extra) + r.stdout[-2000:] + r.stderr[-2000:]
-
-
-def test_parity_round1_wide_kernels_in_the_ablate_build():
-    """round 1's matrix-core forward (29 <= K <= 124) and quadrant-list wide backward: csrc/experiments/, ablate build only"""
-    import subprocess
-    import sys
-    code = ("import sys; sys.path[:0]=['hier-slam_amd','tests'];import scenes;from test_gpu_parity import CASES,_compare;"
-            "[_compare(*((lambda W,H,P,K,kind,sm,sem,var,bg,beh: (lambda csu: (csu[0],csu[1],csu[2],sem,var,None))(scenes.build(W,H,P,K,seed=11,kind=kind,scale_mult=sm,bg=bg,behind_frac=beh)))(*CASES[n]))) "
-            "for n in ('generic_k40_two_chunks','large_tree_k74','flat_k102','odd_k33','odd_k75_ragged','k124_widest_single_pass','wide_deep_tiles_k76')];print('ok')")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # + round 3's sub-block forward on the fp32 matrix cores (hsr_render_fwd_mma.hip)
-    for extra in (dict(HSR_FWD_IMPL="wide"), dict(HSR_BWD_IMPL="mfma"), dict(HSR_FWD_IMPL="mma"), dict(HSR_FWD_IMPL="valu")):
-        r = subprocess.run([sys.executable, "-c", code], cwd=root, env=_ablate_env(**extra), capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0 and "ok" in r.stdout, str(extra) + r.stdout[-2000:] + r.stderr[-2000:]
 
 
 def test_ctypes_glue_matches_too():

@@ -272,7 +272,7 @@ def test_speculative_forward_and_its_fallback_agree_with_the_oracle(monkeypatch)
 @pytest.mark.parametrize("semantic,K", [(True, 26), (True, 74), (False, 0)])
 def test_geometry_only_backward_matches_the_full_one(semantic, K):
     """When only means3D / means2D want a gradient (a tracking iteration optimises the camera pose alone) the library forms the
-    geometry sums only (hsr_backward*: dL_dcolor, dL_dopacity, dL_dsemantics NULL -> render_bwd_geo_kernel).  dL_dmeans3D and
+    geometry sums only (hsr_backward*: dL_dcolor, dL_dopacity, dL_dsemantics NULL -> the geometry-only variant of render_bwd_q_kernel).  dL_dmeans3D and
     dL_dmeans2D must equal those of a full backward of the same render (to atomics-order noise) and the oracle's (1e-4)."""
     import torch
     from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic, _C

@@ -39,35 +39,19 @@ torch.cuda.synchronize()
 T = ((W + 15) // 16) * ((H + 15) // 16)
 n = min(T * 4, 16384) * 8
 buf = (C.c_ulonglong * n)()
-impl = os.environ.get("HSR_BWD_IMPL", "")
-sub = impl != "mfma"   # default backward: round 4's Q-panel kernel; HSR_BWD_IMPL=sub: round 3's butterfly kernel; mfma: the quadrant-list one
-qk = impl == ""
-rc = (_C._lib.hsr_debug_read_trace_q if qk else (_C._lib.hsr_debug_read_trace_sub if sub else _C._lib.hsr_debug_read_trace))(buf, n)
+rc = _C._lib.hsr_debug_read_trace_q(buf, n)
 a = np.frombuffer(buf, dtype=np.uint64).reshape(-1, 8).astype(np.float64)
 a = a[a[:, 0] > 0]
 tot = a[:, 0].mean()
-print("kernel:", ("render_bwd_q_kernel" if qk else "render_bwd_sub_kernel") if sub else "render_bwd_mfma_kernel", "K", K, "geo", GEO, " waves traced:", a.shape[0], "rc", rc)
-if sub:
-    names = ["total", "prologue", "stage+barriers", "loop(incl. flush)", "flush", "chunks", "wave iterations" if qk else "group visits", "chunk set-up (in loop)" if qk else "... with a pixel that accepts"]
-    for i, nm in enumerate(names):
-        print("%-18s mean %10.0f   p10 %10.0f   p90 %10.0f   max %10.0f" % (nm, a[:, i].mean(), np.percentile(a[:, i], 10), np.percentile(a[:, i], 90), a[:, i].max()))
-    print("fractions of wave time: prologue %.2f  stage %.2f  loop %.2f (of which flush + emission %.2f)" % (
-        a[:, 1].mean() / tot, a[:, 2].mean() / tot, a[:, 3].mean() / tot, a[:, 4].mean() / tot))
-    if qk:
-        print("per chunk: set-up %.0f, visits %.0f, flush + emission %.0f cycles ; stage-A evaluations per chunk: %.2f ; visit-loop cycles per stage-A evaluation: %.0f" % (
-            a[:, 7].sum() / a[:, 5].sum(), (a[:, 3] - a[:, 4] - a[:, 7]).sum() / a[:, 5].sum(), a[:, 4].sum() / a[:, 5].sum(), a[:, 6].sum() / a[:, 5].sum(),
-            (a[:, 3] - a[:, 4] - a[:, 7]).sum() / a[:, 6].sum()))
-    else:
-        print("flush + emission cycles per chunk: %.0f ; (16-lane group, splat) visits per chunk: %.1f ; fraction of them in which a pixel accepts the splat: %.3f" % (
-            a[:, 4].sum() / a[:, 5].sum(), a[:, 6].sum() / a[:, 5].sum(), a[:, 7].sum() / a[:, 6].sum()))
-else:
-    names = ["total", "prologue", "stage+barriers", "loop(no flush)", "flush", "emit", "visits", "accepted"]
-    for i, nm in enumerate(names):
-        print("%-16s mean %10.0f   p10 %10.0f   p90 %10.0f   max %10.0f" % (nm, a[:, i].mean(), np.percentile(a[:, i], 10), np.percentile(a[:, i], 90), a[:, i].max()))
-    print("fractions of wave time: prologue %.2f  stage %.2f  loop %.2f (of which flush %.2f, emit %.2f)" % (
-        a[:, 1].mean() / tot, a[:, 2].mean() / tot, a[:, 3].mean() / tot, a[:, 4].mean() / tot, a[:, 5].mean() / tot))
-    print("cycles per visit in loop (excl. flush): %.0f ; per accepted: %.0f ; flush cycles per 16 accepted: %.0f" % (
-        (a[:, 3] - a[:, 4]).sum() / a[:, 6].sum(), (a[:, 3] - a[:, 4]).sum() / a[:, 7].sum(), 16 * a[:, 4].sum() / a[:, 7].sum()))
+print("kernel: render_bwd_q_kernel", "K", K, "geo", GEO, " waves traced:", a.shape[0], "rc", rc)
+names = ["total", "prologue", "stage+barriers", "loop(incl. flush)", "flush", "chunks", "wave iterations", "chunk set-up (in loop)"]
+for i, nm in enumerate(names):
+    print("%-18s mean %10.0f   p10 %10.0f   p90 %10.0f   max %10.0f" % (nm, a[:, i].mean(), np.percentile(a[:, i], 10), np.percentile(a[:, i], 90), a[:, i].max()))
+print("fractions of wave time: prologue %.2f  stage %.2f  loop %.2f (of which flush + emission %.2f)" % (
+    a[:, 1].mean() / tot, a[:, 2].mean() / tot, a[:, 3].mean() / tot, a[:, 4].mean() / tot))
+print("per chunk: set-up %.0f, visits %.0f, flush + emission %.0f cycles ; stage-A evaluations per chunk: %.2f ; visit-loop cycles per stage-A evaluation: %.0f" % (
+    a[:, 7].sum() / a[:, 5].sum(), (a[:, 3] - a[:, 4] - a[:, 7]).sum() / a[:, 5].sum(), a[:, 4].sum() / a[:, 5].sum(), a[:, 6].sum() / a[:, 5].sum(),
+    (a[:, 3] - a[:, 4] - a[:, 7]).sum() / a[:, 6].sum()))
 # per-tile imbalance: max over the four quadrant waves vs their mean
 tiles = a.shape[0] // 4
 q = a[: tiles * 4, 3].reshape(tiles, 4)
