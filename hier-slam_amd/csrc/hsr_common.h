@@ -81,7 +81,7 @@ uint32_t hsr_sort_hist_entries(int R);
 void hsr_set_error(const char* fmt, ...);
 
 // Environment selectors the library reads, each once per process: HSR_BWD_IMPL=valu (the all-VALU backward) | legacy (accumulation
-// mode 2), HSR_BWD_WIDE_PASS=split and HSR_SORT_IMPL=radix|block|wave pick kernel families that give the same results
+// mode 2) and HSR_SORT_IMPL=radix pick paths the default itself takes for some inputs and that give the same results
 // (tests/test_gpu_golden_and_scale.py runs the parity cases under each); HSR_SEMANTIC_ALPHA=exact opts in to the semantic -> alpha term.
 
 #define HSR_HIP_CHECK(expr)                                                                     \

@@ -664,10 +664,10 @@ int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream)
     const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
     const int K = a.semantic ? a.K : 0;
     const bool cl = a.grow_layout == 1;
-    if (K == 0) {
-        if (cl) render_bwd_q_kernel<0, 208, false, true><<<grid, block, 0, stream>>>(a);
-        else render_bwd_q_kernel<0, 208, false, false><<<grid, block, 0, stream>>>(a);
-    } else if (K <= 11) {
+    // K = 0 always has compact rows: they are one line against two, and when P * 16 (the compact stride) reaches 2^30, P * 32 (the
+    // classic one) does too, so the caller runs the all-VALU kernel instead
+    if (K == 0) render_bwd_q_kernel<0, 208, false, true><<<grid, block, 0, stream>>>(a);
+    else if (K <= 11) {
         if (cl) render_bwd_q_kernel<11, 208, false, true><<<grid, block, 0, stream>>>(a);
         else render_bwd_q_kernel<11, 208, false, false><<<grid, block, 0, stream>>>(a);
     } else if (K == 16 && cl) render_bwd_q_kernel<16, 224, false, true><<<grid, block, 0, stream>>>(a);

@@ -24,8 +24,6 @@
 // K <= 27 and the geometry-only path take the Q-panel kernels of hsr_render_bwd_q.hip.
 #include "hsr_tile_common.h"
 #include "hsr_wave_reduce.h"
-#include <stdlib.h>
-#include <string.h>
 
 namespace {
 
@@ -98,12 +96,16 @@ __device__ __forceinline__ f32x4 mma_bf16(u32x4 a, u32x4 b, f32x4 c)
 // Wide trees (K > 27), in channel passes: semantic channels [c0, c0 + ns) of the image; the BASE
 // pass adds the five direct sums and the seven butterfly values, a SEM pass only re-derives alpha and T and feeds the panel.
 // 16 * NG >= ns + (BASE ? 5 : 0).
-// BF: the panel contraction runs on the bf16 matrix cores (split3_bf16): 24 registers of B operand per 16 columns instead of 16.
-template <int NG, bool BASE, int BATCH, bool BF>
-__global__ void __launch_bounds__(256, BF ? 2 : (NG <= 2 ? 4 : (NG <= 4 ? 3 : 2))) render_bwd_subw_kernel(RenderBwdArgs a, int c0, int ns)
+template <int NG, bool BASE>
+__global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_bwd_subw_kernel(RenderBwdArgs a, int c0, int ns)
 {
     static_assert(NG <= 7, "at most 112 channels per pass (the B operand lives in 16 * NG registers)");
-    static_assert(!BF || NG <= 5, "the split B operand of more than 80 columns does not fit the register file at two waves per SIMD");
+    // BF: the panel contraction runs on the bf16 matrix cores (split3_bf16): 24 registers of B operand per 16 columns instead of 16.
+    // Where it paid (500k Gaussians, bwd_render ms, fp32 -> split): 4 column groups 0.495 -> 0.486, 5 groups 0.606 -> 0.573 (1920x1080,
+    // 2M: 2.168 -> 2.058); 3 groups lose (0.407 -> 0.419: 24 B registers per group push the kernel from 3 waves per SIMD to 2); 2 groups
+    // (K <= 27) tie even at 3 waves; 6 and 7 groups do not fit the register file at two waves per SIMD.
+    constexpr bool BF = NG == 4 || NG == 5;
+    constexpr int BATCH = 224;   // splats staged per batch
     constexpr int STRIDE = BF ? 68 : SB_STRIDE;   // floats per panel row; 68: rows 16-byte aligned, b128 reads of 16 rows hit 64 banks
     static_assert(SB_SLOTS * STRIDE <= SB_PANEL, "panel");
     static_assert(BATCH <= 256, "batch slots are bytes");
@@ -428,25 +430,29 @@ __global__ void __launch_bounds__(256, BF ? 2 : (NG <= 2 ? 4 : (NG <= 4 ? 3 : 2)
     }
 }
 
+// Column groups of a pass: the BASE pass has 3..7 (K >= 28 channels, at most 107 of them, + the five direct sums), a SEM pass 1..4
+// (chunks of at most 64 channels).  Only those pairs are instantiated.
 template <bool BASE>
 void launch_subw_pass(const RenderBwdArgs& a, int c0, int ns, dim3 grid, hipStream_t stream)
 {
     const int groups = (ns + (BASE ? 5 : 0) + 15) / 16;
     const dim3 block(256);
-    // bf16 matrix cores on the exact three-way split where they paid (500k Gaussians, bwd_render ms, fp32 -> split):
-    // 4 column groups 0.495 -> 0.486, 5 groups 0.606 -> 0.573 (1920x1080, 2M: 2.168 -> 2.058); 3 groups lose (0.407 -> 0.419: 24 B
-    // registers per group push the kernel from 3 waves per SIMD to 2); 2 groups (K <= 27) tie even at 3 waves; 6 and 7 groups do not fit.
-    if (groups <= 1) render_bwd_subw_kernel<1, BASE, 224, false><<<grid, block, 0, stream>>>(a, c0, ns);
-    else if (groups == 2) render_bwd_subw_kernel<2, BASE, 224, false><<<grid, block, 0, stream>>>(a, c0, ns);
-    else if (groups == 3) render_bwd_subw_kernel<3, BASE, 224, false><<<grid, block, 0, stream>>>(a, c0, ns);
-    else if (groups == 4) render_bwd_subw_kernel<4, BASE, 224, true><<<grid, block, 0, stream>>>(a, c0, ns);
-    else if (groups == 5) render_bwd_subw_kernel<5, BASE, 224, true><<<grid, block, 0, stream>>>(a, c0, ns);
-    else if (groups == 6) render_bwd_subw_kernel<6, BASE, 224, false><<<grid, block, 0, stream>>>(a, c0, ns);
-    else render_bwd_subw_kernel<7, BASE, 224, false><<<grid, block, 0, stream>>>(a, c0, ns);
+    if constexpr (BASE) {
+        if (groups <= 3) render_bwd_subw_kernel<3, true><<<grid, block, 0, stream>>>(a, c0, ns);
+        else if (groups == 4) render_bwd_subw_kernel<4, true><<<grid, block, 0, stream>>>(a, c0, ns);
+        else if (groups == 5) render_bwd_subw_kernel<5, true><<<grid, block, 0, stream>>>(a, c0, ns);
+        else if (groups == 6) render_bwd_subw_kernel<6, true><<<grid, block, 0, stream>>>(a, c0, ns);
+        else render_bwd_subw_kernel<7, true><<<grid, block, 0, stream>>>(a, c0, ns);
+    } else {
+        if (groups <= 1) render_bwd_subw_kernel<1, false><<<grid, block, 0, stream>>>(a, c0, ns);
+        else if (groups == 2) render_bwd_subw_kernel<2, false><<<grid, block, 0, stream>>>(a, c0, ns);
+        else if (groups == 3) render_bwd_subw_kernel<3, false><<<grid, block, 0, stream>>>(a, c0, ns);
+        else render_bwd_subw_kernel<4, false><<<grid, block, 0, stream>>>(a, c0, ns);
+    }
 }
 }  // namespace
 
-// semantic variant with K > 27, packed mode, P * grow_stride < 2^30: BASE pass (59 channels + the base sums) + SEM passes of 64
+// semantic variant with K > 27, packed mode, P * grow_stride < 2^30: BASE pass (up to 107 channels + the base sums) + SEM passes of 64
 int hsr_launch_render_backward_subw(const RenderBwdArgs& a, hipStream_t stream)
 {
     const int tiles = ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
@@ -455,11 +461,9 @@ int hsr_launch_render_backward_subw(const RenderBwdArgs& a, hipStream_t stream)
     // One pass while the B operand (16 registers per 16 columns) fits two waves per SIMD: K + 5 <= 112 columns.  Every pass
     // re-derives alpha and T for every (pixel, splat) pair, and that — not the matrix-core work, which is the same in total —
     // is most of a pass: K = 74 in ONE pass of 80 columns at 2 waves per SIMD instead of 64 + 22 columns at 3 and 4.
-    static const char* e_pass = getenv("HSR_BWD_WIDE_PASS");   // kernel-family selector (parity-tested): "split" = 64-column passes
-    const bool split = e_pass && !strcmp(e_pass, "split");
     // (Other splits were measured too, on 500k Gaussians: every extra pass costs ~0.3-0.5 ms whatever its
     // width — K = 74: one pass 0.62 ms, 27 + 47 channels 0.89 ms, 43 + 31 0.82 ms; K = 102: 0.79 vs 1.16-1.34 ms.)
-    const int first = split ? (K < 59 ? K : 59) : (K < 107 ? K : 107);
+    const int first = K < 107 ? K : 107;
     const int chunk = 64;
     launch_subw_pass<true>(a, 0, first, grid, stream);
     for (int c0 = first; c0 < K; c0 += chunk) launch_subw_pass<false>(a, c0, K - c0 < chunk ? K - c0 : chunk, grid, stream);

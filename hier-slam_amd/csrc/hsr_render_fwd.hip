@@ -14,10 +14,11 @@
 //     batch (one splat per lane: its id two batches ahead, its 40-byte record and its 4K-byte feature
 //     row one batch ahead) are already in flight into registers, so the dependent
 //     point_list -> record global round trips hide behind compute instead of serialising the tile.
-//   * each wave owns an 8x8 quadrant and walks a compacted per-quadrant list built at staging time from
-//     the splats' alpha>=1/255 bounding boxes (hsr_tile_common.h), so splats that cannot touch the
-//     quadrant cost it nothing; of the survivors, one that no lane accepts costs only the alpha test
-//     (wave ballot).  A wave whose 64 pixels are all terminated stops blending but keeps staging.
+//   * each 16-lane group of a wave owns a 4x4 sub-block and walks a compacted per-sub-block list built at
+//     staging time from the splats' alpha>=1/255 regions (subblock_mask, hsr_tile_common.h), so splats that
+//     cannot touch the sub-block cost it nothing; the wave iterates to the longest of its four lists, and a
+//     visit that no lane accepts costs only the alpha test (wave ballot).  A wave whose 64 pixels are all
+//     terminated stops blending but keeps staging.
 //   * records are staged pre-scaled (log2(e) and the -0.5 folded into the conic) so alpha costs one
 //     v_exp_f32 and a handful of FMAs: the kernel is VALU-issue bound, not HBM bound.
 //   * K is a template parameter of the kernel but a run-time argument of the library: known tree
@@ -27,7 +28,7 @@
 
 #ifdef HSR_TRACE
 // Diagnostic build only (make -C hier-slam_amd/csrc trace -> libhsr_rast_trace.so, tools/trace_fwd.py): per-wave shader-cycle counts of
-// the phases of render_fwd_kernel (sub-block variant).  Never in the product.
+// the phases of render_fwd_kernel.  Never in the product.
 __device__ unsigned long long g_hsr_trace_fwd[16384 * 8];
 extern "C" int hsr_debug_read_trace_fwd(unsigned long long* host, int n)
 {
@@ -109,38 +110,31 @@ __device__ __forceinline__ void quad_fma_words(float (&s)[16], const float (&x)[
     }
 }
 
-#ifndef HSR_FWD_BATCH_48
-#define HSR_FWD_BATCH_48 152     // 33..48 channels, four workgroups per CU (4 x 40 720 B of LDS)
-#endif
-#ifndef HSR_FWD_BATCH_WIDE
-#define HSR_FWD_BATCH_WIDE 144   // 81..112 channels (PF), two workgroups per CU (the 128-channel instantiation fits 128)
-#endif
-template <int KC>
-struct FwdCfg {
-    // LDS per staged splat: 32 (x, y, A, B, C, opacity, r, g) + 4 * round4(KC + 2) (features, b, depth)
-    // 33..80 channels: as many entries per batch as three (four up to 48 channels) workgroups per CU leave room for — every batch costs
-    // two workgroup barriers, a list publication and a round of exposed latency (128 -> 144 entries, 152 up to 48 channels: K = 48
-    // 0.278 -> 0.263 ms, K = 64 0.366 -> 0.354, K = 74 0.364 -> 0.351, 1920x1080 / 2M / K = 74 1.260 -> 1.215); the 80-channel instantiation fits 136
-    static constexpr int BATCH = KC <= 32 ? 256 : (KC <= 48 ? HSR_FWD_BATCH_48 : (KC <= 64 ? 144 : (KC == 74 ? 144 : (KC <= 80 ? 136 : 64))));
-};
-
 // KC: semantic channels handled by this launch (0 = none).  BASE: also produce colour/depth/median/
 // opacity/final_T/n_contrib.  MASK: non-semantic variant, writes mask = sum(alpha*T).
 // ALIGNED: the launch covers whole feature rows of an even K (c0 == 0, KC == K): rows are 8-byte
 // aligned and are fetched as float2.
-// SUB: the 16-lane groups of a wave own 4x4 sub-blocks and walk their own lists (hsr_tile_common.h) instead of the wave's
-// quadrant list.
 // PF: the next batch's semantic rows are not parked in KC registers while the current batch is blended; one word per 64-byte
 // line of each row is TOUCHED instead (the loads land in a handful of registers and pull the lines into this XCD's L2), and the rows
 // are read for real — L2 hits — right before they are staged.  K = 74: 238 -> ~160 registers, i.e. three waves per SIMD instead of
 // two, in a kernel whose blend loop is bound by instruction issue.
-template <int KC, bool BASE, bool MASK, bool ALIGNED, bool SUB = false, bool PF = false>
-__global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : (PF ? (KC <= 48 ? 4 : (KC <= 80 ? 3 : 2)) : 1)) render_fwd_kernel(RenderFwdArgs a, int c0)
+template <int KC, bool BASE, bool MASK, bool ALIGNED, bool PF = false>
+__global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC <= 48 ? 4 : (KC <= 80 ? 3 : 2)) : 1)) render_fwd_kernel(RenderFwdArgs a, int c0)
 {
-    // SUB: 240 splats per batch keep the 16 lists + records of K = 26 under 40 KB (four workgroups per CU); K = 16 fits five (31 KB, 96
-    // registers: forward 0.147 -> 0.142 ms); K = 26 with touched rows + quad-shared rows at five: 0.177 vs 0.177 ms, not taken.  (PF at K = 26 with
-    // 184-splat batches and five waves per SIMD was measured too: 96 registers with 5 spills, 0.174 vs 0.165 ms — not taken.)
-    constexpr int BATCH = (SUB && KC <= 32) ? (KC > 26 ? 200 : 240) : ((PF && KC > 80) ? (KC <= 112 ? HSR_FWD_BATCH_WIDE : 128) : FwdCfg<KC>::BATCH);   // KC = 32: 200 x 176 B + lists < 40 KB; PF beyond 80 channels: two workgroups per CU, 128 x (32 + 4 KC + 8) B < 80 KB
+    // Splats per batch.  LDS per staged splat: 32 (x, y, A, B, C, opacity, r, g) + 4 * round4(KC + 2) (features, b, depth), plus the
+    // sixteen sub-block lists.  Every batch costs two workgroup barriers, a list publication and a round of exposed latency, so each
+    // width takes as many entries as its workgroups per CU leave room for:
+    //   * KC <= 26: 240 keep the lists + records of K = 26 under 40 KB (four workgroups per CU); K = 16 fits five (31 KB, 96 registers:
+    //     forward 0.147 -> 0.142 ms); K = 26 with touched rows + quad-shared rows at five: 0.177 vs 0.177 ms, not taken.  (PF at K = 26
+    //     with 184-splat batches and five waves per SIMD was measured too: 96 registers with 5 spills, 0.174 vs 0.165 ms — not taken.)
+    //   * KC = 32: 200 x 176 B + lists < 40 KB.
+    //   * 33..80 channels (PF): three workgroups per CU, four up to 48 channels (4 x 40 720 B of LDS); 128 -> 144 entries, 152 up to
+    //     48 channels: K = 48 0.278 -> 0.263 ms, K = 64 0.366 -> 0.354, K = 74 0.364 -> 0.351, 1920x1080 / 2M / K = 74 1.260 -> 1.215;
+    //     the 80-channel instantiation fits 136.
+    //   * beyond 80 channels (PF): two workgroups per CU, 144 up to 112 channels, 128 x (32 + 4 KC + 8) B < 80 KB at 128.
+    constexpr int BATCH = KC <= 32 ? (KC > 26 ? 200 : 240)
+                                   : (KC <= 48 ? 152 : ((KC <= 64 || KC == 74) ? 144 : (KC <= 80 ? 136 : (KC <= 112 ? 144 : 128))));
+    static_assert(KC <= 32 || PF, "batch sizes beyond 32 channels assume the touched rows (PF)");
     // per staged splat: a 32-byte record { x, y, A, B | C, opacity, r, g } (pre-scaled conic, see hsr_tile_common.h) — all the
     // alpha test needs, in two 16-byte reads at one address — and a feature row { s0 .. s(KC-1), b, depth } whose 16-byte reads
     // pair up with the packed FMAs (blue and depth ride in the row's padding at K = 26): one LDS read and one address
@@ -154,14 +148,12 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
     // take the value from the quad lane that holds it through their DPP operand (quad_perm: no extra instruction, no LDS).
     // Taken where it pays (tools/sweep.sh, 500k Gaussians): the wide per-lane kernels (PF: K = 74 0.393 -> 0.363 ms, 1920x1080 / 2M
     // 1.313 -> 1.257 ms); at K = 16 / 26 the 2 K single FMAs against K packed ones cancel the LDS saving (0.144 -> 0.158, 0.175 -> 0.176).
-    constexpr bool QS = SUB && PF && KC > 0;
+    constexpr bool QS = PF && KC > 0;
     constexpr int NGF = QS ? RW / 16 : 0;            // full 16-channel groups
     constexpr int REM = QS ? (RW % 16) / 4 : 0;      // words per lane of the partial group
     __shared__ float4 s_rec[BATCH * 2];
     __shared__ float4 s_row[BATCH * (RW / 4)];
-    __shared__ uint8_t s_list[SUB ? 1 : 4][256];
-    __shared__ uint8_t s_lcnt[4][4];
-    __shared__ uint8_t s_sublist[SUB ? 16 * HSR_SUB_LSTRIDE : 4];
+    __shared__ uint8_t s_sublist[16 * HSR_SUB_LSTRIDE];
     __shared__ uint8_t s_subcnt[4][16];
     __shared__ int s_wdone[4];
 
@@ -177,7 +169,7 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
         a.point_list = bs.vals;
         a.masks = bs.vals_unsorted;
     }
-    const TileGeom tg = SUB ? tile_geom_sub(tile, a.W, a.H, t) : tile_geom(tile, a.W, a.H, t);
+    const TileGeom tg = tile_geom_sub(tile, a.W, a.H, t);
     const bool inside = tg.inside;
     const size_t N = (size_t)a.W * a.H;
     // the pixel's coordinates live as FLOATS through the blend loop (opaque to the compiler, which would otherwise keep the
@@ -291,10 +283,9 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
         (void)ts0;
         if (s_wdone[0] & s_wdone[1] & s_wdone[2] & s_wdone[3]) break;
         const int cnt = min(BATCH, n - start);
-        uint32_t qmask = 0u;
+        uint32_t mask16 = 0u;
         if (t < cnt) {
-            const uint32_t mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0);
-            qmask = SUB ? mask16 : quadrant_bits(mask16);
+            mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0);
             a.masks[range.x + start + t] = mask16;   // the backward stages the same entries: it reads the mask instead of deriving it again
             s_rec[2 * t] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);
             s_rec[2 * t + 1] = make_float4((-0.5f * HSR_LOG2E) * p_co.z, p_co.w, p_r, p_g);
@@ -310,7 +301,7 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
                 // splats whose alpha never reaches 1/255 on this tile) needs no row — except slot 0, which a group with an EMPTY list
                 // reads with weight 0 (below): an unstaged row is whatever the LDS held (the per-tile sort pads with ~0 = NaN, and
                 // NaN * 0 is NaN: found by a 300-case run of tests/test_gpu_fuzz.py)
-                if (qmask != 0u || t == 0)
+                if (mask16 != 0u || t == 0)
 #pragma unroll
                 for (int g0 = 0; g0 < RW; g0 += 32) {
                     float rv[32];
@@ -360,8 +351,7 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
         }
         const long long tp0 = TRF_NOW();
         (void)tp0;
-        if (SUB) publish_subblock_lists(qmask, t, s_sublist, s_subcnt);
-        else publish_quadrant_lists(qmask, t, s_list, s_lcnt);
+        publish_subblock_lists(mask16, t, s_sublist, s_subcnt);
         TRF_ADD(tr_pub, tp0);
         TRF_ADD(tr_stage, ts0);
         const long long tb1 = TRF_NOW();
@@ -378,90 +368,86 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
         }
         if (wave_done) continue;
 
-        if constexpr (SUB) {
-            // four lists per wave, one per 16-lane group; the wave iterates to the longest of them
-            const int lane = t & 63, sb = wv * 4 + (lane >> 4);
-            const int total = flatten_sublist(sb, lane, s_sublist, s_subcnt);
-            const int m = __builtin_amdgcn_readfirstlane(max(max(__builtin_amdgcn_readlane(total, 0), __builtin_amdgcn_readlane(total, 16)),
-                                                             max(__builtin_amdgcn_readlane(total, 32), __builtin_amdgcn_readlane(total, 48))));
-            const uint8_t* list = s_sublist + sb * HSR_SUB_LSTRIDE;
-            // a group past the end of its list keeps re-reading its last entry, with weight 0 (an empty list is given the always
-            // staged slot 0 as its only entry): an unconditional clamped read instead of a masked one
-            if (total == 0 && (lane & 15) == 0) s_sublist[sb * HSR_SUB_LSTRIDE] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int last = max(total - 1, 0);
-            if constexpr (QS) {
-                constexpr int NW = 4 * NGF + REM;
-                constexpr int NCH = KC + (BASE ? 2 : 0);   // channels that are accumulated: features, then blue, depth
-                int j_next = (int)list[0];
-                for (int k = 0; k < m; k++) {
-                    const int j = j_next;
-                    const bool valid = k < total;
-                    j_next = (int)list[min(k + 1, last)];
-                    const float4 g = s_rec[2 * j];
-                    const float4 h4 = s_rec[2 * j + 1];
-                    const float2 co = make_float2(h4.x, h4.y);
-                    const float dx = g.x - pfx, dy = g.y - pfy;
-                    const float power2 = fmaf(co.x, dy * dy, fmaf(g.w, dx * dy, g.z * (dx * dx)));
-                    const float alpha = fminf(0.99f, co.y * __builtin_amdgcn_exp2f(power2));
-                    bool contrib = valid && !done && power2 <= 0.0f && alpha >= 1.0f / 255.0f;
-                    const float test_T = T * (1.0f - alpha);
-                    if (contrib && test_T < 0.0001f) {
-                        done = true;
-                        contrib = false;
-                    }
-                    if (__ballot(contrib) == 0ull) continue;
-                    const float w = contrib ? alpha * T : 0.f;
-                    if (BASE) {
-                        C0 = fmaf(h4.z, w, C0);
-                        C1 = fmaf(h4.w, w, C1);
-                        if (MASK) Mm += w;
-                    }
-                    const float* rowf = reinterpret_cast<const float*>(s_row) + j * RW;
-                    float fq[NW];
-#pragma unroll
-                    for (int G = 0; G < NGF; G++) {
-                        const float4 f = *reinterpret_cast<const float4*>(rowf + 16 * G + 4 * (lane & 3));
-                        fq[4 * G] = f.x; fq[4 * G + 1] = f.y; fq[4 * G + 2] = f.z; fq[4 * G + 3] = f.w;
-                    }
-#pragma unroll
-                    for (int mm = 0; mm < REM; mm++) fq[4 * NGF + mm] = rowf[16 * NGF + 4 * mm + (lane & 3)];
-                    // word r (either layout) holds channels 4r .. 4r+3, channel c in quad lane c % 4; one asm block per 16 channels
-                    float dummy = 0.f;
-                    auto acc = [&](int c) -> float& { return c < KC ? S[c < KC ? c : 0] : ((BASE && c == KC) ? C2 : ((BASE && c == KC + 1) ? Dd : dummy)); };
-#pragma unroll
-                    for (int b = 0; b < (NCH + 15) / 16; b++) {
-                        const int nw = min(4, (NCH - 16 * b + 3) / 4);   // words of this block: constant after unrolling
-                        float sv[16], xv[4];
-#pragma unroll
-                        for (int i = 0; i < 16; i++) sv[i] = i < 4 * nw ? acc(16 * b + i) : 0.f;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) xv[i] = i < nw ? fq[4 * b + i] : 0.f;
-                        if (nw == 4) quad_fma_words<4>(sv, xv, w);
-                        else if (nw == 3) quad_fma_words<3>(sv, xv, w);
-                        else if (nw == 2) quad_fma_words<2>(sv, xv, w);
-                        else quad_fma_words<1>(sv, xv, w);
-#pragma unroll
-                        for (int i = 0; i < 16; i++)
-                            if (i < 4 * nw && 16 * b + i < NCH) acc(16 * b + i) = sv[i];
-                    }
-                    if (BASE) {
-                        if (contrib && T > 0.5f && test_T < 0.5f) median_at = (uint32_t)(start + j + 1);   // its depth: epilogue
-                    }
-                    if (contrib) {
-                        T = test_T;
-                        last_contributor = (uint32_t)(start + j + 1);
-                    }
-#ifdef HSR_TRACE
-                    tr_iters++;
-#endif
+        // four lists per wave, one per 16-lane group; the wave iterates to the longest of them
+        const int lane = t & 63, sb = wv * 4 + (lane >> 4);
+        const int total = flatten_sublist(sb, lane, s_sublist, s_subcnt);
+        const int m = __builtin_amdgcn_readfirstlane(max(max(__builtin_amdgcn_readlane(total, 0), __builtin_amdgcn_readlane(total, 16)),
+                                                         max(__builtin_amdgcn_readlane(total, 32), __builtin_amdgcn_readlane(total, 48))));
+        const uint8_t* list = s_sublist + sb * HSR_SUB_LSTRIDE;
+        // a group past the end of its list keeps re-reading its last entry, with weight 0 (an empty list is given the always
+        // staged slot 0 as its only entry): an unconditional clamped read instead of a masked one
+        if (total == 0 && (lane & 15) == 0) s_sublist[sb * HSR_SUB_LSTRIDE] = 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int last = max(total - 1, 0);
+        if constexpr (QS) {
+            constexpr int NW = 4 * NGF + REM;
+            constexpr int NCH = KC + (BASE ? 2 : 0);   // channels that are accumulated: features, then blue, depth
+            int j_next = (int)list[0];
+            for (int k = 0; k < m; k++) {
+                const int j = j_next;
+                const bool valid = k < total;
+                j_next = (int)list[min(k + 1, last)];
+                const float4 g = s_rec[2 * j];
+                const float4 h4 = s_rec[2 * j + 1];
+                const float2 co = make_float2(h4.x, h4.y);
+                const float dx = g.x - pfx, dy = g.y - pfy;
+                const float power2 = fmaf(co.x, dy * dy, fmaf(g.w, dx * dy, g.z * (dx * dx)));
+                const float alpha = fminf(0.99f, co.y * __builtin_amdgcn_exp2f(power2));
+                bool contrib = valid && !done && power2 <= 0.0f && alpha >= 1.0f / 255.0f;
+                const float test_T = T * (1.0f - alpha);
+                if (contrib && test_T < 0.0001f) {
+                    done = true;
+                    contrib = false;
                 }
-                TRF_ADD(tr_blend, tl0);
-                resolve_median(start);
-                continue;
+                if (__ballot(contrib) == 0ull) continue;
+                const float w = contrib ? alpha * T : 0.f;
+                if (BASE) {
+                    C0 = fmaf(h4.z, w, C0);
+                    C1 = fmaf(h4.w, w, C1);
+                    if (MASK) Mm += w;
+                }
+                const float* rowf = reinterpret_cast<const float*>(s_row) + j * RW;
+                float fq[NW];
+#pragma unroll
+                for (int G = 0; G < NGF; G++) {
+                    const float4 f = *reinterpret_cast<const float4*>(rowf + 16 * G + 4 * (lane & 3));
+                    fq[4 * G] = f.x; fq[4 * G + 1] = f.y; fq[4 * G + 2] = f.z; fq[4 * G + 3] = f.w;
+                }
+#pragma unroll
+                for (int mm = 0; mm < REM; mm++) fq[4 * NGF + mm] = rowf[16 * NGF + 4 * mm + (lane & 3)];
+                // word r (either layout) holds channels 4r .. 4r+3, channel c in quad lane c % 4; one asm block per 16 channels
+                float dummy = 0.f;
+                auto acc = [&](int c) -> float& { return c < KC ? S[c < KC ? c : 0] : ((BASE && c == KC) ? C2 : ((BASE && c == KC + 1) ? Dd : dummy)); };
+#pragma unroll
+                for (int b = 0; b < (NCH + 15) / 16; b++) {
+                    const int nw = min(4, (NCH - 16 * b + 3) / 4);   // words of this block: constant after unrolling
+                    float sv[16], xv[4];
+#pragma unroll
+                    for (int i = 0; i < 16; i++) sv[i] = i < 4 * nw ? acc(16 * b + i) : 0.f;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) xv[i] = i < nw ? fq[4 * b + i] : 0.f;
+                    if (nw == 4) quad_fma_words<4>(sv, xv, w);
+                    else if (nw == 3) quad_fma_words<3>(sv, xv, w);
+                    else if (nw == 2) quad_fma_words<2>(sv, xv, w);
+                    else quad_fma_words<1>(sv, xv, w);
+#pragma unroll
+                    for (int i = 0; i < 16; i++)
+                        if (i < 4 * nw && 16 * b + i < NCH) acc(16 * b + i) = sv[i];
+                }
+                if (BASE) {
+                    if (contrib && T > 0.5f && test_T < 0.5f) median_at = (uint32_t)(start + j + 1);   // its depth: epilogue
+                }
+                if (contrib) {
+                    T = test_T;
+                    last_contributor = (uint32_t)(start + j + 1);
+                }
+#ifdef HSR_TRACE
+                tr_iters++;
+#endif
             }
+        } else {
             int j_next = (int)list[0];
             for (int k = 0; k < m; k++) {
                 const int j = j_next;
@@ -512,62 +498,10 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
                 tr_iters++;
 #endif
             }
-            TRF_ADD(tr_blend, tl0);
-            resolve_median(start);
-            continue;
         }
-
-        // this wave's compacted list: four segments (one per staging wave), slot order preserved
-        for (int seg = 0; seg < 4; seg++) {
-            const int m = s_lcnt[wv][seg];
-            int j_next = s_list[wv][seg * 64];
-            for (int k = 0; k < m; k++) {
-                const int j = j_next;   // slot fetched one iteration ahead (slot -> record are dependent LDS round trips)
-                j_next = s_list[wv][seg * 64 + min(k + 1, 63)];
-                const float4 g = s_rec[2 * j];
-                const float4 h4 = s_rec[2 * j + 1];
-                const float2 co = make_float2(h4.x, h4.y);
-                const float dx = g.x - pfx, dy = g.y - pfy;
-                const float power2 = fmaf(co.x, dy * dy, fmaf(g.w, dx * dy, g.z * (dx * dx)));  // log2(G)
-                const float alpha = fminf(0.99f, co.y * __builtin_amdgcn_exp2f(power2));
-                bool contrib = !done && power2 <= 0.0f && alpha >= 1.0f / 255.0f;
-                const float test_T = T * (1.0f - alpha);
-                if (contrib && test_T < 0.0001f) {
-                    done = true;
-                    contrib = false;
-                }
-                if (__ballot(contrib) == 0ull) continue;
-                const float w = contrib ? alpha * T : 0.f;
-                if (BASE) {
-                    C0 = fmaf(h4.z, w, C0);
-                    C1 = fmaf(h4.w, w, C1);
-                    if (MASK) Mm += w;
-                }
-                {
-                    const float4* row = &s_row[j * (RW / 4)];
-#pragma unroll
-                    for (int q = 0; q < RW / 4; q++) {
-                        const float4 f = row[q];
-                        const float fv[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            const int c = 4 * q + i;
-                            if (c < KC) S[c < KC ? c : 0] = fmaf(fv[i], w, S[c < KC ? c : 0]);
-                            else if (BASE && c == KC) C2 = fmaf(fv[i], w, C2);
-                            else if (BASE && c == KC + 1) {
-                                Dd = fmaf(fv[i], w, Dd);
-                                if (contrib && T > 0.5f && test_T < 0.5f) median_at = (uint32_t)(start + j + 1);   // its depth: epilogue
-                            }
-                        }
-                    }
-                }
-                if (contrib) {
-                    T = test_T;
-                    last_contributor = (uint32_t)(start + j + 1);
-                }
-            }
-        }
+        TRF_ADD(tr_blend, tl0);
         resolve_median(start);
+        continue;   // not redundant: without it hipcc lays the batch loop out differently (16 more instructions in the kernels without PF)
     }
 
     if (PF && pf_sink == 1.2345678e-30f) T = pf_sink;   // never true for data that matters; keeps the touch loads alive
@@ -595,7 +529,7 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
         }
     }
 #ifdef HSR_TRACE
-    if ((t & 63) == 0 && SUB) {
+    if ((t & 63) == 0) {
         const int wid = tile * 4 + wv;
         if (wid < 16384) {
             unsigned long long* o = g_hsr_trace_fwd + (size_t)wid * 8;
@@ -615,12 +549,12 @@ __global__ void __launch_bounds__(256, (SUB && KC <= 26) ? (KC == 16 ? 5 : 4) : 
 int hsr_launch_render_forward(const RenderFwdArgs& a, hipStream_t stream)
 {
     const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
-    // Default for K <= 28: the per-lane kernel on 4x4 sub-block lists (SUB).  Measured at the headline workload (500k
+    // Every K: the per-lane kernel on 4x4 sub-block lists.  Measured at the headline workload (500k
     // Gaussians, 1200x680, K = 26): 0.18 ms against 0.22 ms for the same kernel on quadrant lists and 0.27 ms for round 1's
     // pair-pipelined matrix-core kernel (EXPERIMENTS.md §4: the ~25 VALU instructions that evaluate alpha per list entry dominate, the
     // matrix cores only take the 15 packed FMAs behind them, and every list entry has to go through the pair).
     if (!a.semantic) {
-        render_fwd_kernel<0, true, true, false, true><<<grid, block, 0, stream>>>(a, 0);
+        render_fwd_kernel<0, true, true, false><<<grid, block, 0, stream>>>(a, 0);
         return HSR_OK;
     }
     // Wide trees.  Round 1 accumulated 29 <= K <= 124 on the matrix cores.  Since round 2 the per-lane kernel on sub-block lists takes
@@ -630,24 +564,24 @@ int hsr_launch_render_forward(const RenderFwdArgs& a, hipStream_t stream)
     // (K = 74 and K = 102 — the reference's large ScanNet tree and its flat Replica label set — have instantiations of their exact width
     // below: rows fetched as aligned float2, no padding channels: K = 74 0.371 vs 0.430 ms through the 80-channel kernel)
     if (a.K >= 27 && a.K <= 128 && a.K != 74 && a.K != 102) {
-        if (a.K <= 32) render_fwd_kernel<32, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-        else if (a.K <= 48) render_fwd_kernel<48, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-        else if (a.K <= 64) render_fwd_kernel<64, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-        else if (a.K <= 80) render_fwd_kernel<80, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-        else if (a.K <= 96) render_fwd_kernel<96, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-        else if (a.K <= 112) render_fwd_kernel<112, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
-        else render_fwd_kernel<128, true, false, false, true, true><<<grid, block, 0, stream>>>(a, 0);
+        if (a.K <= 32) render_fwd_kernel<32, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        else if (a.K <= 48) render_fwd_kernel<48, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        else if (a.K <= 64) render_fwd_kernel<64, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        else if (a.K <= 80) render_fwd_kernel<80, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        else if (a.K <= 96) render_fwd_kernel<96, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        else if (a.K <= 112) render_fwd_kernel<112, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
+        else render_fwd_kernel<128, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
         return HSR_OK;
     }
     switch (a.K) {
-    case 0: render_fwd_kernel<0, true, false, false, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;
-    case 16: render_fwd_kernel<16, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // ScanNet tree
-    case 26: render_fwd_kernel<26, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica tree
-    case 74: render_fwd_kernel<74, true, false, true, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;     // ScanNet large tree
-    case 102: render_fwd_kernel<102, true, false, true, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica flat label set
+    case 0: render_fwd_kernel<0, true, false, false><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;
+    case 16: render_fwd_kernel<16, true, false, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // ScanNet tree
+    case 26: render_fwd_kernel<26, true, false, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica tree
+    case 74: render_fwd_kernel<74, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;     // ScanNet large tree
+    case 102: render_fwd_kernel<102, true, false, true, true><<<grid, block, 0, stream>>>(a, 0); return HSR_OK;   // Replica flat label set
     default:   // K <= 26 or K > 128: 32-channel chunks; the first chunk also produces the base outputs
-        render_fwd_kernel<32, true, false, false, true><<<grid, block, 0, stream>>>(a, 0);
-        for (int c0 = 32; c0 < a.K; c0 += 32) render_fwd_kernel<32, false, false, false, true><<<grid, block, 0, stream>>>(a, c0);
+        render_fwd_kernel<32, true, false, false><<<grid, block, 0, stream>>>(a, 0);
+        for (int c0 = 32; c0 < a.K; c0 += 32) render_fwd_kernel<32, false, false, false><<<grid, block, 0, stream>>>(a, c0);
         return HSR_OK;
     }
 }

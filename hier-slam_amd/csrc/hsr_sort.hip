@@ -16,9 +16,6 @@
 //               (64-bit masks, v_cmp + s_and), the rank among them is a popcount of the lower-lane
 //               mask, and per-wave running digit counters live in LDS.  Order (wave, round, lane) =
 //               input order, so the scatter is stable.
-#include <stdlib.h>
-#include <string.h>
-
 #include "hsr_common.h"
 
 namespace {
@@ -162,13 +159,13 @@ uint32_t hsr_sort_hist_entries(int R) { return hsr_sort_hist_entries_inline((uin
 // After the tile passes every tile's entries are contiguous and still in emission order (ascending Gaussian
 // index).  A stable sort on depth inside the tile then equals the reference's stable 64-bit sort; since
 // (depth, index) pairs are unique inside a tile, sorting the composite key (depth << 32) | index with ANY
-// network gives exactly that order.  One workgroup per tile:
-//   n <= TS_MAX : bitonic network on composite keys in LDS (padding = +inf keys);
+// network gives exactly that order.  One workgroup per tile (block_sort_tile):
+//   n <= TS_MAX : bitonic network on composite keys (padding = +inf keys): in LDS for segments in emission order, in registers
+//                 for the composites of direct binning (tile_sort_pair_kernel sorts those of at most TP_MAX entries);
 //   n  > TS_MAX : block-local stable LSD radix on the 32 depth bits — preceded by the Gaussian-index bytes when the
 //                 segment does not arrive in emission order (direct binning) — ping-ponging inside the tile's own
 //                 segment of the two global buffer pairs (segments of different tiles are disjoint).
 constexpr int TS_MAX = 2048;
-constexpr int TW_MAX = 1024;   // tiles of at most this many entries: one wave each, elements in registers (tile_sort_wave_kernel)
 
 __device__ __forceinline__ void ts_block_radix(uint64_t* ka, uint32_t* va, uint64_t* kb, uint32_t* vb, int r0, int n,
                                                uint32_t* hist /*[256]*/, uint32_t (*wcnt)[256], int gid_passes)
@@ -248,7 +245,7 @@ __device__ __forceinline__ void ts_block_radix(uint64_t* ka, uint32_t* va, uint6
 }
 
 // ---- per-tile sort, TWO waves per tile (round 3) ----
-// At the headline workload every one of the 3 225 tiles holds 263..448 entries: tile_sort_wave_kernel gives each to ONE wave with 8
+// At the headline workload every one of the 3 225 tiles holds 263..448 entries: round 2 gave each to ONE wave with 8
 // elements per lane, and the launch — 3.15 waves per SIMD, all resident, every wave running the same 45-step network at a third of the
 // SIMD's issue rate with a dependent LDS round trip in 21 of the steps — lasts as long as one wave does (27.8 us; waves average 19 us of
 // life, profiles/r02_h_final.json).  Two waves per tile halve the elements per lane (E = 4 for 257..512 entries: 128 lanes x 4), so every
@@ -256,8 +253,8 @@ __device__ __forceinline__ void ts_block_radix(uint64_t* ka, uint32_t* va, uint6
 // a step with stride j >= E exchanges with thread tid128 ^ (j / E): inside the wave for j / E < 64 (wave-level fence), and across the two
 // waves for exactly ONE step of the whole network (k = N, j = N / 2), bracketed by two workgroup barriers (partner's stores visible;
 // partner's loads done before the next step overwrites the slots).  Two pairs = two tiles per 256-thread workgroup; every pair
-// passes exactly those two barriers whatever its tile holds.  16 KB of exchange buffers: all 1 613 workgroups of the headline resident.  Tiles above TP_MAX entries are left to the whole workgroup afterwards (block_sort_tile), as in
-// tile_sort_wave_kernel.
+// passes exactly those two barriers whatever its tile holds.  16 KB of exchange buffers: all 1 613 workgroups of the headline resident.
+// Tiles above TP_MAX entries are left to the whole workgroup afterwards (block_sort_tile).
 constexpr int TP_MAX = 1024;   // E = 8
 constexpr int TQ_MAX = 2048;   // four waves, E = 8: tiles of 1025..2048 entries (block_sort_tile)
 
@@ -341,7 +338,8 @@ __device__ __forceinline__ void block_sort_tile(int tile, const uint2* __restric
         ts_block_radix(keys, vals, keys_alt, vals_alt, r0, n, hist, wcnt, gid_passes);  // ends in (keys, vals)
         return;
     }
-    if (composite_in && n > TP_MAX) {
+    if (composite_in) {
+        // composites reach this point only above TP_MAX entries (the smaller tiles are tile_sort_pair_kernel's)
         // 1025..2048 composites (every tile of the 2M-Gaussian workload at 1200x680): eight per thread in registers, the four waves
         // exchange through LDS in 3 of the 66 steps — instead of the LDS network below (16 bytes read and written per compare-exchange,
         // a workgroup barrier at every stride >= 128: 0.141 ms of that workload's 1.86 ms step)
@@ -365,9 +363,10 @@ __device__ __forceinline__ void block_sort_tile(int tile, const uint2* __restric
     }
     int N = 64;
     while (N < n) N <<= 1;
-    const uint64_t tile_hi = composite_in ? my_tile_hi : (keys[r0] & 0xFFFFFFFF00000000ull);
+    // emission-order segment: keys[] holds (tile << 32) | depth bits, vals[] the index
+    const uint64_t tile_hi = keys[r0] & 0xFFFFFFFF00000000ull;
     for (int i = t; i < N; i += 256)
-        comp[i] = i < n ? (composite_in ? keys[r0 + i] : (((keys[r0 + i] & 0xFFFFFFFFull) << 32) | (uint64_t)vals[r0 + i])) : ~0ull;
+        comp[i] = i < n ? (((keys[r0 + i] & 0xFFFFFFFFull) << 32) | (uint64_t)vals[r0 + i]) : ~0ull;
     __syncthreads();
     // Bitonic network.  Thread t does compare-exchange i = t (+256 m) of a step; for strides j <= 64 the 64 exchanges of a wave
     // stay inside the wave's own 128 elements, and LDS operations of one wave complete in order, so consecutive steps with
@@ -410,134 +409,12 @@ __global__ void __launch_bounds__(256) tile_sort_kernel(const uint2* __restrict_
     __shared__ uint64_t comp[TS_MAX];
     __shared__ uint32_t hist[256];
     __shared__ uint32_t wcnt[4][256];
-    if (composite_in == 2) {   // direct binning, tiles of at most TW_MAX entries belong to tile_sort_wave_kernel
+    if (composite_in == 2) {   // direct binning, tiles of at most TP_MAX entries belong to tile_sort_pair_kernel
         const uint2 rg = ranges[blockIdx.x];
-        if (rg.y - rg.x <= (uint32_t)TW_MAX) return;
+        if (rg.y - rg.x <= (uint32_t)TP_MAX) return;
         composite_in = 1;
     }
     block_sort_tile((int)blockIdx.x, ranges, keys, vals, keys_alt, vals_alt, gid_passes, composite_in, comp, hist, wcnt);
-}
-
-// ---- per-tile sort, one WAVE per tile, for tiles of at most 1024 entries (direct binning composites) ----
-// The block-wide network above is LDS-bound: every compare-exchange is two 8-byte reads and up to two writes with 2- to
-// 8-way bank conflicts at small strides, 45 steps for a 512-entry tile.  Here a lane keeps E = 2, 4 or 8 CONSECUTIVE
-// elements in registers (N = 64 E): the steps with stride j < E — more than half of them — are register-only, and a step
-// with j >= E exchanges whole E-element blocks with lane ^ (j / E) through a conflict-free LDS buffer (16-byte accesses,
-// lanes contiguous) and keeps the smaller or the larger element of every pair.  One wave, so no barriers at all; four
-// tiles per 256-thread workgroup.  Tiles above TW_MAX entries are left to tile_sort_kernel (which skips the others).
-// E = 16 (513..1024 entries, 32 key registers) came late in round 2: on the anisotropic and the 1920x1080 / 2M workloads most tiles
-// hold 500-1000 entries and the block-wide LDS network took 65 / 131 us per frame for them (tools/ktrace_cfg.sh).
-
-template <int E>
-__device__ __forceinline__ void wave_bitonic(uint64_t (&x)[E], int lane, ulonglong2* buf)
-{
-    constexpr int N = 64 * E;
-#pragma unroll
-    for (int k = 2; k <= N; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j < E) {
-                // both partners in this lane's registers
-#pragma unroll
-                for (int r = 0; r < E; r++) {
-                    if ((r & j) == 0) {
-                        const bool up = k < E ? ((r & k) == 0) : (((E * lane) & k) == 0);
-                        const uint64_t a = x[r], b = x[r + j];
-                        const bool sw = (a > b) == up;
-                        x[r] = sw ? b : a;
-                        x[r + j] = sw ? a : b;
-                    }
-                }
-            } else {
-                const int m = j / E;   // partner lane = lane ^ m holds the partner of every one of my elements
-#pragma unroll
-                for (int q = 0; q < E / 2; q++) buf[q * 64 + lane] = make_ulonglong2(x[2 * q], x[2 * q + 1]);
-                // the reads below are of OTHER lanes' stores: per thread the addresses provably differ, so without a
-                // wavefront-scope release/acquire pair the compiler is free to hoist them above the stores
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const bool keep_min = ((lane & m) == 0) == (((E * lane) & k) == 0);
-#pragma unroll
-                for (int q = 0; q < E / 2; q++) {
-                    const ulonglong2 y = buf[q * 64 + (lane ^ m)];
-                    const uint64_t a0 = x[2 * q], a1 = x[2 * q + 1];
-                    x[2 * q] = keep_min ? (a0 < y.x ? a0 : y.x) : (a0 > y.x ? a0 : y.x);
-                    x[2 * q + 1] = keep_min ? (a1 < y.y ? a1 : y.y) : (a1 > y.y ? a1 : y.y);
-                }
-                // ... and the next exchange's stores must stay behind these loads
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            }
-        }
-    }
-}
-
-template <int E>
-__device__ __forceinline__ void wave_sort_tile(int r0, int n, int lane, uint64_t tile_hi, uint64_t* __restrict__ keys,
-                                               uint32_t* __restrict__ vals, ulonglong2* buf)
-{
-    uint64_t x[E];
-#pragma unroll
-    for (int r = 0; r < E; r++) {
-        const int e = E * lane + r;
-        x[r] = e < n ? keys[r0 + e] : ~0ull;
-    }
-    wave_bitonic<E>(x, lane, buf);
-#pragma unroll
-    for (int r = 0; r < E; r++) {
-        const int e = E * lane + r;
-        if (e < n) {
-            keys[r0 + e] = tile_hi | (x[r] >> 32);
-            vals[r0 + e] = (uint32_t)x[r];
-        }
-    }
-}
-
-// Four tiles per workgroup: each wave sorts its tile if it has at most TW_MAX entries; the larger ones of the four are then
-// sorted one after the other by the whole workgroup (block_sort_tile) in the same launch.
-__global__ void __launch_bounds__(256) tile_sort_wave_kernel(int T, const uint2* __restrict__ ranges, uint64_t* __restrict__ keys,
-                                                             uint32_t* __restrict__ vals, uint64_t* __restrict__ keys_alt,
-                                                             uint32_t* __restrict__ vals_alt, int gid_passes, int big_too, BinDevRef ref)
-{
-    // wave phase: per wave E/2 <= 8 rows of 64 x 16 bytes; workgroup phase: comp[TS_MAX], hist[256], wcnt[4][256]
-    constexpr int RAW_WG = TS_MAX * 8 + 256 * 4 + 4 * 256 * 4, RAW_WV = 4 * 8 * 64 * 16;
-    constexpr int RAW = RAW_WG > RAW_WV ? RAW_WG : RAW_WV;
-    __shared__ __attribute__((aligned(16))) unsigned char s_raw[RAW];
-    __shared__ int s_big[4];
-    if (ref.base) {   // speculative forward: the arrays live where num_rendered says
-        BinState bs;
-        if (!hsr_bin_resolve(ref, *ref.R_dev, &bs)) return;
-        keys = bs.keys; vals = bs.vals; keys_alt = bs.keys_unsorted; vals_alt = bs.vals_unsorted;
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int tile = blockIdx.x * 4 + wv;
-    int n = 0, r0 = 0;
-    if (tile < T) {
-        const uint2 rg = ranges[tile];
-        r0 = (int)rg.x;
-        n = (int)(rg.y - rg.x);
-    }
-    if (lane == 0) s_big[wv] = n > TW_MAX;
-    if (n > 0 && n <= TW_MAX) {
-        ulonglong2* buf = reinterpret_cast<ulonglong2*>(s_raw) + wv * (8 * 64);
-        const uint64_t tile_hi = (uint64_t)tile << 32;
-        if (n <= 128) wave_sort_tile<2>(r0, n, lane, tile_hi, keys, vals, buf);
-        else if (n <= 256) wave_sort_tile<4>(r0, n, lane, tile_hi, keys, vals, buf);
-        else if (n <= 512) wave_sort_tile<8>(r0, n, lane, tile_hi, keys, vals, buf);
-        else wave_sort_tile<16>(r0, n, lane, tile_hi, keys, vals, buf);
-    }
-    if (!big_too) return;   // the larger tiles have a launch of their own (one workgroup per tile)
-    __syncthreads();
-    uint64_t* comp = reinterpret_cast<uint64_t*>(s_raw);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(s_raw + TS_MAX * 8);
-    uint32_t (*wcnt)[256] = reinterpret_cast<uint32_t (*)[256]>(s_raw + TS_MAX * 8 + 256 * 4);
-    for (int w = 0; w < 4; w++) {
-        if (!s_big[w]) continue;
-        block_sort_tile(blockIdx.x * 4 + w, ranges, keys, vals, keys_alt, vals_alt, gid_passes, 1, comp, hist, wcnt);
-        __syncthreads();
-    }
 }
 
 template <int E>
@@ -653,22 +530,11 @@ int hsr_launch_tile_sort(BinState& b, int T, int P, const uint2* ranges, hipStre
     int bits = 0;
     while (bits < 32 && (1ull << bits) < (unsigned long long)(P > 1 ? P : 1)) bits++;
     const BinDevRef r = ref ? *ref : BinDevRef{nullptr, nullptr, 0};
-    static const bool block_only = getenv("HSR_SORT_IMPL") && !strcmp(getenv("HSR_SORT_IMPL"), "block");
-    if (block_only) {
-        tile_sort_kernel<<<T, 256, 0, stream>>>(ranges, b.keys, b.vals, b.keys_unsorted, b.vals_unsorted, (bits + 7) / 8, 1, r);
-        return HSR_OK;
-    }
-    // tiles of <= 1024 entries: one wave each, elements in registers; the larger ones by whole workgroups — in the same launch
-    // (four tiles per workgroup, one after the other) while they are the exception, in a launch of their own (one workgroup
+    // tiles of <= TP_MAX entries: two waves each, elements in registers; the larger ones by whole workgroups — in the same launch
+    // (two tiles per workgroup, one after the other) while they are the exception, in a launch of their own (one workgroup
     // per tile) when the previous frame averaged more than 800 entries per tile
     const bool many_big = avg_per_tile_hint > 800;
-    // round 3: two waves per tile (tile_sort_pair_kernel); HSR_SORT_IMPL=wave keeps one wave per tile (parity-tested selector)
-    static const bool one_wave = getenv("HSR_SORT_IMPL") && !strcmp(getenv("HSR_SORT_IMPL"), "wave");
-    if (!one_wave)
-        tile_sort_pair_kernel<<<(T + 1) / 2, 256, 0, stream>>>(T, ranges, b.keys, b.vals, b.keys_unsorted, b.vals_unsorted, (bits + 7) / 8,
-                                                               many_big ? 0 : 1, r);
-    else
-    tile_sort_wave_kernel<<<(T + 3) / 4, 256, 0, stream>>>(T, ranges, b.keys, b.vals, b.keys_unsorted, b.vals_unsorted, (bits + 7) / 8,
+    tile_sort_pair_kernel<<<(T + 1) / 2, 256, 0, stream>>>(T, ranges, b.keys, b.vals, b.keys_unsorted, b.vals_unsorted, (bits + 7) / 8,
                                                            many_big ? 0 : 1, r);
     if (many_big)
         tile_sort_kernel<<<T, 256, 0, stream>>>(ranges, b.keys, b.vals, b.keys_unsorted, b.vals_unsorted, (bits + 7) / 8, 2, r);

@@ -13,12 +13,12 @@
 // which is the reference's power = -0.5*(cx*dx^2 + cz*dy^2) - cy*dx*dy, alpha = min(0.99, o*exp(power))
 // (forward.cu:484-492) up to fp32 rounding (tolerance-tested; thresholds are applied to the same alpha).
 //
-// Per-wave culling: at staging time the lane that owns a splat also computes a conservative bounding
-// box of the region where alpha can reach 1/255 (an ellipse: A*dx^2 + B*dx*dy + C*dy^2 >= -log2(255*o))
-// and, for each quadrant, whether the box touches it.  A wave ballot turns that into a compacted,
-// order-preserving list of batch slots per quadrant, so the blend loop of a wave only ever visits splats
-// that can touch its 64 pixels.  The exact per-pixel tests still run on the survivors, so results do not
-// depend on the box (it only has to be conservative).
+// Per-wave culling: at staging time the lane that owns a splat also tests which 4x4 sub-blocks (and so
+// which quadrants) the region where alpha can reach 1/255 touches (an ellipse: A*dx^2 + B*dx*dy + C*dy^2
+// >= -log2(255*o); subblock_mask below).  Wave ballots turn that into compacted, order-preserving lists of
+// batch slots per quadrant or per sub-block, so the blend loop only ever visits splats that can touch its
+// pixels.  The exact per-pixel tests still run on the survivors, so results do not depend on the culling
+// test (it only has to be conservative).
 #pragma once
 #include "hsr_common.h"
 
@@ -79,29 +79,6 @@ __device__ __forceinline__ TileGeom tile_geom(int tile, int W, int H, int t)
     return g;
 }
 
-// 4-bit mask of the tile's quadrants (bit q = wave q) that the splat's alpha >= 1/255 region can touch.
-// xy: centre, conic (cx, cy, cz), opacity.  Conservative: boxes are inflated by a relative 1e-3 + 0.05 px.
-__device__ __forceinline__ uint32_t quadrant_mask(float x, float y, float cx, float cy, float cz, float opacity, float tile_x0,
-                                                  float tile_y0)
-{
-    // alpha >= 1/255  <=>  power >= -ln(255*o) =: -tau;  no pixel qualifies when 255*o < 1
-    const float t255 = 255.0f * opacity;
-    if (!(t255 >= 1.0f)) return 0u;
-    const float tau2 = 2.0f * __logf(t255) * 1.001f + 1e-4f;  // 2*tau, inflated
-    const float det = cx * cz - cy * cy;
-    // degenerate / non-positive-definite conic: do not cull
-    if (!(det > 0.0f) || !(cx > 0.0f) || !(cz > 0.0f)) return 0xFu;
-    const float inv_det = 1.0f / det;
-    const float hx = sqrtf(tau2 * cz * inv_det) * 1.001f + 0.05f;
-    const float hy = sqrtf(tau2 * cx * inv_det) * 1.001f + 0.05f;
-    const float x0 = x - hx - tile_x0, x1 = x + hx - tile_x0;  // tile-relative extent
-    const float y0 = y - hy - tile_y0, y1 = y + hy - tile_y0;
-    // quadrant pixel centres: [0,7] and [8,15] on each axis
-    const bool xl = x0 <= 7.0f && x1 >= 0.0f, xr = x0 <= 15.0f && x1 >= 8.0f;
-    const bool yt = y0 <= 7.0f && y1 >= 0.0f, yb = y0 <= 15.0f && y1 >= 8.0f;
-    return (uint32_t)(xl && yt) | ((uint32_t)(xr && yt) << 1) | ((uint32_t)(xl && yb) << 2) | ((uint32_t)(xr && yb) << 3);
-}
-
 // Builds the per-quadrant compacted slot lists for one staged batch.  Lane t staged slot t (or nothing
 // when t >= cnt).  s_list[q][sw*64 + k] = k-th slot staged by wave `sw` that touches quadrant q (order
 // preserved); s_lcnt[q][sw] = how many.  Call between the record stores and the barrier before blending.
@@ -136,7 +113,7 @@ __device__ __forceinline__ int build_flat_list(int wv, int lane, const uint8_t (
     return total;
 }
 
-// ---- 4x4 sub-block decomposition (hsr_render_fwd_sub.hip) ----
+// ---- 4x4 sub-block decomposition (hsr_render_fwd.hip, hsr_render_bwd_sub.hip, hsr_render_bwd_q.hip) ----
 // Same tile and quadrant ownership as above, but lane l of a wave owns pixel (4*(gq&1) + (l&3), 4*(gq>>1) + ((l>>2)&3)) of
 // the quadrant, gq = l >> 4: every 16-lane group of the wave is one 4x4 SUB-BLOCK, and walks its own compacted list.  A
 // SLAM-sized splat (alpha >= 1/255 inside a radius of 3-4 px) touches 3 quadrant visits x 64 lanes today but only ~4 of

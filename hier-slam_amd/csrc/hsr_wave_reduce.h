@@ -67,10 +67,6 @@ __device__ __forceinline__ float elem_or_zero(const float (&x)[M], int i)
 HSR_BANKED_PAIR2(pair2_half_mirror, "row_half_mirror", "0xa")
 HSR_BANKED_PAIR2(pair2_ror8, "row_ror:8", "0xc")
 
-#ifndef HSR_REDUCE_SWAP_FIRST
-#define HSR_REDUCE_SWAP_FIRST 0
-#endif
-
 template <int N>
 __device__ __forceinline__ float wave_reduce_transpose(const float (&v)[N], int lane)
 {
@@ -79,22 +75,6 @@ __device__ __forceinline__ float wave_reduce_transpose(const float (&v)[N], int 
     static_assert((N5 + 1) / 2 == 1, "six stages reduce to one register");
     float a[N1], b[N2], c[N3], d[N4], e[N5];
     const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
-#if HSR_REDUCE_SWAP_FIRST
-    // cross-row stages first: a v_permlane*_swap pair-sum is 2 instructions (swap + add) against 3 for a DPP
-    // pair-sum (2 selects + add), so the stages that touch the most registers use the swaps
-#pragma unroll
-    for (int i = 0; i < N1; i++) a[i] = pair32(v[2 * i], elem_or_zero(v, 2 * i + 1));
-#pragma unroll
-    for (int i = 0; i < N2; i++) b[i] = pair16(a[2 * i], elem_or_zero(a, 2 * i + 1));
-#pragma unroll
-    for (int i = 0; i < N3; i++) c[i] = pair_dpp<DPP_ROW_ROR8>(b[2 * i], elem_or_zero(b, 2 * i + 1), b3);
-    // row_half_mirror pairs l with 7-l (flips bits 0..2): it has to come before the xor-2 / xor-1 stages
-#pragma unroll
-    for (int i = 0; i < N4; i++) d[i] = pair_dpp<DPP_ROW_HALF_MIRROR>(c[2 * i], elem_or_zero(c, 2 * i + 1), b2);
-#pragma unroll
-    for (int i = 0; i < N5; i++) e[i] = pair_dpp<DPP_QUAD_XOR2>(d[2 * i], elem_or_zero(d, 2 * i + 1), b1);
-    return pair_dpp<DPP_QUAD_XOR1>(e[0], elem_or_zero(e, 1), b0);
-#else
     // Stage order by cost: the two pairings whose select bit is a DPP BANK bit (row_half_mirror <-> bit 2,
     // row_ror:8 <-> bit 3) need no v_cndmask (2 instructions per pair) and run first, on the most registers;
     // quad_perm xor 1 / xor 2 (3 instructions per pair) follow; the permlane swaps (slow) see 2 + 1 pairs.
@@ -115,18 +95,12 @@ __device__ __forceinline__ float wave_reduce_transpose(const float (&v)[N], int 
 #pragma unroll
     for (int i = 0; i < N5; i++) e[i] = pair16(d[2 * i], elem_or_zero(d, 2 * i + 1));
     return pair32(e[0], elem_or_zero(e, 1));
-#endif
 }
 
 // which value a lane holds after wave_reduce_transpose (select bits in stage order)
 __device__ __forceinline__ int reduce_slot(int l)
 {
-#if HSR_REDUCE_SWAP_FIRST
-    // stage order b5, b4, b3, b2, b1, b0: bit reversal
-    return ((l & 1) << 5) | ((l & 2) << 3) | ((l & 4) << 1) | ((l & 8) >> 1) | ((l & 16) >> 3) | ((l & 32) >> 5);
-#else
     // stage order b2, b3, b0, b1, b4, b5
     return ((l >> 2) & 3) | ((l & 3) << 2) | (l & 0x30);
-#endif
 }
 

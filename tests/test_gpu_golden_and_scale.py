@@ -182,19 +182,6 @@ def test_parity_alternate_kernels(impl):
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-def test_parity_wide_tree_kernel_selectors():
-    """wide trees (K > 27) default to ONE backward pass of up to 112 columns at two waves per SIMD; HSR_BWD_WIDE_PASS=split
-    selects the earlier 64-column passes (what K + 5 > 112 still takes): same results, parity cases in a child process"""
-    import subprocess
-    import sys
-    code = ("import sys; sys.path[:0]=['hier-slam_amd','tests'];import scenes;from test_gpu_parity import CASES,_compare;"
-            "[_compare(*((lambda W,H,P,K,kind,sm,sem,var,bg,beh: (lambda csu: (csu[0],csu[1],csu[2],sem,var,None))(scenes.build(W,H,P,K,seed=11,kind=kind,scale_mult=sm,bg=bg,behind_frac=beh)))(*CASES[n]))) "
-            "for n in ('generic_k40_two_chunks','large_tree_k74','flat_k102','odd_k33','odd_k75_ragged','k52_four_column_groups','k124_widest_single_pass','k130_chunked','wide_deep_tiles_k76')];print('ok')")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=dict(os.environ, HSR_BWD_WIDE_PASS="split"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-
-
 def test_ctypes_glue_matches_too():
     """The four rasterize entry points run through the compiled torch glue (diff_gaussian_rasterization._hsr_torch) when it is
     built; HSR_GLUE=ctypes selects the pure-Python glue over the same C ABI.  Parity cases through that one, in a child process."""
@@ -217,12 +204,12 @@ def test_compiled_glue_is_loaded():
     assert _C._ext is not None, "diff_gaussian_rasterization._hsr_torch is not built (python hier-slam_amd/csrc/build_torch_ext.py)"
 
 
-@pytest.mark.parametrize("impl", ["radix", "wave", "block", "default"])
+@pytest.mark.parametrize("impl", ["radix", "default"])
 def test_radix_binning_path_matches(impl):
     """HSR_SORT_IMPL=radix: emission in Gaussian order + stable tile-bit radix passes + per-tile sort (the path images of more
     than 8192 tiles take) instead of direct tile binning — same sorted keys, values, ranges and offsets, bit for bit.
-    HSR_SORT_IMPL=wave / block: the per-tile sort by one wave per tile / by whole workgroups instead of the default two waves per
-    tile (tile_sort_pair_kernel): every tile size class (<= 256, <= 512, <= 1024, <= 2048, beyond) occurs in the four scenes."""
+    Every tile size class of the default per-tile sort (<= 256, <= 512, <= 1024 entries: two waves per tile, tile_sort_pair_kernel;
+    <= 2048: the whole workgroup, in registers; beyond: block radix) occurs in the scenes."""
     import subprocess
     import sys
     code = ("import sys; sys.path[:0]=['hier-slam_amd','tests'];import scenes;from test_gpu_parity import CASES,_compare;"
