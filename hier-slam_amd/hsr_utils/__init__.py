@@ -6,3 +6,13 @@ shapes and layouts scripts/hierslam.py does.  Nothing here computes on the hot p
 """
 from .camera import setup_camera_tensors, setup_camera  # noqa: F401
 from .synthetic import make_scene, make_upstream_grads  # noqa: F401
+
+_KEYFRAMES = ("keyframe_selection_overlap", "overlap_counts", "KeyframePoses", "mapping_window")
+
+
+def __getattr__(name):
+    # the keyframe selection binds libhsr_rast.so: resolved on first use, so that importing the host-side helpers above stays library-free
+    if name in _KEYFRAMES:
+        from . import keyframes
+        return getattr(keyframes, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
