@@ -7,8 +7,8 @@ rasterize_points.h:18-125) with the same argument order and return tuples, so
     rasterize_gaussians, rasterize_gaussians_backward, mark_visible,
     rasterize_gaussians_semantic, rasterize_gaussians_backward_semantic
 
-The glue only allocates tensors and hands raw device pointers to the C ABI declared in
-include/hsr_rasterizer.h (ctypes; no torch types cross the boundary).  There is NO fallback path: if the
+The glue only allocates tensors and hands raw device pointers to the C ABI of include/hsr_*.h, whose ctypes signatures
+and structures are declared in _abi.py (no torch types cross the boundary).  There is NO fallback path: if the
 shared library is missing or the tensors are not on a HIP device, these functions raise.
 """
 import ctypes as C
@@ -17,99 +17,14 @@ import os
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB_PATH = os.environ.get("HSR_RAST_LIB", os.path.join(os.path.dirname(_HERE), "libhsr_rast.so"))
+from . import _abi
+from ._abi import HSR_ERR_BUFFER_TOO_SMALL, HSR_PENDING, fail as _fail, lib as _lib
+
+# the names this module has always carried (bench.py, the tools and the tests use several of them)
+_LIB_PATH = _abi.LIB_PATH
+_HsrBuffer, _Ticket, _StateLayout = _abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout
 
 NUM_CHANNELS = 3  # reference config.h:15
-
-
-class _HsrBuffer(C.Structure):
-    _fields_ = [("ptr", C.c_void_p), ("capacity", C.c_size_t), ("grow", C.c_void_p), ("user", C.c_void_p)]
-
-
-_GROW_FN = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
-
-
-class _Ticket(C.Structure):
-    """hsr_ticket (include/hsr_rasterizer.h): a forward call that returned before num_rendered was known"""
-    _fields_ = [("seq", C.c_uint32), ("device", C.c_int32), ("slot", C.c_void_p), ("binning_base", C.c_void_p),
-                ("binning_capacity", C.c_size_t), ("prefiltered", C.c_int32), ("rendered", C.c_int32)]
-
-
-HSR_PENDING = -100
-HSR_ERR_BUFFER_TOO_SMALL = -2
-
-
-class _StateLayout(C.Structure):
-    _fields_ = [(n, C.c_size_t) for n in (
-        "geom_depths", "geom_means2D", "geom_conic_opacity", "geom_cov3D", "geom_rgb", "geom_clamped",
-        "geom_tiles_touched", "geom_point_offsets", "geom_radii",
-        "bin_keys_unsorted", "bin_keys", "bin_vals_unsorted", "bin_vals",
-        "img_ranges", "img_final_T", "img_n_contrib", "img_median_pos")]
-
-
-def _load():
-    if not os.path.exists(_LIB_PATH):
-        raise ImportError(
-            "diff_gaussian_rasterization: HIP library not found at %s — build it with "
-            "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
-            "There is no CPU fallback." % _LIB_PATH)
-    lib = C.CDLL(_LIB_PATH)
-    vp, ci, cf, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    bp = C.POINTER(_HsrBuffer)
-    lib.hsr_required_geometry_bytes.restype = sz
-    lib.hsr_required_geometry_bytes.argtypes = [ci]
-    lib.hsr_required_image_bytes.restype = sz
-    lib.hsr_required_image_bytes.argtypes = [ci, ci]
-    lib.hsr_required_binning_bytes.restype = sz
-    lib.hsr_required_binning_bytes.argtypes = [ci]
-    lib.hsr_last_error.restype = C.c_char_p
-    lib.hsr_version.restype = C.c_char_p
-    lib.hsr_mark_visible.restype = ci
-    lib.hsr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
-    lib.hsr_forward.restype = ci
-    lib.hsr_forward.argtypes = [bp, bp, bp, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, ci,
-                                vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.hsr_forward_semantic.restype = ci
-    lib.hsr_forward_semantic.argtypes = [bp, bp, bp, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp,
-                                         cf, cf, ci, vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.hsr_backward.restype = ci
-    lib.hsr_backward.argtypes = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp,
-                                 vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ci, vp]
-    lib.hsr_set_backward_mode.restype = ci
-    lib.hsr_set_backward_mode.argtypes = [ci]
-    lib.hsr_backward_scratch_bytes.restype = sz
-    lib.hsr_backward_scratch_bytes.argtypes = [ci, ci, ci]
-    lib.hsr_backward_semantic.restype = ci
-    lib.hsr_backward_semantic.argtypes = [ci, ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf,
-                                          vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz,
-                                          ci, vp]
-    lib.hsr_stage_name.restype = C.c_char_p
-    lib.hsr_stage_name.argtypes = [ci]
-    lib.hsr_profile_enable.restype = ci
-    lib.hsr_profile_enable.argtypes = [ci]
-    lib.hsr_get_backward_mode.restype = ci
-    lib.hsr_get_backward_mode.argtypes = []
-    lib.hsr_set_semantic_alpha_mode.restype = ci
-    lib.hsr_set_semantic_alpha_mode.argtypes = [ci]
-    lib.hsr_get_semantic_alpha_mode.restype = ci
-    lib.hsr_get_semantic_alpha_mode.argtypes = []
-    lib.hsr_profile_host_wait_ms.restype = C.c_double
-    lib.hsr_profile_host_wait_ms.argtypes = [ci]
-    lib.hsr_profile_select.restype = ci
-    lib.hsr_profile_select.argtypes = [C.c_uint]
-    lib.hsr_profile_read.restype = ci
-    lib.hsr_profile_read.argtypes = [vp, ci]
-    lib.hsr_get_state_layout.restype = ci
-    lib.hsr_get_state_layout.argtypes = [ci, ci, ci, ci, C.POINTER(_StateLayout)]
-    lib.hsr_forward_arm_async.restype = ci
-    lib.hsr_forward_arm_async.argtypes = [C.POINTER(_Ticket)]
-    lib.hsr_forward_end.restype = ci
-    lib.hsr_forward_end.argtypes = [C.POINTER(_Ticket), ci, vp]
-    return lib
-
-
-_lib = _load()
 
 # The same glue as a compiled extension (csrc/hsr_torch_ext.cpp, built by csrc/build_torch_ext.py): used for the four
 # rasterize entry points when present, because the interpreter work per call matters at 0.65 ms per render.  HSR_GLUE=ctypes
@@ -354,10 +269,6 @@ def version():
     return _lib.hsr_version().decode()
 
 
-def _fail(rc, what):
-    raise RuntimeError("%s failed (code %d): %s" % (what, rc, _lib.hsr_last_error().decode()))
-
-
 def _ptr(t):
     """Device pointer of a contiguous fp32/int32 tensor, or NULL for the reference's empty placeholders."""
     if t is None or t.numel() == 0:
@@ -398,7 +309,7 @@ def _grow_dispatch(nbytes, user):
 # ONE callback object for the whole module: every ctypes callback is a reference cycle in itself (function pointer <-> thunk), so a
 # callback per call that closes over its tensor kept the three state buffers of every forward alive until the cyclic collector ran
 # (measured through this glue: one to two iterations' worth of device memory pending at any time)
-_GROW_CB = _GROW_FN(_grow_dispatch)
+_GROW_CB = _abi.GROW_FN(_grow_dispatch)
 
 
 class _Grower:
@@ -650,12 +561,8 @@ def mark_visible(means3D, viewmatrix, projmatrix):
     P = int(means3D.size(0))
     present = torch.zeros((P,), dtype=torch.bool, device=dev)
     if P != 0:
-        with torch.cuda.device(dev):
-            m3, vm, pm = (_prep(x, dev) for x in (means3D, viewmatrix, projmatrix))
-            rc = _lib.hsr_mark_visible(P, _ptr(m3), _ptr(vm), _ptr(pm), present.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream)
-            if rc < 0:
-                _fail(rc, "mark_visible")
+        m3, vm, pm = (_prep(x, dev) for x in (means3D, viewmatrix, projmatrix))
+        _abi.call(_lib.hsr_mark_visible, "mark_visible", dev, P, _ptr(m3), _ptr(vm), _ptr(pm), present.data_ptr())
     return present
 
 

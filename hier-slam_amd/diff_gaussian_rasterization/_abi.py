@@ -1,0 +1,242 @@
+"""The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
+function, and the one way a stream-taking entry point is called.
+
+Everything under include/hsr_*.h is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from this module.  The
+signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
+time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's.  There is NO fallback
+path: a missing library is an ImportError.
+"""
+import ctypes as C
+import os
+
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("HSR_RAST_LIB", os.path.join(os.path.dirname(_HERE), "libhsr_rast.so"))
+
+HSR_ERR_BUFFER_TOO_SMALL = -2
+HSR_PENDING = -100
+
+vp, ci, cu, cf, cd, sz, cs = C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t, C.c_char_p
+ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)      # HOST arrays (level_sizes, level_weight)
+
+
+# ---- structures, named and laid out as the header typedefs -------------------------------------------------------------------------
+class hsr_buffer(C.Structure):
+    _fields_ = [("ptr", vp), ("capacity", sz), ("grow", vp), ("user", vp)]
+
+
+GROW_FN = C.CFUNCTYPE(vp, sz, vp)      # hsr_grow_fn
+
+
+class hsr_ticket(C.Structure):
+    """a forward call that returned before num_rendered was known"""
+    _fields_ = [("seq", C.c_uint32), ("device", C.c_int32), ("slot", vp), ("binning_base", vp), ("binning_capacity", sz),
+                ("prefiltered", C.c_int32), ("rendered", C.c_int32)]
+
+
+class hsr_state_layout(C.Structure):
+    _fields_ = [(n, sz) for n in (
+        "geom_depths", "geom_means2D", "geom_conic_opacity", "geom_cov3D", "geom_rgb", "geom_clamped",
+        "geom_tiles_touched", "geom_point_offsets", "geom_radii",
+        "bin_keys_unsorted", "bin_keys", "bin_vals_unsorted", "bin_vals",
+        "img_ranges", "img_final_T", "img_n_contrib", "img_median_pos")]
+
+
+class hsr_row_table(C.Structure):
+    _fields_ = [("src", vp), ("append", vp), ("dst", vp), ("cols", ci)]
+
+
+class hsr_adam_tensor(C.Structure):
+    _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", C.c_int64),
+                ("step_size", cf), ("bc2_sqrt", cf), ("eps", cf), ("one_minus_beta1", cf), ("beta2", cf), ("one_minus_beta2", cf)]
+
+
+bp, tk = C.POINTER(hsr_buffer), C.POINTER(hsr_ticket)
+
+# ---- signatures: (name, restype, argtypes), in the order of the headers, broken into lines where the prototype breaks ----------------
+SIGNATURES = (
+    # include/hsr_rasterizer.h
+    ("hsr_required_geometry_bytes", sz, [ci]),
+    ("hsr_required_image_bytes", sz, [ci, ci]),
+    ("hsr_required_binning_bytes", sz, [ci]),
+    ("hsr_backward_scratch_bytes", sz, [ci, ci, ci]),
+    ("hsr_set_backward_mode", ci, [ci]),
+    ("hsr_get_backward_mode", ci, []),
+    ("hsr_set_semantic_alpha_mode", ci, [ci]),
+    ("hsr_get_semantic_alpha_mode", ci, []),
+    ("hsr_last_error", cs, []),
+    ("hsr_version", cs, []),
+    ("hsr_mark_visible", ci, [ci, vp, vp, vp,
+                              vp, vp]),
+    ("hsr_forward", ci, [bp, bp, bp,
+                         ci, ci, ci, vp, ci, ci,
+                         vp, vp, vp, vp,
+                         vp, cf, vp, vp,
+                         vp, vp, vp,
+                         cf, cf, ci,
+                         vp, vp, vp, vp, vp,
+                         vp, ci, vp]),
+    ("hsr_forward_semantic", ci, [bp, bp, bp,
+                                  ci, ci, ci, ci, vp, ci, ci,
+                                  vp, vp, vp,
+                                  vp, vp,
+                                  vp, cf, vp, vp,
+                                  vp, vp, vp,
+                                  cf, cf, ci,
+                                  vp, vp, vp, vp,
+                                  vp, vp, ci, vp]),
+    ("hsr_forward_arm_async", ci, [tk]),
+    ("hsr_forward_end", ci, [tk, ci, vp]),
+    ("hsr_backward", ci, [ci, ci, ci, ci, vp, ci, ci,
+                          vp, vp, vp,
+                          vp, cf, vp, vp,
+                          vp, vp, vp,
+                          cf, cf, vp,
+                          vp, vp, vp,
+                          vp, vp, vp,
+                          vp,
+                          vp, vp, vp, vp, vp,
+                          vp, vp, vp, vp, vp,
+                          vp, sz, ci, vp]),
+    ("hsr_backward_semantic", ci, [ci, ci, ci, ci, ci, vp, ci, ci,
+                                   vp, vp, vp,
+                                   vp,
+                                   vp, cf, vp, vp,
+                                   vp, vp, vp,
+                                   cf, cf, vp,
+                                   vp, vp, vp,
+                                   vp, vp, vp,
+                                   vp, vp,
+                                   vp, vp, vp, vp,
+                                   vp, vp,
+                                   vp, vp, vp, vp, vp,
+                                   vp, sz, ci, vp]),
+    ("hsr_get_state_layout", ci, [ci, ci, ci, ci, C.POINTER(hsr_state_layout)]),
+    ("hsr_profile_enable", ci, [ci]),
+    ("hsr_profile_select", ci, [cu]),
+    ("hsr_profile_read", ci, [vp, ci]),
+    ("hsr_stage_name", cs, [ci]),
+    ("hsr_profile_host_wait_ms", cd, [ci]),
+    # include/hsr_frame_prep.h
+    ("hsr_frame_prep_scratch_bytes", sz, [ci]),
+    ("hsr_frame_prep_forward", ci, [ci, ci, ci, ci, vp, vp,
+                                    vp, vp, vp,
+                                    vp, ci, ci, vp, vp,
+                                    vp, vp, vp, vp,
+                                    vp, vp]),
+    ("hsr_frame_prep_backward", ci, [ci, ci, ci, ci, vp, vp,
+                                     vp, vp, vp,
+                                     vp, ci, ci, vp,
+                                     vp, vp, vp,
+                                     vp, vp, vp,
+                                     vp, vp, vp, vp,
+                                     vp, vp, vp, sz, vp]),
+    ("hsr_frame_prep_backward_params", ci, [ci, ci, ci, ci, vp, vp,
+                                            vp, vp, vp,
+                                            vp, ci, ci, vp,
+                                            vp, vp, vp,
+                                            vp, vp, vp,
+                                            vp, vp, vp, vp,
+                                            vp, vp, vp, sz, vp]),
+    # include/hsr_losses.h
+    ("hsr_loss_scratch_bytes", sz, [ci, ci, ci]),
+    ("hsr_loss_l1", ci, [ci, ci, ci, vp, vp, vp, ci, vp,
+                         vp, vp, sz, vp]),
+    ("hsr_loss_tracking_scratch_bytes", sz, [ci, ci]),
+    ("hsr_loss_tracking_value", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                     vp, cf, ci, ci, cf, cf, vp,
+                                     vp, sz, vp]),
+    ("hsr_loss_tracking_grad", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                    vp, cf, ci, cf, cf, vp,
+                                    vp, vp, vp, vp]),
+    ("hsr_loss_ssim", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
+                           sz, vp]),
+    ("hsr_loss_l1_grad", ci, [ci, ci, ci, vp, vp, vp, ci, vp,
+                              vp, vp]),
+    ("hsr_loss_ssim_value", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
+                                 sz, vp]),
+    ("hsr_loss_ssim_grad", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
+                                vp]),
+    ("hsr_loss_tree_ce", ci, [ci, ci, ci, ci, ip, fp, vp,
+                              vp, ci, vp, vp, vp,
+                              sz, vp]),
+    ("hsr_loss_tree_ce_scratch_bytes", sz, [ci, ci]),
+    ("hsr_loss_tree_ce_value", ci, [ci, ci, ci, ci, ip, vp, vp,
+                                    ci, vp, vp, vp, sz,
+                                    vp]),
+    ("hsr_loss_tree_ce_grad", ci, [ci, ci, ci, ci, ip, fp, vp,
+                                   vp, ci, vp, vp, vp,
+                                   vp, cf, vp, vp]),
+    ("hsr_loss_leaf_mlp_ce", ci, [ci, ci, ci, ci, vp, vp, vp, vp,
+                                  ci, vp, vp, vp, vp, vp,
+                                  sz, vp]),
+    # include/hsr_densify.h
+    ("hsr_densify_scratch_bytes", sz, [ci, ci]),
+    ("hsr_densify_frame", ci, [ci, ci, vp, vp, vp, vp,
+                               cf, cf, cf, cf, vp, cf, cf, ci,
+                               vp, vp, vp, vp, vp,
+                               vp, vp, vp, sz, vp]),
+    ("hsr_compact_scratch_bytes", sz, [ci]),
+    ("hsr_prune_mask", ci, [ci, ci, vp, vp, cf,
+                            cf, vp, vp, vp, sz, vp]),
+    ("hsr_compact_append_rows", ci, [ci, vp, ci, ci, C.POINTER(hsr_row_table), ci,
+                                     vp, vp, sz, vp]),
+    # include/hsr_eval.h
+    ("hsr_eval_metrics_scratch_bytes", sz, [ci, ci]),
+    ("hsr_eval_frame_metrics", ci, [ci, ci, vp, vp, vp, vp,
+                                    vp, cf, vp, vp, sz, vp]),
+    ("hsr_eval_labels_flat", ci, [ci, ci, ci, vp, vp, vp]),
+    ("hsr_eval_labels_tree", ci, [ci, ci, ci, ci, ip, vp, vp,
+                                  vp, vp, vp]),
+    ("hsr_eval_leaf_scratch_bytes", sz, [ci]),
+    ("hsr_eval_labels_leaf", ci, [ci, ci, ci, ci, vp, vp, vp, vp,
+                                  vp, sz, vp]),
+    ("hsr_eval_iou_scratch_bytes", sz, [ci, ci]),
+    ("hsr_eval_iou_counts", ci, [ci, ci, vp, vp, ci, vp, vp,
+                                 ci, vp, vp, sz, vp]),
+    ("hsr_eval_frame_miou", ci, [ci, vp, vp, vp]),
+    # include/hsr_optim.h
+    ("hsr_adam_table_entry_bytes", sz, []),
+    ("hsr_adam_step", ci, [ci, C.POINTER(hsr_adam_tensor), vp]),
+    ("hsr_track_keep_best", ci, [ci, ci, vp, vp, vp, vp,
+                                 vp, vp, vp]),
+    # include/hsr_keyframes.h
+    ("hsr_kf_valid_rows", ci, [ci, ci, vp, vp, vp]),
+    ("hsr_kf_sample_scratch_bytes", sz, [ci]),
+    ("hsr_kf_sample_points", ci, [ci, ci, vp, vp, ci, vp, cf, cf,
+                                  cf, cf, vp, vp, vp, vp,
+                                  vp, vp, sz, vp]),
+    ("hsr_kf_round_keys", ci, [ci, vp, vp, vp]),
+    ("hsr_kf_overlap_counts", ci, [ci, vp, vp, ci, vp, vp, ci,
+                                   ci, ci, vp, vp]),
+)
+
+
+def _load():
+    if not os.path.exists(LIB_PATH):
+        raise ImportError(
+            "diff_gaussian_rasterization: HIP library not found at %s — build it with "
+            "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
+            "There is no CPU fallback." % LIB_PATH)
+    loaded = C.CDLL(LIB_PATH)
+    for name, restype, argtypes in SIGNATURES:
+        fn = getattr(loaded, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return loaded
+
+
+lib = _load()
+
+
+def fail(rc, what):
+    raise RuntimeError("%s failed (code %d): %s" % (what, rc, lib.hsr_last_error().decode()))
+
+
+def call(fn, what, dev, *args):
+    """fn(*args, stream) for an entry point that ends in `void* stream`: on device `dev`, on its current stream; raises on a negative
+    return code.  Pass `lib.hsr_x` itself, looked up at the call, so that a replaced attribute of `lib` is what runs."""
+    with torch.cuda.device(dev):
+        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
+    if rc < 0:
+        fail(rc, what)

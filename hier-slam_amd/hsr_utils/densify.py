@@ -11,19 +11,12 @@ each = fused input preparation + ONE no-grad render with this repo's rasterizer 
 Prune / optimizer-preserving concat: hsr_utils/slam_external.py (one fused device compaction).
 
 The Parameter / bookkeeping concatenation is torch, as in the reference (it is bookkeeping on torch objects)."""
-import ctypes as C
-
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _abi
 
-_lib = _glue._lib
-_vp, _ci, _cf, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-_lib.hsr_densify_scratch_bytes.restype = _sz
-_lib.hsr_densify_scratch_bytes.argtypes = [_ci, _ci]
-_lib.hsr_densify_frame.restype = _ci
-_lib.hsr_densify_frame.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _cf, _cf, _vp, _cf, _cf, _ci] + [_vp] * 7 + [_vp, _sz, _vp]
+_lib = _abi.lib
 
 
 def _plane(t, H, W, what):
@@ -50,13 +43,10 @@ def non_presence_points(silhouette, render_depth, gt_depth, color, intrinsics, w
     mask = torch.empty((N,), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     sc = torch.empty(int(_lib.hsr_densify_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.hsr_densify_frame(H, W, sil.data_ptr(), rd.data_ptr(), gt.data_ptr(), col.data_ptr(), float(K[0, 0]), float(K[1, 1]),
-                                    float(K[0, 2]), float(K[1, 2]), c2w.data_ptr(), float(sil_thres), float(depth_factor), N,
-                                    count.data_ptr(), means.data_ptr(), rgb.data_ptr(), ls.data_ptr(), msd.data_ptr(), mask.data_ptr(),
-                                    None, sc.data_ptr(), sc.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        _glue._fail(rc, "hsr_densify_frame")
+    _abi.call(_lib.hsr_densify_frame, "hsr_densify_frame", dev, H, W, sil.data_ptr(), rd.data_ptr(), gt.data_ptr(), col.data_ptr(),
+              float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), c2w.data_ptr(), float(sil_thres), float(depth_factor), N,
+              count.data_ptr(), means.data_ptr(), rgb.data_ptr(), ls.data_ptr(), msd.data_ptr(), mask.data_ptr(), None, sc.data_ptr(),
+              sc.numel())
     M = int(count.item())
     return torch.cat((means[:M], rgb[:M]), dim=1), msd[:M], mask.bool(), ls[:M, None]
 

@@ -18,28 +18,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _abi
 
-_lib = _glue._lib
-_vp, _ci, _sz = C.c_void_p, C.c_int, C.c_size_t
-_lib.hsr_eval_metrics_scratch_bytes.restype = _sz
-_lib.hsr_eval_metrics_scratch_bytes.argtypes = [_ci, _ci]
-_lib.hsr_eval_frame_metrics.restype = _ci
-_lib.hsr_eval_frame_metrics.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp, _sz, _vp]
-_lib.hsr_eval_labels_flat.restype = _ci
-_lib.hsr_eval_labels_flat.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp]
-_lib.hsr_eval_labels_tree.restype = _ci
-_lib.hsr_eval_labels_tree.argtypes = [_ci, _ci, _ci, _ci, C.POINTER(_ci), _vp, _vp, _vp, _vp, _vp]
-_lib.hsr_eval_leaf_scratch_bytes.restype = _sz
-_lib.hsr_eval_leaf_scratch_bytes.argtypes = [_ci]
-_lib.hsr_eval_labels_leaf.restype = _ci
-_lib.hsr_eval_labels_leaf.argtypes = [_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_eval_iou_scratch_bytes.restype = _sz
-_lib.hsr_eval_iou_scratch_bytes.argtypes = [_ci, _ci]
-_lib.hsr_eval_iou_counts.restype = _ci
-_lib.hsr_eval_iou_counts.argtypes = [_ci, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _sz, _vp]
-_lib.hsr_eval_frame_miou.restype = _ci
-_lib.hsr_eval_frame_miou.argtypes = [_ci, _vp, _vp, _vp]
+_lib = _abi.lib
 
 MAX_CLASSES, MAX_LEVELS, LEAF_MAX_K, LEAF_MAX_C, MAX_DILATION = 4096, 16, 32, 256, 1024
 _class_cache = {}
@@ -62,17 +43,6 @@ def _plane(t, what, H, W, dtype=torch.float32):
     return t
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _call(fn, name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = fn(*args, _stream(dev))
-    if rc < 0:
-        _glue._fail(rc, name)
-
-
 def frame_metrics(im, gt_im, depth, gt_depth, final_opacity=None, sil_thres=None):
     """float64 [3] on the device: psnr, depth_l1, depth_rmse of one frame (utils/eval_helpers.py:1258-1295).  im / gt_im: [3,H,W];
     depth / gt_depth / final_opacity: [1,H,W] or [H,W], all float32.  With final_opacity and sil_thres (the reference's
@@ -93,8 +63,8 @@ def frame_metrics(im, gt_im, depth, gt_depth, final_opacity=None, sil_thres=None
     dev = a.device
     out = torch.empty(3, dtype=torch.float64, device=dev)
     sc = torch.empty(int(_lib.hsr_eval_metrics_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-    _call(_lib.hsr_eval_frame_metrics, "hsr_eval_frame_metrics", dev, H, W, a.data_ptr(), b.data_ptr(), d.data_ptr(), gd.data_ptr(),
-          None if op is None else op.data_ptr(), 0.0 if sil_thres is None else float(sil_thres), out.data_ptr(), sc.data_ptr(), sc.numel())
+    _abi.call(_lib.hsr_eval_frame_metrics, "hsr_eval_frame_metrics", dev, H, W, a.data_ptr(), b.data_ptr(), d.data_ptr(), gd.data_ptr(),
+              None if op is None else op.data_ptr(), 0.0 if sil_thres is None else float(sil_thres), out.data_ptr(), sc.data_ptr(), sc.numel())
     return out
 
 
@@ -144,7 +114,7 @@ def semantic_labels(im_semantic, mode, *, level_sizes=None, tree_table=None, mlp
     dev = z.device
     out = torch.empty((H, W), dtype=torch.int32, device=dev)
     if mode == "flat":
-        _call(_lib.hsr_eval_labels_flat, "hsr_eval_labels_flat", dev, K, H, W, z.data_ptr(), out.data_ptr())
+        _abi.call(_lib.hsr_eval_labels_flat, "hsr_eval_labels_flat", dev, K, H, W, z.data_ptr(), out.data_ptr())
         return out
     if mode == "tree":
         if level_sizes is None or tree_table is None:
@@ -157,8 +127,8 @@ def semantic_labels(im_semantic, mode, *, level_sizes=None, tree_table=None, mlp
         if table.numel() != int(np.prod(sizes)):
             raise RuntimeError("hsr_utils.evaluate: tree_table has %d entries, the levels %s need %d" % (table.numel(), sizes, int(np.prod(sizes))))
         levels = torch.empty((L, H, W), dtype=torch.int32, device=dev)
-        _call(_lib.hsr_eval_labels_tree, "hsr_eval_labels_tree", dev, K, H, W, L, (_ci * L)(*sizes), z.data_ptr(), table.data_ptr(),
-              out.data_ptr(), levels.data_ptr())
+        _abi.call(_lib.hsr_eval_labels_tree, "hsr_eval_labels_tree", dev, K, H, W, L, (C.c_int * L)(*sizes), z.data_ptr(), table.data_ptr(),
+                  out.data_ptr(), levels.data_ptr())
         return out, levels
     if mode == "leaf":
         if mlp is None:
@@ -173,8 +143,8 @@ def semantic_labels(im_semantic, mode, *, level_sizes=None, tree_table=None, mlp
             raise RuntimeError("hsr_utils.evaluate: the leaf head takes K <= %d planes and C <= %d classes (got K=%d C=%d)"
                                % (LEAF_MAX_K, LEAF_MAX_C, K, Cc))
         sc = torch.empty(int(_lib.hsr_eval_leaf_scratch_bytes(Cc)), dtype=torch.uint8, device=dev)
-        _call(_lib.hsr_eval_labels_leaf, "hsr_eval_labels_leaf", dev, K, Cc, H, W, z.data_ptr(), w.contiguous().data_ptr(), b.data_ptr(),
-              out.data_ptr(), sc.data_ptr(), sc.numel())
+        _abi.call(_lib.hsr_eval_labels_leaf, "hsr_eval_labels_leaf", dev, K, Cc, H, W, z.data_ptr(), w.contiguous().data_ptr(), b.data_ptr(),
+                  out.data_ptr(), sc.data_ptr(), sc.numel())
         return out
     raise RuntimeError("hsr_utils.evaluate: mode must be 'flat', 'tree' or 'leaf' (got %r)" % (mode,))
 
@@ -220,8 +190,8 @@ def iou_counts(pred, gt, num_classes=None, class_ids=None, dilation_ratio=0.02):
         ids, rows = _classes(class_ids, dev)
     out = torch.empty((Cc, 6), dtype=torch.int64, device=dev)
     sc = torch.empty(int(_lib.hsr_eval_iou_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-    _call(_lib.hsr_eval_iou_counts, "hsr_eval_iou_counts", dev, H, W, p.data_ptr(), g.data_ptr(), Cc,
-          None if ids is None else ids.data_ptr(), None if rows is None else rows.data_ptr(), d, out.data_ptr(), sc.data_ptr(), sc.numel())
+    _abi.call(_lib.hsr_eval_iou_counts, "hsr_eval_iou_counts", dev, H, W, p.data_ptr(), g.data_ptr(), Cc,
+              None if ids is None else ids.data_ptr(), None if rows is None else rows.data_ptr(), d, out.data_ptr(), sc.data_ptr(), sc.numel())
     return out
 
 
@@ -232,7 +202,7 @@ def frame_miou(counts):
     if q.dim() != 2 or q.shape[1] != 6:
         raise RuntimeError("hsr_utils.evaluate: counts must be [C,6] (got %s)" % (tuple(q.shape),))
     out = torch.empty(2, dtype=torch.float64, device=q.device)
-    _call(_lib.hsr_eval_frame_miou, "hsr_eval_frame_miou", q.device, q.shape[0], q.data_ptr(), out.data_ptr())
+    _abi.call(_lib.hsr_eval_frame_miou, "hsr_eval_frame_miou", q.device, q.shape[0], q.data_ptr(), out.data_ptr())
     return out
 
 

@@ -11,35 +11,15 @@ then ONE np.random.permutation over the ids with a non-zero count (:93).  Under 
 Five kernel launches per call whatever the number of keyframes; the host reads n_valid (it bounds randint), the counts at the end, and
 fx, fy, cx, cy when the intrinsics live on the device.  There is no CPU path.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _abi
 
-_lib = _glue._lib
-_vp, _ci, _cf, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-_lib.hsr_kf_valid_rows.restype = _ci
-_lib.hsr_kf_valid_rows.argtypes = [_ci, _ci, _vp, _vp, _vp]
-_lib.hsr_kf_sample_scratch_bytes.restype = _sz
-_lib.hsr_kf_sample_scratch_bytes.argtypes = [_ci]
-_lib.hsr_kf_sample_points.restype = _ci
-_lib.hsr_kf_sample_points.argtypes = [_ci, _ci, _vp, _vp, _ci, _vp, _cf, _cf, _cf, _cf, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_kf_round_keys.restype = _ci
-_lib.hsr_kf_round_keys.argtypes = [_ci, _vp, _vp, _vp]
-_lib.hsr_kf_overlap_counts.restype = _ci
-_lib.hsr_kf_overlap_counts.argtypes = [_ci, _vp, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp]
+_lib = _abi.lib
 
 MAX_POINTS = 4096
 EDGE = 20            # utils/keyframe_selection.py:78
-
-
-def _call(fn, name, dev, *args):
-    with torch.cuda.device(dev):
-        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        _glue._fail(rc, name)
 
 
 def _depth_plane(gt_depth):
@@ -98,7 +78,7 @@ def round_keys(values):
         raise RuntimeError("hsr_utils.keyframes: values must be a float32 tensor on a HIP device; there is no CPU path")
     v = values.contiguous()
     out = torch.empty_like(v)
-    _call(_lib.hsr_kf_round_keys, "hsr_kf_round_keys", v.device, v.numel(), v.data_ptr(), out.data_ptr())
+    _abi.call(_lib.hsr_kf_round_keys, "hsr_kf_round_keys", v.device, v.numel(), v.data_ptr(), out.data_ptr())
     return out
 
 
@@ -107,7 +87,7 @@ def valid_row_prefix(gt_depth):
     d = _depth_plane(gt_depth)
     H, W = d.shape
     prefix = torch.empty(H + 1, dtype=torch.int32, device=d.device)
-    _call(_lib.hsr_kf_valid_rows, "hsr_kf_valid_rows", d.device, H, W, d.data_ptr(), prefix.data_ptr())
+    _abi.call(_lib.hsr_kf_valid_rows, "hsr_kf_valid_rows", d.device, H, W, d.data_ptr(), prefix.data_ptr())
     return prefix
 
 
@@ -131,9 +111,9 @@ def sample_points(gt_depth, w2c, intrinsics, ranks, row_prefix=None):
     keep = torch.empty((n,), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
     sc = torch.empty(int(_lib.hsr_kf_sample_scratch_bytes(n)), dtype=torch.uint8, device=dev)
-    _call(_lib.hsr_kf_sample_points, "hsr_kf_sample_points", dev, H, W, d.data_ptr(), row_prefix.data_ptr(), n, r.data_ptr(),
-          float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), c2w.data_ptr(), pts.data_ptr(), pix.data_ptr(), keep.data_ptr(),
-          count.data_ptr(), sc.data_ptr(), sc.numel())
+    _abi.call(_lib.hsr_kf_sample_points, "hsr_kf_sample_points", dev, H, W, d.data_ptr(), row_prefix.data_ptr(), n, r.data_ptr(),
+              float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2]), c2w.data_ptr(), pts.data_ptr(), pix.data_ptr(), keep.data_ptr(),
+              count.data_ptr(), sc.data_ptr(), sc.numel())
     return pts, pix, keep, count
 
 
@@ -149,8 +129,8 @@ def project_counts(pts, count, poses, intrinsics, W, H):
     K = intrinsics.detach().to(device=dev, dtype=torch.float32).contiguous()
     if K.numel() != 9:
         raise RuntimeError("hsr_utils.keyframes: intrinsics must be [3,3] (got %s)" % (tuple(intrinsics.shape),))
-    _call(_lib.hsr_kf_overlap_counts, "hsr_kf_overlap_counts", dev, int(pts.shape[0]), None if count is None else count.data_ptr(),
-          pts.data_ptr(), n_kf, p.data_ptr(), K.data_ptr(), int(W), int(H), EDGE, out.data_ptr())
+    _abi.call(_lib.hsr_kf_overlap_counts, "hsr_kf_overlap_counts", dev, int(pts.shape[0]), None if count is None else count.data_ptr(),
+              pts.data_ptr(), n_kf, p.data_ptr(), K.data_ptr(), int(W), int(H), EDGE, out.data_ptr())
     return out
 
 

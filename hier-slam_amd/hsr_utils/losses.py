@@ -16,39 +16,9 @@ import ctypes as C
 
 import torch
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _abi
 
-_lib = _glue._lib
-_vp, _ci, _sz = C.c_void_p, C.c_int, C.c_size_t
-_lib.hsr_loss_scratch_bytes.restype = _sz
-_lib.hsr_loss_scratch_bytes.argtypes = [_ci, _ci, _ci]
-_lib.hsr_loss_l1.restype = _ci
-_lib.hsr_loss_l1.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_loss_ssim.restype = _ci
-_lib.hsr_loss_ssim.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_loss_l1_grad.restype = _ci
-_lib.hsr_loss_l1_grad.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp]
-_lib.hsr_loss_ssim_value.restype = _ci
-_lib.hsr_loss_ssim_value.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_loss_ssim_grad.restype = _ci
-_lib.hsr_loss_ssim_grad.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp]
-_lib.hsr_loss_tree_ce.restype = _ci
-_lib.hsr_loss_tree_ce.argtypes = [_ci, _ci, _ci, _ci, C.POINTER(_ci), C.POINTER(C.c_float), _vp, _vp, _ci, _vp, _vp, _vp, _sz, _vp]
-
-_lib.hsr_loss_tree_ce_scratch_bytes.restype = _sz
-_lib.hsr_loss_tree_ce_scratch_bytes.argtypes = [_ci, _ci]
-_lib.hsr_loss_tree_ce_value.restype = _ci
-_lib.hsr_loss_tree_ce_value.argtypes = [_ci, _ci, _ci, _ci, C.POINTER(_ci), _vp, _vp, _ci, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_loss_tree_ce_grad.restype = _ci
-_lib.hsr_loss_tree_ce_grad.argtypes = [_ci, _ci, _ci, _ci, C.POINTER(_ci), C.POINTER(C.c_float), _vp, _vp, _ci, _vp, _vp, _vp, _vp, C.c_float, _vp, _vp]
-_lib.hsr_loss_tracking_scratch_bytes.restype = _sz
-_lib.hsr_loss_tracking_scratch_bytes.argtypes = [_ci, _ci]
-_lib.hsr_loss_tracking_value.restype = _ci
-_lib.hsr_loss_tracking_value.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, C.c_float, _ci, _ci, C.c_float, C.c_float, _vp, _vp, _sz, _vp]
-_lib.hsr_loss_tracking_grad.restype = _ci
-_lib.hsr_loss_tracking_grad.argtypes = [_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, C.c_float, _ci, C.c_float, C.c_float, _vp, _vp, _vp, _vp, _vp]
-_lib.hsr_loss_leaf_mlp_ce.restype = _ci
-_lib.hsr_loss_leaf_mlp_ce.argtypes = [_ci, _ci, _ci, _ci] + [_vp] * 4 + [_ci] + [_vp] * 5 + [_sz, _vp]
+_lib = _abi.lib
 
 SUM, MEAN = 0, 1
 LEAF_MAX_K, LEAF_MAX_C = 31, 128
@@ -69,10 +39,6 @@ def _chw(t, what):
 
 def _scratch(ch, H, W, dev):
     return torch.empty(int(_lib.hsr_loss_scratch_bytes(ch, H, W)), dtype=torch.uint8, device=dev)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 class _L1(torch.autograd.Function):
@@ -96,11 +62,8 @@ class _L1(torch.autograd.Function):
         ctx.two_pass = bool(pred.requires_grad) and (int(reduction) == SUM or m is None)
         grad = torch.empty_like(p) if (pred.requires_grad and not ctx.two_pass) else None
         sc = _scratch(Cc, H, W, dev)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_l1(Cc, H, W, p.data_ptr(), g.data_ptr(), None if m is None else m.data_ptr(), int(reduction),
-                                  out.data_ptr(), None if grad is None else grad.data_ptr(), sc.data_ptr(), sc.numel(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_l1")
+        _abi.call(_lib.hsr_loss_l1, "hsr_loss_l1", dev, Cc, H, W, p.data_ptr(), g.data_ptr(), None if m is None else m.data_ptr(),
+                  int(reduction), out.data_ptr(), None if grad is None else grad.data_ptr(), sc.data_ptr(), sc.numel())
         ctx.grad = None if grad is None else grad.view(shape)
         if ctx.two_pass:
             ctx.save_for_backward(p, g, m if m is not None else torch.empty(0, device=dev))
@@ -116,11 +79,8 @@ class _L1(torch.autograd.Function):
         dev = p.device
         gg = g.to(device=dev, dtype=torch.float32).contiguous()
         grad = torch.empty_like(p)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_l1_grad(Cc, H, W, p.data_ptr(), gt.data_ptr(), m.data_ptr() if has_mask else None, reduction, gg.data_ptr(),
-                                       grad.data_ptr(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_l1_grad")
+        _abi.call(_lib.hsr_loss_l1_grad, "hsr_loss_l1_grad", dev, Cc, H, W, p.data_ptr(), gt.data_ptr(), m.data_ptr() if has_mask else None,
+                  reduction, gg.data_ptr(), grad.data_ptr())
         return grad.view(shape), None, None, None
 
 
@@ -137,11 +97,8 @@ class _SSIM(torch.autograd.Function):
         # value pass now (it leaves the three partial-derivative maps), the adjoint correlation in backward() times the incoming gradient
         maps = torch.empty((3, Cc, H, W), dtype=torch.float32, device=dev) if img1.requires_grad else None
         sc = torch.empty(4096 + 4 * Cc * ((H + 31) // 32) * ((W + 31) // 32), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_ssim_value(Cc, H, W, a.data_ptr(), b.data_ptr(), out.data_ptr(), None if maps is None else maps.data_ptr(),
-                                          sc.data_ptr(), sc.numel(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_ssim_value")
+        _abi.call(_lib.hsr_loss_ssim_value, "hsr_loss_ssim_value", dev, Cc, H, W, a.data_ptr(), b.data_ptr(), out.data_ptr(),
+                  None if maps is None else maps.data_ptr(), sc.data_ptr(), sc.numel())
         ctx.want = maps is not None
         if ctx.want:
             ctx.save_for_backward(a, b, maps)
@@ -157,10 +114,8 @@ class _SSIM(torch.autograd.Function):
         dev = a.device
         gg = g.to(device=dev, dtype=torch.float32).contiguous()
         grad = torch.empty_like(a)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_ssim_grad(Cc, H, W, a.data_ptr(), b.data_ptr(), maps.data_ptr(), gg.data_ptr(), grad.data_ptr(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_ssim_grad")
+        _abi.call(_lib.hsr_loss_ssim_grad, "hsr_loss_ssim_grad", dev, Cc, H, W, a.data_ptr(), b.data_ptr(), maps.data_ptr(), gg.data_ptr(),
+                  grad.data_ptr())
         return grad.view(shape), None
 
 
@@ -175,18 +130,15 @@ class _TreeCE(torch.autograd.Function):
         if lab.shape[0] < L:
             raise RuntimeError("hsr_utils.losses: %d label planes for %d levels" % (lab.shape[0], L))
         lab = lab[:L].to(device=dev, dtype=torch.int64).contiguous()   # the reference calls .long()
-        sizes = (_ci * L)(*[int(s) for s in level_sizes])
+        sizes = (C.c_int * L)(*[int(s) for s in level_sizes])
         w = None if weights is None else (C.c_float * L)(*[float(x) for x in weights])
         # value now, gradient when (and if) autograd asks for it — the gradient pass multiplies by the incoming gradient itself, so
         # no K x H x W gradient is stashed and none is multiplied by `g` afterwards (include/hsr_losses.h, hsr_loss_tree_ce_value / _grad)
         out = torch.empty(L, dtype=torch.float32, device=dev)
         inv = torch.empty(L, dtype=torch.float32, device=dev)
         sc = torch.empty(int(_lib.hsr_loss_tree_ce_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_tree_ce_value(K, H, W, L, sizes, z.data_ptr(), lab.data_ptr(), int(ignore_index), out.data_ptr(),
-                                             inv.data_ptr(), sc.data_ptr(), sc.numel(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_tree_ce_value")
+        _abi.call(_lib.hsr_loss_tree_ce_value, "hsr_loss_tree_ce_value", dev, K, H, W, L, sizes, z.data_ptr(), lab.data_ptr(),
+                  int(ignore_index), out.data_ptr(), inv.data_ptr(), sc.data_ptr(), sc.numel())
         ctx.want = bool(logits.requires_grad)
         if ctx.want:
             ctx.save_for_backward(z, lab, inv)
@@ -209,11 +161,8 @@ class _TreeCE(torch.autograd.Function):
         dev = z.device
         g = g_total.to(device=dev, dtype=torch.float32).contiguous()
         grad = torch.empty_like(z)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_tree_ce_grad(K, H, W, L, sizes, w, z.data_ptr(), lab.data_ptr(), ignore_index, inv.data_ptr(), g.data_ptr(),
-                                            None, None, 0.0, grad.data_ptr(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_tree_ce_grad")
+        _abi.call(_lib.hsr_loss_tree_ce_grad, "hsr_loss_tree_ce_grad", dev, K, H, W, L, sizes, w, z.data_ptr(), lab.data_ptr(), ignore_index,
+                  inv.data_ptr(), g.data_ptr(), None, None, 0.0, grad.data_ptr())
         return grad.view(shape), None, None, None, None
 
 
@@ -273,12 +222,9 @@ class _TrackingLoss(torch.autograd.Function):
         dev = d.device
         out = torch.empty(4, dtype=torch.float32, device=dev)
         sc = torch.empty(int(_lib.hsr_loss_tracking_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_tracking_value(Cc, H, W, None if a is None else a.data_ptr(), None if b is None else b.data_ptr(), d.data_ptr(),
-                                              gd.data_ptr(), None if s is None else s.data_ptr(), float(sil_thres), int(bool(use_sil)), int(reduction),
-                                              float(w_depth), float(w_im), out.data_ptr(), sc.data_ptr(), sc.numel(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_tracking_value")
+        _abi.call(_lib.hsr_loss_tracking_value, "hsr_loss_tracking_value", dev, Cc, H, W, None if a is None else a.data_ptr(),
+                  None if b is None else b.data_ptr(), d.data_ptr(), gd.data_ptr(), None if s is None else s.data_ptr(), float(sil_thres),
+                  int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(), sc.data_ptr(), sc.numel())
         ctx.want = (bool(im is not None and im.requires_grad), bool(depth.requires_grad))
         if any(ctx.want):
             e = torch.empty(0, device=dev)
@@ -300,12 +246,9 @@ class _TrackingLoss(torch.autograd.Function):
         d_im = torch.empty_like(a) if ctx.want[0] else None
         d_d = torch.empty_like(d) if ctx.want[1] else None
         inv_ptr = out.data_ptr() + 12 if reduction == MEAN else None     # &out4[3]: 1 / selected pixels
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_tracking_grad(Cc, H, W, a.data_ptr() if Cc else None, b.data_ptr() if Cc else None, d.data_ptr(), gd.data_ptr(),
-                                             s.data_ptr() if use_sil else None, sil_thres, use_sil, w_depth, w_im, gg.data_ptr(), inv_ptr,
-                                             None if d_im is None else d_im.data_ptr(), None if d_d is None else d_d.data_ptr(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_tracking_grad")
+        _abi.call(_lib.hsr_loss_tracking_grad, "hsr_loss_tracking_grad", dev, Cc, H, W, a.data_ptr() if Cc else None,
+                  b.data_ptr() if Cc else None, d.data_ptr(), gd.data_ptr(), s.data_ptr() if use_sil else None, sil_thres, use_sil, w_depth,
+                  w_im, gg.data_ptr(), inv_ptr, None if d_im is None else d_im.data_ptr(), None if d_d is None else d_d.data_ptr())
         return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d), None, None, None, None, None, None, None)
 
 
@@ -389,12 +332,9 @@ class _LeafMLP(torch.autograd.Function):
         d_w = torch.empty_like(w) if (need[1] or need[2]) else None
         d_b = torch.empty_like(b) if (need[1] or need[2]) else None
         sc = _scratch(K, H, W, dev)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_leaf_mlp_ce(K, C, H, W, z.data_ptr(), w.data_ptr(), b.data_ptr(), lab.data_ptr(), int(ignore_index),
-                                           out.data_ptr(), None if d_sem is None else d_sem.data_ptr(), None if d_w is None else d_w.data_ptr(),
-                                           None if d_b is None else d_b.data_ptr(), sc.data_ptr(), sc.numel(), _stream(dev))
-        if rc < 0:
-            _glue._fail(rc, "hsr_loss_leaf_mlp_ce")
+        _abi.call(_lib.hsr_loss_leaf_mlp_ce, "hsr_loss_leaf_mlp_ce", dev, K, C, H, W, z.data_ptr(), w.data_ptr(), b.data_ptr(), lab.data_ptr(),
+                  int(ignore_index), out.data_ptr(), None if d_sem is None else d_sem.data_ptr(), None if d_w is None else d_w.data_ptr(),
+                  None if d_b is None else d_b.data_ptr(), sc.data_ptr(), sc.numel())
         ctx.grads = (None if d_sem is None else d_sem.view(sem.shape), None if d_w is None else d_w.view(weight.shape),
                      None if d_b is None else d_b.view(bias.shape))
         return out[0]
@@ -428,7 +368,7 @@ class _SemanticHeads(torch.autograd.Function):
         if wt.shape[1] != K or bias.numel() != Cc:
             raise RuntimeError("hsr_utils.losses: weight %s / bias %s do not match %d input channels" % (tuple(weight.shape), tuple(bias.shape), K))
         b = _dev2(bias.reshape(-1), "bias")
-        sizes = (_ci * L)(*[int(s) for s in level_sizes])
+        sizes = (C.c_int * L)(*[int(s) for s in level_sizes])
         levels = torch.empty(L, dtype=torch.float32, device=dev)
         inv = torch.empty(L, dtype=torch.float32, device=dev)
         leaf = torch.empty(1, dtype=torch.float32, device=dev)
@@ -438,16 +378,11 @@ class _SemanticHeads(torch.autograd.Function):
         d_b = torch.empty_like(b) if (need[1] or need[2]) else None
         sc1 = torch.empty(int(_lib.hsr_loss_tree_ce_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
         sc2 = _scratch(K, H, W, dev)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_loss_tree_ce_value(K, H, W, L, sizes, z.data_ptr(), tree_lab.data_ptr(), int(ignore_index), levels.data_ptr(),
-                                             inv.data_ptr(), sc1.data_ptr(), sc1.numel(), _stream(dev))
-            if rc < 0:
-                _glue._fail(rc, "hsr_loss_tree_ce_value")
-            rc = _lib.hsr_loss_leaf_mlp_ce(K, Cc, H, W, z.data_ptr(), wt.data_ptr(), b.data_ptr(), leaf_lab.data_ptr(), int(ignore_index),
-                                           leaf.data_ptr(), None if d_sem is None else d_sem.data_ptr(), None if d_w is None else d_w.data_ptr(),
-                                           None if d_b is None else d_b.data_ptr(), sc2.data_ptr(), sc2.numel(), _stream(dev))
-            if rc < 0:
-                _glue._fail(rc, "hsr_loss_leaf_mlp_ce")
+        _abi.call(_lib.hsr_loss_tree_ce_value, "hsr_loss_tree_ce_value", dev, K, H, W, L, sizes, z.data_ptr(), tree_lab.data_ptr(),
+                  int(ignore_index), levels.data_ptr(), inv.data_ptr(), sc1.data_ptr(), sc1.numel())
+        _abi.call(_lib.hsr_loss_leaf_mlp_ce, "hsr_loss_leaf_mlp_ce", dev, K, Cc, H, W, z.data_ptr(), wt.data_ptr(), b.data_ptr(),
+                  leaf_lab.data_ptr(), int(ignore_index), leaf.data_ptr(), None if d_sem is None else d_sem.data_ptr(),
+                  None if d_w is None else d_w.data_ptr(), None if d_b is None else d_b.data_ptr(), sc2.data_ptr(), sc2.numel())
         ctx.want = need
         if need[0]:
             ctx.save_for_backward(z, tree_lab, inv)
@@ -470,11 +405,8 @@ class _SemanticHeads(torch.autograd.Function):
             gg = g.to(device=dev, dtype=torch.float32).contiguous()
             wl = (C.c_float * L)(*([w_tree] * L))
             grad = torch.empty_like(z)
-            with torch.cuda.device(dev):
-                rc = _lib.hsr_loss_tree_ce_grad(K, H, W, L, sizes, wl, z.data_ptr(), tree_lab.data_ptr(), ignore_index, inv.data_ptr(),
-                                                gg.data_ptr(), d_sem.data_ptr(), gg.data_ptr(), w_leaf, grad.data_ptr(), _stream(dev))
-            if rc < 0:
-                _glue._fail(rc, "hsr_loss_tree_ce_grad")
+            _abi.call(_lib.hsr_loss_tree_ce_grad, "hsr_loss_tree_ce_grad", dev, K, H, W, L, sizes, wl, z.data_ptr(), tree_lab.data_ptr(),
+                      ignore_index, inv.data_ptr(), gg.data_ptr(), d_sem.data_ptr(), gg.data_ptr(), w_leaf, grad.data_ptr())
             out_sem = grad.view(shape)
         gl = g * w_leaf
         return (out_sem, None if (d_w is None or not ctx.want[1]) else d_w * gl, None if (d_b is None or not ctx.want[2]) else d_b * gl,

@@ -14,32 +14,17 @@ group with plain-number lr / betas / eps, weight_decay == 0 and amsgrad, maximiz
 weight decay off (and foreach not explicitly False).  Every other tensor goes through torch's own functional adam() with its
 group's settings, in the same step().
 """
-import ctypes as C
 import numbers
 
 import torch
 from torch.optim.adam import adam as _torch_adam
 from torch.optim.optimizer import _get_scalar_dtype
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _abi
 
-_lib = _glue._lib
-_vp, _ci = C.c_void_p, C.c_int
+_lib = _abi.lib
+_AdamTensor = _abi.hsr_adam_tensor
 
-
-class _AdamTensor(C.Structure):
-    """hsr_adam_tensor (include/hsr_optim.h)"""
-    _fields_ = [("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp), ("numel", C.c_int64),
-                ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("eps", C.c_float), ("one_minus_beta1", C.c_float),
-                ("beta2", C.c_float), ("one_minus_beta2", C.c_float)]
-
-
-_lib.hsr_adam_table_entry_bytes.restype = C.c_size_t
-_lib.hsr_adam_table_entry_bytes.argtypes = []
-_lib.hsr_adam_step.restype = _ci
-_lib.hsr_adam_step.argtypes = [_ci, C.POINTER(_AdamTensor), _vp]
-_lib.hsr_track_keep_best.restype = _ci
-_lib.hsr_track_keep_best.argtypes = [_ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
 
 def _dense(t):
     """non-overlapping and dense: the numel elements fill one contiguous span of memory, in some order of the dimensions"""
@@ -137,10 +122,7 @@ class Adam(torch.optim.Adam):
                 self._torch_step(group, rest)
         for dev, entries in tables.items():
             arr = (_AdamTensor * len(entries))(*entries)
-            with torch.cuda.device(dev):
-                rc = _lib.hsr_adam_step(len(entries), arr, torch.cuda.current_stream(dev).cuda_stream)
-            if rc < 0:
-                _glue._fail(rc, "hsr_adam_step")
+            _abi.call(_lib.hsr_adam_step, "hsr_adam_step", dev, len(entries), arr)
         self.last_fused_tensors = sum(len(e) for e in tables.values())
         self.last_fused_numel = fused_numel
         return loss
@@ -178,13 +160,8 @@ class TrackingCandidate:
                                % (self.best_loss.device, loss.dtype, tuple(loss.shape), loss.device))
         if not (rots.is_contiguous() and trans.is_contiguous() and rots.device == loss.device and trans.device == loss.device):
             raise RuntimeError("TrackingCandidate.update: cam_unnorm_rots / cam_trans must stay contiguous on %s" % loss.device)
-        dev = loss.device
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_track_keep_best(rots.shape[2], self.time_idx, loss.data_ptr(), self.best_loss.data_ptr(), rots.data_ptr(),
-                                          trans.data_ptr(), self.cam_unnorm_rot.data_ptr(), self.cam_tran.data_ptr(),
-                                          torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _glue._fail(rc, "hsr_track_keep_best")
+        _abi.call(_lib.hsr_track_keep_best, "hsr_track_keep_best", loss.device, rots.shape[2], self.time_idx, loss.data_ptr(),
+                  self.best_loss.data_ptr(), rots.data_ptr(), trans.data_ptr(), self.cam_unnorm_rot.data_ptr(), self.cam_tran.data_ptr())
 
     @torch.no_grad()
     def restore(self, params):

@@ -15,27 +15,13 @@ ONE order-preserving device compaction (include/hsr_densify.h: hsr_prune_mask + 
 one scan, one copy kernel, one read-back of the new row count.  Results are bit-identical to the reference's (pinned by
 tests/golden/densify_prune_concat.npz, which holds the reference's own outputs).  There is no CPU path.
 """
-import ctypes as C
-
 import torch
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _abi
 
-_lib = _glue._lib
-_vp, _ci, _cf, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_lib = _abi.lib
+_RowTable = _abi.hsr_row_table
 MAX_TABLES = 40   # HSR_MAX_ROW_TABLES
-
-
-class _RowTable(C.Structure):
-    _fields_ = [("src", _vp), ("append", _vp), ("dst", _vp), ("cols", _ci)]
-
-
-_lib.hsr_compact_scratch_bytes.restype = _sz
-_lib.hsr_compact_scratch_bytes.argtypes = [_ci]
-_lib.hsr_prune_mask.restype = _ci
-_lib.hsr_prune_mask.argtypes = [_ci, _ci, _vp, _vp, _cf, _cf, _vp, _vp, _vp, _sz, _vp]
-_lib.hsr_compact_append_rows.restype = _ci
-_lib.hsr_compact_append_rows.argtypes = [_ci, _vp, _ci, _ci, C.POINTER(_RowTable), _ci, _vp, _vp, _sz, _vp]
 
 CAMERA_KEYS = ('cam_unnorm_rots', 'cam_trans')     # not per-Gaussian: never pruned or extended (:141)
 VARIABLE_KEYS = ('means2D_gradient_accum', 'denom', 'max_2D_radius', 'timestep')   # :160-164
@@ -78,12 +64,8 @@ def compact_append(tensors, keep=None, appended=None, n_append=0, scanned=None):
     else:
         scratch = torch.empty(int(_lib.hsr_compact_scratch_bytes(P)), dtype=torch.uint8, device=dev)
         rows_dev = torch.empty(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.hsr_compact_append_rows(P, keep.data_ptr() if keep is not None else None, 1 if scanned is not None else 0,
-                                          len(tensors), tabs, int(n_append), rows_dev.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                                          torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        _glue._fail(rc, "hsr_compact_append_rows")
+    _abi.call(_lib.hsr_compact_append_rows, "hsr_compact_append_rows", dev, P, keep.data_ptr() if keep is not None else None,
+              1 if scanned is not None else 0, len(tensors), tabs, int(n_append), rows_dev.data_ptr(), scratch.data_ptr(), scratch.numel())
     rows = P + n_append if keep is None else int(rows_dev.item())
     return [o[:rows].reshape((rows,) + tuple(t.shape[1:])) for o, t in zip(out, tensors)]
 
@@ -171,12 +153,9 @@ def prune_mask(params, variables, removal_opacity_threshold, remove_big):
     scratch = torch.empty(int(_lib.hsr_compact_scratch_bytes(P)), dtype=torch.uint8, device=dev)
     kept = torch.empty(1, dtype=torch.int32, device=dev)
     lo2, ls2 = _rows2d(lo, "logit_opacities"), _rows2d(ls, "log_scales")
-    with torch.cuda.device(dev):
-        rc = _lib.hsr_prune_mask(P, int(ls2.shape[1]), lo2.data_ptr() if P else None, ls2.data_ptr() if P else None,
-                                 float(removal_opacity_threshold), float(big), keep.data_ptr() if P else None, kept.data_ptr(),
-                                 scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc < 0:
-        _glue._fail(rc, "hsr_prune_mask")
+    _abi.call(_lib.hsr_prune_mask, "hsr_prune_mask", dev, P, int(ls2.shape[1]), lo2.data_ptr() if P else None,
+              ls2.data_ptr() if P else None, float(removal_opacity_threshold), float(big), keep.data_ptr() if P else None,
+              kept.data_ptr(), scratch.data_ptr(), scratch.numel())
     return keep, (scratch, kept)
 
 

@@ -18,24 +18,13 @@ There is no CPU path: tensors must live on a HIP device and libhsr_rast.so must 
 Deviation kept on purpose: for anisotropic Gaussians (log_scales [P,3]) the reference's semantic variant tiles the
 scales to [P,9] (slam_helpers.py:215) and the rasterizer then reads out of bounds; here scales stay [P,3].
 """
-import ctypes as C
-
 import torch
 
-from diff_gaussian_rasterization import _C as _glue
+from diff_gaussian_rasterization import _C as _glue, _abi
 
 ROT_PARAMS, ROT_TRANSFORMED = 0, 1
 
-_lib = _glue._lib
-_vp, _ci, _sz = C.c_void_p, C.c_int, C.c_size_t
-_lib.hsr_frame_prep_scratch_bytes.restype = _sz
-_lib.hsr_frame_prep_scratch_bytes.argtypes = [_ci]
-_lib.hsr_frame_prep_forward.restype = _ci
-_lib.hsr_frame_prep_forward.argtypes = [_ci, _ci, _ci, _ci] + [_vp] * 6 + [_ci, _ci] + [_vp] * 8
-_lib.hsr_frame_prep_backward.restype = _ci
-_lib.hsr_frame_prep_backward.argtypes = [_ci, _ci, _ci, _ci] + [_vp] * 6 + [_ci, _ci] + [_vp] * 14 + [_sz, _vp]
-_lib.hsr_frame_prep_backward_params.restype = _ci
-_lib.hsr_frame_prep_backward_params.argtypes = _lib.hsr_frame_prep_backward.argtypes
+_lib = _abi.lib
 
 
 def _dev_f32(t, what):
@@ -89,14 +78,10 @@ class _FramePrep(torch.autograd.Function):
         out_op = torch.empty_like(logit_opacities)
         out_sc = torch.empty((P, 3), **o)
         out_sil = torch.empty((P, 3), **o) if w2c is not None else torch.empty(0, **o)
-        with torch.cuda.device(dev):
-            rc = _lib.hsr_frame_prep_forward(P, S, int(transform_rots), int(rot_source), _p(means3D), _p(unnorm_rotations),
-                                             _p(logit_opacities), _p(log_scales), cam_unnorm_rots.data_ptr(), cam_trans.data_ptr(),
-                                             frames, time_idx, None if w2c is None else w2c.data_ptr(), _p(out_means),
-                                             _p(out_tr), _p(out_rot), _p(out_op), _p(out_sc),
-                                             _p(out_sil) if w2c is not None else None, torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            _glue._fail(rc, "hsr_frame_prep_forward")
+        _abi.call(_lib.hsr_frame_prep_forward, "hsr_frame_prep_forward", dev, P, S, int(transform_rots), int(rot_source), _p(means3D),
+                  _p(unnorm_rotations), _p(logit_opacities), _p(log_scales), cam_unnorm_rots.data_ptr(), cam_trans.data_ptr(),
+                  frames, time_idx, None if w2c is None else w2c.data_ptr(), _p(out_means), _p(out_tr), _p(out_rot), _p(out_op),
+                  _p(out_sc), _p(out_sil) if w2c is not None else None)
         ctx.save_for_backward(means3D, unnorm_rotations, logit_opacities, log_scales, cam_unnorm_rots, cam_trans,
                               w2c if w2c is not None else torch.empty(0, **o))
         ctx.meta = (P, S, transform_rots, int(rot_source), frames, time_idx, bool(gaussians_grad), bool(camera_grad), w2c is not None)
@@ -131,15 +116,12 @@ class _FramePrep(torch.autograd.Function):
         scratch = torch.empty(int(_lib.hsr_frame_prep_scratch_bytes(P)), dtype=torch.uint8, device=dev)
 
         def run(g_tr_arg, d_unnorm_out, cam_out):
-            with torch.cuda.device(dev):
-                rc = _lib.hsr_frame_prep_backward_params(
-                    P, S, int(transform_rots), rot_source, _p(means3D), _p(unnorm_rotations), _p(logit_opacities), _p(log_scales),
-                    cam_unnorm_rots.data_ptr(), cam_trans.data_ptr(), frames, time_idx, w2c.data_ptr() if has_sil else None,
-                    _p(g_means), _p(g_tr_arg), _p(g_rot), _p(g_op), _p(g_sc), _p(g_sil), _p(d_means), _p(d_unnorm_out), _p(d_logit),
-                    _p(d_ls), _p(d_rots) if cam_out else None, _p(d_trans) if cam_out else None, scratch.data_ptr(), scratch.numel(),
-                    torch.cuda.current_stream(dev).cuda_stream)
-            if rc < 0:
-                _glue._fail(rc, "hsr_frame_prep_backward")
+            _abi.call(
+                _lib.hsr_frame_prep_backward_params, "hsr_frame_prep_backward", dev,
+                P, S, int(transform_rots), rot_source, _p(means3D), _p(unnorm_rotations), _p(logit_opacities), _p(log_scales),
+                cam_unnorm_rots.data_ptr(), cam_trans.data_ptr(), frames, time_idx, w2c.data_ptr() if has_sil else None,
+                _p(g_means), _p(g_tr_arg), _p(g_rot), _p(g_op), _p(g_sc), _p(g_sil), _p(d_means), _p(d_unnorm_out), _p(d_logit),
+                _p(d_ls), _p(d_rots) if cam_out else None, _p(d_trans) if cam_out else None, scratch.data_ptr(), scratch.numel())
 
         run(g_tr, d_unnorm, camera_grad)
         if gaussians_grad:

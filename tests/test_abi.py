@@ -1,7 +1,8 @@
-"""CPU suite: the C-ABI library loads and exports exactly what include/hsr_rasterizer.h declares, the
-ctypes glue agrees with the header's parameter lists, and host-only entry points behave (no compute calls:
-there is no GPU here)."""
+"""CPU suite: the C-ABI library loads and exports exactly what include/hsr_*.h declare, the ctypes signatures, structures and limits
+of diff_gaussian_rasterization/_abi.py agree with the headers type class by type class, and host-only entry points behave (no compute
+calls: there is no GPU here)."""
 import ctypes as C
+import glob
 import os
 import re
 
@@ -9,60 +10,160 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsr_rasterizer.h")
-HEADERS = [HEADER, os.path.join(ROOT, "include", "hsr_frame_prep.h"), os.path.join(ROOT, "include", "hsr_losses.h"),
-           os.path.join(ROOT, "include", "hsr_densify.h")]
+HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "hsr_*.h")))    # a glob: the next header is covered without an edit
+N_PROTOTYPES = 63      # asserted as a number: a regex that silently stops matching must not pass
+
+# what the four older headers declare at least (the newer three are pinned exactly, each in its own suite: test_eval_cpu.py,
+# test_optim_cpu.py, test_keyframes_cpu.py)
+DECLARED = {
+    "hsr_rasterizer.h": {
+        "hsr_forward", "hsr_forward_semantic", "hsr_backward", "hsr_backward_semantic", "hsr_mark_visible", "hsr_required_geometry_bytes",
+        "hsr_required_image_bytes", "hsr_required_binning_bytes", "hsr_last_error", "hsr_version", "hsr_get_state_layout",
+        "hsr_profile_enable", "hsr_profile_read", "hsr_stage_name"},
+    "hsr_frame_prep.h": {"hsr_frame_prep_forward", "hsr_frame_prep_backward", "hsr_frame_prep_backward_params",
+                         "hsr_frame_prep_scratch_bytes"},
+    "hsr_losses.h": {
+        "hsr_loss_l1", "hsr_loss_l1_grad", "hsr_loss_ssim", "hsr_loss_ssim_value", "hsr_loss_ssim_grad", "hsr_loss_tree_ce",
+        "hsr_loss_tree_ce_value", "hsr_loss_tree_ce_grad", "hsr_loss_tree_ce_scratch_bytes", "hsr_loss_tracking_value",
+        "hsr_loss_tracking_grad", "hsr_loss_tracking_scratch_bytes", "hsr_loss_leaf_mlp_ce", "hsr_loss_scratch_bytes"},
+    "hsr_densify.h": {"hsr_densify_frame", "hsr_densify_scratch_bytes", "hsr_prune_mask", "hsr_compact_append_rows",
+                      "hsr_compact_scratch_bytes"},
+}
+SCALARS = {"int": "int", "unsigned": "unsigned", "float": "float", "double": "double", "size_t": "size_t"}
+
+
+def _source(path):
+    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+
+
+def _classify(decl, named):
+    """the class of one C parameter (`named`: the declaration ends in the parameter's name) or return type: one of SCALARS,
+    "const char*" (a return type only; as a parameter it is a device pointer like any other), or ("pointer", pointee type)"""
+    words = decl.replace("*", " * ").split()
+    if named:
+        assert re.fullmatch(r"\w+", words[-1]), decl
+        words = words[:-1]
+    if "*" in words:
+        assert words.count("*") == 1 and words[-1] == "*", decl
+        pointee = [w for w in words[:-1] if w != "const"]
+        assert len(pointee) == 1, decl
+        return "const char*" if (not named and words == ["const", "char", "*"]) else ("pointer", pointee[0])
+    assert len(words) == 1 and words[0] in SCALARS, "unparsed C type: %r" % decl
+    return SCALARS[words[0]]
 
 
 def _prototypes():
-    src = "\n".join(open(h).read() for h in HEADERS)
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    """every function prototype of every header: name -> (header file name, class of the return type, [class of each parameter])"""
     protos = {}
-    for m in re.finditer(r"\b(?:int|size_t|const char\*)\s+(hsr_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
-        name, params = m.group(1), m.group(2).strip()
-        n = 0 if params in ("", "void") else len([p for p in params.split(",") if p.strip()])
-        protos[name] = n
+    for path in HEADERS:
+        for m in re.finditer(r"^((?:const\s+)?\w+\s*\*?)\s*(hsr_\w+)\s*\(([^;{}()]*)\)\s*;", _source(path), flags=re.M):
+            ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+            assert name not in protos, name
+            params = [] if params in ("", "void") else [_classify(p, True) for p in params.split(",")]
+            protos[name] = (os.path.basename(path), _classify(ret, False), params)
     return protos
+
+
+def _ctype_class(t):
+    """the class of a ctypes type, in the vocabulary of _classify; a pointer names its pointee where ctypes knows it"""
+    for ct, cls in ((C.c_int, "int"), (C.c_uint, "unsigned"), (C.c_float, "float"), (C.c_double, "double"), (C.c_size_t, "size_t"),
+                    (C.c_char_p, "const char*")):
+        if t is ct:
+            return cls
+    if t is C.c_void_p:
+        return ("pointer", None)
+    if isinstance(t, type) and issubclass(t, C._Pointer):
+        pointee = t._type_
+        return ("pointer", pointee.__name__ if issubclass(pointee, C.Structure) else _ctype_class(pointee))
+    raise AssertionError("a ctypes type this test does not know: %r" % (t,))
+
+
+def _agree(declared, header):
+    """does a ctypes class satisfy a header class?  Scalars must be equal.  Any ctypes pointer satisfies a pointer, but one that
+    names its pointee must name the header's: POINTER(struct) the same struct, POINTER(c_int) an int."""
+    if isinstance(header, tuple) and isinstance(declared, tuple):
+        return declared[1] is None or declared[1] == header[1]
+    return declared == header
+
+
+def check_signature(name, proto):
+    """the declared ctypes signature of `name` agrees with its prototype (an entry of _prototypes()) class by class"""
+    from diff_gaussian_rasterization import _abi
+    header, ret, params = proto
+    fn = getattr(_abi.lib, name)
+    assert fn.argtypes is not None and len(fn.argtypes) == len(params), (name, len(fn.argtypes or ()), len(params))
+    assert _agree(_ctype_class(fn.restype), ret), "%s (%s): restype %r, the header returns %r" % (name, header, fn.restype, ret)
+    for i, (t, cls) in enumerate(zip(fn.argtypes, params)):
+        assert _agree(_ctype_class(t), cls), "%s (%s): parameter %d (from 0) is %s, the header says %r" % (name, header, i, t.__name__, cls)
+
+
+def check_header(header):
+    """every prototype of include/<header> is exported by the library and bound with the header's types; returns their names"""
+    from diff_gaussian_rasterization import _C
+    protos = {n: p for n, p in _prototypes().items() if p[0] == header}
+    lib = C.CDLL(_C._LIB_PATH)
+    for name, proto in protos.items():
+        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
+        check_signature(name, proto)
+    return set(protos)
 
 
 def test_library_exports_every_declared_symbol():
     from diff_gaussian_rasterization import _C
     protos = _prototypes()
-    assert {"hsr_forward", "hsr_forward_semantic", "hsr_backward", "hsr_backward_semantic", "hsr_mark_visible",
-            "hsr_required_geometry_bytes", "hsr_required_image_bytes", "hsr_required_binning_bytes", "hsr_last_error",
-            "hsr_version", "hsr_get_state_layout", "hsr_profile_enable", "hsr_profile_read", "hsr_stage_name",
-            "hsr_frame_prep_forward", "hsr_frame_prep_backward", "hsr_frame_prep_scratch_bytes",
-            "hsr_loss_l1", "hsr_loss_ssim", "hsr_loss_tree_ce", "hsr_loss_leaf_mlp_ce", "hsr_loss_scratch_bytes", "hsr_densify_frame", "hsr_densify_scratch_bytes",
-            "hsr_prune_mask", "hsr_compact_append_rows", "hsr_compact_scratch_bytes"} <= set(protos)
+    assert len(HEADERS) >= 7 and len(protos) == N_PROTOTYPES, (len(HEADERS), len(protos))
+    for header, names in DECLARED.items():
+        assert names <= {n for n, p in protos.items() if p[0] == header}, header
     lib = C.CDLL(_C._LIB_PATH)
     for name in protos:
         assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
 
 
 def test_ctypes_signatures_match_header():
-    from diff_gaussian_rasterization import _C
+    """every prototype has a declared signature whose restype and argtypes agree with it class by class (int / unsigned / float /
+    double / size_t / const char* / pointer): ctypes converts silently, so a c_int where the header says float would hand a kernel a
+    wrong value and nothing else would notice"""
+    from diff_gaussian_rasterization import _abi
     protos = _prototypes()
-    for name in ("hsr_forward", "hsr_forward_semantic", "hsr_backward", "hsr_backward_semantic", "hsr_mark_visible",
-                 "hsr_get_state_layout", "hsr_required_binning_bytes", "hsr_required_image_bytes"):
-        fn = getattr(_C._lib, name)
-        assert len(fn.argtypes) == protos[name], (name, len(fn.argtypes), protos[name])
-    from hsr_utils import slam_helpers
-    for name in ("hsr_frame_prep_forward", "hsr_frame_prep_backward", "hsr_frame_prep_backward_params", "hsr_frame_prep_scratch_bytes"):
-        fn = getattr(slam_helpers._lib, name)
-        assert len(fn.argtypes) == protos[name], (name, len(fn.argtypes), protos[name])
-    from hsr_utils import densify
-    for name in ("hsr_densify_frame", "hsr_densify_scratch_bytes"):
-        fn = getattr(densify._lib, name)
-        assert len(fn.argtypes) == protos[name], (name, len(fn.argtypes), protos[name])
-    from hsr_utils import slam_external
-    for name in ("hsr_prune_mask", "hsr_compact_append_rows", "hsr_compact_scratch_bytes"):
-        fn = getattr(slam_external._lib, name)
-        assert len(fn.argtypes) == protos[name], (name, len(fn.argtypes), protos[name])
-    from hsr_utils import losses
-    for name in ("hsr_loss_l1", "hsr_loss_l1_grad", "hsr_loss_ssim", "hsr_loss_ssim_value", "hsr_loss_ssim_grad", "hsr_loss_tree_ce", "hsr_loss_tree_ce_value", "hsr_loss_tree_ce_grad", "hsr_loss_tree_ce_scratch_bytes",
-                 "hsr_loss_tracking_value", "hsr_loss_tracking_grad", "hsr_loss_tracking_scratch_bytes", "hsr_loss_leaf_mlp_ce", "hsr_loss_scratch_bytes"):
-        fn = getattr(losses._lib, name)
-        assert len(fn.argtypes) == protos[name], (name, len(fn.argtypes), protos[name])
+    table = [s[0] for s in _abi.SIGNATURES]
+    assert sorted(table) == sorted(protos), set(table) ^ set(protos)      # every prototype once, nothing else
+    for path in HEADERS:      # and each header's functions in the header's order, so that a line can be read against its prototype
+        of_header = [n for n, p in protos.items() if p[0] == os.path.basename(path)]
+        assert [n for n in table if n in of_header] == of_header, path
+    for name, proto in protos.items():
+        check_signature(name, proto)
+
+
+def test_structures_match_header():
+    """the five ctypes structures carry the field names of their typedefs, in order; the Adam entry keeps the library's size"""
+    from diff_gaussian_rasterization import _C, _abi
+    from hsr_utils import optim, slam_external
+    src = "\n".join(_source(h) for h in HEADERS)
+    checked = set()
+    for m in re.finditer(r"typedef struct (hsr_\w+) \{(.*?)\} \1;", src, flags=re.S):
+        mirror = getattr(_abi, m.group(1), None)
+        if mirror is None:
+            continue
+        names = [re.search(r"(\w+)\s*$", d).group(1) for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
+        assert names == [f[0] for f in mirror._fields_], m.group(1)
+        checked.add(mirror)
+    assert checked == {_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout, _abi.hsr_adam_tensor, _abi.hsr_row_table}
+    assert (_C._HsrBuffer, _C._Ticket, _C._StateLayout) == (_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout)
+    assert optim._AdamTensor is _abi.hsr_adam_tensor and slam_external._RowTable is _abi.hsr_row_table
+    assert _abi.lib.hsr_adam_table_entry_bytes() == C.sizeof(_abi.hsr_adam_tensor) == 64
+
+
+def test_python_limits_equal_header_defines():
+    from diff_gaussian_rasterization import _C
+    from hsr_utils import evaluate, keyframes, losses, slam_external
+    defines = {m.group(1): int(m.group(2)) for h in HEADERS
+               for m in re.finditer(r"^#define\s+(HSR_\w+)\s+\(?(-?\d+)\)?\s*$", _source(h), flags=re.M)}
+    for value, name in ((evaluate.MAX_CLASSES, "HSR_EVAL_MAX_CLASSES"), (evaluate.MAX_LEVELS, "HSR_EVAL_MAX_LEVELS"),
+                        (evaluate.LEAF_MAX_K, "HSR_EVAL_LEAF_MAX_K"), (evaluate.LEAF_MAX_C, "HSR_EVAL_LEAF_MAX_C"),
+                        (evaluate.MAX_DILATION, "HSR_EVAL_MAX_DILATION"), (keyframes.MAX_POINTS, "HSR_KF_MAX_POINTS"),
+                        (losses.SUM, "HSR_LOSS_SUM"), (losses.MEAN, "HSR_LOSS_MEAN"), (_C.HSR_PENDING, "HSR_PENDING"),
+                        (_C.HSR_ERR_BUFFER_TOO_SMALL, "HSR_ERR_BUFFER_TOO_SMALL"), (slam_external.MAX_TABLES, "HSR_MAX_ROW_TABLES")):
+        assert value == defines[name], (name, value, defines[name])
 
 
 def test_host_only_entry_points():

@@ -1,18 +1,12 @@
 """CPU suite for the map evaluation: the checker's boundary restatements agree with each other bit for bit, the host-only pieces of
-hsr_utils/evaluate.py (trajectory ATE, tree lookup table) match the reference's semantics, and the C ABI of include/hsr_eval.h is
-exported and bound with the right parameter counts."""
-import ctypes as C
-import os
-import re
-
+hsr_utils/evaluate.py (trajectory ATE, tree lookup table) match the reference's semantics, and the host-only entry points of
+include/hsr_eval.h answer and its prototypes are exported and bound with the right types (the one checker of tests/test_abi.py)."""
 import numpy as np
 import pytest
 import torch
 
 import eval_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsr_eval.h")
+from test_abi import check_header
 
 
 def blob_labels(g, H, W, values, n_blobs=12):
@@ -132,25 +126,10 @@ def test_tree_lookup_table_missing_and_duplicate():
     assert t[(0 * 3 + 1) * 4 + 2] == 9 and t[(1 * 3 + 0) * 4 + 0] == 11 and (t == -1).sum() == 21
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\b(?:int|size_t)\s+(hsr_eval_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
-        params = m.group(2).strip()
-        protos[m.group(1)] = 0 if params in ("", "void") else len([p for p in params.split(",") if p.strip()])
-    return protos
-
-
 def test_eval_abi_exported_and_bound():
-    from diff_gaussian_rasterization import _C
-    from hsr_utils import evaluate
-    protos = _prototypes()
     assert {"hsr_eval_frame_metrics", "hsr_eval_labels_flat", "hsr_eval_labels_tree", "hsr_eval_labels_leaf", "hsr_eval_iou_counts",
-            "hsr_eval_frame_miou", "hsr_eval_metrics_scratch_bytes", "hsr_eval_leaf_scratch_bytes", "hsr_eval_iou_scratch_bytes"} <= set(protos)
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, n in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        assert len(getattr(evaluate._lib, name).argtypes) == n, name
+            "hsr_eval_frame_miou", "hsr_eval_metrics_scratch_bytes", "hsr_eval_leaf_scratch_bytes",
+            "hsr_eval_iou_scratch_bytes"} <= check_header("hsr_eval.h")
 
 
 def test_scratch_sizes_host_only():

@@ -1,19 +1,18 @@
 """CPU suite for the keyframe selection: tests/keyframe_ref.py in fp32 on the CPU reproduces the committed outputs of the reference's own
 keyframe_selection_overlap (tests/golden/keyframes/*.npz, written by tests/golden/make_keyframe_golden.py), the fixtures meet the
-conditions the borderline rule needs, and the C ABI of include/hsr_keyframes.h is exported and bound with the right parameter counts."""
-import ctypes as C
+conditions the borderline rule needs, and the prototypes of include/hsr_keyframes.h are exported and bound with the right types (the
+one checker of tests/test_abi.py)."""
 import glob
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import keyframe_ref as R
+from test_abi import check_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "hsr_keyframes.h")
 FIXTURES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "keyframes", "*.npz")))
 NAMES = [os.path.basename(p)[:-4] for p in FIXTURES]
 
@@ -98,25 +97,9 @@ def test_selection_order_is_stable_descending():
     assert R.selection_order([]) == [] and R.selection_order([0, 0]) == []
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\b(?:int|size_t)\s+(hsr_kf_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
-        params = m.group(2).strip()
-        protos[m.group(1)] = 0 if params in ("", "void") else len([p for p in params.split(",") if p.strip()])
-    return protos
-
-
 def test_keyframes_abi_exported_and_bound():
-    from diff_gaussian_rasterization import _C
-    from hsr_utils import keyframes
-    protos = _prototypes()
     assert {"hsr_kf_valid_rows", "hsr_kf_sample_points", "hsr_kf_sample_scratch_bytes", "hsr_kf_round_keys",
-            "hsr_kf_overlap_counts"} == set(protos)
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, n in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        assert len(getattr(keyframes._lib, name).argtypes) == n, name
+            "hsr_kf_overlap_counts"} == check_header("hsr_keyframes.h")
 
 
 def test_argument_validation_without_gpu():

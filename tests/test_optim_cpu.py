@@ -1,34 +1,20 @@
-"""CPU suite for the optimizer step (include/hsr_optim.h, hsr_utils/optim.py): the library exports what the header declares, the
-ctypes glue agrees with the header, host-side argument checks work without a GPU, and on CPU tensors hsr_utils.optim.Adam is
-torch.optim.Adam (every tensor falls back to torch's own functional adam())."""
+"""CPU suite for the optimizer step (include/hsr_optim.h, hsr_utils/optim.py): the table entry's layout agrees with the library,
+host-side argument checks work without a GPU, and on CPU tensors hsr_utils.optim.Adam is torch.optim.Adam (every tensor falls back to
+torch's own functional adam()).  The header's prototypes are exported and bound with the right types (the one checker of tests/test_abi.py)."""
 import ctypes as C
 import os
 import re
 
 import torch
 
+from test_abi import check_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "hsr_optim.h")
 
 
-def _prototypes():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"\b(?:int|size_t|const char\*)\s+(hsr_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
-        name, params = m.group(1), m.group(2).strip()
-        protos[name] = 0 if params in ("", "void") else len([p for p in params.split(",") if p.strip()])
-    return protos
-
-
 def test_header_prototypes_are_exported_and_bound():
-    from diff_gaussian_rasterization import _C
-    from hsr_utils import optim
-    protos = _prototypes()
-    assert set(protos) == {"hsr_adam_table_entry_bytes", "hsr_adam_step", "hsr_track_keep_best"}
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, n in protos.items():
-        assert hasattr(lib, name), name
-        assert len(getattr(optim._lib, name).argtypes) == n, (name, n)
+    assert check_header("hsr_optim.h") == {"hsr_adam_table_entry_bytes", "hsr_adam_step", "hsr_track_keep_best"}
 
 
 def test_table_entry_layout_matches_the_library():
