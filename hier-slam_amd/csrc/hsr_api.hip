@@ -47,15 +47,19 @@ uint32_t higher_msb(uint32_t n)  // reference getHigherMsb, rasterizer_impl.cu:3
     return msb;
 }
 
+// HSR_BWD_IMPL, read here and nowhere else: "legacy" initialises the accumulation mode, "valu" forces the all-VALU tile kernel
+bool bwd_impl_is(const char* name)
+{
+    static const char* e = getenv("HSR_BWD_IMPL");
+    return e && !strcmp(e, name);
+}
+
 // backward accumulation mode: 0 packed per-Gaussian rows (default), 2 legacy separate arrays (1, per-instance rows, was an
 // experiment and is refused).  Initialised from HSR_BWD_IMPL=legacy, changed with hsr_set_backward_mode().
 int g_bwd_mode = -1;
 int backward_mode()
 {
-    if (g_bwd_mode < 0) {
-        const char* e = getenv("HSR_BWD_IMPL");
-        g_bwd_mode = (e && !strcmp(e, "legacy")) ? 2 : 0;
-    }
+    if (g_bwd_mode < 0) g_bwd_mode = bwd_impl_is("legacy") ? 2 : 0;
     return g_bwd_mode;
 }
 
@@ -69,6 +73,38 @@ int semantic_alpha_mode()
         g_sem_alpha_mode = (e && !strcmp(e, "exact")) ? 1 : 0;
     }
     return g_sem_alpha_mode;
+}
+
+// ---- the backward's plan (hsr_backward_plan): accumulation mode, tile kernel, row layout and stride, decided HERE and nowhere else ----
+struct BwdPlanState { int accumulation; bool force_valu, sem_alpha_exact; };   // the process-wide inputs, read once per plan
+BwdPlanState backward_plan_state() { return {backward_mode(), bwd_impl_is("valu"), semantic_alpha_mode() == 1}; }
+
+// Pure arithmetic; offered: bytes of scratch on offer (HSR_SCRATCH_AS_PLANNED, the largest size_t, is ample by its value).
+//   packed: fp32 atomics into ONE 64-byte-aligned row per Gaussian in the scratch, unpacked by the per-Gaussian kernel — half the
+//       atomic requests of the reference's six arrays; the scratch is sized for the CLASSIC stride whatever the rows turn out to be;
+//   geometry-only is granted on packed rows of 16 floats while the Q-geo kernel can address them (HSR_BWD_IMPL=valu does not apply);
+//   else Q-panel (K <= 27) or subw on rows they can address, compact where the Q-panel kernel writes them and that saves a line;
+//   else the all-VALU kernel, on classic rows or — legacy: no scratch, or too little — straight into the six output arrays.
+hsr_backward_plan plan_backward(int P, int K, bool geo_request, size_t offered, const BwdPlanState& st)
+{
+    hsr_backward_plan p = {2, HSR_BWD_KERNEL_VALU, 0, 0, 0, 0, 0};
+    const size_t classic_bytes = (size_t)P * hsr_grow_stride(K) * sizeof(float);
+    if (P <= 0 || st.accumulation == 2 || offered < classic_bytes + 256) return p;
+    p.accumulation = 0;
+    p.scratch_bytes = classic_bytes + 512;
+    if (geo_request && hsr_rows_fit_32bit(P, 16)) {
+        p.geometry_only = 1;
+        p.kernel = HSR_BWD_KERNEL_QGEO;
+        p.row_stride = 16;   // one 64-byte line per Gaussian: columns 0..6
+    } else {
+        const bool q = !st.force_valu && K <= 27;
+        p.row_layout = q && hsr_grow_compact_pays(K) && hsr_rows_fit_32bit(P, hsr_grow_stride_l(1, K));
+        p.row_stride = hsr_grow_stride_l(p.row_layout, K);
+        if (!st.force_valu && hsr_rows_fit_32bit(P, p.row_stride)) p.kernel = q ? HSR_BWD_KERNEL_Q : HSR_BWD_KERNEL_SUBW;
+    }
+    // the exact semantic -> alpha passes ride on packed rows; their guard tests the classic stride (16 when geometry-only)
+    p.semantic_alpha = st.sem_alpha_exact && K > 0 && hsr_rows_fit_32bit(P, p.geometry_only ? 16 : hsr_grow_stride(K));
+    return p;
 }
 
 int acquire(hsr_buffer* b, size_t need, const char* what, char** out)
@@ -127,7 +163,7 @@ struct AsyncRing {
 };
 constexpr int HSR_ASYNC_SLOTS = 256;   // forwards in flight per device before a slot is reused
 std::mutex g_async_mu;
-AsyncRing g_async_ring[64];
+AsyncRing g_async_ring[HSR_MAX_DEVICES];
 thread_local hsr_ticket* g_armed_ticket = nullptr;
 
 // ---- optional per-stage timing with HIP events (hsr_profile_*) ----
@@ -292,7 +328,7 @@ int ring_slot(uint32_t* seq_out, volatile uint32_t** host_out, uint32_t** dev_ou
 {
     int d = 0;
     HSR_HIP_CHECK(hipGetDevice(&d));
-    if (d < 0 || d >= 64) {
+    if (d < 0 || d >= HSR_MAX_DEVICES) {
         hsr_set_error("device index %d out of range", d);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -619,16 +655,10 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     const int* radii = in.radii ? in.radii : g.radii;
     const int K = in.semantic ? in.K : 0;
 
-    // Accumulation modes (hsr_backward_scratch_bytes() sizes the scratch for the one in force):
-    //   packed (default with scratch): fp32 atomics into ONE 64-byte-aligned row per Gaussian, unpacked by
-    //       the per-Gaussian kernel — half the atomic requests of the reference's six separate arrays;
-    //   legacy (no scratch): atomics straight into the six output arrays.
-    int glayout = 0;   // set below once the accumulation mode is known
-    int gstride = hsr_grow_stride(K);
-    const bool use_packed = backward_mode() != 2 && in.scratch &&
-                            in.scratch_bytes >= (size_t)P * gstride * sizeof(float) + 256;
-    const bool geo = geo_request && use_packed && (size_t)P * 16 < ((size_t)1 << 30);
-    if (geo_request && !geo) {
+    const BwdPlanState state = backward_plan_state();
+    const hsr_backward_plan plan = plan_backward(P, K, geo_request, in.scratch ? in.scratch_bytes : 0, state);
+    const bool use_packed = plan.accumulation == 0;
+    if (geo_request && !plan.geometry_only) {
         hsr_set_error("dL_dcolor / dL_dopacity / dL_dsemantics may only all be NULL (geometry-only gradients) in the packed accumulation mode");
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -638,9 +668,9 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     }
     // opt-in exact semantic -> alpha term: extra passes over the packed rows (a geometry-only caller that passes no dL_dpix_sem has no
     // semantic loss: nothing to add)
-    const bool sem_alpha = semantic_alpha_mode() == 1 && K > 0 && in.dL_dpix_sem != nullptr;
+    const bool sem_alpha = state.sem_alpha_exact && K > 0 && in.dL_dpix_sem != nullptr;
     if (sem_alpha) {
-        if (!use_packed || (size_t)P * (size_t)(geo ? 16 : hsr_grow_stride(K)) >= ((size_t)1 << 30)) {
+        if (!plan.semantic_alpha) {   // (tests the classic stride, not the rows' own)
             hsr_set_error("the exact semantic -> alpha mode needs the packed accumulation mode (a scratch buffer of hsr_backward_scratch_bytes) and P * row stride < 2^30");
             return HSR_ERR_INVALID_ARGUMENT;
         }
@@ -651,16 +681,11 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     }
     float* grow = nullptr;
     if (use_packed) {
-        if (geo) gstride = 16;   // one 64-byte line per Gaussian: columns 0..6
-        else {
-            glayout = hsr_backward_row_layout(K, true, P);   // compact rows where the tile kernel that will run writes them and they save a line
-            gstride = hsr_grow_stride_l(glayout, K);
-        }
         char* sp = in.scratch;
-        take(sp, grow, (size_t)P * gstride);
+        take(sp, grow, (size_t)P * plan.row_stride);
         StageTimer tm(HSR_STAGE_BWD_ZERO, stream);
         // only the rows of visible Gaussians (radii > 0): nothing else is added into or read back (hsr_backward_pre.hip)
-        hsr_launch_zero_visible_rows(P, radii, grow, gstride, stream);
+        hsr_launch_zero_visible_rows(P, radii, grow, plan.row_stride, stream);
         if (!in.colors_precomp && in.shs && in.dL_dsh && in.M > 0)
             HSR_HIP_CHECK(hipMemsetAsync(in.dL_dsh, 0, sizeof(float) * 3 * (size_t)in.M * (size_t)P, stream));
     } else {
@@ -679,14 +704,10 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
         ra.dL_dmean2D = in.dL_dmean2D; ra.dL_dconic = in.dL_dconic; ra.dL_dopacity = in.dL_dopacity;
         ra.dL_dcolor = in.dL_dcolor; ra.dL_dsemantics = in.dL_dsemantics; ra.dL_ddepth = in.dL_ddepth;
         ra.grow = grow;
-        ra.grow_stride = gstride;
-        ra.grow_layout = glayout;
+        ra.grow_stride = plan.row_stride;
+        ra.grow_layout = plan.row_layout;
         StageTimer tm(HSR_STAGE_BWD_RENDER, stream);
-        if (geo) {
-            hsr_launch_render_backward_qgeo(ra, stream);
-        } else {
-            hsr_launch_render_backward(ra, stream);
-        }
+        if ((rc = hsr_launch_render_backward(plan.kernel, ra, stream)) != HSR_OK) return rc;
         if (sem_alpha) {
             ra.semantics = in.semantics;
             hsr_launch_render_backward_qsema(ra, stream);
@@ -707,7 +728,7 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     pb.K = K;
     pb.out_mean2D = in.dL_dmean2D; pb.out_conic = in.dL_dconic; pb.out_opacity = in.dL_dopacity; pb.out_color = in.dL_dcolor;
     pb.out_semantics = in.dL_dsemantics; pb.out_depth = in.dL_ddepth;
-    pb.grow = grow; pb.grow_stride = gstride; pb.grow_layout = glayout; pb.geo = geo ? 1 : 0;
+    pb.grow = grow; pb.grow_stride = plan.row_stride; pb.grow_layout = plan.row_layout; pb.geo = plan.geometry_only;
     if (pb.shs && (!in.dL_dsh || !in.campos)) {
         hsr_set_error("shs given without dL_dsh / campos");
         return HSR_ERR_INVALID_ARGUMENT;
@@ -788,8 +809,17 @@ size_t hsr_required_image_bytes(int width, int height) { return hsr_carve_img(nu
 size_t hsr_required_binning_bytes(int num_rendered) { return hsr_carve_bin(nullptr, num_rendered, nullptr) + 256; }
 size_t hsr_backward_scratch_bytes(int P, int K, int num_rendered)
 {
-    if (P <= 0 || K < 0 || backward_mode() == 2) return 0;
-    return (size_t)P * hsr_grow_stride(K) * sizeof(float) + 512;  // packed per-Gaussian rows
+    if (P <= 0 || K < 0) return 0;
+    return plan_backward(P, K, false, HSR_SCRATCH_AS_PLANNED, backward_plan_state()).scratch_bytes;   // packed per-Gaussian rows
+}
+int hsr_plan_backward(int P, int K, int geometry_only, size_t scratch_offered, hsr_backward_plan* plan)
+{
+    if (P < 0 || K < 0 || !plan) {
+        hsr_set_error("hsr_plan_backward: P=%d K=%d must not be negative, plan must not be NULL", P, K);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    *plan = plan_backward(P, K, geometry_only != 0, scratch_offered, backward_plan_state());
+    return HSR_OK;
 }
 
 const char* hsr_last_error(void) { return g_err; }

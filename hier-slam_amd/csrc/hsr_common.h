@@ -199,11 +199,15 @@ struct RenderBwdArgs {
     const float* semantics = nullptr;   // [P,K] features: read by the exact semantic -> alpha passes only (hsr_launch_render_backward_qsema)
     int sem_c0 = 0;                      // ... first channel of the pass
 };
-int hsr_launch_render_backward(const RenderBwdArgs& a, hipStream_t stream);
+// The matrix-core tile kernels address the packed rows with 32-bit element indices: P * stride must stay below 2^30.  The ONE
+// statement of that limit: the plan (hsr_api.hip, plan_backward) decides with it, the launchers below check it.
+inline bool hsr_rows_fit_32bit(int P, int stride) { return (size_t)P * (size_t)stride < ((size_t)1 << 30); }
+// kernel: HSR_BWD_KERNEL_* of the call's hsr_backward_plan (include/hsr_rasterizer.h), whose layout and stride a.grow_* carry.
+// The three specialised launchers refuse (HSR_ERR_INVALID_ARGUMENT, nothing launched) arguments their kernels cannot take.
+int hsr_launch_render_backward(int kernel, const RenderBwdArgs& a, hipStream_t stream);
 int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream);     // K <= 27, packed mode: round 4, both per-pixel factors in LDS panels, moments per chunk
 int hsr_launch_render_backward_qgeo(const RenderBwdArgs& a, hipStream_t stream);  // geometry gradients only, same scheme
 int hsr_launch_render_backward_qsema(const RenderBwdArgs& a, hipStream_t stream); // packed rows: + the exact semantic -> alpha term into columns 0..5 (opt-in)
-int hsr_backward_row_layout(int K_semantic, bool packed, int P);   // layout hsr_launch_render_backward will expect for this K (0 unless it takes the Q-panel kernel and the compact row saves a line)
 int hsr_launch_render_backward_subw(const RenderBwdArgs& a, hipStream_t stream);  // K > 27, packed mode: sub-block masks, channel passes
 
 struct PreBwdArgs {

@@ -16,9 +16,7 @@
 // per lane.  One global_atomic_add_f32 wave-instruction
 // per (wave, splat) then carries all 10+K sums.  Waves own 8x8 quadrants and walk compacted
 // per-quadrant lists (hsr_tile_common.h); of the survivors, a splat no lane accepts is skipped.
-#include <stdlib.h>
-#include <string.h>
-
+#include "../../include/hsr_rasterizer.h"
 #include "hsr_tile_common.h"
 #include "hsr_wave_reduce.h"
 
@@ -258,36 +256,29 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a, int c0
 
 }  // namespace
 
-// Which kernel family takes packed rows of K semantic channels: shared by the launcher below and by hsr_api.hip, which sizes the rows
-// (the compact layout exists only in the Q-panel kernels).
-static bool backward_takes_q(int Ksem)
+// One case per kernel of the plan (hsr_api.hip, plan_backward), which has also fixed a.grow_layout and a.grow_stride.  Default (packed
+// accumulation rows, a.grow): the matrix-core kernels on 4x4 sub-block lists — the Q-panel kernel for K <= 27 and its geometry-only
+// variant (hsr_render_bwd_q.hip), one-pass `subw` beyond (hsr_render_bwd_sub.hip).  They address the packed rows with 32-bit element
+// indices; beyond 2^30 row elements (P > 22 M Gaussians at K = 26), in the legacy accumulation mode (no scratch: atomics straight
+// into the six output arrays, like the reference) and under HSR_BWD_IMPL=valu (A/B timing, tests) the plan names the all-VALU kernel
+// of this file: 64-bit addressing, any K, packed rows of the classic layout or none.
+int hsr_launch_render_backward(int kernel, const RenderBwdArgs& a, hipStream_t stream)
 {
-    static const char* impl = getenv("HSR_BWD_IMPL");
-    static const bool valu = impl && !strcmp(impl, "valu");
-    return !valu && Ksem <= 27;
-}
-int hsr_backward_row_layout(int K_semantic, bool packed, int P)
-{
-    // (beyond 2^30 row elements the all-VALU kernel takes over, with classic rows: same test as in the launcher)
-    return (packed && backward_takes_q(K_semantic) && hsr_grow_compact_pays(K_semantic) &&
-            (size_t)P * (size_t)hsr_grow_stride_l(1, K_semantic) < ((size_t)1 << 30)) ? 1 : 0;
-}
-
-int hsr_launch_render_backward(const RenderBwdArgs& a, hipStream_t stream)
-{
+    switch (kernel) {
+    case HSR_BWD_KERNEL_Q: return hsr_launch_render_backward_q(a, stream);
+    case HSR_BWD_KERNEL_QGEO: return hsr_launch_render_backward_qgeo(a, stream);
+    case HSR_BWD_KERNEL_SUBW: return hsr_launch_render_backward_subw(a, stream);
+    case HSR_BWD_KERNEL_VALU: break;
+    default:
+        hsr_set_error("backward tile kernel %d is none of HSR_BWD_KERNEL_*", kernel);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (a.grow && a.grow_layout != 0) {
+        hsr_set_error("the all-VALU backward kernel writes packed rows of the classic layout only");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
     const int tiles = ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
     const dim3 grid(hsr_tile_grid(tiles)), block(256);
-    // Default (packed accumulation rows, a.grow): the matrix-core kernels on 4x4 sub-block lists — the Q-panel kernel for K <= 27
-    // (hsr_render_bwd_q.hip), one-pass `subw` beyond (hsr_render_bwd_sub.hip).  They address the packed rows with 32-bit element
-    // indices; beyond 2^30 row elements (P > 22 M Gaussians at K = 26), in the legacy accumulation mode (no scratch: atomics straight
-    // into the six output arrays, like the reference) and under HSR_BWD_IMPL=valu (A/B timing, tests) the all-VALU kernel of this file
-    // takes over: 64-bit addressing, any K.
-    const bool rows_fit_32bit = !a.grow || (size_t)a.P * (size_t)a.grow_stride < ((size_t)1 << 30);
-    static const char* impl = getenv("HSR_BWD_IMPL");
-    static const bool force_valu = impl && !strcmp(impl, "valu");
-    const int Ksem = a.semantic ? a.K : 0;
-    if (!force_valu && rows_fit_32bit && a.grow)
-        return Ksem > 27 ? hsr_launch_render_backward_subw(a, stream) : hsr_launch_render_backward_q(a, stream);
     if (!a.semantic || a.K == 0) {
         render_bwd_kernel<0, true><<<grid, block, 0, stream>>>(a, 0);
         return HSR_OK;

@@ -658,12 +658,17 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
 
 }  // namespace
 
-// packed mode, K <= 27, P * grow_stride < 2^30 (32-bit row addressing): the caller checks.  a.grow_layout: hsr_backward_row_layout.
+// packed mode, K <= 27, P * grow_stride < 2^30 (32-bit row addressing).  a.grow_layout / a.grow_stride: the plan's (hsr_api.hip).
 int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream)
 {
     const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
     const int K = a.semantic ? a.K : 0;
     const bool cl = a.grow_layout == 1;
+    if (K < 0 || K > 27 || (K == 0 && !cl) || !a.grow || a.grow_stride != hsr_grow_stride_l(a.grow_layout, K) ||
+        !hsr_rows_fit_32bit(a.P, a.grow_stride)) {
+        hsr_set_error("Q-panel backward kernel: needs 0 <= K <= 27 (got %d; compact rows at K = 0), packed rows of the layout's stride (got %d) and P * stride < 2^30", K, a.grow_stride);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
     // K = 0 always has compact rows: they are one line against two, and when P * 16 (the compact stride) reaches 2^30, P * 32 (the
     // classic one) does too, so the caller runs the all-VALU kernel instead
     if (K == 0) render_bwd_q_kernel<0, 208, false, true><<<grid, block, 0, stream>>>(a);
@@ -693,6 +698,10 @@ int hsr_launch_render_backward_qsema(const RenderBwdArgs& a0, hipStream_t stream
 // geometry-only gradients (a.grow_stride == 16): any K
 int hsr_launch_render_backward_qgeo(const RenderBwdArgs& a, hipStream_t stream)
 {
+    if (!a.grow || a.grow_stride != 16 || !hsr_rows_fit_32bit(a.P, 16)) {
+        hsr_set_error("geometry-only backward kernel: needs packed rows of 16 floats (got stride %d) and P * 16 < 2^30", a.grow_stride);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
     render_bwd_q_kernel<0, 208, true><<<dim3(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), dim3(256), 0, stream>>>(a);
     return HSR_OK;
 }

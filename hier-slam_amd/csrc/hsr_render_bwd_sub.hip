@@ -458,6 +458,10 @@ int hsr_launch_render_backward_subw(const RenderBwdArgs& a, hipStream_t stream)
     const int tiles = ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
     const dim3 grid(hsr_tile_grid(tiles));
     const int K = a.K;
+    if (!a.semantic || K <= 27 || !a.grow || a.grow_layout != 0 || a.grow_stride != hsr_grow_stride(K) || !hsr_rows_fit_32bit(a.P, a.grow_stride)) {
+        hsr_set_error("subw backward kernel: needs the semantic variant with K > 27 (got %d), classic packed rows (got stride %d) and P * stride < 2^30", K, a.grow_stride);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
     // One pass while the B operand (16 registers per 16 columns) fits two waves per SIMD: K + 5 <= 112 columns.  Every pass
     // re-derives alpha and T for every (pixel, splat) pair, and that — not the matrix-core work, which is the same in total —
     // is most of a pass: K = 74 in ONE pass of 80 columns at 2 waves per SIMD instead of 64 + 22 columns at 3 and 4.

@@ -189,11 +189,14 @@ backward_common(bool semantic, const OptT& background, const at::Tensor& means3D
     c10::DeviceGuard guard(dev);
     const auto fopt = at::TensorOptions().dtype(at::kFloat).device(dev);
     auto fresh = [&](at::IntArrayRef shape) { return P == 0 ? at::zeros(shape, fopt) : at::empty(shape, fopt); };   // fully overwritten when P > 0
-    // with a scratch buffer dL_dconic and dL_ddepths are intermediates nobody reads (the reference keeps them inside
-    // RasterizeGaussiansBackwardCUDA, rasterize_points.cu:380-383): not allocated, not written
-    const size_t nscratch = P ? hsr_backward_scratch_bytes((int)P, (int)K, (int)R) : 0;
+    // what the library will do with this call (include/hsr_rasterizer.h): asked once, everything below is allocated from it.
     // geometry-only (tracking iteration): no gradient wanted for colours, opacities, semantics, scales, rotations, SH, cov3D
-    const bool geo = geometry_only && nscratch && hsr_get_backward_mode() == 0 && colors.has_value() && colors->defined() && colors->numel() != 0;
+    hsr_backward_plan plan;
+    const int prc = hsr_plan_backward((int)P, (int)K, geometry_only && colors.has_value() && colors->defined() && colors->numel() != 0,
+                                      HSR_SCRATCH_AS_PLANNED, &plan);
+    if (prc < 0) fail(prc, "hsr_plan_backward");
+    const bool geo = plan.geometry_only != 0;
+    const size_t nscratch = plan.scratch_bytes;
     // gradient sink (diff_gaussian_rasterization/_C.py set_gradient_sink): pre-allocated outputs — views of a communication
     // bucket — for means3D, colours, semantics, opacities, scales, rotations (checked for shape / dtype / device / layout there)
     auto take = [&](size_t i, at::IntArrayRef shape) {
@@ -207,7 +210,9 @@ backward_common(bool semantic, const OptT& background, const at::Tensor& means3D
         dL_dscales = take(4, {P, 3}); dL_drotations = take(5, {P, 4});
     }
     at::Tensor dL_dconic, dL_ddepths, dL_dcov3D, scratch;
-    if (!nscratch) { dL_dconic = fresh({P, 2, 2}); dL_ddepths = fresh({P, 1}); }
+    // with packed rows in the scratch dL_dconic and dL_ddepths are intermediates nobody reads (the reference keeps them inside
+    // RasterizeGaussiansBackwardCUDA, rasterize_points.cu:380-383): not allocated, not written
+    if (plan.accumulation != 0) { dL_dconic = fresh({P, 2, 2}); dL_ddepths = fresh({P, 1}); }
     if ((want_cov3D_grad && !geo) || P == 0) dL_dcov3D = fresh({P, 6});
     if (P != 0) {
         const at::Tensor bg_ = prep(background, dev), m3_ = prep(means3D, dev), sh_ = prep(sh, dev), col_ = prep(colors, dev);

@@ -239,9 +239,6 @@ def _from_sink(name, shape, dev):
         raise RuntimeError("gradient sink returned a tensor of the wrong shape / dtype / device / layout for %s" % name)
     return t
 
-def _rows_or_legacy():
-    return int(_lib.hsr_get_backward_mode()) != 0
-
 
 def set_backward_mode(mode):
     """'packed' (default: one gradient row per Gaussian) or 'legacy' (atomics into the reference's six arrays); 'rows' (a removed
@@ -474,20 +471,24 @@ def _backward_common(semantic, background, means3D, radii, colors, semantics, sc
     K = int(dL_dout_semantic.size(0)) if semantic else 0
     fopt = dict(dtype=torch.float32, device=dev)
     new = torch.zeros if P == 0 else torch.empty  # the library overwrites every element when P > 0
-    packed_ok = P != 0 and int(_lib.hsr_backward_scratch_bytes(P, K, int(R))) > 0 and int(_lib.hsr_backward_scratch_bytes(P, K, 0)) > 0
-    geo = bool(geometry_only) and packed_ok and colors is not None and colors.numel() != 0 and not _rows_or_legacy()
+    # what the library will do with this call (include/hsr_rasterizer.h): asked once, everything below is allocated from it
+    plan = _abi.hsr_backward_plan()
+    rc = _lib.hsr_plan_backward(P, K, int(bool(geometry_only) and colors is not None and colors.numel() != 0),
+                                _abi.HSR_SCRATCH_AS_PLANNED, C.byref(plan))
+    if rc < 0:
+        _fail(rc, "hsr_plan_backward")
+    geo, packed = bool(plan.geometry_only), plan.accumulation == 0
     pre = (lambda i: sunk[i] if (sunk is not None and sunk[i] is not None) else None)
     take = (lambda i, shape: pre(i) if pre(i) is not None else new(shape, **fopt))
     dL_dmeans3D = take(0, (P, 3))
     dL_dmeans2D = new((P, 3), **fopt)
     dL_dcolors = None if geo else take(1, (P, NUM_CHANNELS))
     dL_dsemantics = None if geo else take(2, (P, K))
-    # with a scratch buffer (every mode but 'legacy') dL_dconic and dL_ddepths are intermediates nobody reads (the reference
-    # keeps them inside RasterizeGaussiansBackwardCUDA, rasterize_points.cu:380-383): not allocated, not written;
+    # with packed rows in a scratch buffer (every mode but 'legacy') dL_dconic and dL_ddepths are intermediates nobody reads (the
+    # reference keeps them inside RasterizeGaussiansBackwardCUDA, rasterize_points.cu:380-383): not allocated, not written;
     # dL_dcov3D only when the caller wants it (want_cov3D_grad=False from the autograd node when cov3D_precomp needs no grad)
-    packed_scratch = P != 0 and int(_lib.hsr_backward_scratch_bytes(P, K, int(R))) > 0
-    dL_dconic = None if packed_scratch else new((P, 2, 2), **fopt)
-    dL_ddepths = None if packed_scratch else new((P, 1), **fopt)
+    dL_dconic = None if packed else new((P, 2, 2), **fopt)
+    dL_ddepths = None if packed else new((P, 1), **fopt)
     dL_dopacity = None if geo else take(3, (P, 1))
     dL_dcov3D = new((P, 6), **fopt) if ((want_cov3D_grad and not geo) or P == 0) else None
     dL_dsh = None if geo else new((P, M, 3), **fopt)
@@ -502,9 +503,8 @@ def _backward_common(semantic, background, means3D, radii, colors, semantics, sc
                                             dL_dout_final_opacity)]
             bg_, m3_, sh_, col_, sem_, sc_, rot_, cov_, vm_, pm_, cp_, gcol, gsem, gdep, gmed, gop = tens
             radii_ = _prep(radii, dev, torch.int32)
-            # Backward scratch, sized by the library for the accumulation mode in force (include/hsr_rasterizer.h):
-            # default: packed per-Gaussian gradient rows (P x stride floats) — halves the atomic requests
-            nscratch = int(_lib.hsr_backward_scratch_bytes(P, K, int(R)))
+            # Backward scratch, sized by the plan: packed per-Gaussian gradient rows (P x stride floats) — halves the atomic requests
+            nscratch = int(plan.scratch_bytes)
             scratch = torch.empty(nscratch, dtype=torch.uint8, device=dev) if nscratch else None
             common_tail = (_ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations),
                            _ptr(scratch), nscratch, int(bool(debug)), stream)

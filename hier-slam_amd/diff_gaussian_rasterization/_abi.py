@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("HSR_RAST_LIB", os.path.join(os.path.dirname(_HERE), "
 
 HSR_ERR_BUFFER_TOO_SMALL = -2
 HSR_PENDING = -100
+HSR_SCRATCH_AS_PLANNED = C.c_size_t(-1).value
 
 vp, ci, cu, cf, cd, sz, cs = C.c_void_p, C.c_int, C.c_uint, C.c_float, C.c_double, C.c_size_t, C.c_char_p
 ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)      # HOST arrays (level_sizes, level_weight)
@@ -43,6 +44,12 @@ class hsr_state_layout(C.Structure):
         "img_ranges", "img_final_T", "img_n_contrib", "img_median_pos")]
 
 
+class hsr_backward_plan(C.Structure):
+    """what one backward call will do (hsr_plan_backward); kernel: 0 Q-panel, 1 Q-geo, 2 subw, 3 all-VALU"""
+    _fields_ = [("accumulation", C.c_int), ("kernel", C.c_int), ("row_layout", C.c_int), ("row_stride", C.c_int),
+                ("geometry_only", C.c_int), ("semantic_alpha", C.c_int), ("scratch_bytes", C.c_size_t)]
+
+
 class hsr_row_table(C.Structure):
     _fields_ = [("src", vp), ("append", vp), ("dst", vp), ("cols", ci)]
 
@@ -63,6 +70,7 @@ SIGNATURES = (
     ("hsr_backward_scratch_bytes", sz, [ci, ci, ci]),
     ("hsr_set_backward_mode", ci, [ci]),
     ("hsr_get_backward_mode", ci, []),
+    ("hsr_plan_backward", ci, [ci, ci, ci, sz, C.POINTER(hsr_backward_plan)]),
     ("hsr_set_semantic_alpha_mode", ci, [ci]),
     ("hsr_get_semantic_alpha_mode", ci, []),
     ("hsr_last_error", cs, []),

@@ -70,9 +70,33 @@ size_t hsr_backward_scratch_bytes(int P, int K, int num_rendered);
  *   0 packed : fp32 atomics into one 64-byte-aligned scratch row per Gaussian, unpacked by the per-Gaussian
  *              kernel — about half the atomic requests of the reference's six separate arrays (default);
  *   1        : refused (HSR_ERR_INVALID_ARGUMENT): the per-instance-rows experiment was measured slower and removed;
- *   2 legacy : atomics straight into the six output arrays, as the reference does; needs no scratch. */
+ *   2 legacy : atomics straight into the six output arrays, as the reference does; needs no scratch.
+ * The mode is one input of the plan below, which is what a backward call actually does. */
 int hsr_set_backward_mode(int mode);
 int hsr_get_backward_mode(void);   /* 0 packed, 2 legacy */
+
+/* What one backward call will do: every decision hsr_backward* takes before it launches anything, made in ONE place from the
+ * sizes, the scratch on offer and the process-wide state (the accumulation mode above, HSR_BWD_IMPL=valu, the semantic -> alpha
+ * mode below).  hsr_backward* computes the same plan from its own arguments; a caller asks for it first to know what to allocate. */
+enum { HSR_BWD_KERNEL_Q = 0,      /* Q-panel matrix-core kernel: packed rows, K <= 27 */
+       HSR_BWD_KERNEL_QGEO,       /* its geometry-only variant: 16-float rows, any K */
+       HSR_BWD_KERNEL_SUBW,       /* one-pass sub-block kernel: packed rows, K > 27 */
+       HSR_BWD_KERNEL_VALU };     /* all-VALU kernel, 64-bit addressing: legacy mode, HSR_BWD_IMPL=valu, P * row_stride >= 2^30 */
+typedef struct hsr_backward_plan {
+    int accumulation;     /* 0 packed rows in the scratch, 2 legacy (the numbers of hsr_get_backward_mode) */
+    int kernel;           /* HSR_BWD_KERNEL_*: the tile kernel that runs */
+    int row_layout;       /* packed rows: 0 classic, 1 compact (the channel columns start in line 0: one 64-byte line less) */
+    int row_stride;       /* floats per packed row; 0 in legacy */
+    int geometry_only;    /* 1: the geometry-only request is granted (dL_dcolor, dL_dopacity, dL_dsemantics may all be NULL) */
+    int semantic_alpha;   /* 1: the exact semantic -> alpha mode is in force and these rows can carry its passes */
+    size_t scratch_bytes; /* what the caller should allocate for `scratch`; 0 in legacy */
+} hsr_backward_plan;
+#define HSR_SCRATCH_AS_PLANNED ((size_t)-1)
+/* Fills *plan for P Gaussians and K semantic channels (0: hsr_backward).  geometry_only: the caller would like to pass NULL for
+ * dL_dcolor, dL_dopacity and dL_dsemantics (it has colors_precomp); where the plan does not grant that, the call needs them all.
+ * scratch_offered: bytes of scratch the caller has (0: none; less than the packed rows need: legacy for this call), or
+ * HSR_SCRATCH_AS_PLANNED: it will allocate plan->scratch_bytes.  Host arithmetic only: touches no device. */
+int hsr_plan_backward(int P, int K, int geometry_only, size_t scratch_offered, hsr_backward_plan* plan);
 
 /* Gradient of the semantic loss with respect to alpha (process-wide; default 0, or HSR_SEMANTIC_ALPHA=exact):
  *   0 reference : none.  The reference stages the features for this term into a shared array nothing writes

@@ -11,7 +11,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "hsr_*.h")))    # a glob: the next header is covered without an edit
-N_PROTOTYPES = 63      # asserted as a number: a regex that silently stops matching must not pass
+N_PROTOTYPES = 64      # asserted as a number: a regex that silently stops matching must not pass
 
 # what the four older headers declare at least (the newer three are pinned exactly, each in its own suite: test_eval_cpu.py,
 # test_optim_cpu.py, test_keyframes_cpu.py)
@@ -135,7 +135,7 @@ def test_ctypes_signatures_match_header():
 
 
 def test_structures_match_header():
-    """the five ctypes structures carry the field names of their typedefs, in order; the Adam entry keeps the library's size"""
+    """the six ctypes structures carry the field names of their typedefs, in order; the Adam entry keeps the library's size"""
     from diff_gaussian_rasterization import _C, _abi
     from hsr_utils import optim, slam_external
     src = "\n".join(_source(h) for h in HEADERS)
@@ -147,7 +147,8 @@ def test_structures_match_header():
         names = [re.search(r"(\w+)\s*$", d).group(1) for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
         assert names == [f[0] for f in mirror._fields_], m.group(1)
         checked.add(mirror)
-    assert checked == {_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout, _abi.hsr_adam_tensor, _abi.hsr_row_table}
+    assert checked == {_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout, _abi.hsr_adam_tensor, _abi.hsr_row_table,
+                       _abi.hsr_backward_plan}
     assert (_C._HsrBuffer, _C._Ticket, _C._StateLayout) == (_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout)
     assert optim._AdamTensor is _abi.hsr_adam_tensor and slam_external._RowTable is _abi.hsr_row_table
     assert _abi.lib.hsr_adam_table_entry_bytes() == C.sizeof(_abi.hsr_adam_tensor) == 64

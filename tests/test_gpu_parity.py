@@ -271,16 +271,12 @@ def test_speculative_forward_and_its_fallback_agree_with_the_oracle(monkeypatch)
     assert _C._binning_hint[key] == R
 
 
-@pytest.mark.parametrize("semantic,K", [(True, 26), (True, 74), (False, 0)])
-def test_geometry_only_backward_matches_the_full_one(semantic, K):
-    """When only means3D / means2D want a gradient (a tracking iteration optimises the camera pose alone) the library forms the
-    geometry sums only (hsr_backward*: dL_dcolor, dL_dopacity, dL_dsemantics NULL -> the geometry-only variant of render_bwd_q_kernel).  dL_dmeans3D and
-    dL_dmeans2D must equal those of a full backward of the same render (to atomics-order noise) and the oracle's (1e-4)."""
-    import torch
-    from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic, _C
-    from harness import _cam_to, run_oracle, assert_close
-    W, H, P = 203, 131, 3000
-    cam, sc, up = scenes.build(W, H, P, K, seed=11, kind="slam", scale_mult=3.0)
+def _pose_only_and_full_gradients(cam, sc, up, semantic):
+    """(dL_dmeans3D, dL_dmeans2D) of one render, once with only means3D / means2D requiring a gradient ("pose": the geometry-only
+    request) and once with every input requiring one ("full")"""
+    from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic
+    from harness import _cam_to
+    P = sc["means3D"].shape[0]
     dev = torch.device("cuda:0")
     camd = _cam_to(cam, dev)
     grads = {}
@@ -288,8 +284,6 @@ def test_geometry_only_backward_matches_the_full_one(semantic, K):
         means3D = sc["means3D"].to(dev).clone().requires_grad_(True)
         means2D = torch.zeros(P, 3, device=dev, requires_grad=True)
         rest = {n: sc[n].to(dev).clone().requires_grad_(mode == "full") for n in ("opacities", "colors_precomp", "scales", "rotations")}
-        seen = {}
-        real = _C._lib.hsr_backward_semantic if semantic else _C._lib.hsr_backward
         if semantic:
             sem = sc["semantics_precomp"].to(dev).clone().requires_grad_(mode == "full")
             outs = GaussianRasterizer_semantic(camd)(means3D=means3D, means2D=means2D, opacities=rest["opacities"], colors_precomp=rest["colors_precomp"],
@@ -311,9 +305,37 @@ def test_geometry_only_backward_matches_the_full_one(semantic, K):
     for a, b, name in ((grads["pose"][0], grads["full"][0], "means3D"), (grads["pose"][1], grads["full"][1], "means2D")):
         assert np.isfinite(a).all()
         assert np.abs(a - b).max() <= 1e-5 * max(1.0, np.abs(b).max()), name
+    return grads
+
+
+@pytest.mark.parametrize("semantic,K", [(True, 26), (True, 74), (False, 0)])
+def test_geometry_only_backward_matches_the_full_one(semantic, K):
+    """When only means3D / means2D want a gradient (a tracking iteration optimises the camera pose alone) the library forms the
+    geometry sums only (hsr_backward*: dL_dcolor, dL_dopacity, dL_dsemantics NULL -> the geometry-only variant of render_bwd_q_kernel).  dL_dmeans3D and
+    dL_dmeans2D must equal those of a full backward of the same render (to atomics-order noise) and the oracle's (1e-4)."""
+    cam, sc, up = scenes.build(203, 131, 3000, K, seed=11, kind="slam", scale_mult=3.0)
+    grads = _pose_only_and_full_gradients(cam, sc, up, semantic)
     oo, go, so = run_oracle(cam, sc, up, semantic=semantic, variant="sr")
     assert_close("means3D (geometry-only) vs oracle", grads["pose"][0], go["means3D"])
     assert_close("means2D (geometry-only) vs oracle", grads["pose"][1], go["means2D"])
+
+
+# K at which the backward's plan (hsr_plan_backward; its table: tests/test_backward_plan.py) changes the packed rows' layout, their
+# stride or the tile kernel: the last K of one choice and the first of the next, which the K of CASES straddle but do not hit
+PLAN_EDGE_K = [4, 5, 12, 20, 21, 27, 28]
+
+
+@pytest.mark.parametrize("K", PLAN_EDGE_K)
+def test_parity_at_the_row_layout_and_kernel_edges(K):
+    cam, sc, up = scenes.build(64, 48, 400, K, seed=7, kind="aniso", scale_mult=2.0)
+    _compare(cam, sc, up, True, "sr", None)
+
+
+@pytest.mark.parametrize("K", PLAN_EDGE_K)
+def test_geometry_only_backward_at_the_row_layout_and_kernel_edges(K):
+    """the geometry-only request at the same K: its 16-float rows and kernel do not depend on K, the full backward's do"""
+    cam, sc, up = scenes.build(64, 48, 400, K, seed=7, kind="aniso", scale_mult=2.0)
+    _pose_only_and_full_gradients(cam, sc, up, True)
 
 
 def test_backward_argument_checks_in_a_ctypes_child():
