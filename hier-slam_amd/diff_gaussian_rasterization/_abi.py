@@ -1,9 +1,10 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from this module.  The
-signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
-time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's.  There is NO fallback
+Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
+this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
+time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
+include/hsr_*.h; SIGNATURES_EXT against include/ext/ with the same checker, from the extension's own suite).  There is NO fallback
 path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -220,6 +221,14 @@ SIGNATURES = (
                                    ci, ci, vp, vp]),
 )
 
+# ---- extensions: headers under include/ext/, outside the counted set of include/hsr_*.h; checked by their own suites ---------------
+SIGNATURES_EXT = (
+    # include/ext/hsr_msssim.h
+    ("hsr_eval_msssim_scratch_bytes", sz, [ci, ci]),
+    ("hsr_eval_msssim", ci, [ci, ci, vp, vp, vp, vp,
+                             cf, vp, vp, sz, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -228,7 +237,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in SIGNATURES:
+    for name, restype, argtypes in SIGNATURES + SIGNATURES_EXT:
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

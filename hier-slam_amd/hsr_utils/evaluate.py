@@ -6,6 +6,8 @@
                                                                                     :135-156, leaf MLP :1251-1255
     tree_lookup_table(label_mapping_tree, level_sizes)                             the dict of transfer_tree_2_label as a dense table
     iou_counts(pred, gt, num_classes=, class_ids=, dilation_ratio=0.02)            calculate_iou :83-90, boundary_iou :37-81, per class
+    ms_ssim(im, gt_im, gt_depth, final_opacity=None, sil_thres=None, details=False) MS-SSIM :722, :946, :1272; restated, not pinned
+                                                                                    by the reference's package (include/ext/hsr_msssim.h)
     frame_miou(counts)                                                             mean IoU / boundary IoU of a frame :1487-1498
     evaluate_frame(...)                                                            the per-frame body of eval_semantic_tree_newrender
     trajectory_ate(gt_w2c_list, est_w2c_list)                                      evaluate_ate + align :218-275, :1555-1577 (numpy)
@@ -23,6 +25,7 @@ from diff_gaussian_rasterization import _abi
 _lib = _abi.lib
 
 MAX_CLASSES, MAX_LEVELS, LEAF_MAX_K, LEAF_MAX_C, MAX_DILATION = 4096, 16, 32, 256, 1024
+MSSSIM_SCALES, MSSSIM_MIN_SIDE, MSSSIM_OUT = 5, 161, 31
 _class_cache = {}
 
 
@@ -66,6 +69,39 @@ def frame_metrics(im, gt_im, depth, gt_depth, final_opacity=None, sil_thres=None
     _abi.call(_lib.hsr_eval_frame_metrics, "hsr_eval_frame_metrics", dev, H, W, a.data_ptr(), b.data_ptr(), d.data_ptr(), gd.data_ptr(),
               None if op is None else op.data_ptr(), 0.0 if sil_thres is None else float(sil_thres), out.data_ptr(), sc.data_ptr(), sc.numel())
     return out
+
+
+def ms_ssim(im, gt_im, gt_depth, final_opacity=None, sil_thres=None, details=False):
+    """0-dim float64 device tensor: the multi-scale SSIM of one frame as the reference scores it (utils/eval_helpers.py:1259-1272:
+    ms_ssim(data_range=1.0, size_average=True) of the two images after both were multiplied by gt_depth > 0 and, with final_opacity
+    and sil_thres, by the silhouette mask).  Five scales of a valid 11-tap Gaussian filter (sigma 1.5) with 2x2 average pools
+    between them, weights 0.0448, 0.2856, 0.3001, 0.2363, 0.1333; include/ext/hsr_msssim.h states every step.  Restated from the
+    definition, not pinned by the reference's package (pytorch_msssim).  im / gt_im: [3,H,W]; gt_depth / final_opacity: [1,H,W] or
+    [H,W], all float32; min(H, W) > 160.  details=True also returns the float64 [5,3,2] table of the per-scale, per-channel means of
+    cs and ssim before the relu.  No host synchronisation, no copy of the images."""
+    a = _dev(im, "im")
+    if a.dim() != 3 or a.shape[0] != 3:
+        raise RuntimeError("hsr_utils.evaluate: im must be [3,H,W] (got %s)" % (tuple(im.shape),))
+    H, W = a.shape[1:]
+    b = _dev(gt_im, "gt_im")
+    if b.shape != a.shape:
+        raise RuntimeError("hsr_utils.evaluate: gt_im %s differs from im %s" % (tuple(b.shape), tuple(a.shape)))
+    gd = _plane(gt_depth, "gt_depth", H, W)
+    if (final_opacity is None) != (sil_thres is None):
+        raise RuntimeError("hsr_utils.evaluate: final_opacity and sil_thres go together")
+    op = None if final_opacity is None else _plane(final_opacity, "final_opacity", H, W)
+    if min(H, W) < MSSSIM_MIN_SIDE:
+        raise AssertionError("hsr_utils.evaluate: ms_ssim needs an image whose smaller side is larger than %d, for the 4 downsamplings "
+                             "of an 11-tap window (got H=%d W=%d)" % (MSSSIM_MIN_SIDE - 1, H, W))
+    dev = a.device
+    out = torch.empty(MSSSIM_OUT, dtype=torch.float64, device=dev)
+    sc = torch.empty(int(_lib.hsr_eval_msssim_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _abi.call(_lib.hsr_eval_msssim, "hsr_eval_msssim", dev, H, W, a.data_ptr(), b.data_ptr(), gd.data_ptr(),
+              None if op is None else op.data_ptr(), 0.0 if sil_thres is None else float(sil_thres), out.data_ptr(), sc.data_ptr(), sc.numel())
+    return (out[0], out[1:].view(MSSSIM_SCALES, 3, 2)) if details else out[0]
+
+
+_ms_ssim = ms_ssim      # evaluate_frame's flag carries the function's name
 
 
 def tree_lookup_table(label_mapping_tree, level_sizes, device="cuda"):
@@ -207,11 +243,12 @@ def frame_miou(counts):
 
 
 def evaluate_frame(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, *, final_opacity=None, sil_thres=None, level_sizes=None,
-                   tree_table=None, mlp=None, num_classes=None, class_ids=None, dilation_ratio=0.02):
+                   tree_table=None, mlp=None, num_classes=None, class_ids=None, dilation_ratio=0.02, ms_ssim=False):
     """The per-frame scores of eval_semantic_tree_newrender (utils/eval_helpers.py:1258-1498) without MS-SSIM and LPIPS: a dict of
     0-dim device tensors psnr, depth_l1, depth_rmse (float64), miou, mbiou (float64).  im / im_semantic / depth / final_opacity as the
     semantic rasterizer returns them; gt_labels: the leaf label map ([H,W], int; label_gt[-1] for tree datasets).  `mode` and its
-    arguments as semantic_labels; num_classes / class_ids as iou_counts.  No host synchronisation."""
+    arguments as semantic_labels; num_classes / class_ids as iou_counts.  With ms_ssim=True the dict is without LPIPS only: it gains
+    the key ms_ssim (float64, the function ms_ssim of this module on the same images and masks).  No host synchronisation."""
     m = frame_metrics(im, gt_im, depth, gt_depth, final_opacity, sil_thres)
     lab = semantic_labels(im_semantic, mode, level_sizes=level_sizes, tree_table=tree_table, mlp=mlp)
     if mode == "tree":
@@ -221,7 +258,10 @@ def evaluate_frame(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, *, 
     if g.dtype != torch.int32:
         g = g.to(torch.int32)
     s = frame_miou(iou_counts(lab, g, num_classes=num_classes, class_ids=class_ids, dilation_ratio=dilation_ratio))
-    return {"psnr": m[0], "depth_l1": m[1], "depth_rmse": m[2], "miou": s[0], "mbiou": s[1]}
+    scores = {"psnr": m[0], "depth_l1": m[1], "depth_rmse": m[2], "miou": s[0], "mbiou": s[1]}
+    if ms_ssim:
+        scores["ms_ssim"] = _ms_ssim(im, gt_im, gt_depth, final_opacity, sil_thres)
+    return scores
 
 
 def _align(model, data):
@@ -264,5 +304,5 @@ def trajectory_ate(gt_w2c_list, est_w2c_list, first_frame_w2c=None):
     return float(err.mean())
 
 
-__all__ = ["frame_metrics", "semantic_labels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
+__all__ = ["frame_metrics", "ms_ssim", "semantic_labels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
            "dilation_pixels"]
