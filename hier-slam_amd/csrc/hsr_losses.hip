@@ -470,7 +470,7 @@ __global__ __launch_bounds__(TB) void tree_ce2_kernel(const float* __restrict__ 
                 float s = 0.f, picked = 0.f;
 #pragma unroll
                 for (int c = 0; c < CE_REG; c++) {
-                    picked = c == lab ? z[c] : picked;
+                    picked = (c == lab && c < n) ? z[c] : picked;   // slots c >= n hold -inf: an out-of-range label matches no class
                     z[c] = c < n ? expf(z[c] - m) : 0.f;
                     s += z[c];
                 }
@@ -652,16 +652,20 @@ __global__ void __launch_bounds__(256, 3) leaf_mlp_ce_kernel(const float* __rest
         float m2 = -INFINITY, sum = 0.f, picked = 0.f;
         {
             auto class1 = [&](int c, const float (&w)[KU]) {
+                // no contraction here: z2 - nm must use the ROUNDED z2 that the running maximum and `picked` hold.  Contracted to
+                // fma(z, log2e, -nm) it leaves the rounding residual of z2 in the exponent, 2^residual is 1 or 1 + 2^-23, and a one-class
+                // head's log-sum-exp is no longer its logit: the loss is then ~1e-7 per pixel, not 0
+#pragma clang fp contract(off)
                 // two interleaved partial sums: the pairs (w[2j], w[2j+1]) x (sv[2j], sv[2j+1]) become v_pk_fma_f32 — half the
                 // instructions of a 28-deep v_fmac chain, and the kernel's time is the instructions it issues
                 lm_f32x2 zz = {0.f, 0.f};
 #pragma unroll
                 for (int k = 0; k < KU; k += 2) zz = __builtin_elementwise_fma(lm_f32x2{w[k], w[k + 1]}, lm_f32x2{sv[k], sv[k + 1]}, zz);
                 const float z = zz.x + zz.y;
-                picked = c == lab ? z : picked;
                 const float z2 = z * L2E;
+                picked = c == lab ? z2 : picked;   // in base 2, like the log-sum-exp it is subtracted from
                 const float nm = fmaxf(m2, z2);
-                sum = sum * __builtin_amdgcn_exp2f(m2 - nm) + __builtin_amdgcn_exp2f(z2 - nm);
+                sum = fmaf(sum, __builtin_amdgcn_exp2f(m2 - nm), __builtin_amdgcn_exp2f(z2 - nm));
                 m2 = nm;
             };
             // two register sets, ping-pong (rotating one set into the other costs a scalar move per weight per class, and a
@@ -675,9 +679,10 @@ __global__ void __launch_bounds__(256, 3) leaf_mlp_ce_kernel(const float* __rest
                 if (c + 1 < C) class1(c + 1, wb);
             }
         }
-        const float lse2 = m2 + __builtin_amdgcn_logf(sum);   // log2-sum-exp2;  lse = lse2 * ln 2
-        const float lse = lse2 * LN2;
-        loss_acc += valid ? lse - picked : 0.f;
+        // log2-sum-exp2;  lse = lse2 * ln 2.  The label's logit is subtracted before that scaling: both terms carry the same rounding of
+        // z * log2(e), so a one-class head loses exactly 0 (lse2 * ln 2 - z does not: the two roundings leave ~1e-7 |z| per pixel)
+        const float lse2 = m2 + __builtin_amdgcn_logf(sum);
+        loss_acc += valid ? (lse2 - picked) * LN2 : 0.f;
         const float gscale = valid ? inv : 0.f;
 
         // pass 2: gradients.  A runtime loop over the classes (the class arithmetic exists once in the code: unrolling it

@@ -82,7 +82,8 @@ int hsr_loss_ssim_grad(int C, int H, int W, const float* img1, const float* img2
  * calls .long()).  out_grad ([K,H,W], may be NULL) receives d (sum_l level_weight[l] * loss_l) / d logits; channels
  * outside every level get 0.  `level_sizes` and `level_weight` are HOST arrays of num_levels entries; level_weight == NULL
  * means all ones.  Labels must lie in [0, level_sizes[l]) or equal ignore_index (torch asserts this; here an out-of-range
- * label is treated as matching no class). */
+ * label is treated as matching no class: its pixel contributes the log-sum-exp and gets the plain softmax as its gradient,
+ * and such a pixel still counts toward the mean).  hsr_loss_leaf_mlp_ce follows the same rule. */
 int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight, const float* logits,
                      const int64_t* labels, int ignore_index, float* out_level_loss, float* out_grad, char* scratch,
                      size_t scratch_bytes, void* stream);

@@ -89,7 +89,9 @@ def ssim(img1, img2, window_size=11):
 
 def tree_cross_entropy(logits, labels, level_sizes, ignore_index=-100):
     """sum over levels of CrossEntropyLoss(logits[begin:end] as [H*W, n_l], labels[l])  (scripts/hierslam.py:963-974).
-    logits [K,H,W]; labels [L,H,W] integer, L >= len(level_sizes).  Returns (per-level losses, d sum / d logits)."""
+    logits [K,H,W]; labels [L,H,W] integer, L >= len(level_sizes).  Returns (per-level losses, d sum / d logits).
+    A label outside [0, n_l) that is not ignore_index (torch asserts; include/hsr_losses.h: "matching no class") still counts
+    toward the mean, contributes its log-sum-exp and gets the plain softmax, no one-hot, as its gradient."""
     z = np.asarray(logits, np.float64)
     K, H, W = z.shape
     grad = np.zeros_like(z)
@@ -103,11 +105,13 @@ def tree_cross_entropy(logits, labels, level_sizes, ignore_index=-100):
         m = zl.max(axis=0)
         e = np.exp(zl - m)
         lse = m + np.log(e.sum(axis=0))
-        safe = np.where(valid, lab, 0)
-        picked = zl[safe, np.arange(zl.shape[1])]
+        hit = valid & (lab >= 0) & (lab < n_l)             # out of range: no class matches
+        safe = np.where(hit, lab, 0)
+        cols = np.arange(zl.shape[1])
+        picked = np.where(hit, zl[safe, cols], 0.0)
         losses.append(((lse - picked) * valid).sum() / cnt if cnt else float("nan"))
         sm = e / e.sum(axis=0)
-        sm[safe, np.arange(zl.shape[1])] -= 1.0
+        sm[safe, cols] -= hit
         if cnt:
             grad[begin:begin + n_l] = (sm * valid / cnt).reshape(n_l, H, W)
         begin += n_l
@@ -116,7 +120,8 @@ def tree_cross_entropy(logits, labels, level_sizes, ignore_index=-100):
 
 def leaf_mlp_cross_entropy(sem, weight, bias, labels, ignore_index=-100):
     """logits = Conv2d(K, C, 1)(sem) (scripts/hierslam.py:1756, :976-978), CrossEntropyLoss()(logits as [H*W, C], labels)
-    (:979-982).  sem [K,H,W], weight [C,K], bias [C], labels [H,W].  Returns (loss, d_sem, d_weight, d_bias)."""
+    (:979-982).  sem [K,H,W], weight [C,K], bias [C], labels [H,W].  Returns (loss, d_sem, d_weight, d_bias).
+    Out-of-range labels as in tree_cross_entropy: counted, log-sum-exp as the loss, softmax without one-hot as the gradient."""
     s_ = np.asarray(sem, np.float64)
     K, H, W = s_.shape
     w, b = np.asarray(weight, np.float64).reshape(-1, K), np.asarray(bias, np.float64)
@@ -128,9 +133,11 @@ def leaf_mlp_cross_entropy(sem, weight, bias, labels, ignore_index=-100):
     m = z.max(axis=0)
     e = np.exp(z - m)
     lse = m + np.log(e.sum(axis=0))
-    safe = np.where(valid, lab, 0)
-    loss = ((lse - z[safe, np.arange(z.shape[1])]) * valid).sum() / cnt if cnt else float("nan")
+    hit = valid & (lab >= 0) & (lab < z.shape[0])
+    safe = np.where(hit, lab, 0)
+    cols = np.arange(z.shape[1])
+    loss = ((lse - np.where(hit, z[safe, cols], 0.0)) * valid).sum() / cnt if cnt else float("nan")
     g = e / e.sum(axis=0)
-    g[safe, np.arange(z.shape[1])] -= 1.0
+    g[safe, cols] -= hit
     g = g * valid / cnt if cnt else np.zeros_like(g)
     return loss, (w.T @ g).reshape(K, H, W), g @ x.T, g.sum(axis=1)
