@@ -4,8 +4,8 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT against include/ext/ with the same checker, from the extension's own suite).  There is NO fallback
-path: a missing library is an ImportError.
+include/hsr_*.h; SIGNATURES_EXT and SIGNATURES_EXT_MAP_INIT against include/ext/ with the same checker, each from its extension's own
+suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
 import os
@@ -229,6 +229,15 @@ SIGNATURES_EXT = (
                              cf, vp, vp, sz, vp]),
 )
 
+# include/ext/hsr_map_init.h: a table of its own (SIGNATURES_EXT is pinned to the MS-SSIM header by that header's suite)
+SIGNATURES_EXT_MAP_INIT = (
+    ("hsr_map_init_scratch_bytes", sz, [ci, ci]),
+    ("hsr_map_init_frame", ci, [ci, ci, vp, vp, cf, cf, cf, cf, vp,
+                                cf, ci, ci, vp, vp, vp,
+                                vp, vp, vp, vp,
+                                vp, sz, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -237,7 +246,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in SIGNATURES + SIGNATURES_EXT:
+    for name, restype, argtypes in SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT:
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

@@ -8,6 +8,7 @@ from .camera import setup_camera_tensors, setup_camera  # noqa: F401
 from .synthetic import make_scene, make_upstream_grads  # noqa: F401
 
 _KEYFRAMES = ("keyframe_selection_overlap", "overlap_counts", "KeyframePoses", "mapping_window")
+_SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "SlamSession")
 
 
 def __getattr__(name):
@@ -15,4 +16,7 @@ def __getattr__(name):
     if name in _KEYFRAMES:
         from . import keyframes
         return getattr(keyframes, name)
+    if name in _SLAM:      # the loop driver binds the library too
+        from . import slam
+        return getattr(slam, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
