@@ -776,7 +776,7 @@ size_t hsr_carve_img(char* base, int W, int H, ImgState* out)
     char* p = base;
     ImgState s;
     const size_t N = (size_t)W * H;
-    const size_t T = (size_t)((W + HSR_TILE_X - 1) / HSR_TILE_X) * ((H + HSR_TILE_Y - 1) / HSR_TILE_Y);
+    const size_t T = (size_t)hsr_num_tiles(W, H);
     take(p, s.ranges, T);
     take(p, s.final_T, N);
     take(p, s.n_contrib, N);

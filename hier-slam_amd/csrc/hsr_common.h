@@ -76,7 +76,6 @@ __host__ __device__ inline bool hsr_bin_resolve(const BinDevRef& ref, uint32_t R
 size_t hsr_carve_geom(char* base, int P, GeomState* out);
 size_t hsr_carve_img(char* base, int W, int H, ImgState* out);
 size_t hsr_carve_bin(char* base, int R, BinState* out);
-uint32_t hsr_sort_hist_entries(int R);
 
 void hsr_set_error(const char* fmt, ...);
 
@@ -140,7 +139,6 @@ int hsr_launch_tile_sort(BinState& b, int T, int P, const uint2* ranges, hipStre
                          int avg_per_tile_hint = 0);  // per-tile (depth, index) sort; hint: entries per tile of the previous frame
 int hsr_sort_tile_passes(int end_bit);
 bool hsr_sort_emit_into_sorted_buffers(int end_bit);
-int hsr_launch_tile_ranges(int R, int T, const uint64_t* keys, uint2* ranges, hipStream_t stream);
 int hsr_launch_tile_ranges_only(int R, const uint64_t* keys, uint2* ranges, hipStream_t stream);
 
 struct RenderFwdArgs {

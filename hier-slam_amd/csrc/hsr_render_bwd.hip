@@ -54,8 +54,8 @@ __global__ void __launch_bounds__(256) render_bwd_kernel(RenderBwdArgs a, int c0
     __shared__ uint8_t s_flat[4][256];
     __shared__ int s_wmax[4];
 
-    const int tile = hsr_block_tile(blockIdx.x, ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y));
-    if (tile >= ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)) return;
+    const int tile = hsr_block_tile(blockIdx.x, hsr_num_tiles(a.W, a.H));
+    if (tile >= hsr_num_tiles(a.W, a.H)) return;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const TileGeom tg = tile_geom(tile, a.W, a.H, t);
     const bool inside = tg.inside;
@@ -277,7 +277,7 @@ int hsr_launch_render_backward(int kernel, const RenderBwdArgs& a, hipStream_t s
         hsr_set_error("the all-VALU backward kernel writes packed rows of the classic layout only");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const int tiles = ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
+    const int tiles = hsr_num_tiles(a.W, a.H);
     const dim3 grid(hsr_tile_grid(tiles)), block(256);
     if (!a.semantic || a.K == 0) {
         render_bwd_kernel<0, true><<<grid, block, 0, stream>>>(a, 0);

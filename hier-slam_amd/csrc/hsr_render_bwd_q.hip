@@ -39,7 +39,7 @@
 //     4.57 M requests at the headline = 0.225 ms at the memory side's rate, 0.28 measured with or without the instruction savings.
 //     What helps there is fewer LINES: compact rows (hsr_tile_common.h) make K = 0 one line instead of two and 12 <= K <= 20 two
 //     instead of three; K = 26 needs 36 floats and stays at three.
-#include "hsr_tile_common.h"
+#include "hsr_bwd_tile.h"
 
 #ifdef HSR_TRACE
 // Diagnostic build only (make -C hier-slam_amd/csrc trace -> libhsr_rast_trace.so, tools/trace_bwd.py): per-wave cycle counts of
@@ -58,21 +58,6 @@ extern "C" int hsr_debug_read_trace_q(unsigned long long* host, int n)
 #endif
 
 namespace {
-
-// see hsr_render_bwd_sub.hip: makes the staging registers of the next batch "used" before the first atomics of this batch are issued
-#define HSR_SETTLE_STAGING()                                                                                                   \
-    asm volatile("" ::"v"(id_next), "v"(p_xy.x), "v"(p_xy.y), "v"(p_co.x), "v"(p_co.y), "v"(p_co.z), "v"(p_co.w), "v"(p_r), "v"(p_g), \
-                 "v"(p_b), "v"(p_d), "v"(p_mask))
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// orders the LDS accesses of ONE wave (stores before it are visible to the wave's loads after it); no workgroup barrier
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int Q_ROWS = 16;                        // quadrant-list entries per chunk (M dimension of the matrix-core flush)
 constexpr int Q_CAP = 40;                         // (row, group) pairs a chunk may visit: one 16-pixel SEGMENT of each panel per pair.  A chunk of 16 rows
@@ -127,8 +112,8 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
     __shared__ float s_medj[BATCH];                    // median-depth gradient of each staged splat: see "median" below
     __shared__ uint8_t s_segtab[4][Q_ROWS][4];         // segment of each (row, group) pair of the chunk, Q_SEG_ZERO where the group does not visit the row
 
-    const int tile = hsr_block_tile(blockIdx.x, ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y));
-    if (tile >= ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)) return;
+    const int tile = hsr_block_tile(blockIdx.x, hsr_num_tiles(a.W, a.H));
+    if (tile >= hsr_num_tiles(a.W, a.H)) return;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, gq = lane >> 4, l16 = lane & 15;
     const TileGeom tg = tile_geom_sub(tile, a.W, a.H, t);
     const bool inside = tg.inside;
@@ -192,15 +177,9 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
                 else if (ch == KC + 4) v = dpo;
                 gv[g][c] = v;
             }
-        // the panels are private to the wave: a wave-level fence orders its LDS stores and loads, the four waves do not have to meet
 #pragma unroll
         for (int g = 0; g < NG; g++) {
-#pragma unroll
-            for (int c = 0; c < 16; c++) pw[lane * 17 + c] = gv[g][c];
-            wave_lds_fence();
-#pragma unroll
-            for (int m = 0; m < 16; m++) Breg[g][m] = pw[(4 * m + (lane >> 4)) * 17 + (lane & 15)];
-            wave_lds_fence();
+            HSR_BWD_TRANSPOSE_B(pw, lane, gv[g], Breg[g]);
         }
     }
     if (lane < 2 * Q_SEGW) {   // the zero segments (GEO: one, of float2)
@@ -225,31 +204,8 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
     const uint2 DUMMY_ELEM = make_uint2((uint32_t)(BATCH * ENTB), (uint32_t)Q_SEG_DUMMY * SEGB);
     uint2* const ordp = &s_ord[wv][gq][0];
 
-    // ---- software-pipelined staging ----
-    int id_next = 0, id_cur = 0;
-    float2 p_xy = {0, 0};
-    float4 p_co = {0, 0, 0, 0};
-    float p_r = 0, p_g = 0, p_b = 0, p_d = 0;
-    uint32_t p_mask = 0u;
-    const int n_list = (int)(range.y - range.x);
-    auto fetch_id = [&](int hi) -> int { return (int)a.point_list[range.x + min(max(hi - 1 - t, 0), max(n_list - 1, 0))]; };
-    auto fetch_mask = [&](int hi) -> uint32_t { return a.masks[range.x + min(max(hi - 1 - t, 0), max(n_list - 1, 0))]; };
-    auto load_record = [&](int id_of) {
-        const size_t id = (size_t)id_of;
-        id_cur = id_of;
-        const float4* rec = a.rec + 4 * id;
-        const float4 r0 = rec[0], r2 = rec[2];
-        p_co = rec[1];
-        p_xy = make_float2(r0.x, r0.y);
-        p_d = r0.z;
-        p_r = r2.x; p_g = r2.y; p_b = r2.z;
-    };
-    if (n_list > 0) {
-        const int id0 = fetch_id(hi_all);
-        id_next = fetch_id(hi_all - BATCH);
-        load_record(id0);
-        p_mask = fetch_mask(hi_all);
-    }
+    HSR_BWD_STAGING_DECLARE();
+    HSR_BWD_STAGING_PRIME(hi_all, BATCH);
 
     // the chunk's segments -> packed rows
     auto flush = [&](int nrows) {
@@ -458,9 +414,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             s_mask[t] = (uint16_t)mask;
             s_id[t] = id_cur;
             s_medj[t] = 0.f;
-            s_ent[REC4 * t] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);
-            s_ent[REC4 * t + 1] = make_float4(p_r, p_g, p_b, p_d);
-            s_ent[REC4 * t + 2] = make_float4((-0.5f * HSR_LOG2E) * p_co.z, p_co.w, (-0.5f * HSR_LOG2E) * p_co.y, 0.f);   // C', opacity, B' / 2
+            HSR_BWD_STORE_RECORD(s_ent, REC4 * t);
             if (SEMA) {   // the splat's features of this pass's channels (zero past K); read here, once per staged splat
                 const float* f = a.semantics + (size_t)id_cur * (size_t)a.K;
 #pragma unroll
@@ -487,12 +441,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             const int jm = hi - 1 - median_at;
             if (jm >= 0 && jm < cnt && dpm != 0.f) atomicAdd(&s_medj[jm], dpm);
         }
-        {
-            const int id_use = id_next;            // ids of the next batch, requested a whole batch ago
-            id_next = fetch_id(hi - 2 * BATCH);
-            load_record(id_use);
-            p_mask = fetch_mask(hi - BATCH);
-        }
+        HSR_BWD_STAGING_ADVANCE(hi, BATCH);
         TR_ADD(tr_stage, ts);
         if (hi - cnt >= wmax) {   // this wave's pixels all stopped in front of this batch
             HSR_SETTLE_STAGING();
@@ -531,9 +480,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             if (touch) {
                 ordp[__popc(gmask & ((1u << l16) - 1u))] = make_uint2(eoff, seg * SEGB);
             }
-            // wave-uniform iteration count: the longest of the four lists
-            const int iters = __builtin_amdgcn_readfirstlane(max(max(__popc((uint32_t)ball & 0xFFFFu), __popc((uint32_t)(ball >> 16) & 0xFFFFu)),
-                                                                 max(__popc((uint32_t)(ball >> 32) & 0xFFFFu), __popc((uint32_t)(ball >> 48)))));
+            const int iters = longest_group_list(ball);
             wave_lds_fence();
             // A wave issues one instruction every 7-10 cycles whatever the instruction, so what a visit costs is its instruction count and
             // what the chip delivers is that count times the waves in flight (profiles/r04_b_pmc_*.json.txt).  The visit is software-
@@ -661,7 +608,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
 // packed mode, K <= 27, P * grow_stride < 2^30 (32-bit row addressing).  a.grow_layout / a.grow_stride: the plan's (hsr_api.hip).
 int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream)
 {
-    const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
+    const dim3 grid(hsr_tile_grid(hsr_num_tiles(a.W, a.H))), block(256);
     const int K = a.semantic ? a.K : 0;
     const bool cl = a.grow_layout == 1;
     if (K < 0 || K > 27 || (K == 0 && !cl) || !a.grow || a.grow_stride != hsr_grow_stride_l(a.grow_layout, K) ||
@@ -687,7 +634,7 @@ int hsr_launch_render_backward_q(const RenderBwdArgs& a, hipStream_t stream)
 int hsr_launch_render_backward_qsema(const RenderBwdArgs& a0, hipStream_t stream)
 {
     RenderBwdArgs a = a0;
-    const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
+    const dim3 grid(hsr_tile_grid(hsr_num_tiles(a.W, a.H))), block(256);
     for (int c0 = 0; c0 < a.K; c0 += 16) {
         a.sem_c0 = c0;
         render_bwd_q_kernel<16, 208, true, false, true><<<grid, block, 0, stream>>>(a);
@@ -702,6 +649,6 @@ int hsr_launch_render_backward_qgeo(const RenderBwdArgs& a, hipStream_t stream)
         hsr_set_error("geometry-only backward kernel: needs packed rows of 16 floats (got stride %d) and P * 16 < 2^30", a.grow_stride);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    render_bwd_q_kernel<0, 208, true><<<dim3(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), dim3(256), 0, stream>>>(a);
+    render_bwd_q_kernel<0, 208, true><<<dim3(hsr_tile_grid(hsr_num_tiles(a.W, a.H))), dim3(256), 0, stream>>>(a);
     return HSR_OK;
 }

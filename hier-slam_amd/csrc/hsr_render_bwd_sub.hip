@@ -22,27 +22,10 @@
 // waves can meet is an LDS table, and ds_add_f32 costs ~170 cycles per wave-instruction on gfx950 (measured with exactly
 // that design: 1.03 ms, of which 0.68 ms LDS atomics).
 // K <= 27 and the geometry-only path take the Q-panel kernels of hsr_render_bwd_q.hip.
-#include "hsr_tile_common.h"
+#include "hsr_bwd_tile.h"
 #include "hsr_wave_reduce.h"
 
 namespace {
-
-// Makes the staging registers of the next batch "used" BEFORE the first atomics of this batch are issued: hipcc then waits for their
-// loads here — they were issued a chunk of blending ago and have landed — instead of at the next batch's staging, where the same
-// s_waitcnt would also have to sit out every atomic issued in between (loads, stores and atomics retire through one in-order counter).
-#define HSR_SETTLE_STAGING()                                                                                                   \
-    asm volatile("" ::"v"(id_next), "v"(p_xy.x), "v"(p_xy.y), "v"(p_co.x), "v"(p_co.y), "v"(p_co.z), "v"(p_co.w), "v"(p_r), "v"(p_g), \
-                 "v"(p_b), "v"(p_d), "v"(p_mask))
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// orders the LDS accesses of ONE wave (stores before it are visible to the wave's loads after it); no workgroup barrier
-__device__ __forceinline__ void wave_lds_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 constexpr int SB_SLOTS = 16;        // quadrant-list entries per chunk (M dimension of the matrix-core flush)
 constexpr int SB_STRIDE = 66;       // floats per panel row
@@ -122,8 +105,8 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
     __shared__ __attribute__((aligned(16))) uint32_t s_cid[4][SB_SLOTS];   // packed-row offset (Gaussian id x row stride) of each chunk row
     __shared__ __attribute__((aligned(16))) float s_u7[4][SB_SLOTS * 8 * 4];   // [row][value 0..7][group]: butterfly sums; the four groups of a value are ONE 16-byte read at emission
 
-    const int tile = hsr_block_tile(blockIdx.x, ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y));
-    if (tile >= ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)) return;
+    const int tile = hsr_block_tile(blockIdx.x, hsr_num_tiles(a.W, a.H));
+    if (tile >= hsr_num_tiles(a.W, a.H)) return;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6, gq = lane >> 4, l16 = lane & 15;
     const TileGeom tg = tile_geom_sub(tile, a.W, a.H, t);
     const bool inside = tg.inside;
@@ -175,12 +158,10 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
             }
             gv[c] = v;
         }
+        if (BF) {   // the transposition of HSR_BWD_TRANSPOSE_B, read back eight pixels at a time and split
 #pragma unroll
-        for (int c = 0; c < 16; c++) panel[lane * 17 + c] = gv[c];
-        // the panel is private to the wave: a wave-level fence orders its LDS stores and loads, the four waves do not have to meet
-        // (they would wait for the slowest wave's 30-odd global loads twice per channel group)
-        wave_lds_fence();
-        if (BF) {
+            for (int c = 0; c < 16; c++) panel[lane * 17 + c] = gv[c];
+            wave_lds_fence();
 #pragma unroll
             for (int s2 = 0; s2 < 2; s2++) {
                 float x[8];
@@ -188,11 +169,10 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
                 for (int e = 0; e < 8; e++) x[e] = panel[(32 * s2 + 8 * (lane >> 4) + e) * 17 + (lane & 15)];
                 split3_bf16(x, Bh[g][s2], Bm[g][s2], Bl[g][s2]);
             }
+            wave_lds_fence();
         } else {
-#pragma unroll
-            for (int m = 0; m < 16; m++) Breg[g][m] = panel[(4 * m + (lane >> 4)) * 17 + (lane & 15)];
+            HSR_BWD_TRANSPOSE_B(panel, lane, gv, Breg[g]);
         }
-        wave_lds_fence();
     }
     __syncthreads();   // s_wmax
     const int hi_all = max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3]));
@@ -289,36 +269,8 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
         }
     };
 
-    // ---- software-pipelined staging ----
-    int id_next = 0, id_cur = 0;
-    float2 p_xy = {0, 0};
-    float4 p_co = {0, 0, 0, 0};
-    float p_r = 0, p_g = 0, p_b = 0, p_d = 0;
-    uint32_t p_mask = 0u;
-    // unconditional, clamped staging loads, the id of the batch after next requested before the next batch's records: see
-    // render_fwd_kernel (a load inside a divergent `if`, or into a register the loads before it took their addresses from, is waited
-    // for where it is issued — and the (rec == NULL) fallback kept three of these values in a scratch slot).  a.rec is never NULL.
-    const int n_list = (int)(range.y - range.x);
-    auto fetch_id = [&](int hi) -> int { return (int)a.point_list[range.x + min(max(hi - 1 - t, 0), max(n_list - 1, 0))]; };
-    // the forward's staging phase left the 16-bit sub-block mask of every list entry it staged in a.masks (the backward stages a subset
-    // of those entries: it stops at the tile's largest n_contrib): one 4-byte load per entry instead of ~460 instructions of subblock_mask
-    auto fetch_mask = [&](int hi) -> uint32_t { return a.masks[range.x + min(max(hi - 1 - t, 0), max(n_list - 1, 0))]; };
-    auto load_record = [&](int id_of) {
-        const size_t id = (size_t)id_of;
-        id_cur = id_of;
-        const float4* rec = a.rec + 4 * id;
-        const float4 r0 = rec[0], r2 = rec[2];
-        p_co = rec[1];
-        p_xy = make_float2(r0.x, r0.y);
-        p_d = r0.z;
-        p_r = r2.x; p_g = r2.y; p_b = r2.z;
-    };
-    if (n_list > 0) {
-        const int id0 = fetch_id(hi_all);
-        id_next = fetch_id(hi_all - BATCH);
-        load_record(id0);
-        p_mask = fetch_mask(hi_all);
-    }
+    HSR_BWD_STAGING_DECLARE();
+    HSR_BWD_STAGING_PRIME(hi_all, BATCH);
 
     for (int hi = hi_all; hi > 0; hi -= BATCH) {
         const int cnt = min(BATCH, hi);
@@ -328,22 +280,14 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
         uint32_t qmask = 0u;
         if (t < cnt) {
             const uint32_t mask = p_mask;
-            qmask = (uint32_t)((mask & 0xFu) != 0u) | ((uint32_t)((mask & 0xF0u) != 0u) << 1) | ((uint32_t)((mask & 0xF00u) != 0u) << 2) |
-                    ((uint32_t)((mask & 0xF000u) != 0u) << 3);
+            qmask = quadrant_bits(mask);
             s_mask[t] = (uint16_t)mask;
             s_id[t] = id_cur;
-            s_ent[3 * t] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);
-            s_ent[3 * t + 1] = make_float4(p_r, p_g, p_b, p_d);
-            s_ent[3 * t + 2] = make_float4((-0.5f * HSR_LOG2E) * p_co.z, p_co.w, (-0.5f * HSR_LOG2E) * p_co.y, 0.f);   // C', opacity, B' / 2
+            HSR_BWD_STORE_RECORD(s_ent, 3 * t);
         }
         publish_quadrant_lists(qmask, t, s_list, s_lcnt);
         __syncthreads();
-        {
-            const int id_use = id_next;            // ids of the next batch, requested a whole batch ago
-            id_next = fetch_id(hi - 2 * BATCH);
-            load_record(id_use);
-            p_mask = fetch_mask(hi - BATCH);
-        }
+        HSR_BWD_STAGING_ADVANCE(hi, BATCH);
         if (hi - cnt >= wmax) {   // this wave's pixels all stopped in front of this batch
             HSR_SETTLE_STAGING();
             continue;
@@ -362,9 +306,7 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
                 s_cid[wv][l16] = (uint32_t)s_id[jr] * (uint32_t)a.grow_stride;   // once per chunk row, not once per emitted register
             }
             clear_chunk();
-            // wave-uniform (readfirstlane: the loop counter then lives in a scalar register, not in a VALU down-counter)
-            const int iters = __builtin_amdgcn_readfirstlane(max(max(__popc((uint32_t)ball & 0xFFFFu), __popc((uint32_t)(ball >> 16) & 0xFFFFu)),
-                                                                 max(__popc((uint32_t)(ball >> 32) & 0xFFFFu), __popc((uint32_t)(ball >> 48)))));
+            const int iters = longest_group_list(ball);
             uint32_t todo = (uint32_t)(ball >> (16 * gq)) & 0xFFFFu;   // this group's entries, visited in list order
             int r_next = todo ? __builtin_ctz(todo) : 0;
             int j_next = s_cj[wv][r_next];
@@ -455,7 +397,7 @@ void launch_subw_pass(const RenderBwdArgs& a, int c0, int ns, dim3 grid, hipStre
 // semantic variant with K > 27, packed mode, P * grow_stride < 2^30: BASE pass (up to 107 channels + the base sums) + SEM passes of 64
 int hsr_launch_render_backward_subw(const RenderBwdArgs& a, hipStream_t stream)
 {
-    const int tiles = ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y);
+    const int tiles = hsr_num_tiles(a.W, a.H);
     const dim3 grid(hsr_tile_grid(tiles));
     const int K = a.K;
     if (!a.semantic || K <= 27 || !a.grow || a.grow_layout != 0 || a.grow_stride != hsr_grow_stride(K) || !hsr_rows_fit_32bit(a.P, a.grow_stride)) {

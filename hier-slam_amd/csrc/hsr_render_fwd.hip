@@ -157,8 +157,8 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     __shared__ uint8_t s_subcnt[4][16];
     __shared__ int s_wdone[4];
 
-    const int tile = hsr_block_tile(blockIdx.x, ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y));
-    if (tile >= ((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y)) return;
+    const int tile = hsr_block_tile(blockIdx.x, hsr_num_tiles(a.W, a.H));
+    if (tile >= hsr_num_tiles(a.W, a.H)) return;
     const int t = threadIdx.x, wv = t >> 6;
     if (a.bin.base) {   // speculative forward: the list lives where num_rendered says
         BinState bs;
@@ -548,7 +548,7 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
 
 int hsr_launch_render_forward(const RenderFwdArgs& a, hipStream_t stream)
 {
-    const dim3 grid(hsr_tile_grid(((a.W + HSR_TILE_X - 1) / HSR_TILE_X) * ((a.H + HSR_TILE_Y - 1) / HSR_TILE_Y))), block(256);
+    const dim3 grid(hsr_tile_grid(hsr_num_tiles(a.W, a.H))), block(256);
     // Every K: the per-lane kernel on 4x4 sub-block lists.  Measured at the headline workload (500k
     // Gaussians, 1200x680, K = 26): 0.18 ms against 0.22 ms for the same kernel on quadrant lists and 0.27 ms for round 1's
     // pair-pipelined matrix-core kernel (EXPERIMENTS.md §4: the ~25 VALU instructions that evaluate alpha per list entry dominate, the

@@ -152,8 +152,6 @@ __global__ void __launch_bounds__(SORT_THREADS) sort_scatter_kernel(const uint64
 
 }  // namespace
 
-uint32_t hsr_sort_hist_entries(int R) { return hsr_sort_hist_entries_inline((uint32_t)(R > 0 ? R : 0)); }
-
 
 // ---- phase 2: per-tile sort by (depth bits, Gaussian index) ----
 // After the tile passes every tile's entries are contiguous and still in emission order (ascending Gaussian

@@ -29,6 +29,7 @@
 // record (and its 4K-byte semantic row) into a different L2.  Here XCD x walks the contiguous tile range
 // [x * ceil(T/8), (x+1) * ceil(T/8)) in order: horizontally and vertically adjacent tiles run on the same XCD at about the
 // same time and share those lines.  Launch hsr_tile_grid(T) workgroups; workgroups mapped past T exit at once.
+__host__ __device__ inline int hsr_num_tiles(int W, int H) { return ((W + HSR_TILE_X - 1) / HSR_TILE_X) * ((H + HSR_TILE_Y - 1) / HSR_TILE_Y); }
 __host__ __device__ inline int hsr_tile_grid(int T) { return 8 * ((T + 7) / 8); }
 __device__ __forceinline__ int hsr_block_tile(int b, int T) { return (b & 7) * ((T + 7) >> 3) + (b >> 3); }
 

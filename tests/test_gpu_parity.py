@@ -331,6 +331,18 @@ def test_parity_at_the_row_layout_and_kernel_edges(K):
     _compare(cam, sc, up, True, "sr", None)
 
 
+# The wide-tree kernel's channel passes: the last K of one column-group count and the first K of the next.  The BASE pass has
+# ceil((K + 5) / 16) column groups (3..7) up to K = 107, the first SEM pass takes the next 64 channels in ceil(ns / 16) groups (1..4),
+# K = 172 starts a second SEM pass.
+SUBW_PASS_EDGE_K = [43, 44, 59, 60, 75, 76, 91, 92, 107, 108, 123, 124, 139, 140, 155, 156, 171, 172]
+
+
+@pytest.mark.parametrize("K", SUBW_PASS_EDGE_K)
+def test_parity_at_the_wide_tree_pass_edges(K):
+    cam, sc, up = scenes.build(64, 48, 400, K, seed=7, kind="aniso", scale_mult=2.0)
+    _compare(cam, sc, up, True, "sr", None)
+
+
 @pytest.mark.parametrize("K", PLAN_EDGE_K)
 def test_geometry_only_backward_at_the_row_layout_and_kernel_edges(K):
     """the geometry-only request at the same K: its 16-float rows and kernel do not depend on K, the full backward's do"""
