@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT and SIGNATURES_EXT_MAP_INIT against include/ext/ with the same checker, each from its extension's own
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT and SIGNATURES_EXT_FRAME_RESAMPLE against include/ext/ with the same checker, each from its extension's own
 suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -238,6 +238,12 @@ SIGNATURES_EXT_MAP_INIT = (
                                 vp, sz, vp]),
 )
 
+# include/ext/hsr_frame_resample.h: again a table of its own (the two above are pinned by their suites)
+SIGNATURES_EXT_FRAME_RESAMPLE = (
+    ("hsr_frame_resample", ci, [ci, ci, vp, vp, ci, ci, vp, vp,
+                                ci, ci, vp, vp, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -246,7 +252,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT:
+    for name, restype, argtypes in SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE:
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

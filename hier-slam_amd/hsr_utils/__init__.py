@@ -4,11 +4,12 @@ These mirror caller-side conventions of the reference (utils/recon_helpers.py:4-
 scripts/hierslam.py:361-389) so that tests and bench.py feed the rasterizer the same
 shapes and layouts scripts/hierslam.py does.  Nothing here computes on the hot path.
 """
-from .camera import setup_camera_tensors, setup_camera  # noqa: F401
+from .camera import setup_camera_tensors, setup_camera, scale_intrinsics  # noqa: F401
 from .synthetic import make_scene, make_upstream_grads  # noqa: F401
 
 _KEYFRAMES = ("keyframe_selection_overlap", "overlap_counts", "KeyframePoses", "mapping_window")
-_SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "SlamSession")
+_SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "SlamSession",
+         "resample_frame")
 
 
 def __getattr__(name):

@@ -36,6 +36,22 @@ def setup_camera(w, h, k, w2c, near=0.01, far=100, device="cuda"):
     return Camera(**setup_camera_tensors(w, h, k, w2c, near, far, device))
 
 
+def scale_intrinsics(intrinsics, h_ratio, w_ratio):
+    """The intrinsics of a frame resized by h_ratio = h_new / h_old and w_ratio = w_new / w_old, the job of the reference's helper of the
+    same name (datasets/gradslam_datasets/datautils.py:73-117; the ratios as basedataset.py:140 forms them): a float32 copy of a numpy
+    array or torch tensor [...,3,3] or [...,4,4] whose fx and cx are multiplied by w_ratio and whose fy and cy by h_ratio.  Anything
+    else is a TypeError, another shape a ValueError; the input is not written to."""
+    from_numpy = isinstance(intrinsics, np.ndarray)
+    if not from_numpy and not torch.is_tensor(intrinsics):
+        raise TypeError("scale_intrinsics: a numpy array or a torch tensor is needed, not %s" % type(intrinsics).__name__)
+    if tuple(intrinsics.shape[-2:]) not in ((3, 3), (4, 4)):
+        raise ValueError("scale_intrinsics: the last two dimensions must be 3x3 or 4x4, not %s" % (tuple(intrinsics.shape),))
+    out = np.array(intrinsics, dtype=np.float32) if from_numpy else intrinsics.detach().to(torch.float32, copy=True)
+    out[..., 0, [0, 2]] *= w_ratio      # fx, cx
+    out[..., 1, [1, 2]] *= h_ratio      # fy, cy
+    return out
+
+
 def replica_intrinsics(w=1200, h=680):
     """configs/data/replica_semantic.yaml:5-8 (fx=fy=600, cx=599.5, cy=339.5 at 1200x680), scaled."""
     sx, sy = w / 1200.0, h / 680.0

@@ -1,8 +1,10 @@
 """The SLAM loop of scripts/hierslam.py as a library: first-frame map, pose seeding, and the per-frame tracking and mapping steps, joined
-from the device rows this package already has plus one new one, the first-frame map (row 8, include/ext/hsr_map_init.h).
+from the device rows this package already has plus two of its own (row 8): the first-frame map
+(include/ext/hsr_map_init.h) and the resample of a frame to the tracking and densification sizes (include/ext/hsr_frame_resample.h).
 
     initialize_first_timestep(color, depth, intrinsics, w2c, num_frames, scene_radius_depth_ratio, mean_sq_dist_method,
                               gaussian_distribution, num_semantic=None)        scripts/hierslam.py:419-578 with :144-194 and :322-409
+    resample_frame(color, depth, sizes)                                        basedataset.py:223-227 (colour, bilinear), :248-252 (depth, nearest)
     initialize_camera_pose(params, curr_time_idx, forward_prop)                :1354-1373
     update_poses(params, sliding_window_kf)                                    :57-70
     matrix_to_quaternion(matrix)                                               what the use_gt_poses branch needs (:1895-1904)
@@ -11,6 +13,7 @@ from the device rows this package already has plus one 
         step(frame)            pose seeding, track_frame, map_frame (every map_every frames), add_keyframe, in the reference's order;
                                the first call (frame id 0) builds the map from the frame and maps it without densification
         track_frame(frame)     :1808-1904      map_frame(frame)     :1927-2083      add_keyframe(frame)     :2107-2124
+        tracking_data(frame)   :1792-1799      densify_data(frame)  :1933-1941      {'im', 'depth', 'cam', 'intrinsics'} at that size
 
 `config` is a dict with the reference's key names (configs/*/*.py): tracking / mapping (num_iters, lrs, loss_weights, sil_thres,
 use_sil_for_loss, use_l1, ignore_outlier_depth_loss; tracking: forward_prop, use_gt_poses, use_depth_loss_thres, depth_loss_thres;
@@ -20,8 +23,25 @@ Three values the reference takes from its dataset object are keys here, since th
 num_semantic (absent or None: a map without semantics; an int: flat classes; a list: the classes per tree level, K = their sum) and
 num_semantic_class (the leaf head's classes, with model.flag_use_embedding = 1).
 
+Tracking and densification may run at sizes of their own (:1543-1563): data.tracking_image_height / _width and
+data.densification_image_height / _width (or the same keys at the top level).  Absent keys mean the frame's own size, which is the
+camera's (cam.image_height / image_width; desired_image_* is not read); a height without its width, or the reverse, is a KeyError.  The
+session then has tracking_cam / tracking_intrinsics and densify_cam / densify_intrinsics (scale_intrinsics by new / old, setup_camera
+with the first frame's w2c, :441 and :1698); with the frame's own size they are the very objects cam / intrinsics and nothing is
+resampled.  track_frame renders with tracking_cam against the tracking frame (:1792-1799, :1830-1840) and records radii at that size,
+as get_loss(tracking_curr_data) does; map_frame hands the silhouette densification the densification frame, camera and intrinsics
+(:1933-1951); the first-frame map is built from the densification frame and intrinsics, scene_radius from its depth (:435-456).
+Keyframe selection, the mapping iterations, the keyframes and render() stay at the frame's own size (:1966, :1986-2075, :2107-2124).
+Both reduced frames come from ONE resample_frame launch per frame (one shared level when the two sizes are equal), cached for the
+current frame.  The reference resamples the SENSOR image to each size; the session resamples the frame it is given: the same thing
+when the frame is at sensor resolution, not when the frame was itself resized — a caller who needs the reference's frames there
+passes 'tracking_im' / 'tracking_depth' / 'densify_im' / 'densify_depth' in the frame, and they are used in place of the resample.
+Semantic sessions take the same route: :1949 passes densify_curr_data to the semantic densification and :480-496 is the first-frame
+code, although the reference never constructs the densification dataset for that branch (its own comment at :480: "not run").
+
 A frame is a dict: 'id' (its time index), 'im' [3,H,W] in 0..1, 'depth' [1,H,W], both float32 on the device; optional 'gt_w2c' [4,4]
-(relative to frame 0; read by use_gt_poses and by the keyframe rule's validity test) and 'semantic_label_gt' [levels (+1 leaf),H,W].
+(relative to frame 0; read by use_gt_poses and by the keyframe rule's validity test), 'semantic_label_gt' [levels (+1 leaf),H,W] and
+the four reduced tensors named above.  A frame dict is never modified.
 
 No dataset code, no logging service, no plotting, no checkpoint resume.  There is no CPU path for anything that renders; the pose seeding,
 the keyframe rule and the config handling are plain torch / Python and run anywhere.
@@ -64,6 +84,35 @@ def map_init_frame(color, depth, intrinsics, w2c, scene_radius_depth_ratio, S, c
     M = int(count.item())
     n = min(M, cap)
     return M, means[:n], rgb[:n], ls[:n], rots[:n], opac[:n], radius
+
+
+RESAMPLE_MAX_SIDE = 16384      # HSR_RESAMPLE_MAX_SIDE
+
+
+def resample_frame(color, depth, sizes):
+    """hsr_frame_resample on one RGB-D frame: `sizes` is a list of one or two (h, w); returns [(color_i [3,h,w], depth_i [1,h,w]), ...].
+    Colour bilinear with half-pixel centres and a replicated border, depth nearest with its bits copied, both as cv2.resize does in
+    basedataset.py:223-227 and :248-252 (include/ext/hsr_frame_resample.h states every step).  One launch for both levels, no host
+    synchronisation.  Non-contiguous input is made contiguous."""
+    if not (torch.is_tensor(color) and torch.is_tensor(depth) and color.is_cuda and depth.is_cuda and color.dtype == torch.float32
+            and depth.dtype == torch.float32):
+        raise RuntimeError("hsr_utils.slam: color and depth must be float32 tensors on a HIP device; there is no CPU path")
+    H, W = depth.shape[-2:]
+    if color.dim() != 3 or tuple(color.shape) != (3, H, W) or depth.numel() != H * W:
+        raise RuntimeError("hsr_utils.slam: color must be [3,H,W] and depth [H,W] or [1,H,W]; got %s and %s" % (tuple(color.shape), tuple(depth.shape)))
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if len(sizes) not in (1, 2):
+        raise ValueError("hsr_utils.slam: resample_frame takes one or two sizes, not %d" % len(sizes))
+    for side in (H, W) + tuple(v for hw in sizes for v in hw):
+        if not 1 <= side <= RESAMPLE_MAX_SIDE:
+            raise ValueError("hsr_utils.slam: resample_frame sides must be 1..%d; got a frame of %dx%d and sizes %s" % (RESAMPLE_MAX_SIDE, H, W, sizes))
+    dev = depth.device
+    col, d = color.contiguous(), depth.reshape(H, W).contiguous()
+    out = [(torch.empty((3, h, w), dtype=torch.float32, device=dev), torch.empty((1, h, w), dtype=torch.float32, device=dev)) for h, w in sizes]
+    (h1, w1), (c1, d1) = (sizes[1], out[1]) if len(sizes) == 2 else ((0, 0), (None, None))
+    _abi.call(_lib.hsr_frame_resample, "hsr_frame_resample", dev, H, W, col.data_ptr(), d.data_ptr(), sizes[0][0], sizes[0][1],
+              out[0][0].data_ptr(), out[0][1].data_ptr(), h1, w1, None if c1 is None else c1.data_ptr(), None if d1 is None else d1.data_ptr())
+    return out
 
 
 def _scale_columns(gaussian_distribution, semantic):
@@ -219,6 +268,15 @@ def normalize_config(config):
         cfg['num_frames'] = cfg['data']['num_frames']
     if int(cfg['num_frames']) < 1:
         raise ValueError("num_frames must be the number of frames of the run (there is no dataset to take the length of)")
+    data = cfg.get('data') or {}
+    for use in ('tracking', 'densification'):      # :1544-1563; absent: the frame's own size (None here; the session knows the frame)
+        hk, wk = use + '_image_height', use + '_image_width'
+        h, w = (cfg[k] if k in cfg else data.get(k) for k in (hk, wk))
+        if (h is None) != (w is None):             # the reference reads the other key of the pair at :1550 / :1560
+            raise KeyError("config['data']['%s']" % (wk if w is None else hk))
+        if h is not None and (int(h) < 1 or int(w) < 1):
+            raise ValueError("%s and %s must be positive, not %r and %r" % (hk, wk, h, w))
+        cfg[hk], cfg[wk] = (None, None) if h is None else (int(h), int(w))
     cfg.setdefault('num_semantic', None)
     if cfg['num_semantic'] is not None and cfg['model']['flag_use_embedding'] == 1 and 'num_semantic_class' not in cfg:
         raise KeyError("config['num_semantic_class']")
@@ -251,12 +309,72 @@ class SlamSession:
         self.keyframe_list, self.keyframe_time_indices, self.gt_w2c_all_frames = [], [], []
         self.last_window = None
         self.num_tracking_iters = 0
+        cfg = self.config
+        self.tracking_cam, self.tracking_intrinsics = self._level_camera(cfg['tracking_image_height'], cfg['tracking_image_width'])
+        self.densify_cam, self.densify_intrinsics = self._level_camera(cfg['densification_image_height'], cfg['densification_image_width'])
+        self._levels = None      # the reduced frames of the current frame: (key, {'tracking': (im, depth), 'densify': (im, depth)}, the frame's tensors)
+
+    # -- tracking and densification resolutions --
+    def _level_camera(self, h, w):
+        """(camera, intrinsics) of a level of h x w pixels: the session's own objects when that is the frame's size (or no size was
+        given), else intrinsics scaled by new / old (basedataset.py:140) and setup_camera on them (scripts/hierslam.py:441, :1698)"""
+        if h is None or (h, w) == (self.cam.image_height, self.cam.image_width):
+            return self.cam, self.intrinsics
+        from .camera import scale_intrinsics, setup_camera
+        k = scale_intrinsics(self.intrinsics, h / self.cam.image_height, w / self.cam.image_width)
+        k_host = k.detach().cpu().numpy() if torch.is_tensor(k) else k
+        w2c = self.first_frame_w2c
+        w2c_host = w2c.detach().cpu().numpy() if torch.is_tensor(w2c) else np.asarray(w2c)
+        level = setup_camera(w, h, k_host[..., :3, :3], w2c_host, device=self.cam.viewmatrix.device)
+        # what is not a matter of size comes from the session's camera; near / far are setup_camera's defaults, as in the reference
+        # (a settings tuple does not carry the planes its projection was built with)
+        return level._replace(**{f: getattr(self.cam, f) for f in ('bg', 'scale_modifier', 'sh_degree', 'prefiltered', 'debug')}), k
+
+    def _level_data(self, frame):
+        """the tracking and densification images and depths of `frame`, computed once per frame (kept until a frame with another id
+        or other tensors comes): the caller's own 'tracking_im' / 'tracking_depth' / 'densify_im' / 'densify_depth' where the frame has
+        them, the frame's tensors where the level has the frame's size, else ONE resample_frame call for every level still missing
+        (one level, shared, when both have the same size)"""
+        key = (int(frame['id']), frame['im'].data_ptr(), frame['depth'].data_ptr()) + tuple(
+            None if frame.get(k) is None else frame[k].data_ptr() for k in ('tracking_im', 'tracking_depth', 'densify_im', 'densify_depth'))
+        if self._levels is not None and self._levels[0] == key:
+            return self._levels[1]
+        levels, wanted = {}, {}
+        for use, cam in (('tracking', self.tracking_cam), ('densify', self.densify_cam)):
+            h, w = cam.image_height, cam.image_width
+            im, depth = frame.get(use + '_im'), frame.get(use + '_depth')
+            if im is not None or depth is not None:
+                if im is None or depth is None or tuple(im.shape) != (3, h, w) or tuple(depth.shape) != (1, h, w):
+                    raise RuntimeError("hsr_utils.slam: frame %d: '%s_im' must be [3,%d,%d] and '%s_depth' [1,%d,%d]; got %s and %s" % (
+                        key[0], use, h, w, use, h, w, None if im is None else tuple(im.shape), None if depth is None else tuple(depth.shape)))
+                levels[use] = (im, depth)
+            elif cam is self.cam:
+                levels[use] = (frame['im'], frame['depth'])
+            else:
+                wanted.setdefault((h, w), []).append(use)
+        if wanted:
+            for (_hw, uses), pair in zip(wanted.items(), resample_frame(frame['im'], frame['depth'], list(wanted))):
+                for use in uses:
+                    levels[use] = pair
+        self._levels = (key, levels, (frame['im'], frame['depth']))      # the tensors kept alive: their pointers are the key
+        return levels
+
+    def tracking_data(self, frame):
+        """what the tracking loop compares against (scripts/hierslam.py:1792-1799): {'im', 'depth', 'cam', 'intrinsics'} at tracking size"""
+        im, depth = self._level_data(frame)['tracking']
+        return {'im': im, 'depth': depth, 'cam': self.tracking_cam, 'intrinsics': self.tracking_intrinsics}
+
+    def densify_data(self, frame):
+        """what the silhouette densification and the first-frame map read (:1933-1941, :435-450), at densification size"""
+        im, depth = self._level_data(frame)['densify']
+        return {'im': im, 'depth': depth, 'cam': self.densify_cam, 'intrinsics': self.densify_intrinsics}
 
     # -- first frame --
     def initialize(self, frame):
         cfg = self.config
+        dd = self.densify_data(frame)      # :435-450: the densification frame and intrinsics; its depth gives scene_radius too (:456)
         self.params, self.variables = initialize_first_timestep(
-            frame['im'], frame['depth'], self.intrinsics, self.first_frame_w2c, self.num_frames, cfg['scene_radius_depth_ratio'],
+            dd['im'], dd['depth'], dd['intrinsics'], self.first_frame_w2c, self.num_frames, cfg['scene_radius_depth_ratio'],
             cfg['mean_sq_dist_method'], cfg['gaussian_distribution'], self.num_semantic)
         if self.flag_use_semantic and cfg['model']['flag_use_embedding'] == 1:      # :1755-1758
             dev = self.params['means3D'].device
@@ -265,20 +383,21 @@ class SlamSession:
         return self.params, self.variables
 
     # -- rendering and losses --
-    def _render(self, time_idx, gaussians_grad, camera_grad, retain_means2D=False):
+    def _render(self, time_idx, gaussians_grad, camera_grad, retain_means2D=False, cam=None):
         from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic
         from . import slam_helpers as SH
+        cam = self.cam if cam is None else cam
         tg = SH.transform_to_frame(self.params, time_idx, gaussians_grad=gaussians_grad, camera_grad=camera_grad)
         if self.flag_use_semantic:
             rv = SH.transformed_params2rendervar_semantic(self.params, tg)
             if retain_means2D:
                 rv['means2D'].retain_grad()
-            im, radius, sem, depth, _median, opac = GaussianRasterizer_semantic(raster_settings=self.cam)(**rv)
+            im, radius, sem, depth, _median, opac = GaussianRasterizer_semantic(raster_settings=cam)(**rv)
         else:
             rv = SH.transformed_params2rendervar(self.params, tg)
             if retain_means2D:
                 rv['means2D'].retain_grad()
-            im, radius, depth, _median, opac, _mask = GaussianRasterizer(raster_settings=self.cam)(**rv)
+            im, radius, depth, _median, opac, _mask = GaussianRasterizer(raster_settings=cam)(**rv)
             sem = None
         return rv, im, radius, sem, depth, opac
 
@@ -367,10 +486,11 @@ class SlamSession:
             return
         self.optimizer = optimizer = optim.Adam(_param_groups(params, trk['lrs']))
         candidate = optim.TrackingCandidate(params, time_idx)
+        data = self.tracking_data(frame)      # :1792-1799: the frame itself unless tracking has a size of its own
         it, extended = 0, False
         while True:
-            rv, im, radius, _sem, depth, opac = self._render(time_idx, gaussians_grad=False, camera_grad=True)
-            loss, parts = self._tracking_loss(frame, im, depth, opac)
+            rv, im, radius, _sem, depth, opac = self._render(time_idx, gaussians_grad=False, camera_grad=True, cam=data['cam'])
+            loss, parts = self._tracking_loss(data, im, depth, opac)
             self._note_seen(rv, radius)
             loss.backward()
             optimizer.step()
@@ -406,8 +526,7 @@ class SlamSession:
         cfg, mp = self.config, self.config['mapping']
         time_idx = int(frame['id'])
         if mp['add_new_gaussians'] and time_idx > 0:
-            data = {'cam': self.cam, 'im': frame['im'], 'depth': frame['depth'], 'id': time_idx, 'intrinsics': self.intrinsics,
-                    'w2c': self.first_frame_w2c}
+            data = dict(self.densify_data(frame), id=time_idx, w2c=self.first_frame_w2c)      # :1933-1941
             if self.flag_use_semantic:
                 self.params, self.variables = densify.add_new_gaussians_semantic_newrender(
                     self.params, self.variables, data, mp['sil_thres'], time_idx, cfg['mean_sq_dist_method'], self.num_semantic, flag_use_render=1)
@@ -483,4 +602,4 @@ class SlamSession:
 
 
 __all__ = ["initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "is_mapping_frame",
-           "normalize_config", "map_init_frame", "frame_w2c", "SlamSession"]
+           "normalize_config", "map_init_frame", "resample_frame", "frame_w2c", "SlamSession"]

@@ -4,7 +4,11 @@ optimizer): world->camera preparation, semantic render, mapping losses, backward
 Times (a) the fused preparation + rasterizer + fused loss heads of this repo and (b) the same rasterizer with the
 reference's torch eager chains either side of it.  One JSON line.
 
-    python tools/bench_iteration.py [--P 500000] [--iters 20]"""
+    python tools/bench_iteration.py [--P 500000] [--iters 20] [--tracking-size HxW]
+
+--tracking-size HxW times the tracking iteration alone, as SlamSession.track_frame runs it (prep with camera_grad, semantic render,
+losses.tracking_loss, backward, one-launch Adam step), with device events, the same 1200x680 map seen through a camera of H x W pixels
+with intrinsics scaled by new / old (hsr_utils.camera.scale_intrinsics): 680x1200 is the frame's own size, 340x600 a quarter of its pixels."""
 import argparse
 import json
 import os
@@ -22,15 +26,19 @@ sys.path.insert(0, os.path.join(ROOT, "hier-slam_amd"))
 REPEATS = 3
 
 
-def measure(P=500000, W=1200, H=680, iters=20):
+def measure(P=500000, W=1200, H=680, iters=20, tracking_size=None):
     from diff_gaussian_rasterization import GaussianRasterizer_semantic
     from hsr_utils import slam_helpers as SH, losses as L, setup_camera, make_scene
-    from hsr_utils.camera import replica_intrinsics
+    from hsr_utils.camera import replica_intrinsics, scale_intrinsics
     sizes = [2, 4, 6, 6, 8]
     K = sum(sizes)
     kmat = replica_intrinsics(W, H)
-    cam = setup_camera(W, H, kmat, np.eye(4), device="cuda")
     sc = make_scene(P, W, H, K, kmat, seed=0)
+    if tracking_size is not None:      # the same map through a smaller (or larger) camera; every per-pixel tensor below takes its size
+        map_h, map_w = H, W
+        H, W = tracking_size
+        kmat = scale_intrinsics(kmat, H / map_h, W / map_w)
+    cam = setup_camera(W, H, kmat, np.eye(4), device="cuda")
     g = torch.Generator().manual_seed(0)
     params = {"means3D": sc["means3D"], "unnorm_rotations": sc["rotations"], "logit_opacities": torch.logit(sc["opacities"].clamp(1e-4, 1 - 1e-4)),
               "log_scales": sc["scales"][:, :1].log(), "rgb_colors": sc["colors_precomp"], "semantic": sc["semantics_precomp"]}
@@ -145,6 +153,33 @@ def measure(P=500000, W=1200, H=680, iters=20):
             torch.cuda.synchronize()
             best = min(best, (time.perf_counter() - t0) / iters * 1e3)
         return best
+    def time_tracking_step():
+        """the iteration of SlamSession.track_frame: tracking(True) plus the optimizer step, timed with device events"""
+        from hsr_utils import optim
+        lrs = dict({k: 0.0 for k in params}, cam_unnorm_rots=4e-4, cam_trans=2e-3)
+        opt = optim.Adam([{'params': [v], 'name': k, 'lr': lrs[k]} for k, v in params.items()])
+
+        def one():
+            tracking(True)
+            opt.step()
+            opt.zero_grad(set_to_none=True)
+        for _ in range(5):
+            one()
+        best = float("inf")
+        for _ in range(REPEATS):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                one()
+            e1.record()
+            torch.cuda.synchronize()
+            best = min(best, e0.elapsed_time(e1) / iters)
+        return best
+    if tracking_size is not None:
+        return {"workload": "tracking iteration with optimizer step: prep + semantic render + tracking_loss + backward + Adam, camera %dx%d, "
+                            "map of a %dx%d frame, P=%d, K=%d" % (W, H, map_w, map_h, P, K),
+                "tracking_size": "%dx%d" % (H, W), "tracking_step_device_ms": round(time_tracking_step(), 4), "iters": iters, "repeats": REPEATS}
     if os.environ.get("HSR_ITER_ONLY") == "mapping":     # for a kernel trace of the fused mapping iteration alone (tools/ktrace_iter.sh)
         return {"fused_ms": timeit(True)}
     if os.environ.get("HSR_ITER_ONLY") == "leaf":
@@ -176,5 +211,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--P", type=int, default=500000)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--tracking-size", default=None, metavar="HxW", help="time the tracking iteration alone with a camera of H x W pixels")
     a = ap.parse_args()
-    print(json.dumps(measure(a.P, iters=a.iters)))
+    size = None if a.tracking_size is None else tuple(int(v) for v in a.tracking_size.lower().split("x"))
+    if size is not None and (len(size) != 2 or min(size) < 1):
+        ap.error("--tracking-size takes HxW, e.g. 340x600")
+    print(json.dumps(measure(a.P, iters=a.iters, tracking_size=size)))
