@@ -1,0 +1,392 @@
+// hsr_loss_outlier.hip — the outlier-rejecting loss head (gfx950), DESIGN.md §7 row 2: the ignore_outlier_depth_loss branch of the
+// reference's get_loss* (scripts/hierslam.py:909-937).  See include/ext/hsr_loss_outlier.h for the semantics, line by line.
+//
+// What it replaces: a dozen eager launches (sub, abs, gt, mul, median = a sort of H*W values, mul, lt, and, isnan, not, and), a bool
+// mask tensor, two masked-L1 nodes and a weighted sum.  Here the exact median is a radix select over the bits of the error, which is
+// never negative and therefore orders as an unsigned integer: 11 + 11 + 10 bits in three launches.
+//   hist_kernel<0|1|2> : every workgroup counts the digit of its pixels (pass 1 and 2: of those that agree with the digits already
+//                        decided) into a 2048-bin histogram in LDS and adds its non-zero bins into the pass's global histogram with
+//                        integer atomics.  Passes 1 and 2 begin with EVERY workgroup finding the bin that holds the rank in the
+//                        global histograms of the launches before (8 KB each, finished: the kernel boundary is the only
+//                        synchronisation; no workgroup reads within a launch what another wrote in it).  A NaN counter rides along.
+//   value_kernel       : every workgroup finds the three digits again (24 KB of reads), forms median and threshold, and sums the
+//                        masked terms of its pixels (the mask lives in a register); one partial per workgroup.
+//   finish_kernel      : fixed-order sum of the partials in double, as the tracking head's (hsr_losses.hip, tracking_finish_kernel).
+//   grad_kernel        : when autograd asks; the mask recomputed from the threshold in device memory.
+// Integer counts throughout the selection, fixed-order float sums: every output is the same bits on every run.
+// Compiled with -ffp-contract=off: error and threshold are computed as written.  Denormals are kept (hipcc's default for fp32 on gfx9).
+#include "hsr_common.h"
+#include "../../include/ext/hsr_loss_outlier.h"
+
+namespace {
+
+constexpr int LB = 256;               // threads per workgroup
+constexpr int ITEMS = 4;              // pixels per thread until the grid stops growing
+constexpr int MAX_BLOCKS = 512;       // then the workgroups stride: 2 per CU; each pays a 2048-bin clear, flush and up to three rank searches
+constexpr int BINS = 2048;            // 11 bits; the last pass uses 1024 of them
+constexpr int HIST_WORDS = 3 * BINS;  // the three global histograms, then the control words
+constexpr int CTL_NAN = HIST_WORDS;   // number of NaN errors
+constexpr size_t ZERO_BYTES = (size_t)(HIST_WORDS + 4) * sizeof(unsigned);      // 24592: a multiple of 16, from the scratch's start
+constexpr size_t PART_OFF = (ZERO_BYTES + 255) & ~(size_t)255;                  // float partials [MAX_BLOCKS][2]
+constexpr size_t COUNT_OFF = PART_OFF + (size_t)MAX_BLOCKS * 2 * sizeof(float); // unsigned selected [MAX_BLOCKS]
+constexpr size_t SCRATCH_BYTES = COUNT_OFF + (size_t)MAX_BLOCKS * sizeof(unsigned);
+
+// scripts/hierslam.py:911, in this order
+__device__ __forceinline__ float depth_error(float gt, float d)
+{
+    return fabsf(gt - d) * (gt > 0.f ? 1.f : 0.f);
+}
+
+__device__ __forceinline__ bool outlier_selected(float gt, float d, float thr, float sil, float sil_thres, int use_sil)
+{
+    return depth_error(gt, d) < thr && gt > 0.f && !(d != d) && (!use_sil || sil > sil_thres);
+}
+
+struct Rank { unsigned bin, rank; };
+
+// The bin of hist[0 .. LB * PER) that holds the element of 0-based rank `rank`, and the rank of that element inside the bin.  All LB
+// threads call it; `hist` was finished by an earlier launch.  A rank beyond the total (it never is: every pixel is counted) gives {0, 0}.
+template <int PER>
+__device__ __forceinline__ Rank find_bin(const unsigned* hist, unsigned rank, unsigned* s_wave, unsigned* s_res)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned c[PER], t = 0;
+#pragma unroll
+    for (int k = 0; k < PER; k++) {
+        c[k] = hist[threadIdx.x * PER + k];
+        t += c[k];
+    }
+    unsigned incl = t;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += v;
+    }
+    if (threadIdx.x == 0) s_res[0] = s_res[1] = 0;
+    if (lane == 63) s_wave[wv] = incl;
+    __syncthreads();
+    for (int w = 0; w < wv; w++) incl += s_wave[w];
+    const unsigned excl = incl - t;
+    if (excl <= rank && rank < incl) {      // exactly one thread
+        unsigned r = rank - excl, bin = PER - 1;
+        bool found = false;
+#pragma unroll
+        for (int k = 0; k < PER; k++)
+            if (!found) {
+                if (r < c[k]) {
+                    bin = k;
+                    found = true;
+                } else {
+                    r -= c[k];
+                }
+            }
+        s_res[0] = threadIdx.x * PER + bin;
+        s_res[1] = r;
+    }
+    __syncthreads();
+    const Rank out{s_res[0], s_res[1]};
+    __syncthreads();      // s_wave / s_res are free for the next search
+    return out;
+}
+
+// PASS 0: bits 31..21 of every error;  1: bits 20..10 of those whose bits 31..21 hold the rank;  2: bits 9..0 of those whose bits 31..10 do
+template <int PASS>
+__global__ __launch_bounds__(LB) void hist_kernel(const float* __restrict__ depth, const float* __restrict__ gt_depth, unsigned N,
+                                                  unsigned* hist /* [HIST_WORDS + 4] */)
+{
+    __shared__ unsigned s_hist[BINS];
+    __shared__ unsigned s_wave[LB / 64], s_res[2];
+    for (int b = threadIdx.x; b < BINS; b += LB) s_hist[b] = 0;
+    unsigned prefix = 0;
+    if (PASS >= 1) {
+        const Rank a = find_bin<BINS / LB>(hist, (N - 1) / 2, s_wave, s_res);
+        prefix = a.bin;
+        if (PASS == 2) prefix = (a.bin << 11) | find_bin<BINS / LB>(hist + BINS, a.rank, s_wave, s_res).bin;
+    }
+    __syncthreads();
+    unsigned nan = 0;
+    for (unsigned i = blockIdx.x * LB + threadIdx.x; i < N; i += gridDim.x * LB) {      // i + stride < 2^31 + 2^17
+        const float e = depth_error(gt_depth[i], depth[i]);
+        const unsigned key = __float_as_uint(e);      // key >> 21 <= 2047 whatever the bits
+        if (PASS == 0) {
+            nan += e != e ? 1u : 0u;
+            atomicAdd(&s_hist[key >> 21], 1u);
+        } else if (PASS == 1) {
+            if ((key >> 21) == prefix) atomicAdd(&s_hist[(key >> 10) & 0x7ffu], 1u);
+        } else {
+            if ((key >> 10) == prefix) atomicAdd(&s_hist[key & 0x3ffu], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned* out = hist + PASS * BINS;
+    for (int b = threadIdx.x; b < (PASS == 2 ? 1024 : BINS); b += LB) {
+        const unsigned c = s_hist[b];
+        if (c) atomicAdd(&out[b], c);
+    }
+    if (PASS == 0) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nan += __shfl_xor(nan, o, 64);
+        if ((threadIdx.x & 63) == 0 && nan) atomicAdd(&hist[CTL_NAN], nan);
+    }
+}
+
+// the median from the three finished histograms; all LB threads
+__device__ __forceinline__ float block_median(const unsigned* hist, unsigned N, unsigned* s_wave, unsigned* s_res)
+{
+    const Rank a = find_bin<BINS / LB>(hist, (N - 1) / 2, s_wave, s_res);
+    const Rank b = find_bin<BINS / LB>(hist + BINS, a.rank, s_wave, s_res);
+    const Rank c = find_bin<1024 / LB>(hist + 2 * BINS, b.rank, s_wave, s_res);
+    const unsigned key = (a.bin << 21) | (b.bin << 10) | c.bin;
+    return hist[CTL_NAN] ? __uint_as_float(0x7fc00000u) : __uint_as_float(key);
+}
+
+__global__ __launch_bounds__(LB) void median_kernel(const unsigned* hist, unsigned N, float* __restrict__ out2)
+{
+    __shared__ unsigned s_wave[LB / 64], s_res[2];
+    const float med = block_median(hist, N, s_wave, s_res);
+    if (threadIdx.x == 0) {
+        out2[0] = med;
+        out2[1] = 10.0f * med;
+    }
+}
+
+__device__ __forceinline__ float block_sum(float v, float* s_red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) s_red[wv] = v;
+    __syncthreads();
+    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+__global__ __launch_bounds__(LB) void value_kernel(const float* __restrict__ im, const float* __restrict__ gt_im, int C,
+                                                   const float* __restrict__ depth, const float* __restrict__ gt_depth,
+                                                   const float* __restrict__ sil, float sil_thres, int use_sil, unsigned N,
+                                                   const unsigned* hist, float* __restrict__ partials /* [nblk][2]: depth sum, colour sum */,
+                                                   unsigned* __restrict__ counts /* [nblk]: selected pixels */, float* __restrict__ out6)
+{
+    __shared__ unsigned s_wave[LB / 64], s_res[2];
+    __shared__ float s_red[LB / 64];
+    const float med = block_median(hist, N, s_wave, s_res);
+    const float thr = 10.0f * med;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        out6[4] = med;
+        out6[5] = thr;
+    }
+    float acc_d = 0.f, acc_c = 0.f;
+    unsigned n = 0;
+    for (unsigned i = blockIdx.x * LB + threadIdx.x; i < N; i += gridDim.x * LB) {
+        const float gd = gt_depth[i], d = depth[i];
+        const bool sel = outlier_selected(gd, d, thr, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
+        acc_d += sel ? fabsf(gd - d) : 0.f;
+        n += sel ? 1u : 0u;
+        for (int c = 0; c < C; c++) {
+            const float e = fabsf(gt_im[(size_t)c * N + i] - im[(size_t)c * N + i]);
+            acc_c += sel ? e : 0.f;
+        }
+    }
+    const float td = block_sum(acc_d, s_red);
+    const float tc = block_sum(acc_c, s_red);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[2 * (size_t)blockIdx.x] = td;
+        partials[2 * (size_t)blockIdx.x + 1] = tc;
+        counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    }
+}
+
+// out[0] = depth term, out[1] = colour term, out[2] = w_depth * out[0] + w_im * out[1], out[3] = 1 / selected pixels; *out_selected.
+// mean: the terms are means over the selection (colour: tiled over its C planes); an empty selection gives NaN like torch.
+__global__ __launch_bounds__(LB) void finish_kernel(const float* __restrict__ partials, const unsigned* __restrict__ counts, int nblocks,
+                                                    float w_depth, float w_im, int mean, int C, float* __restrict__ out,
+                                                    int* __restrict__ out_selected)
+{
+    __shared__ double s_acc[LB][2];
+    __shared__ unsigned s_cnt[LB];
+    double a0 = 0.0, a1 = 0.0;
+    unsigned n = 0;      // < 2^31
+    for (int b = threadIdx.x; b < nblocks; b += LB) {
+        a0 += (double)partials[2 * (size_t)b];
+        a1 += (double)partials[2 * (size_t)b + 1];
+        n += counts[b];
+    }
+    s_acc[threadIdx.x][0] = a0;
+    s_acc[threadIdx.x][1] = a1;
+    s_cnt[threadIdx.x] = n;
+    __syncthreads();
+    for (int o = LB / 2; o >= 1; o >>= 1) {
+        if (threadIdx.x < o) {
+            s_acc[threadIdx.x][0] += s_acc[threadIdx.x + o][0];
+            s_acc[threadIdx.x][1] += s_acc[threadIdx.x + o][1];
+            s_cnt[threadIdx.x] += s_cnt[threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const float inv = 1.0f / (float)s_cnt[0];
+        const double dterm = mean ? s_acc[0][0] * (double)inv : s_acc[0][0];
+        const double cterm = mean ? (C > 0 ? s_acc[0][1] * (double)inv / (double)C : 0.0) : s_acc[0][1];
+        out[0] = (float)dterm;
+        out[1] = (float)cterm;
+        out[2] = (float)((double)w_depth * dterm + (double)w_im * cterm);
+        out[3] = inv;
+        out_selected[0] = (int)s_cnt[0];
+    }
+}
+
+__global__ __launch_bounds__(LB) void grad_kernel(const float* __restrict__ im, const float* __restrict__ gt_im, int C,
+                                                  const float* __restrict__ depth, const float* __restrict__ gt_depth,
+                                                  const float* __restrict__ sil, float sil_thres, int use_sil, unsigned N,
+                                                  const float* __restrict__ threshold, const float* __restrict__ upstream, float w_depth,
+                                                  float w_im, const float* __restrict__ inv_count, float* __restrict__ d_im,
+                                                  float* __restrict__ d_depth)
+{
+    const float thr = threshold[0];
+    const float up = upstream ? upstream[0] : 1.0f;
+    const float inv = inv_count ? inv_count[0] : 1.0f;   // mean reduction: 1 / selected pixels (the value pass's out6[3])
+    const float sd = w_depth * up * inv, sc = w_im * up * (inv_count ? inv / (float)(C > 0 ? C : 1) : 1.0f);
+    for (unsigned i = blockIdx.x * LB + threadIdx.x; i < N; i += gridDim.x * LB) {
+        const float gd = gt_depth[i], d = depth[i];
+        const bool sel = outlier_selected(gd, d, thr, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
+        if (d_depth) {
+            const float e = d - gd;   // d |gt - d| / d d = sign(d - gt)
+            d_depth[i] = sel ? (e > 0.f ? sd : (e < 0.f ? -sd : 0.f)) : 0.f;
+        }
+        if (d_im)
+            for (int c = 0; c < C; c++) {
+                const float e = im[(size_t)c * N + i] - gt_im[(size_t)c * N + i];
+                d_im[(size_t)c * N + i] = sel ? (e > 0.f ? sc : (e < 0.f ? -sc : 0.f)) : 0.f;
+            }
+    }
+}
+
+int blocks_for(unsigned N)
+{
+    const unsigned nb = (N + LB * ITEMS - 1) / (LB * ITEMS);
+    return (int)(nb < 1 ? 1 : (nb > MAX_BLOCKS ? MAX_BLOCKS : nb));
+}
+
+int check_maps(const char* who, int H, int W, const float* depth, const float* gt_depth)
+{
+    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !depth || !gt_depth) {
+        hsr_set_error("%s: invalid sizes H=%d W=%d (H, W >= 1, H * W < 2^31) or NULL depth / gt_depth", who, H, W);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    return HSR_OK;
+}
+
+int check_colour(const char* who, int C, const float* im, const float* gt_im, const float* sil, int use_sil)
+{
+    if ((C != 0 && C != 3) || (C > 0 && (!im || !gt_im)) || (use_sil && !sil)) {
+        hsr_set_error("%s: C=%d is neither 0 nor 3, or NULL im / gt_im / silhouette", who, C);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    return HSR_OK;
+}
+
+int check_scratch(const char* who, const char* scratch, size_t have)
+{
+    if (!scratch || have < SCRATCH_BYTES || (reinterpret_cast<uintptr_t>(scratch) & 15) != 0) {
+        hsr_set_error("%s: scratch is NULL, not 16-byte aligned or too small: %zu bytes needed, %zu given", who, SCRATCH_BYTES, have);
+        return HSR_ERR_BUFFER_TOO_SMALL;
+    }
+    return HSR_OK;
+}
+
+// zeroing + the three histogram passes; leaves the finished histograms at the scratch's start
+int launch_select(unsigned N, int nb, const float* depth, const float* gt_depth, char* scratch, hipStream_t stream)
+{
+    unsigned* hist = reinterpret_cast<unsigned*>(scratch);
+    HSR_HIP_CHECK(hipMemsetAsync(scratch, 0, ZERO_BYTES, stream));
+    hist_kernel<0><<<nb, LB, 0, stream>>>(depth, gt_depth, N, hist);
+    hist_kernel<1><<<nb, LB, 0, stream>>>(depth, gt_depth, N, hist);
+    hist_kernel<2><<<nb, LB, 0, stream>>>(depth, gt_depth, N, hist);
+    return HSR_OK;
+}
+
+}  // namespace
+
+extern "C" size_t hsr_loss_outlier_scratch_bytes(int H, int W)
+{
+    (void)H;
+    (void)W;
+    return SCRATCH_BYTES;
+}
+
+extern "C" int hsr_loss_outlier_median(int H, int W, const float* depth, const float* gt_depth, float* out2, char* scratch,
+                                       size_t scratch_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_maps("loss_outlier_median", H, W, depth, gt_depth);
+    if (rc != HSR_OK) return rc;
+    if (!out2) {
+        hsr_set_error("loss_outlier_median: out2 is NULL");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    rc = check_scratch("loss_outlier_median", scratch, scratch_bytes);
+    if (rc != HSR_OK) return rc;
+    const unsigned N = (unsigned)H * (unsigned)W;
+    rc = launch_select(N, blocks_for(N), depth, gt_depth, scratch, stream);
+    if (rc != HSR_OK) return rc;
+    median_kernel<<<1, LB, 0, stream>>>(reinterpret_cast<const unsigned*>(scratch), N, out2);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}
+
+extern "C" int hsr_loss_outlier_value(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
+                                      const float* silhouette, float sil_thres, int use_sil, int reduction, float w_depth, float w_im,
+                                      float* out6, int* out_selected, char* scratch, size_t scratch_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_maps("loss_outlier_value", H, W, depth, gt_depth);
+    if (rc != HSR_OK) return rc;
+    rc = check_colour("loss_outlier_value", C, im, gt_im, silhouette, use_sil);
+    if (rc != HSR_OK) return rc;
+    if (!out6 || !out_selected || (reduction != HSR_LOSS_SUM && reduction != HSR_LOSS_MEAN)) {
+        hsr_set_error("loss_outlier_value: out6 / out_selected is NULL or reduction is neither HSR_LOSS_SUM nor HSR_LOSS_MEAN");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    rc = check_scratch("loss_outlier_value", scratch, scratch_bytes);
+    if (rc != HSR_OK) return rc;
+    const unsigned N = (unsigned)H * (unsigned)W;
+    const int nb = blocks_for(N);
+    rc = launch_select(N, nb, depth, gt_depth, scratch, stream);
+    if (rc != HSR_OK) return rc;
+    float* partials = reinterpret_cast<float*>(scratch + PART_OFF);
+    unsigned* counts = reinterpret_cast<unsigned*>(scratch + COUNT_OFF);
+    value_kernel<<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, silhouette, sil_thres, use_sil, N,
+                                        reinterpret_cast<const unsigned*>(scratch), partials, counts, out6);
+    finish_kernel<<<1, LB, 0, stream>>>(partials, counts, nb, w_depth, w_im, reduction == HSR_LOSS_MEAN ? 1 : 0, C, out6, out_selected);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}
+
+extern "C" int hsr_loss_outlier_grad(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
+                                     const float* silhouette, float sil_thres, int use_sil, float w_depth, float w_im, const float* threshold,
+                                     const float* upstream, const float* inv_count, float* d_im, float* d_depth, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = check_maps("loss_outlier_grad", H, W, depth, gt_depth);
+    if (rc != HSR_OK) return rc;
+    rc = check_colour("loss_outlier_grad", C, im, gt_im, silhouette, use_sil);
+    if (rc != HSR_OK) return rc;
+    if (!threshold) {
+        hsr_set_error("loss_outlier_grad: threshold is NULL (pass &out6[5] of the value pass)");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    const unsigned N = (unsigned)H * (unsigned)W;
+    if (C == 0) d_im = nullptr;
+    if (!d_im && !d_depth) return HSR_OK;      // nothing asked for, nothing launched
+    const unsigned want = (N + LB * ITEMS - 1) / (LB * ITEMS);
+    const unsigned nb = want > 65536u ? 65536u : want;      // the rest by striding; i + stride < 2^31 + 2^24
+    grad_kernel<<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, silhouette, sil_thres, use_sil, N, threshold, upstream, w_depth, w_im,
+                                       inv_count, d_im, d_depth);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}

@@ -4,8 +4,8 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT and SIGNATURES_EXT_FRAME_RESAMPLE against include/ext/ with the same checker, each from its extension's own
-suite).  There is NO fallback path: a missing library is an ImportError.
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE and SIGNATURES_EXT_LOSS_OUTLIER against include/ext/ with
+the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
 import os
@@ -244,6 +244,19 @@ SIGNATURES_EXT_FRAME_RESAMPLE = (
                                 ci, ci, vp, vp, vp]),
 )
 
+# include/ext/hsr_loss_outlier.h: a table of its own as well (the three above are pinned by their suites)
+SIGNATURES_EXT_LOSS_OUTLIER = (
+    ("hsr_loss_outlier_scratch_bytes", sz, [ci, ci]),
+    ("hsr_loss_outlier_median", ci, [ci, ci, vp, vp, vp, vp, sz,
+                                     vp]),
+    ("hsr_loss_outlier_value", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                    vp, cf, ci, ci, cf, cf, vp,
+                                    vp, vp, sz, vp]),
+    ("hsr_loss_outlier_grad", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                   vp, cf, ci, cf, cf, vp,
+                                   vp, vp, vp, vp, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -252,7 +265,8 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE:
+    for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
+                                    + SIGNATURES_EXT_LOSS_OUTLIER):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

@@ -9,6 +9,8 @@ value and the gradient together (include/hsr_losses.h).
                                                        im_semantic, i_level, dataset), labels[i_level])   scripts/hierslam.py:963-974
     cross_entropy_planar(logits, labels)               CrossEntropyLoss on [C,H,W] logits (flat classes, :947-954; leaf MLP, :976-983)
 
+    depth_error_median(depth, gt_depth)                (median, 10 * median) of the ignore_outlier_depth_loss mask   scripts/hierslam.py:911-912
+
 `mapping_image_loss(im, gt)` is the reference's mapping colour term 0.8*L1 + 0.2*(1 - SSIM) (scripts/hierslam.py:939).
 Gradients flow to the FIRST argument only (the rendered map); the ground truth is data.  There is no CPU path.
 """
@@ -252,26 +254,113 @@ class _TrackingLoss(torch.autograd.Function):
         return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d), None, None, None, None, None, None, None)
 
 
-def tracking_loss(im, gt_im, depth, gt_depth, silhouette=None, sil_thres=0.99, use_sil_for_loss=True, loss_weights=None, return_parts=False):
-    """The tracking loss of the reference's get_loss* with its shipped tracking settings (scripts/hierslam.py:903-937, :1003-1016:
-    use_l1, ignore_outlier_depth_loss=False):
+class _OutlierLoss(torch.autograd.Function):
+    """_TrackingLoss with the reference's ignore_outlier_depth_loss mask (include/ext/hsr_loss_outlier.h): the value pass finds the exact
+    median of the depth error on the device (three histogram passes, no sort, no host read) and sums the masked terms; the gradient pass,
+    when autograd asks, recomputes the mask from the threshold the value pass left in device memory.  No mask tensor."""
+
+    @staticmethod
+    def forward(ctx, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, w_depth, w_im, reduction):
+        d, gd = _chw(depth, "depth"), _chw(gt_depth.detach(), "gt_depth")
+        if im is None:      # depth term alone (the mapping branch)
+            a = b = None
+            Cc, (H, W) = 0, d.shape[-2:]
+        else:
+            a, b = _chw(im, "im"), _chw(gt_im.detach(), "gt_im")
+            Cc, H, W = a.shape
+        if (a is not None and b.shape != a.shape) or d.numel() != H * W or gd.numel() != H * W:
+            raise RuntimeError("hsr_utils.losses: the outlier-rejecting loss wants im / gt_im [3,H,W] and depth / gt_depth [1,H,W] of one size")
+        s = None
+        if use_sil:
+            s = _chw(silhouette.detach(), "silhouette")
+            if s.numel() != H * W:
+                raise RuntimeError("hsr_utils.losses: silhouette must be [1,H,W] like the depth map")
+        dev = d.device
+        out = torch.empty(6, dtype=torch.float32, device=dev)
+        selected = torch.empty(1, dtype=torch.int32, device=dev)
+        sc = torch.empty(int(_lib.hsr_loss_outlier_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+        _abi.call(_abi.lib.hsr_loss_outlier_value, "hsr_loss_outlier_value", dev, Cc, H, W, None if a is None else a.data_ptr(),
+                  None if b is None else b.data_ptr(), d.data_ptr(), gd.data_ptr(), None if s is None else s.data_ptr(), float(sil_thres),
+                  int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(), selected.data_ptr(), sc.data_ptr(),
+                  sc.numel())
+        ctx.want = (bool(im is not None and im.requires_grad), bool(depth.requires_grad))
+        if any(ctx.want):
+            e = torch.empty(0, device=dev)
+            ctx.save_for_backward(a if a is not None else e, b if b is not None else e, d, gd, s if s is not None else e, out)
+            ctx.meta = (Cc, H, W, float(sil_thres), int(bool(use_sil)), float(w_depth), float(w_im), None if im is None else tuple(im.shape),
+                        tuple(depth.shape), int(reduction))
+        parts, stats, count = out[:2].detach(), out[4:6].detach(), selected[0]
+        ctx.mark_non_differentiable(parts, stats, count)
+        return out[2], parts, stats, count
+
+    @staticmethod
+    def backward(ctx, g, _g_parts, _g_stats, _g_count):
+        if g is None or not any(ctx.want):
+            return (None,) * 10
+        a, b, d, gd, s, out = ctx.saved_tensors
+        Cc, H, W, sil_thres, use_sil, w_depth, w_im, shape_im, shape_d, reduction = ctx.meta
+        dev = d.device
+        gg = g.to(device=dev, dtype=torch.float32).contiguous()
+        d_im = torch.empty_like(a) if ctx.want[0] else None
+        d_d = torch.empty_like(d) if ctx.want[1] else None
+        inv_ptr = out.data_ptr() + 12 if reduction == MEAN else None     # &out6[3]: 1 / selected pixels
+        _abi.call(_abi.lib.hsr_loss_outlier_grad, "hsr_loss_outlier_grad", dev, Cc, H, W, a.data_ptr() if Cc else None,
+                  b.data_ptr() if Cc else None, d.data_ptr(), gd.data_ptr(), s.data_ptr() if use_sil else None, sil_thres, use_sil, w_depth,
+                  w_im, out.data_ptr() + 20, gg.data_ptr(), inv_ptr, None if d_im is None else d_im.data_ptr(),
+                  None if d_d is None else d_d.data_ptr())
+        return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d), None, None, None, None, None, None, None)
+
+
+def depth_error_median(depth, gt_depth):
+    """(median, threshold) of the reference's ignore_outlier_depth_loss mask (scripts/hierslam.py:911-912) as 0-dim device tensors:
+    torch.median of torch.abs(gt_depth - depth) * (gt_depth > 0) — the lower middle value, NaN if any error is NaN — and 10 * median.
+    Exact (a radix select on the device: no sort, no host read)."""
+    d, gd = _chw(depth.detach(), "depth"), _chw(gt_depth.detach(), "gt_depth")
+    H, W = d.shape[-2:]
+    if d.shape[0] != 1 or gd.shape != d.shape:
+        raise RuntimeError("hsr_utils.losses: depth_error_median wants depth and gt_depth [1,H,W] or [H,W] of one size")
+    dev = d.device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    sc = torch.empty(int(_lib.hsr_loss_outlier_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _abi.call(_abi.lib.hsr_loss_outlier_median, "hsr_loss_outlier_median", dev, H, W, d.data_ptr(), gd.data_ptr(), out.data_ptr(), sc.data_ptr(),
+              sc.numel())
+    return out[0], out[1]
+
+
+def tracking_loss(im, gt_im, depth, gt_depth, silhouette=None, sil_thres=0.99, use_sil_for_loss=True, loss_weights=None, return_parts=False,
+                  ignore_outlier_depth_loss=False, return_selected=False):
+    """The tracking loss of the reference's get_loss* (scripts/hierslam.py:903-937, :1003-1016, use_l1):
         mask = (gt_depth > 0) & ~isnan(depth) & (silhouette > sil_thres)     [the last factor if use_sil_for_loss]
         loss = loss_weights['depth'] * |gt_depth - depth|[mask].sum() + loss_weights['im'] * |gt_im - im|[tiled mask].sum()
     as one autograd node: one pass for the value, one for both gradients.  loss_weights: dict with 'im' and 'depth' (default the
     reference's tracking weights, im 0.5 / depth 1.0).  return_parts: also [depth sum, colour sum] (values, no gradient path).
-    The outlier-rejecting variant (a global median of the depth error) is not fused: compose masked_l1 with a torch mask for it."""
+    ignore_outlier_depth_loss (:910-913): the mask additionally keeps only the pixels whose depth error
+    |gt_depth - depth| * (gt_depth > 0) is below 10 times its median over the whole map — fused as well (the exact median on the device,
+    include/ext/hsr_loss_outlier.h).  With it the colour term is masked whether or not the silhouette is used (:932), so
+    use_sil_for_loss=False is accepted; return_selected (with this flag only): also the number of selected pixels, a 0-dim int32 device
+    tensor."""
     lw = loss_weights or {"im": 0.5, "depth": 1.0}
     if use_sil_for_loss and silhouette is None:
         raise RuntimeError("hsr_utils.losses: tracking_loss with use_sil_for_loss needs the rendered silhouette / final opacity map")
+    if ignore_outlier_depth_loss:
+        total, parts, _stats, count = _OutlierLoss.apply(im, gt_im, depth, gt_depth, silhouette, float(sil_thres), bool(use_sil_for_loss),
+                                                         float(lw["depth"]), float(lw["im"]), SUM)
+        out = (total,) + ((parts,) if return_parts else ()) + ((count,) if return_selected else ())
+        return out if len(out) > 1 else total
+    if return_selected:
+        raise RuntimeError("hsr_utils.losses: tracking_loss counts the selected pixels only with ignore_outlier_depth_loss")
     total, parts = _TrackingLoss.apply(im, gt_im, depth, gt_depth, silhouette, float(sil_thres), bool(use_sil_for_loss), float(lw["depth"]),
                                        float(lw["im"]), SUM)
     return (total, parts) if return_parts else total
 
 
-def mapping_depth_loss(depth, gt_depth):
-    """The depth term of the mapping branch of get_loss* (scripts/hierslam.py:905-927 with the shipped mapping settings: no silhouette
-    mask, no outlier rejection):  torch.abs(gt_depth - depth)[(gt_depth > 0) & ~isnan(depth)].mean()  — mask, count and mean in one pass,
-    the gradient in a second when autograd asks (no mask tensor, no count pre-pass)."""
+def mapping_depth_loss(depth, gt_depth, ignore_outlier_depth_loss=False):
+    """The depth term of the mapping branch of get_loss* (scripts/hierslam.py:905-927, no silhouette mask):
+    torch.abs(gt_depth - depth)[(gt_depth > 0) & ~isnan(depth)].mean()  — mask, count and mean in one pass, the gradient in a second when
+    autograd asks (no mask tensor, no count pre-pass).  ignore_outlier_depth_loss (:910-913): the mask additionally keeps only the pixels
+    whose depth error is below 10 times its median (the fused outlier-rejecting head, include/ext/hsr_loss_outlier.h)."""
+    if ignore_outlier_depth_loss:
+        return _OutlierLoss.apply(None, None, depth, gt_depth, None, 0.0, False, 1.0, 0.0, MEAN)[0]
     total, _parts = _TrackingLoss.apply(None, None, depth, gt_depth, None, 0.0, False, 1.0, 0.0, MEAN)
     return total
 

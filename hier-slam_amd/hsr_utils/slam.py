@@ -417,7 +417,8 @@ class SlamSession:
 
     @staticmethod
     def _outlier_mask(gt_depth, depth):
-        """the ignore_outlier_depth_loss mask (:910-913)"""
+        """the ignore_outlier_depth_loss mask (:910-913) restated in torch: the pixels the fused head (hsr_utils.losses,
+        ignore_outlier_depth_loss=True) selects.  The session's losses do not call it; tests/test_gpu_slam_session_outlier.py compares the two."""
         err = torch.abs(gt_depth - depth) * (gt_depth > 0)
         return (err < 10 * err.median()) & (gt_depth > 0) & ~torch.isnan(depth)
 
@@ -432,19 +433,16 @@ class SlamSession:
             d = L.masked_l1(depth, frame['depth'], ((frame['depth'] > 0) & ~torch.isnan(depth)).detach(), "sum")
             c = L.masked_l1(im, frame['im'], None, "sum")
             return L.weighted_sum((d, c), (lw['depth'], lw['im'])), torch.stack((d.detach(), c.detach()))
-        mask = self._outlier_mask(frame['depth'], depth.detach())
-        if trk['use_sil_for_loss']:
-            mask = mask & (opac.detach() > trk['sil_thres'])
-        d = L.masked_l1(depth, frame['depth'], mask, "sum")
-        c = L.masked_l1(im, frame['im'], mask, "sum")
-        return L.weighted_sum((d, c), (lw['depth'], lw['im'])), torch.stack((d.detach(), c.detach()))
+        # :910-913, :932: the outlier-rejecting mask (restated by _outlier_mask) on both terms, fused: no median sort, no mask tensor
+        return L.tracking_loss(im, frame['im'], depth, frame['depth'], opac if trk['use_sil_for_loss'] else None, trk['sil_thres'],
+                               trk['use_sil_for_loss'], lw, return_parts=True, ignore_outlier_depth_loss=True)
 
     def _mapping_loss(self, data, im, sem, depth, it):
         from . import losses as L
         mp = self.config['mapping']
         lw = mp['loss_weights']
         if mp['ignore_outlier_depth_loss']:
-            d = L.masked_l1(depth, data['depth'], self._outlier_mask(data['depth'], depth.detach()), "mean")
+            d = L.mapping_depth_loss(depth, data['depth'], ignore_outlier_depth_loss=True)
         else:
             d = L.mapping_depth_loss(depth, data['depth'])
         terms, weights = [d, L.mapping_image_loss(im, data['im'])], [lw['depth'], lw['im']]

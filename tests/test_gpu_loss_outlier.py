@@ -1,0 +1,300 @@
+"""GPU suite for the outlier-rejecting loss head (include/ext/hsr_loss_outlier.h, hsr_utils.losses with ignore_outlier_depth_loss=True).
+
+The oracle of every case is tests/outlier_ref.py (scripts/hierslam.py:909-937 restated in torch) run on the CPU on the same fp32 inputs:
+    median, threshold        bit-equal, NaN included
+    selected pixels          equal to the reference mask's count
+    both terms, the total    within VAL_TOL of tests/test_gpu_losses.py (the bound of hsr_loss_tracking_value) of the float64 sums
+    SUM gradients            bit-equal to torch autograd of the restatement (where the depth is NaN torch's abs backward turns the 0 off the
+                             mask into 0 * sign(NaN) = NaN; the head writes the 0, as the tracking head does: compared after nan_to_num)
+    MEAN gradients           within 1 ulp of torch autograd (the head multiplies by 1 / selected, torch divides by selected)
+    gradient off the mask    0
+Each case runs in tracking form (C = 3, SUM, silhouette on and off) and in mapping form (C = 0, MEAN), with the upstream gradient 1 and 0.37.
+The cases are the smallest shapes at which the selection can go wrong; they are listed at CASES.  The largest distances of the first MI355X
+run are in profiles/loss_outlier_gpu.log."""
+import functools
+
+import pytest
+import torch
+
+import outlier_ref as R
+from test_gpu_losses import VAL_TOL
+
+pytestmark = pytest.mark.gpu
+
+SIL_THRES = 0.6
+NAN, INF = float("nan"), float("inf")
+
+
+def _noisy(H, W, seed, holes=0.1, outliers=0.05):
+    """gt depth 0.5..5 m with holes, a rendered depth = gt + Gaussian noise (sigma 1 cm), `outliers` of the pixels 50 times noisier"""
+    g = torch.Generator().manual_seed(seed)
+    gt = 0.5 + 4.5 * torch.rand(H, W, generator=g)
+    noise = 0.01 * torch.randn(H, W, generator=g)
+    noise = torch.where(torch.rand(H, W, generator=g) < outliers, 50 * noise, noise)
+    depth = gt + noise
+    gt = torch.where(torch.rand(H, W, generator=g) < holes, torch.zeros(()), gt)
+    return depth, gt
+
+
+def _from_errors(errors, shape, holes=0, seed=0, hole_depth=1.0):
+    """depth 0 and gt = the given errors (so that e = gt exactly), shuffled, then `holes` pixels of gt = 0 under a depth of hole_depth"""
+    g = torch.Generator().manual_seed(seed)
+    e = torch.as_tensor(errors, dtype=torch.float32)
+    n = shape[0] * shape[1]
+    assert e.numel() + holes == n
+    gt = torch.cat([e, torch.zeros(holes)])
+    depth = torch.cat([torch.zeros(e.numel()), torch.full((holes,), hole_depth)])
+    perm = torch.randperm(n, generator=g)
+    return depth[perm].reshape(shape).contiguous(), gt[perm].reshape(shape).contiguous()
+
+
+def _with(pair, **cells):
+    """a case with single cells replaced: d_IJ = value / g_IJ = value for depth / gt at row I, column J"""
+    depth, gt = pair[0].clone(), pair[1].clone()
+    for key, v in cells.items():
+        t = depth if key[0] == "d" else gt
+        i, j = (int(x) for x in key[2:].split("_"))
+        t[i, j] = v
+    return depth, gt
+
+
+def _small():      # 3 x 5, every pixel valid, errors 0.1 .. 1.5
+    gt = torch.arange(1, 16, dtype=torch.float32).reshape(3, 5) * 0.25 + 1.0
+    return gt - 0.1 * torch.arange(1, 16, dtype=torch.float32).reshape(3, 5), gt
+
+
+_DEN = 2.0 ** -149      # the smallest fp32 denormal
+CASES = {
+    # one pixel: selected; a hole: median 0, nothing is < 0, the mean of nothing is NaN
+    "1x1_valid": lambda: (torch.tensor([[1.5]]), torch.tensor([[2.0]])),
+    "1x1_hole": lambda: (torch.tensor([[1.5]]), torch.tensor([[0.0]])),
+    # e = {1, 20}: the lower median 1 selects one pixel, an upper median would select both; the same on 2 x 2
+    "1x2_lower_median": lambda: (torch.zeros(1, 2), torch.tensor([[1.0, 20.0]])),
+    "2x2_lower_median": lambda: (torch.zeros(2, 2), torch.tensor([[1.0, 20.0], [20.0, 1.0]])),
+    # n = 35, rank 17: 18 zeros reach it (median 0, empty selection); 17 do not (the smallest positive error, 0.05, is the median)
+    "5x7_18_holes": lambda: _from_errors([0.05 + 0.07 * k for k in range(17)], (5, 7), holes=18, seed=1),
+    "5x7_17_holes": lambda: _from_errors([0.05 + 0.07 * k for k in range(18)], (5, 7), holes=17, seed=2),
+    # every valid pixel has the error 0.5 (2.0 - 1.5, exact): all of them are selected
+    "equal_errors": lambda: (torch.full((9, 13), 1.5), torch.where(torch.arange(117).reshape(9, 13) % 4 == 0, 0.0, 2.0)),
+    # keys that differ only in the bits of the last pass (9..0), and only in those of the middle pass (20..10)
+    "32x32_last_pass": lambda: _from_errors([1.0 + k * 2.0 ** -23 for k in range(1024)], (32, 32), seed=3),
+    "32x32_middle_pass": lambda: _from_errors([1.0 + k * 2.0 ** -13 for k in range(1024)], (32, 32), seed=4),
+    # median 0.5, threshold 5.0, one pixel at exactly 5.0: the strict < excludes it
+    "tie_at_threshold": lambda: _from_errors([0.5] * 5 + [5.0, 0.25, 0.25, 7.0], (3, 3), seed=5),
+    # denormal errors (a denormal gt against depth 0): median 311000 * 2^-149, four pixels beyond ten times it
+    "denormal_errors": lambda: _from_errors([(300000 + 1000 * k) * _DEN for k in range(16)] + [m * _DEN for m in (
+        2000000, 2400000, 2800000, 3100000, 3110000, 4000000, 6000000, 8388607)], (4, 6), seed=6),
+    # NaN and inf depth: a NaN error anywhere makes the median NaN and the selection empty; an inf error on a valid pixel only drops out
+    "nan_depth_valid_pixel": lambda: _with(_small(), d_1_2=NAN),
+    "nan_depth_under_hole": lambda: _with(_small(), d_1_2=NAN, g_1_2=0.0),
+    "inf_depth_under_hole": lambda: _with(_small(), d_2_4=INF, g_2_4=0.0),
+    "inf_depth_valid_pixel": lambda: _with(_small(), d_0_3=INF),
+    # a negative gt is a hole: its error is 0 and it is never selected
+    "negative_gt": lambda: _with(_small(), g_0_0=-1.0, g_1_1=-0.5, g_2_2=-3.0, g_2_3=0.0),
+    # tails of a wave and of a workgroup; several workgroups
+    "37x23": lambda: _noisy(37, 23, seed=7),
+    "129x67": lambda: _noisy(129, 67, seed=8),
+    # many workgroups, a non-trivial bin in all three passes
+    "340x600": lambda: _noisy(340, 600, seed=9, holes=0.03),
+}
+FORMS = ["tracking_sil", "tracking_nosil", "mapping"]
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(case):
+    """the fp32 CPU inputs of a case: depth, gt_depth [H,W]; im, gt_im [3,H,W]; silhouette [H,W]"""
+    depth, gt = CASES[case]()
+    H, W = depth.shape
+    g = torch.Generator().manual_seed(100 + len(case))
+    im, gt_im, sil = torch.rand(3, H, W, generator=g), torch.rand(3, H, W, generator=g), torch.rand(H, W, generator=g)
+    im[:, 0, 0] = gt_im[:, 0, 0]              # an exact zero of the colour error: gradient 0 there, as torch's sign(0)
+    if H * W <= 4:
+        sil = torch.ones(H, W)                # the tiny cases are about the median: the silhouette keeps what it selects
+    return depth.contiguous(), gt.contiguous(), im, gt_im, sil
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case, use_sil):
+    depth, gt, im, gt_im, sil = _inputs(case)
+    return R.outlier_ref(depth, gt, im, gt_im, sil if use_sil else None, SIL_THRES)
+
+
+def _bits(t):
+    return t.detach().cpu().reshape(-1).view(torch.int32)
+
+
+def _same_bits(got, want):
+    """bit-equal, where every NaN counts as the same NaN"""
+    g, w = got.detach().cpu().reshape(-1), want.detach().cpu().reshape(-1)
+    return bool(((_bits(g) == _bits(w)) | (torch.isnan(g) & torch.isnan(w))).all())
+
+
+def _ulps(a, b):
+    """largest distance in units in the last place between two fp32 tensors (ordered-integer view; +0 and -0 coincide)"""
+    def ordered(t):
+        i = _bits(t).to(torch.int64)
+        return torch.where(i < 0, -(i & 0x7fffffff), i)
+    return int((ordered(a) - ordered(b)).abs().max())
+
+
+def _within(got, ref):
+    return abs(got - ref) <= VAL_TOL * abs(ref)
+
+
+def _raw_value(case, form, scratch=None):
+    """hsr_loss_outlier_value through the C ABI: (out6, selected) as CPU tensors"""
+    from diff_gaussian_rasterization import _abi
+    depth, gt, im, gt_im, sil = (t.cuda() for t in _inputs(case))
+    H, W = depth.shape
+    tracking, use_sil = form != "mapping", form == "tracking_sil"
+    out6 = torch.full((6,), -7.0, device="cuda")
+    sel = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    if scratch is None:
+        scratch = torch.empty(int(_abi.lib.hsr_loss_outlier_scratch_bytes(H, W)), dtype=torch.uint8, device="cuda")
+    _abi.call(_abi.lib.hsr_loss_outlier_value, "hsr_loss_outlier_value", depth.device, 3 if tracking else 0, H, W,
+              im.data_ptr() if tracking else None, gt_im.data_ptr() if tracking else None, depth.data_ptr(), gt.data_ptr(),
+              sil.data_ptr() if use_sil else None, SIL_THRES, int(use_sil), 0 if tracking else 1, R.W_DEPTH if tracking else 1.0,
+              R.W_IM if tracking else 0.0, out6.data_ptr(), sel.data_ptr(), scratch.data_ptr(), scratch.numel())
+    torch.cuda.synchronize()
+    return out6.cpu(), int(sel.cpu())
+
+
+def _check_raw(case, form, out6, selected):
+    """the value pass's outputs against the restatement; returns the largest relative distance of the terms"""
+    ref = _reference(case, form == "tracking_sil")
+    assert _same_bits(out6[4], ref["median"]) and _same_bits(out6[5], ref["threshold"]), (case, form, out6[4:], ref["median"], ref["threshold"])
+    assert selected == ref["count"], (case, form, selected, ref["count"])
+    n = ref["count"]
+    if form == "mapping":
+        want = [ref["depth_sum"] / n if n else NAN, 0.0]
+        want.append(want[0])
+    else:
+        want = [ref["depth_sum"], ref["colour_sum"], R.W_DEPTH * ref["depth_sum"] + R.W_IM * ref["colour_sum"]]
+    worst = 0.0
+    for k, w in enumerate(want):
+        got = float(out6[k].double())
+        if w != w:
+            assert got != got, (case, form, k, got)
+            continue
+        assert _within(got, w), (case, form, k, got, w)
+        worst = max(worst, abs(got - w) / abs(w) if w else 0.0)
+    inv = float(out6[3])
+    assert inv == float(torch.tensor(1.0) / torch.tensor(float(n))) if n else inv == INF
+    return worst
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("case", list(CASES))
+def test_value_and_gradients_equal_the_restatement(case, form):
+    from hsr_utils import losses as L
+    depth, gt, im, gt_im, sil = _inputs(case)
+    use_sil = form == "tracking_sil"
+    ref = _reference(case, use_sil)
+    mask = ref["mask"]
+    worst = _check_raw(case, form, *_raw_value(case, form))
+    median, threshold = L.depth_error_median(depth.cuda(), gt.cuda())
+    assert _same_bits(median, ref["median"]) and _same_bits(threshold, ref["threshold"])
+    worst_ulps = 0
+    for up in (1.0, 0.37):
+        d = depth.cuda().reshape(1, *depth.shape).requires_grad_(True)
+        if form == "mapping":
+            got = L.mapping_depth_loss(d, gt.cuda()[None], ignore_outlier_depth_loss=True)
+            (got * up).backward()
+            want_value, want_d = R.autograd_mapping(depth, gt, up)
+            g_d = d.grad[0].cpu()
+            if ref["count"]:
+                assert _within(float(got.detach()), ref["depth_sum"] / ref["count"])
+                worst_ulps = max(worst_ulps, _ulps(g_d, torch.nan_to_num(want_d)))
+                assert worst_ulps <= 1, (case, up, worst_ulps)
+            else:
+                assert torch.isnan(got) and torch.isnan(want_value)
+        else:
+            a = im.cuda().requires_grad_(True)
+            got, parts, count = L.tracking_loss(a, gt_im.cuda(), d, gt.cuda()[None], sil.cuda()[None] if use_sil else None, SIL_THRES, use_sil,
+                                                {"depth": R.W_DEPTH, "im": R.W_IM}, return_parts=True, ignore_outlier_depth_loss=True,
+                                                return_selected=True)
+            (got * up).backward()
+            assert int(count) == ref["count"] and count.dtype == torch.int32 and count.dim() == 0
+            assert _within(float(parts[0]), ref["depth_sum"]) and _within(float(parts[1]), ref["colour_sum"])
+            assert _within(float(got.detach()), R.W_DEPTH * ref["depth_sum"] + R.W_IM * ref["colour_sum"])
+            want_a, want_d = R.autograd_tracking(depth, gt, im, gt_im, sil if use_sil else None, SIL_THRES, up)
+            g_d, g_a = d.grad[0].cpu(), a.grad.cpu()
+            assert torch.equal(g_a, want_a) and _ulps(g_a, want_a) == 0, (case, form, up)
+            assert torch.equal(g_d, torch.nan_to_num(want_d)) and _ulps(g_d, torch.nan_to_num(want_d)) == 0, (case, form, up)
+            assert not g_a[:, ~mask].any()
+            if ref["count"] > 1:
+                assert g_a[:, mask].any()
+        assert not torch.isnan(g_d).any() and not g_d[~mask].any()      # 0 off the mask, whatever the pixel holds
+        if ref["count"]:
+            assert (g_d[mask] != 0).all()                                  # no case has an exact zero of the depth error on its mask
+    print("loss_outlier %s %s: median %.9g selected %d of %d; terms off float64 by %.3g (bound %.1g); mean gradient off torch by %d ulp"
+          % (case, form, float(ref["median"]), ref["count"], mask.numel(), worst, VAL_TOL, worst_ulps))
+
+
+def test_the_cases_are_what_they_claim():
+    """the properties the cases are there for, on the CPU restatement"""
+    ref = {c: _reference(c, False) for c in CASES}
+    assert ref["1x1_valid"]["count"] == 1 and ref["1x1_hole"]["count"] == 0 and float(ref["1x1_hole"]["median"]) == 0.0
+    assert ref["1x2_lower_median"]["count"] == 1 and ref["2x2_lower_median"]["count"] == 2
+    assert float(ref["5x7_18_holes"]["median"]) == 0.0 and ref["5x7_18_holes"]["count"] == 0
+    assert float(ref["5x7_17_holes"]["median"]) == pytest.approx(0.05) and 0 < ref["5x7_17_holes"]["count"] < 18
+    assert ref["equal_errors"]["count"] == int((_inputs("equal_errors")[1] > 0).sum()) > 0
+    for c, shift in (("32x32_last_pass", 10), ("32x32_middle_pass", 21)):
+        keys = _bits(_inputs(c)[1])
+        assert len(set((keys >> shift).tolist())) == 1 and len(set(keys.tolist())) == 1024 and ref[c]["count"] == 1024
+    assert len(set((_bits(_inputs("32x32_middle_pass")[1]) & 0x3ff).tolist())) == 1
+    assert float(ref["tie_at_threshold"]["threshold"]) == 5.0 and ref["tie_at_threshold"]["count"] == 7
+    den = _inputs("denormal_errors")[1]
+    assert float(den.max()) < 2.0 ** -126 and float(ref["denormal_errors"]["median"]) == 311000 * _DEN and ref["denormal_errors"]["count"] == 20
+    for c in ("nan_depth_valid_pixel", "nan_depth_under_hole", "inf_depth_under_hole"):
+        assert torch.isnan(ref[c]["median"]) and ref[c]["count"] == 0
+    assert torch.isfinite(ref["inf_depth_valid_pixel"]["median"]) and ref["inf_depth_valid_pixel"]["count"] == 14
+    assert ref["negative_gt"]["count"] == 11
+    bins = _bits(torch.abs(_inputs("340x600")[1] - _inputs("340x600")[0]) * (_inputs("340x600")[1] > 0))
+    m = int(_bits(ref["340x600"]["median"]))
+    assert int((bins >> 21 == m >> 21).sum()) > 1000 and int((bins >> 10 == m >> 10).sum()) > 1      # the rank's bin is shared in every pass
+    assert 0.8 * 204000 < ref["340x600"]["count"] < 0.97 * 204000
+
+
+def test_scratch_reuse_and_repeat():
+    """two calls on ONE scratch with different inputs are each correct, and two calls on the same input give the same bits"""
+    from diff_gaussian_rasterization import _abi
+    scratch = torch.empty(int(_abi.lib.hsr_loss_outlier_scratch_bytes(129, 67)), dtype=torch.uint8, device="cuda")
+    scratch.fill_(0xA5)                       # the head zeroes what it counts into: whatever the scratch held
+    first = _raw_value("129x67", "tracking_sil", scratch)
+    _check_raw("129x67", "tracking_sil", *first)
+    _check_raw("37x23", "mapping", *_raw_value("37x23", "mapping", scratch))
+    _check_raw("5x7_18_holes", "tracking_nosil", *_raw_value("5x7_18_holes", "tracking_nosil", scratch))
+    again = _raw_value("129x67", "tracking_sil", scratch)
+    assert torch.equal(_bits(first[0]), _bits(again[0])) and first[1] == again[1]
+    big = (_raw_value("340x600", "tracking_nosil"), _raw_value("340x600", "tracking_nosil"))
+    assert torch.equal(_bits(big[0][0]), _bits(big[1][0])) and big[0][1] == big[1][1]
+
+
+def test_default_path_never_reaches_the_outlier_head(monkeypatch):
+    """without the keyword tracking_loss and mapping_depth_loss call what they called before; with it, the new entry point"""
+    from diff_gaussian_rasterization import _abi
+    from hsr_utils import losses as L
+    depth, gt, im, gt_im, sil = (t.cuda() for t in _inputs("37x23"))
+    calls = {"outlier": 0, "tracking": 0}
+    real_outlier, real_tracking = _abi.lib.hsr_loss_outlier_value, _abi.lib.hsr_loss_tracking_value
+
+    def spy_outlier(*args):
+        calls["outlier"] += 1
+        return real_outlier(*args)
+
+    def spy_tracking(*args):
+        calls["tracking"] += 1
+        return real_tracking(*args)
+    monkeypatch.setattr(_abi.lib, "hsr_loss_outlier_value", spy_outlier)
+    monkeypatch.setattr(_abi.lib, "hsr_loss_tracking_value", spy_tracking)
+    plain_t = L.tracking_loss(im, gt_im, depth[None], gt[None], sil[None], SIL_THRES)
+    plain_m = L.mapping_depth_loss(depth[None], gt[None])
+    off_t = L.tracking_loss(im, gt_im, depth[None], gt[None], sil[None], SIL_THRES, ignore_outlier_depth_loss=False)
+    off_m = L.mapping_depth_loss(depth[None], gt[None], ignore_outlier_depth_loss=False)
+    assert calls == {"outlier": 0, "tracking": 4}
+    assert torch.equal(plain_t, off_t) and torch.equal(plain_m, off_m)
+    on_t = L.tracking_loss(im, gt_im, depth[None], gt[None], sil[None], SIL_THRES, ignore_outlier_depth_loss=True)
+    on_m = L.mapping_depth_loss(depth[None], gt[None], ignore_outlier_depth_loss=True)
+    assert calls == {"outlier": 2, "tracking": 4}
+    assert float(on_t) < float(plain_t) and float(on_m) < float(plain_m)      # the outliers are gone from both
