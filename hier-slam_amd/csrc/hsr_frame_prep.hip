@@ -69,10 +69,13 @@ __device__ __forceinline__ float4 normalize4(float4 v, float* n_out = nullptr)
     return make_float4(v.x / d, v.y / d, v.z / d, v.w / d);
 }
 
-// adjoint of y = v / |v|:  (g - y (y.g)) / |v|
+// adjoint of y = v / max(|v|, eps), F.normalize as torch.autograd differentiates it: (g - y (y.g)) / |v| where |v| >= eps; below eps the
+// clamp has no gradient, the divisor is the constant eps and the projection term is gone: g / eps (finite at |v| = 0 too)
 __device__ __forceinline__ float4 normalize_adjoint(float4 v, float4 g)
 {
-    const float n = fmaxf(norm4(v), 1e-12f);
+    const float nv = norm4(v);
+    const float n = fmaxf(nv, 1e-12f);
+    if (nv < 1e-12f) return make_float4(g.x / n, g.y / n, g.z / n, g.w / n);
     const float4 y = make_float4(v.x / n, v.y / n, v.z / n, v.w / n);
     const float d = y.x * g.x + y.y * g.y + y.z * g.z + y.w * g.w;
     return make_float4((g.x - y.x * d) / n, (g.y - y.y * d) / n, (g.z - y.z * d) / n, (g.w - y.w * d) / n);
@@ -263,10 +266,11 @@ __global__ __launch_bounds__(PREP_FINISH_BLOCK) void frame_prep_finish_kernel(Pr
     }
     if (a.transform_rots)
         for (int c = 0; c < 4; c++) dq[c] += S[12 + c];
-    {   // F.normalize(cam_unnorm_rots[..., t])
-        const double n = fmax((double)ps.nhat, 1e-12);
+    {   // F.normalize(cam_unnorm_rots[..., t]): the same clamp as normalize_adjoint, g / eps below it
+        const double n = (double)fmaxf(ps.nhat, 1e-12f);
         double d = 0.0;
-        for (int c = 0; c < 4; c++) d += (double)ps.q[c] * dq[c];
+        if (!(ps.nhat < 1e-12f))
+            for (int c = 0; c < 4; c++) d += (double)ps.q[c] * dq[c];
         for (int c = 0; c < 4; c++) d_cam_rot[c0 + c * cs] = (float)((dq[c] - (double)ps.q[c] * d) / n);
     }
 }

@@ -3,10 +3,10 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this file; the product path
 (hier-slam_amd/csrc/hsr_frame_prep.hip behind include/hsr_frame_prep.h) never does.
 
-PARITY UNPINNED: the reference functions restated here allocate on 'cuda' unconditionally
-(utils/slam_helpers.py:298, :319, :234; utils/slam_external.py:28), so they cannot run in a GPU-less container,
-and the reference ships no fixtures for them.  What pins this file instead is tests/test_frame_prep.py: an
-independently written torch (CPU, float64) expression of the same maths differentiated by torch.autograd.
+PINNED by the reference's own outputs: tests/golden/slam_helpers/frame_prep.npz holds what the reference's functions return and what
+torch.autograd derives for them on the CPU (tests/golden/make_slam_helpers_golden.py), rows below F.normalize's eps included, and
+tests/test_slam_helpers_golden.py holds this file to it.  tests/test_frame_prep.py adds an independently written torch (CPU, float64)
+expression of the same maths differentiated by torch.autograd.
 
 Follows, line by line in meaning (not in code):
   transform_to_frame                      utils/slam_helpers.py:278-330
@@ -84,10 +84,12 @@ def forward(means3D, unnorm_rotations, logit_opacities, log_scales, cam_unnorm_r
 
 
 def _normalize_adjoint(x, g):
-    """adjoint of y = x / max(|x|, eps) along the last axis (|x| > eps assumed, as in every test)."""
+    """adjoint of y = x / max(|x|, eps) along the last axis, as torch.autograd gives it for F.normalize: the clamp passes no gradient
+    below eps, so a row with |x| < eps gets g / eps (no projection term; finite at |x| = 0); (g - y (y.g)) / |x| otherwise."""
     n = np.sqrt((x * x).sum(axis=-1, keepdims=True))
-    y = x / n
-    return (g - y * (y * g).sum(axis=-1, keepdims=True)) / n
+    d = np.maximum(n, EPS)
+    y = x / d
+    return np.where(n < EPS, g / EPS, (g - y * (y * g).sum(axis=-1, keepdims=True)) / d)
 
 
 def backward(means3D, unnorm_rotations, logit_opacities, log_scales, cam_unnorm_rots, cam_trans, time_idx, grads,
@@ -132,13 +134,13 @@ def backward(means3D, unnorm_rotations, logit_opacities, log_scales, cam_unnorm_
         g_u += _normalize_adjoint(u, g_rot)
     else:
         if transform_rots:
-            un = u / np.sqrt((u * u).sum(axis=1, keepdims=True))
+            un = u / np.maximum(np.sqrt((u * u).sum(axis=1, keepdims=True)), EPS)
             tr = _quat_mult(q, un)
         else:
             tr = u
         g_tr += _normalize_adjoint(tr, g_rot)
     if transform_rots:
-        un = u / np.sqrt((u * u).sum(axis=1, keepdims=True))
+        un = u / np.maximum(np.sqrt((u * u).sum(axis=1, keepdims=True)), EPS)
         gw, gx, gy, gz = g_tr[:, 0], g_tr[:, 1], g_tr[:, 2], g_tr[:, 3]
         w2_, x2, y2, z2 = un[:, 0], un[:, 1], un[:, 2], un[:, 3]
         dq += np.array([(gw * w2_ + gx * x2 + gy * y2 + gz * z2).sum(), (-gw * x2 + gx * w2_ - gy * z2 + gz * y2).sum(),

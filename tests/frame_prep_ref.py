@@ -1,6 +1,6 @@
 """Independent torch (CPU, float64) expression of the rasterizer-input preparation, differentiated by
-torch.autograd: the pin for oracle/frame_prep_oracle.py (the reference's own functions need a CUDA device,
-utils/slam_helpers.py:298, so they cannot be run here)."""
+torch.autograd: a second pin for oracle/frame_prep_oracle.py, beside the reference's own outputs
+(tests/golden/slam_helpers/frame_prep.npz, tests/test_slam_helpers_golden.py)."""
 import torch
 import torch.nn.functional as F
 

@@ -211,3 +211,69 @@ def test_depth_silhouette_bundle_is_not_reused_for_another_w2c():
     w_a[2, 3] = -0.25                                                          # in-place edit of the first matrix
     rv_c = SH.transformed_params2depthplussilhouette(t, w_a, tg)
     assert torch.allclose(rv_c["colors_precomp"][:, 0], d_a - 0.25, atol=1e-5)
+
+
+# ---- pinned by the REFERENCE's own outputs: tests/golden/slam_helpers/frame_prep.npz holds what utils/slam_helpers.py's transform_to_frame and
+# its four builders return on the CPU and what torch.autograd derives for them (tests/golden/make_slam_helpers_golden.py); read through
+# tests/slam_helpers_fixture.py.  P = 1 / 257 (one forward block + 1) / 1025 (one 4 x 256 backward block + 1), S = 1 / 3, time_idx = 0 / T - 1,
+# the four detach-flag combinations, and P = 64 edge maps: quaternion rows of norm 0, 5e-20, 5e-13, 2e-12 around F.normalize's eps (on the
+# Gaussians and on the pose), logit_opacities of +-90, log_scales of -90 and 40. ----
+def _fixture_cases():
+    import slam_helpers_fixture as GF
+    return GF.frame_prep_cases()
+
+
+@pytest.mark.parametrize("name", _fixture_cases())
+def test_prep_matches_the_reference_outputs(name):
+    """Forward: FWD_RTOL / FWD_ATOL against the reference's values, NaN and inf where it has them; where its matmul keeps a mean outside
+    that, the criterion of tests/test_gpu_map_init.py: the kernel is at most twice as far from the float64 oracle as the reference is.
+    Gradients: BWD_TOL of each tensor's largest entry, None where the reference leaves .grad unset, pose columns other than time_idx
+    exactly zero; in the edge maps the four rows around eps one by one (below eps: g / eps, no projection term).
+    On an MI355X (profiles/slam_helpers_golden_gpu.log): every forward output within 2e-6 (the fall-back was not needed), gradients at most
+    1.2e-6 of a tensor's maximum; with the parent commit's normalize_adjoint the six edge cases fail (0.02 - 0.13 of the maximum)."""
+    import frame_prep_oracle as O
+    import slam_helpers_fixture as GF
+    from hsr_utils import slam_helpers as SH
+    c = GF.frame_prep_case(name)
+    P = c["P"]
+    t = {k: torch.tensor(v, device="cuda", requires_grad=True) for k, v in c["inputs"].items()}
+    t["rgb_colors"], t["semantic"] = torch.zeros(P, 3, device="cuda"), torch.zeros(P, 5, device="cuda")
+    w2c = None if c["w2c"] is None else torch.tensor(c["w2c"], device="cuda")
+    tg = SH.transform_to_frame(t, c["time_idx"], gaussians_grad=c["gaussians_grad"], camera_grad=c["camera_grad"])
+    if c["builder"] == "semantic":
+        rv = SH.transformed_params2rendervar_semantic(t, tg)
+    elif c["builder"] == "rendervar":
+        rv = SH.transformed_params2rendervar(t, tg)
+    elif c["builder"] == "silhouette":
+        rv = SH.transformed_params2silhouette(t, tg)
+        assert np.array_equal(rv["colors_precomp"].cpu().numpy(), c["out"]["sil_color"])
+    else:
+        rv = SH.transformed_params2depthplussilhouette(t, w2c, tg)
+    got = dict(means3D=rv["means3D"], unnorm_rotations=tg["unnorm_rotations"], rotations=rv["rotations"], opacities=rv["opacities"],
+               scales=rv["scales"])
+    if c["builder"] == "depthsil":
+        got["depth_sil"] = rv["colors_precomp"]
+    assert tuple(rv["means2D"].shape) == (P, 3) and rv["means2D"].requires_grad and not rv["means2D"].detach().any()
+    with np.errstate(all="ignore"):
+        f64 = O.forward(**c["inputs"], time_idx=c["time_idx"], rot_source=c["rot_source"], w2c=c["w2c"], dtype=np.float64)
+    for k, v in got.items():
+        g, want = v.detach().cpu().numpy(), c["out"][k]
+        assert g.shape == want.shape and g.dtype == want.dtype, k
+        for cls in (np.isnan, np.isposinf, np.isneginf):
+            assert np.array_equal(cls(g), cls(want)), "%s %s: %s sits elsewhere than in the reference" % (name, k, cls.__name__)
+        fin = np.isfinite(want) & np.isfinite(f64[k])
+        d_kernel = float(np.abs(g[fin] - f64[k][fin]).max()) if fin.any() else 0.0
+        d_ref = float(np.abs(want[fin] - f64[k][fin]).max()) if fin.any() else 0.0
+        holds = GF.forward_holds(g, want)
+        print("frame_prep %-28s %-16s within 2e-6 of the reference: %-5s  |kernel - f64| %.3e   |reference - f64| %.3e"
+              % (name, k, holds, d_kernel, d_ref))
+        assert holds or d_kernel <= 2.0 * d_ref, (name, k, d_kernel, d_ref)
+    up = {k: torch.tensor(v, device="cuda") for k, v in c["upstream"].items()}
+    loss = sum((got[k] * up[k]).sum() for k in got)
+    loss.backward()
+    grads = {k: (None if t[k].grad is None else t[k].grad.cpu().numpy()) for k in GF.PARAM_KEYS}
+    worst = GF.check_gradients(c, grads)
+    print("frame_prep %-28s gradients: largest distance from the reference %.3e of a tensor's maximum (bound %.0e)" % (name, worst, BWD_TOL))
+    if name in ("edge_semantic_S1", "edge_pose_semantic_S1"):
+        np.testing.assert_allclose(grads["unnorm_rotations"][:3], GF.expected_below_eps_rows(c), rtol=1e-6)
+        print("frame_prep %-28s rows below eps: %s" % (name, grads["unnorm_rotations"][:3].tolist()))
