@@ -1,18 +1,21 @@
-// hsr_loss_outlier.hip — the outlier-rejecting loss head (gfx950), DESIGN.md §7 row 2: the ignore_outlier_depth_loss branch of the
-// reference's get_loss* (scripts/hierslam.py:909-937).  See include/ext/hsr_loss_outlier.h for the semantics, line by line.
-//
-// What it replaces: a dozen eager launches (sub, abs, gt, mul, median = a sort of H*W values, mul, lt, and, isnan, not, and), a bool
-// mask tensor, two masked-L1 nodes and a weighted sum.  Here the exact median is a radix select over the bits of the error, which is
-// never negative and therefore orders as an unsigned integer: 11 + 11 + 10 bits in three launches.
+// hsr_loss_masked.hip — the masked-L1 loss head (gfx950), DESIGN.md §7: the depth and colour terms of the reference's get_loss*
+// (scripts/hierslam.py:903-937) behind two ABIs that differ in one factor of the mask:
+//   hsr_loss_tracking_* (include/hsr_losses.h):          mask = (gt > 0) & ~isnan(d) [& (silhouette > sil_thres)]
+//   hsr_loss_outlier_*  (include/ext/hsr_loss_outlier.h): the same & (|gt - d| * (gt > 0) < 10 * median of that error over the map),
+//                                                         the ignore_outlier_depth_loss branch (:909-913)
+// What it replaces: six mask kernels, two boolean gathers, two abs / sum chains and their autograd, and with rejection a dozen more (sub,
+// abs, gt, mul, median = a sort of H*W values, mul, lt, and, ...) and a bool mask tensor.  Here the mask lives in a register.
+//   value_kernel<OUTLIER>  : both masked sums and the selection count of a workgroup's pixels; one partial per workgroup.  The OUTLIER
+//                            instance first finds the three digits of the median again (24 KB of reads) and forms the threshold.
+//   finish_kernel          : fixed-order sum of the partials in double; terms, weighted total, 1 / selected pixels.
+//   grad_kernel            : when autograd asks; the mask recomputed (with rejection: from the threshold in device memory).
+// The exact median is a radix select over the bits of the error, which is never negative and therefore orders as an unsigned integer:
+// 11 + 11 + 10 bits in three launches.
 //   hist_kernel<0|1|2> : every workgroup counts the digit of its pixels (pass 1 and 2: of those that agree with the digits already
 //                        decided) into a 2048-bin histogram in LDS and adds its non-zero bins into the pass's global histogram with
 //                        integer atomics.  Passes 1 and 2 begin with EVERY workgroup finding the bin that holds the rank in the
 //                        global histograms of the launches before (8 KB each, finished: the kernel boundary is the only
 //                        synchronisation; no workgroup reads within a launch what another wrote in it).  A NaN counter rides along.
-//   value_kernel       : every workgroup finds the three digits again (24 KB of reads), forms median and threshold, and sums the
-//                        masked terms of its pixels (the mask lives in a register); one partial per workgroup.
-//   finish_kernel      : fixed-order sum of the partials in double, as the tracking head's (hsr_losses.hip, tracking_finish_kernel).
-//   grad_kernel        : when autograd asks; the mask recomputed from the threshold in device memory.
 // Integer counts throughout the selection, fixed-order float sums: every output is the same bits on every run.
 // Compiled with -ffp-contract=off: error and threshold are computed as written.  Denormals are kept (hipcc's default for fp32 on gfx9).
 #include "hsr_common.h"
@@ -21,8 +24,8 @@
 namespace {
 
 constexpr int LB = 256;               // threads per workgroup
-constexpr int ITEMS = 4;              // pixels per thread until the grid stops growing
-constexpr int MAX_BLOCKS = 512;       // then the workgroups stride: 2 per CU; each pays a 2048-bin clear, flush and up to three rank searches
+constexpr int ITEMS = 4;              // pixels per thread: the grid is ceil(N / (LB * ITEMS)) until a cap stops it
+constexpr int MAX_BLOCKS = 512;       // with rejection; then the workgroups stride: 2 per CU; each pays a 2048-bin clear, flush and up to three rank searches
 constexpr int BINS = 2048;            // 11 bits; the last pass uses 1024 of them
 constexpr int HIST_WORDS = 3 * BINS;  // the three global histograms, then the control words
 constexpr int CTL_NAN = HIST_WORDS;   // number of NaN errors
@@ -37,9 +40,11 @@ __device__ __forceinline__ float depth_error(float gt, float d)
     return fabsf(gt - d) * (gt > 0.f ? 1.f : 0.f);
 }
 
-__device__ __forceinline__ bool outlier_selected(float gt, float d, float thr, float sil, float sil_thres, int use_sil)
+// the mask of a pixel; reject: additionally the error below the threshold (strict: a NaN threshold selects nothing).  Not thr = +inf for
+// the plain mask: an infinite depth on a valid pixel has the error inf, inf < inf is false, and the plain mask selects that pixel
+__device__ __forceinline__ bool selected(bool reject, float gt, float d, float thr, float sil, float sil_thres, int use_sil)
 {
-    return depth_error(gt, d) < thr && gt > 0.f && !(d != d) && (!use_sil || sil > sil_thres);
+    return (!reject || depth_error(gt, d) < thr) && gt > 0.f && !(d != d) && (!use_sil || sil > sil_thres);
 }
 
 struct Rank { unsigned bin, rank; };
@@ -161,32 +166,43 @@ __device__ __forceinline__ float block_sum(float v, float* s_red)
     return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
 }
 
+// OUTLIER: the threshold from the finished histograms, one pixel per thread and trip (the grid is capped at MAX_BLOCKS and strides);
+// otherwise no threshold, ITEMS pixels per thread and a grid that covers N in one trip.  Either way a thread adds its terms in index order.
+template <bool OUTLIER>
 __global__ __launch_bounds__(LB) void value_kernel(const float* __restrict__ im, const float* __restrict__ gt_im, int C,
                                                    const float* __restrict__ depth, const float* __restrict__ gt_depth,
                                                    const float* __restrict__ sil, float sil_thres, int use_sil, unsigned N,
                                                    const unsigned* hist, float* __restrict__ partials /* [nblk][2]: depth sum, colour sum */,
                                                    unsigned* __restrict__ counts /* [nblk]: selected pixels */, float* __restrict__ out6)
 {
+    constexpr unsigned PER = OUTLIER ? 1 : ITEMS;
     __shared__ unsigned s_wave[LB / 64], s_res[2];
     __shared__ float s_red[LB / 64];
-    const float med = block_median(hist, N, s_wave, s_res);
-    const float thr = 10.0f * med;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        out6[4] = med;
-        out6[5] = thr;
+    float thr = 0.f;
+    if constexpr (OUTLIER) {
+        const float med = block_median(hist, N, s_wave, s_res);
+        thr = 10.0f * med;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            out6[4] = med;
+            out6[5] = thr;
+        }
     }
     float acc_d = 0.f, acc_c = 0.f;
     unsigned n = 0;
-    for (unsigned i = blockIdx.x * LB + threadIdx.x; i < N; i += gridDim.x * LB) {
-        const float gd = gt_depth[i], d = depth[i];
-        const bool sel = outlier_selected(gd, d, thr, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
-        acc_d += sel ? fabsf(gd - d) : 0.f;
-        n += sel ? 1u : 0u;
-        for (int c = 0; c < C; c++) {
-            const float e = fabsf(gt_im[(size_t)c * N + i] - im[(size_t)c * N + i]);
-            acc_c += sel ? e : 0.f;
+    for (unsigned base = blockIdx.x * LB * PER; base < N; base += gridDim.x * LB * PER)      // no wrap: base < N < 2^31, stride < N + LB * PER
+#pragma unroll
+        for (unsigned it = 0; it < PER; it++) {
+            const unsigned i = base + threadIdx.x + it * LB;
+            if (i >= N) break;
+            const float gd = gt_depth[i], d = depth[i];
+            const bool sel = selected(OUTLIER, gd, d, thr, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
+            acc_d += sel ? fabsf(gd - d) : 0.f;
+            n += sel ? 1u : 0u;
+            for (int c = 0; c < C; c++) {
+                const float e = fabsf(gt_im[(size_t)c * N + i] - im[(size_t)c * N + i]);
+                acc_c += sel ? e : 0.f;
+            }
         }
-    }
     const float td = block_sum(acc_d, s_red);
     const float tc = block_sum(acc_c, s_red);
 #pragma unroll
@@ -201,11 +217,12 @@ __global__ __launch_bounds__(LB) void value_kernel(const float* __restrict__ im,
     }
 }
 
-// out[0] = depth term, out[1] = colour term, out[2] = w_depth * out[0] + w_im * out[1], out[3] = 1 / selected pixels; *out_selected.
+// out[0] = depth term, out[1] = colour term, out[2] = w_depth * out[0] + w_im * out[1], out[3] = 1 / selected pixels; *out_selected if asked.
 // mean: the terms are means over the selection (colour: tiled over its C planes); an empty selection gives NaN like torch.
+// Thread t sums partials t, t + 256, ... in double, then a halving tree: a fixed order.
 __global__ __launch_bounds__(LB) void finish_kernel(const float* __restrict__ partials, const unsigned* __restrict__ counts, int nblocks,
                                                     float w_depth, float w_im, int mean, int C, float* __restrict__ out,
-                                                    int* __restrict__ out_selected)
+                                                    int* __restrict__ out_selected /* may be NULL */)
 {
     __shared__ double s_acc[LB][2];
     __shared__ unsigned s_cnt[LB];
@@ -234,12 +251,17 @@ __global__ __launch_bounds__(LB) void finish_kernel(const float* __restrict__ pa
         const double cterm = mean ? (C > 0 ? s_acc[0][1] * (double)inv / (double)C : 0.0) : s_acc[0][1];
         out[0] = (float)dterm;
         out[1] = (float)cterm;
-        out[2] = (float)((double)w_depth * dterm + (double)w_im * cterm);
+        // One fused multiply-add, written out so that the file's -ffp-contract=off does not decide it: the tracking entry has always
+        // rounded here once (its finish was compiled with contraction: v_mul_f64, v_fmac_f64).  The outlier entry used to round the
+        // depth product as well; its out6[2] can differ from that only where the double lies within one double-ulp of an fp32 rounding
+        // boundary, and then by one fp32 ulp.
+        out[2] = (float)fma((double)w_depth, dterm, (double)w_im * cterm);
         out[3] = inv;
-        out_selected[0] = (int)s_cnt[0];
+        if (out_selected) out_selected[0] = (int)s_cnt[0];
     }
 }
 
+// threshold == NULL: the plain mask.  Up to 65536 workgroups, then they stride: i + stride < 2^31 + 2^24
 __global__ __launch_bounds__(LB) void grad_kernel(const float* __restrict__ im, const float* __restrict__ gt_im, int C,
                                                   const float* __restrict__ depth, const float* __restrict__ gt_depth,
                                                   const float* __restrict__ sil, float sil_thres, int use_sil, unsigned N,
@@ -247,13 +269,14 @@ __global__ __launch_bounds__(LB) void grad_kernel(const float* __restrict__ im, 
                                                   float w_im, const float* __restrict__ inv_count, float* __restrict__ d_im,
                                                   float* __restrict__ d_depth)
 {
-    const float thr = threshold[0];
+    const bool reject = threshold != nullptr;
+    const float thr = reject ? threshold[0] : 0.f;
     const float up = upstream ? upstream[0] : 1.0f;
-    const float inv = inv_count ? inv_count[0] : 1.0f;   // mean reduction: 1 / selected pixels (the value pass's out6[3])
+    const float inv = inv_count ? inv_count[0] : 1.0f;   // mean reduction: 1 / selected pixels (the value pass's out[3])
     const float sd = w_depth * up * inv, sc = w_im * up * (inv_count ? inv / (float)(C > 0 ? C : 1) : 1.0f);
     for (unsigned i = blockIdx.x * LB + threadIdx.x; i < N; i += gridDim.x * LB) {
         const float gd = gt_depth[i], d = depth[i];
-        const bool sel = outlier_selected(gd, d, thr, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
+        const bool sel = selected(reject, gd, d, thr, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
         if (d_depth) {
             const float e = d - gd;   // d |gt - d| / d d = sign(d - gt)
             d_depth[i] = sel ? (e > 0.f ? sd : (e < 0.f ? -sd : 0.f)) : 0.f;
@@ -266,34 +289,39 @@ __global__ __launch_bounds__(LB) void grad_kernel(const float* __restrict__ im, 
     }
 }
 
-int blocks_for(unsigned N)
+// ceil(N / (LB * ITEMS)) workgroups, at least one, at most `cap`
+unsigned blocks_for(unsigned N, unsigned cap)
 {
     const unsigned nb = (N + LB * ITEMS - 1) / (LB * ITEMS);
-    return (int)(nb < 1 ? 1 : (nb > MAX_BLOCKS ? MAX_BLOCKS : nb));
+    return nb < 1 ? 1 : (nb > cap ? cap : nb);
 }
 
-int check_maps(const char* who, int H, int W, const float* depth, const float* gt_depth)
+// the tracking entry's scratch: float [nb][2], then unsigned [nb], nb uncapped
+size_t tracking_bytes(int H, int W)
+{
+    const size_t nb = ((size_t)H * W + LB * ITEMS - 1) / (LB * ITEMS);
+    return (nb * 3 * sizeof(float) + 255) & ~(size_t)255;
+}
+
+// any_c: the tracking ABI takes every C >= 0, the outlier ABI 0 or 3
+int check_maps(const char* who, bool any_c, int C, int H, int W, const float* im, const float* gt_im, const float* depth,
+               const float* gt_depth, const float* sil, int use_sil)
 {
     if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !depth || !gt_depth) {
         hsr_set_error("%s: invalid sizes H=%d W=%d (H, W >= 1, H * W < 2^31) or NULL depth / gt_depth", who, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    return HSR_OK;
-}
-
-int check_colour(const char* who, int C, const float* im, const float* gt_im, const float* sil, int use_sil)
-{
-    if ((C != 0 && C != 3) || (C > 0 && (!im || !gt_im)) || (use_sil && !sil)) {
-        hsr_set_error("%s: C=%d is neither 0 nor 3, or NULL im / gt_im / silhouette", who, C);
+    if (C < 0 || (!any_c && C != 0 && C != 3) || (C > 0 && (!im || !gt_im)) || (use_sil && !sil)) {
+        hsr_set_error("%s: C=%d is %s, or NULL im / gt_im / silhouette", who, C, any_c ? "negative" : "neither 0 nor 3");
         return HSR_ERR_INVALID_ARGUMENT;
     }
     return HSR_OK;
 }
 
-int check_scratch(const char* who, const char* scratch, size_t have)
+int check_scratch(const char* who, const char* scratch, size_t have, size_t need, unsigned align)
 {
-    if (!scratch || have < SCRATCH_BYTES || (reinterpret_cast<uintptr_t>(scratch) & 15) != 0) {
-        hsr_set_error("%s: scratch is NULL, not 16-byte aligned or too small: %zu bytes needed, %zu given", who, SCRATCH_BYTES, have);
+    if (!scratch || have < need || (reinterpret_cast<uintptr_t>(scratch) & (align - 1)) != 0) {
+        hsr_set_error("%s: scratch is NULL, not %u-byte aligned or too small: %zu bytes needed, %zu given", who, align, need, have);
         return HSR_ERR_BUFFER_TOO_SMALL;
     }
     return HSR_OK;
@@ -310,7 +338,74 @@ int launch_select(unsigned N, int nb, const float* depth, const float* gt_depth,
     return HSR_OK;
 }
 
+// both value entries.  reject: the outlier one (out = out6, out_selected required, its fixed scratch layout)
+int masked_value(const char* who, bool reject, int C, int H, int W, const float* im, const float* gt_im, const float* depth,
+                 const float* gt_depth, const float* sil, float sil_thres, int use_sil, int reduction, float w_depth, float w_im, float* out,
+                 int* out_selected, char* scratch, size_t scratch_bytes, hipStream_t stream)
+{
+    int rc = check_maps(who, !reject, C, H, W, im, gt_im, depth, gt_depth, sil, use_sil);
+    if (rc != HSR_OK) return rc;
+    if (!out || (reject && !out_selected) || (reduction != HSR_LOSS_SUM && reduction != HSR_LOSS_MEAN)) {
+        hsr_set_error("%s: out%s is NULL or reduction is neither HSR_LOSS_SUM nor HSR_LOSS_MEAN", who, reject ? "6 / out_selected" : "4");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    rc = reject ? check_scratch(who, scratch, scratch_bytes, SCRATCH_BYTES, 16) : check_scratch(who, scratch, scratch_bytes, tracking_bytes(H, W), 4);
+    if (rc != HSR_OK) return rc;
+    const unsigned N = (unsigned)H * (unsigned)W;
+    const int nb = (int)blocks_for(N, reject ? MAX_BLOCKS : ~0u);
+    float* partials = reinterpret_cast<float*>(reject ? scratch + PART_OFF : scratch);
+    unsigned* counts = reject ? reinterpret_cast<unsigned*>(scratch + COUNT_OFF) : reinterpret_cast<unsigned*>(partials + 2 * (size_t)nb);
+    if (reject) {
+        rc = launch_select(N, nb, depth, gt_depth, scratch, stream);
+        if (rc != HSR_OK) return rc;
+        value_kernel<true><<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, sil, sil_thres, use_sil, N,
+                                                  reinterpret_cast<const unsigned*>(scratch), partials, counts, out);
+    } else {
+        value_kernel<false><<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, sil, sil_thres, use_sil, N, nullptr, partials, counts, out);
+    }
+    finish_kernel<<<1, LB, 0, stream>>>(partials, counts, nb, w_depth, w_im, reduction == HSR_LOSS_MEAN ? 1 : 0, C, out, out_selected);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}
+
+// both gradient entries.  threshold == NULL: the tracking one
+int masked_grad(const char* who, int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
+                const float* sil, float sil_thres, int use_sil, float w_depth, float w_im, const float* threshold, const float* upstream,
+                const float* inv_count, float* d_im, float* d_depth, hipStream_t stream)
+{
+    const int rc = check_maps(who, !threshold, C, H, W, im, gt_im, depth, gt_depth, sil, use_sil);
+    if (rc != HSR_OK) return rc;
+    const unsigned N = (unsigned)H * (unsigned)W;
+    if (C == 0) d_im = nullptr;
+    if (!d_im && !d_depth) return HSR_OK;      // nothing asked for, nothing launched
+    grad_kernel<<<blocks_for(N, 65536u), LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, sil, sil_thres, use_sil, N, threshold, upstream, w_depth,
+                                                          w_im, inv_count, d_im, d_depth);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}
+
 }  // namespace
+
+extern "C" size_t hsr_loss_tracking_scratch_bytes(int H, int W)
+{
+    return H < 1 || W < 1 ? 1024 : tracking_bytes(H, W) + 256;
+}
+
+extern "C" int hsr_loss_tracking_value(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
+                                       const float* silhouette, float sil_thres, int use_sil, int reduction, float w_depth, float w_im,
+                                       float* out4, char* scratch, size_t scratch_bytes, void* stream)
+{
+    return masked_value("loss_tracking_value", false, C, H, W, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, reduction, w_depth,
+                        w_im, out4, nullptr, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+extern "C" int hsr_loss_tracking_grad(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
+                                      const float* silhouette, float sil_thres, int use_sil, float w_depth, float w_im, const float* upstream,
+                                      const float* inv_count, float* d_im, float* d_depth, void* stream)
+{
+    return masked_grad("loss_tracking_grad", C, H, W, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, w_depth, w_im, nullptr,
+                       upstream, inv_count, d_im, d_depth, (hipStream_t)stream);
+}
 
 extern "C" size_t hsr_loss_outlier_scratch_bytes(int H, int W)
 {
@@ -323,16 +418,16 @@ extern "C" int hsr_loss_outlier_median(int H, int W, const float* depth, const f
                                        size_t scratch_bytes, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_maps("loss_outlier_median", H, W, depth, gt_depth);
+    int rc = check_maps("loss_outlier_median", false, 0, H, W, nullptr, nullptr, depth, gt_depth, nullptr, 0);
     if (rc != HSR_OK) return rc;
     if (!out2) {
         hsr_set_error("loss_outlier_median: out2 is NULL");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    rc = check_scratch("loss_outlier_median", scratch, scratch_bytes);
+    rc = check_scratch("loss_outlier_median", scratch, scratch_bytes, SCRATCH_BYTES, 16);
     if (rc != HSR_OK) return rc;
     const unsigned N = (unsigned)H * (unsigned)W;
-    rc = launch_select(N, blocks_for(N), depth, gt_depth, scratch, stream);
+    rc = launch_select(N, (int)blocks_for(N, MAX_BLOCKS), depth, gt_depth, scratch, stream);
     if (rc != HSR_OK) return rc;
     median_kernel<<<1, LB, 0, stream>>>(reinterpret_cast<const unsigned*>(scratch), N, out2);
     HSR_HIP_CHECK(hipGetLastError());
@@ -341,52 +436,20 @@ extern "C" int hsr_loss_outlier_median(int H, int W, const float* depth, const f
 
 extern "C" int hsr_loss_outlier_value(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
                                       const float* silhouette, float sil_thres, int use_sil, int reduction, float w_depth, float w_im,
-                                      float* out6, int* out_selected, char* scratch, size_t scratch_bytes, void* stream_)
+                                      float* out6, int* out_selected, char* scratch, size_t scratch_bytes, void* stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_maps("loss_outlier_value", H, W, depth, gt_depth);
-    if (rc != HSR_OK) return rc;
-    rc = check_colour("loss_outlier_value", C, im, gt_im, silhouette, use_sil);
-    if (rc != HSR_OK) return rc;
-    if (!out6 || !out_selected || (reduction != HSR_LOSS_SUM && reduction != HSR_LOSS_MEAN)) {
-        hsr_set_error("loss_outlier_value: out6 / out_selected is NULL or reduction is neither HSR_LOSS_SUM nor HSR_LOSS_MEAN");
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    rc = check_scratch("loss_outlier_value", scratch, scratch_bytes);
-    if (rc != HSR_OK) return rc;
-    const unsigned N = (unsigned)H * (unsigned)W;
-    const int nb = blocks_for(N);
-    rc = launch_select(N, nb, depth, gt_depth, scratch, stream);
-    if (rc != HSR_OK) return rc;
-    float* partials = reinterpret_cast<float*>(scratch + PART_OFF);
-    unsigned* counts = reinterpret_cast<unsigned*>(scratch + COUNT_OFF);
-    value_kernel<<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, silhouette, sil_thres, use_sil, N,
-                                        reinterpret_cast<const unsigned*>(scratch), partials, counts, out6);
-    finish_kernel<<<1, LB, 0, stream>>>(partials, counts, nb, w_depth, w_im, reduction == HSR_LOSS_MEAN ? 1 : 0, C, out6, out_selected);
-    HSR_HIP_CHECK(hipGetLastError());
-    return HSR_OK;
+    return masked_value("loss_outlier_value", true, C, H, W, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, reduction, w_depth,
+                        w_im, out6, out_selected, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
 extern "C" int hsr_loss_outlier_grad(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
                                      const float* silhouette, float sil_thres, int use_sil, float w_depth, float w_im, const float* threshold,
-                                     const float* upstream, const float* inv_count, float* d_im, float* d_depth, void* stream_)
+                                     const float* upstream, const float* inv_count, float* d_im, float* d_depth, void* stream)
 {
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_maps("loss_outlier_grad", H, W, depth, gt_depth);
-    if (rc != HSR_OK) return rc;
-    rc = check_colour("loss_outlier_grad", C, im, gt_im, silhouette, use_sil);
-    if (rc != HSR_OK) return rc;
     if (!threshold) {
         hsr_set_error("loss_outlier_grad: threshold is NULL (pass &out6[5] of the value pass)");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const unsigned N = (unsigned)H * (unsigned)W;
-    if (C == 0) d_im = nullptr;
-    if (!d_im && !d_depth) return HSR_OK;      // nothing asked for, nothing launched
-    const unsigned want = (N + LB * ITEMS - 1) / (LB * ITEMS);
-    const unsigned nb = want > 65536u ? 65536u : want;      // the rest by striding; i + stride < 2^31 + 2^24
-    grad_kernel<<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, silhouette, sil_thres, use_sil, N, threshold, upstream, w_depth, w_im,
-                                       inv_count, d_im, d_depth);
-    HSR_HIP_CHECK(hipGetLastError());
-    return HSR_OK;
+    return masked_grad("loss_outlier_grad", C, H, W, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, w_depth, w_im, threshold,
+                       upstream, inv_count, d_im, d_depth, (hipStream_t)stream);
 }

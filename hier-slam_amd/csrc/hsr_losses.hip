@@ -13,6 +13,8 @@
 //   * tree cross-entropy: one thread per pixel walks the levels, channels are read with stride H*W (coalesced across
 //     the wave), online log-sum-exp, then softmax - onehot straight into the planar gradient — no [H*W, n] permute.
 // All HBM-bound; algorithmic bytes per pixel: L1 4C*3 (+1 mask), SSIM 4C*(2 + 3) fwd + 4C*(3 + 2 + 1) bwd, CE 4K*3 + 8L.
+// The tracking loss of include/hsr_losses.h (hsr_loss_tracking_*: mask, both masked sums and their gradients as one head) is not here: it
+// shares its kernels with the outlier-rejecting head in hsr_loss_masked.hip.
 #include "hsr_common.h"
 #include "../../include/hsr_losses.h"
 #include <cmath>
@@ -113,100 +115,6 @@ __global__ __launch_bounds__(LB) void l1_kernel(const float* __restrict__ pred, 
     }
     const float tot = block_sum(acc, s_red);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
-}
-
-// ---------------------------------------------------------------- tracking loss
-// The tracking branch of the reference's get_loss* (scripts/hierslam.py:903-937 with its shipped configs: use_l1, use_sil_for_loss,
-// no outlier rejection):  mask = (gt_depth > 0) & ~isnan(depth) & (silhouette > sil_thres);  depth term = sum |gt_depth - depth|[mask],
-// colour term = sum |gt_im - im|[mask tiled over the channels].  In torch that is six mask kernels, two boolean gathers, two abs / sum
-// chains and their autograd; here ONE pass forms both sums (the mask lives in a register) and ONE pass, run when autograd asks, writes
-// both gradients times the upstream gradient it reads from device memory.  Unselected pixels contribute nothing, whatever they hold.
-constexpr int TRK_ITEMS = 4;   // pixels per thread
-
-__device__ __forceinline__ bool tracking_selected(float gt_d, float d, float sil, float sil_thres, int use_sil)
-{
-    return gt_d > 0.f && !(d != d) && (!use_sil || sil > sil_thres);
-}
-
-__global__ __launch_bounds__(LB) void tracking_value_kernel(const float* __restrict__ im, const float* __restrict__ gt_im, int C,
-                                                            const float* __restrict__ depth, const float* __restrict__ gt_depth,
-                                                            const float* __restrict__ sil, float sil_thres, int use_sil, int N,
-                                                            float* __restrict__ partials /* [nblk][3]: depth sum, colour sum, selected pixels */)
-{
-    __shared__ float s_red[4];
-    float acc_d = 0.f, acc_c = 0.f, acc_n = 0.f;
-    for (int i = blockIdx.x * LB * TRK_ITEMS + threadIdx.x, it = 0; it < TRK_ITEMS; it++, i += LB) {
-        if (i >= N) break;
-        const float gd = gt_depth[i], d = depth[i];
-        const bool sel = tracking_selected(gd, d, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
-        acc_d += sel ? fabsf(gd - d) : 0.f;
-        acc_n += sel ? 1.f : 0.f;   // exact in fp32: at most LB * TRK_ITEMS per block
-        for (int c = 0; c < C; c++) {
-            const float e = fabsf(gt_im[(size_t)c * N + i] - im[(size_t)c * N + i]);
-            acc_c += sel ? e : 0.f;
-        }
-    }
-    const float td = block_sum(acc_d, s_red);
-    const float tc = block_sum(acc_c, s_red);
-    const float tn = block_sum(acc_n, s_red);
-    if (threadIdx.x == 0) {
-        partials[3 * (size_t)blockIdx.x] = td;
-        partials[3 * (size_t)blockIdx.x + 1] = tc;
-        partials[3 * (size_t)blockIdx.x + 2] = tn;
-    }
-}
-
-// out[0] = depth term, out[1] = colour term, out[2] = w_depth * out[0] + w_im * out[1], out[3] = 1 / selected pixels (fixed order, double).
-// mean: the terms are means over the selection (colour: over the selection tiled over its C planes) — an empty selection gives NaN like torch.
-__global__ __launch_bounds__(1024) void tracking_finish_kernel(const float* __restrict__ partials, int nblocks, float w_depth, float w_im,
-                                                               int mean, int C, float* __restrict__ out)
-{
-    __shared__ double s_acc[256][4];
-    const int k = threadIdx.x & 3, j = threadIdx.x >> 2;   // 256 row groups x (3 columns + 1 idle)
-    double acc = 0.0;
-    if (k < 3)
-        for (int b = j; b < nblocks; b += 256) acc += (double)partials[3 * (size_t)b + k];
-    s_acc[j][k] = acc;
-    __syncthreads();
-    for (int o = 128; o >= 1; o >>= 1) {
-        if (j < o) s_acc[j][k] += s_acc[j + o][k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const double n = s_acc[0][2];
-        const float inv = 1.0f / (float)n;
-        const double dterm = mean ? s_acc[0][0] * (double)inv : s_acc[0][0];
-        const double cterm = mean ? (C > 0 ? s_acc[0][1] * (double)inv / (double)C : 0.0) : s_acc[0][1];
-        out[0] = (float)dterm;
-        out[1] = (float)cterm;
-        out[2] = (float)((double)w_depth * dterm + (double)w_im * cterm);
-        out[3] = inv;
-    }
-}
-
-__global__ __launch_bounds__(LB) void tracking_grad_kernel(const float* __restrict__ im, const float* __restrict__ gt_im, int C,
-                                                           const float* __restrict__ depth, const float* __restrict__ gt_depth,
-                                                           const float* __restrict__ sil, float sil_thres, int use_sil, int N,
-                                                           const float* __restrict__ upstream, float w_depth, float w_im,
-                                                           const float* __restrict__ inv_count, float* __restrict__ d_im, float* __restrict__ d_depth)
-{
-    const float up = upstream ? upstream[0] : 1.0f;
-    const float inv = inv_count ? inv_count[0] : 1.0f;   // mean reduction: 1 / selected pixels (the value pass's out[3])
-    const float sd = w_depth * up * inv, sc = w_im * up * (inv_count ? inv / (float)(C > 0 ? C : 1) : 1.0f);
-    for (int i = blockIdx.x * LB * TRK_ITEMS + threadIdx.x, it = 0; it < TRK_ITEMS; it++, i += LB) {
-        if (i >= N) break;
-        const float gd = gt_depth[i], d = depth[i];
-        const bool sel = tracking_selected(gd, d, use_sil ? sil[i] : 1.f, sil_thres, use_sil);
-        if (d_depth) {
-            const float e = d - gd;   // d |gt - d| / d d = sign(d - gt)
-            d_depth[i] = sel ? (e > 0.f ? sd : (e < 0.f ? -sd : 0.f)) : 0.f;
-        }
-        if (d_im)
-            for (int c = 0; c < C; c++) {
-                const float e = im[(size_t)c * N + i] - gt_im[(size_t)c * N + i];
-                d_im[(size_t)c * N + i] = sel ? (e > 0.f ? sc : (e < 0.f ? -sc : 0.f)) : 0.f;
-            }
-    }
 }
 
 // ---------------------------------------------------------------- SSIM
@@ -873,104 +781,6 @@ extern "C" int hsr_loss_l1(int C, int H, int W, const float* pred, const float* 
 }
 
 namespace {
-int check_tracking(const char* who, int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
-                   const float* sil, int use_sil)
-{
-    if (C < 0 || H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || (C > 0 && (!im || !gt_im)) || !depth || !gt_depth || (use_sil && !sil)) {
-        hsr_set_error("%s: invalid sizes C=%d H=%d W=%d or NULL im / gt_im / depth / gt_depth / silhouette", who, C, H, W);
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    return HSR_OK;
-}
-}  // namespace
-
-extern "C" size_t hsr_loss_tracking_scratch_bytes(int H, int W)
-{
-    if (H < 1 || W < 1) return 1024;
-    const size_t nb = ((size_t)H * W + LB * TRK_ITEMS - 1) / (LB * TRK_ITEMS);
-    return align256(nb * 3 * sizeof(float)) + 256;
-}
-
-extern "C" int hsr_loss_tracking_value(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
-                                       const float* silhouette, float sil_thres, int use_sil, int reduction, float w_depth, float w_im,
-                                       float* out4, char* scratch, size_t scratch_bytes, void* stream_)
-{
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_tracking("loss_tracking_value", C, H, W, im, gt_im, depth, gt_depth, silhouette, use_sil);
-    if (rc != HSR_OK) return rc;
-    if (!out4 || (reduction != HSR_LOSS_SUM && reduction != HSR_LOSS_MEAN)) {
-        hsr_set_error("loss_tracking_value: out4 is NULL or reduction is neither HSR_LOSS_SUM nor HSR_LOSS_MEAN");
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    rc = check_scratch("loss_tracking_value", scratch, scratch_bytes, hsr_loss_tracking_scratch_bytes(H, W) - 256);
-    if (rc != HSR_OK) return rc;
-    const int N = H * W;
-    const int nb = (N + LB * TRK_ITEMS - 1) / (LB * TRK_ITEMS);
-    float* partials = reinterpret_cast<float*>(scratch);
-    tracking_value_kernel<<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, silhouette, sil_thres, use_sil, N, partials);
-    tracking_finish_kernel<<<1, 1024, 0, stream>>>(partials, nb, w_depth, w_im, reduction == HSR_LOSS_MEAN ? 1 : 0, C, out4);
-    HSR_HIP_CHECK(hipGetLastError());
-    return HSR_OK;
-}
-
-extern "C" int hsr_loss_tracking_grad(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
-                                      const float* silhouette, float sil_thres, int use_sil, float w_depth, float w_im, const float* upstream,
-                                      const float* inv_count, float* d_im, float* d_depth, void* stream_)
-{
-    hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_tracking("loss_tracking_grad", C, H, W, im, gt_im, depth, gt_depth, silhouette, use_sil);
-    if (rc != HSR_OK) return rc;
-    const int N = H * W;
-    const int nb = (N + LB * TRK_ITEMS - 1) / (LB * TRK_ITEMS);
-    if (d_im || d_depth)
-        tracking_grad_kernel<<<nb, LB, 0, stream>>>(im, gt_im, C, depth, gt_depth, silhouette, sil_thres, use_sil, N, upstream, w_depth, w_im, inv_count,
-                                                    C > 0 ? d_im : nullptr, d_depth);
-    HSR_HIP_CHECK(hipGetLastError());
-    return HSR_OK;
-}
-
-extern "C" int hsr_loss_ssim(int C, int H, int W, const float* img1, const float* img2, float* out_ssim, float* out_grad, char* scratch,
-                             size_t scratch_bytes, void* stream_)
-{
-    hipStream_t stream = (hipStream_t)stream_;
-    if (C < 1 || H < 1 || W < 1 || !img1 || !img2 || !out_ssim) {
-        hsr_set_error("loss_ssim: invalid sizes C=%d H=%d W=%d or NULL img1/img2/out_ssim", C, H, W);
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    const size_t N = (size_t)H * W;
-    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
-    const size_t tiles = (size_t)grid.x * grid.y * C;
-    const size_t map_bytes = align256((size_t)C * N * sizeof(float) * 3);
-    int rc = check_scratch("loss_ssim", scratch, scratch_bytes, (out_grad ? map_bytes : 0) + align256(tiles * sizeof(float)));
-    if (rc != HSR_OK) return rc;
-    // the reference's 1-D window: gaussian(11, 1.5) as float32, normalised in float32 (utils/slam_external.py:54-56)
-    Gauss win;
-    {
-        float sum = 0.f;
-        for (int x = 0; x < 11; x++) {
-            win.g[x] = (float)std::exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
-            sum += win.g[x];
-        }
-        for (int x = 0; x < 11; x++) win.g[x] = win.g[x] / sum;
-    }
-    float *d_mu1 = nullptr, *d_s11 = nullptr, *d_s12 = nullptr;
-    char* cur = scratch;
-    if (out_grad) {
-        d_mu1 = reinterpret_cast<float*>(cur);
-        d_s11 = d_mu1 + (size_t)C * N;
-        d_s12 = d_s11 + (size_t)C * N;
-        cur += map_bytes;
-    }
-    float* partials = reinterpret_cast<float*>(cur);
-    const float inv_n = (float)(1.0 / ((double)C * (double)N));
-    ssim_forward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, win, d_mu1, d_s11, d_s12, partials);
-    finish_kernel<<<1, LB, 0, stream>>>(partials, (int)tiles, 1, 1, nullptr, inv_n, out_ssim);
-    if (out_grad) ssim_backward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, win, d_mu1, d_s11, d_s12, inv_n, nullptr, out_grad);
-    HSR_HIP_CHECK(hipGetLastError());
-    return HSR_OK;
-}
-
-namespace {
 Gauss ssim_window()
 {
     // the reference's 1-D window: gaussian(11, 1.5) as float32, normalised in float32 (utils/slam_external.py:54-56)
@@ -983,28 +793,64 @@ Gauss ssim_window()
     for (int x = 0; x < 11; x++) win.g[x] = win.g[x] / sum;
     return win;
 }
+
+dim3 ssim_grid(int C, int H, int W) { return dim3((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C); }
+
+float ssim_inv_n(int C, int H, int W) { return (float)(1.0 / ((double)C * (double)((size_t)H * W))); }
+
+// the mean SSIM into out_ssim; maps (3 * C * H * W floats or NULL) receives the three partial-derivative maps; partials: one float per tile
+void launch_ssim_value(int C, int H, int W, const float* img1, const float* img2, float* maps, float* partials, float* out_ssim, hipStream_t stream)
+{
+    const size_t CN = (size_t)C * H * W;
+    const dim3 grid = ssim_grid(C, H, W);
+    ssim_forward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, ssim_window(), maps, maps ? maps + CN : nullptr, maps ? maps + 2 * CN : nullptr,
+                                                 partials);
+    finish_kernel<<<1, LB, 0, stream>>>(partials, (int)(grid.x * grid.y * grid.z), 1, 1, nullptr, ssim_inv_n(C, H, W), out_ssim);
+}
+
+// the adjoint correlation of the value pass's maps, times upstream[0] (DEVICE, NULL = 1)
+void launch_ssim_grad(int C, int H, int W, const float* img1, const float* img2, const float* maps, const float* upstream, float* out_grad,
+                      hipStream_t stream)
+{
+    const size_t CN = (size_t)C * H * W;
+    ssim_backward_kernel<<<ssim_grid(C, H, W), LB, 0, stream>>>(img1, img2, H, W, ssim_window(), maps, maps + CN, maps + 2 * CN, ssim_inv_n(C, H, W),
+                                                                upstream, out_grad);
+}
 }  // namespace
+
+// One call: value and, if out_grad is given, gradient; the maps sit at the front of the scratch, then the partials.
+extern "C" int hsr_loss_ssim(int C, int H, int W, const float* img1, const float* img2, float* out_ssim, float* out_grad, char* scratch,
+                             size_t scratch_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (C < 1 || H < 1 || W < 1 || !img1 || !img2 || !out_ssim) {
+        hsr_set_error("loss_ssim: invalid sizes C=%d H=%d W=%d or NULL img1/img2/out_ssim", C, H, W);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    const dim3 grid = ssim_grid(C, H, W);
+    const size_t map_bytes = out_grad ? align256((size_t)C * H * W * sizeof(float) * 3) : 0;
+    int rc = check_scratch("loss_ssim", scratch, scratch_bytes, map_bytes + align256((size_t)grid.x * grid.y * C * sizeof(float)));
+    if (rc != HSR_OK) return rc;
+    float* maps = out_grad ? reinterpret_cast<float*>(scratch) : nullptr;
+    launch_ssim_value(C, H, W, img1, img2, maps, reinterpret_cast<float*>(scratch + map_bytes), out_ssim, stream);
+    if (out_grad) launch_ssim_grad(C, H, W, img1, img2, maps, nullptr, out_grad, stream);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}
 
 // Two-pass form for an autograd node: the value pass leaves the three partial-derivative maps in `maps` (3 * C * H * W floats, the
 // caller's: they must live until the gradient pass), the gradient pass is the adjoint correlation times the upstream gradient.
 extern "C" int hsr_loss_ssim_value(int C, int H, int W, const float* img1, const float* img2, float* out_ssim, float* maps, char* scratch,
                                    size_t scratch_bytes, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (C < 1 || H < 1 || W < 1 || !img1 || !img2 || !out_ssim) {
         hsr_set_error("loss_ssim_value: invalid sizes C=%d H=%d W=%d or NULL img1/img2/out_ssim", C, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const size_t N = (size_t)H * W;
-    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
-    const size_t tiles = (size_t)grid.x * grid.y * C;
-    int rc = check_scratch("loss_ssim_value", scratch, scratch_bytes, align256(tiles * sizeof(float)));
+    const dim3 grid = ssim_grid(C, H, W);
+    int rc = check_scratch("loss_ssim_value", scratch, scratch_bytes, align256((size_t)grid.x * grid.y * C * sizeof(float)));
     if (rc != HSR_OK) return rc;
-    float* partials = reinterpret_cast<float*>(scratch);
-    const float inv_n = (float)(1.0 / ((double)C * (double)N));
-    ssim_forward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, ssim_window(), maps, maps ? maps + (size_t)C * N : nullptr,
-                                                 maps ? maps + 2 * (size_t)C * N : nullptr, partials);
-    finish_kernel<<<1, LB, 0, stream>>>(partials, (int)tiles, 1, 1, nullptr, inv_n, out_ssim);
+    launch_ssim_value(C, H, W, img1, img2, maps, reinterpret_cast<float*>(scratch), out_ssim, (hipStream_t)stream_);
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
@@ -1012,16 +858,11 @@ extern "C" int hsr_loss_ssim_value(int C, int H, int W, const float* img1, const
 extern "C" int hsr_loss_ssim_grad(int C, int H, int W, const float* img1, const float* img2, const float* maps, const float* upstream,
                                   float* out_grad, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (C < 1 || H < 1 || W < 1 || !img1 || !img2 || !maps || !out_grad) {
         hsr_set_error("loss_ssim_grad: invalid sizes C=%d H=%d W=%d or NULL img1/img2/maps/out_grad", C, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const size_t N = (size_t)H * W;
-    const dim3 grid((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C);
-    const float inv_n = (float)(1.0 / ((double)C * (double)N));
-    ssim_backward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, ssim_window(), maps, maps + (size_t)C * N, maps + 2 * (size_t)C * N, inv_n,
-                                                  upstream, out_grad);
+    launch_ssim_grad(C, H, W, img1, img2, maps, upstream, out_grad, (hipStream_t)stream_);
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
@@ -1061,52 +902,6 @@ extern "C" int hsr_loss_l1_grad(int C, int H, int W, const float* pred, const fl
     return HSR_OK;
 }
 
-extern "C" int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight,
-                                const float* logits, const int64_t* labels, int ignore_index, float* out_level_loss, float* out_grad,
-                                char* scratch, size_t scratch_bytes, void* stream_)
-{
-    hipStream_t stream = (hipStream_t)stream_;
-    if (K < 1 || H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !logits || !labels || !out_level_loss || !level_sizes) {
-        hsr_set_error("loss_tree_ce: invalid sizes K=%d H=%d W=%d or NULL logits/labels/level_sizes/out_level_loss", K, H, W);
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    if (num_levels < 1 || num_levels > HSR_LOSS_MAX_LEVELS) {
-        hsr_set_error("loss_tree_ce: num_levels=%d outside [1, %d]", num_levels, HSR_LOSS_MAX_LEVELS);
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    Levels lv;
-    lv.n = num_levels;
-    int begin = 0;
-    for (int l = 0; l < num_levels; l++) {
-        if (level_sizes[l] < 1) {
-            hsr_set_error("loss_tree_ce: level %d has %d classes", l, level_sizes[l]);
-            return HSR_ERR_INVALID_ARGUMENT;
-        }
-        lv.begin[l] = begin;
-        lv.size[l] = level_sizes[l];
-        lv.weight[l] = level_weight ? level_weight[l] : 1.0f;
-        begin += level_sizes[l];
-    }
-    if (begin > K) {
-        hsr_set_error("loss_tree_ce: levels cover %d channels but the map has K=%d", begin, K);  // the reference would slice short
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    const int N = H * W;
-    const int nb = (N + LB - 1) / LB;
-    const size_t part_bytes = align256((size_t)nb * HSR_LOSS_MAX_LEVELS * sizeof(float));
-    int rc = check_scratch("loss_tree_ce", scratch, scratch_bytes, 2 * part_bytes + 256);
-    if (rc != HSR_OK) return rc;
-    float* partials = reinterpret_cast<float*>(scratch);
-    unsigned* cparts = reinterpret_cast<unsigned*>(scratch + part_bytes);
-    float* inv = reinterpret_cast<float*>(scratch + 2 * part_bytes);
-    ce_count_kernel<<<nb, LB, 0, stream>>>(labels, N, num_levels, ignore_index, cparts);
-    count_finish_kernel<<<1, LB, 0, stream>>>(cparts, nb, HSR_LOSS_MAX_LEVELS, num_levels, inv);
-    tree_ce_kernel<<<nb, LB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, inv, out_grad, partials);
-    finish_kernel<<<1, LB, 0, stream>>>(partials, nb, HSR_LOSS_MAX_LEVELS, num_levels, inv, 1.0f, out_level_loss);
-    HSR_HIP_CHECK(hipGetLastError());
-    return HSR_OK;
-}
-
 namespace {
 int parse_levels(const char* who, int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight, Levels* lv)
 {
@@ -1137,6 +932,34 @@ int parse_levels(const char* who, int K, int H, int W, int num_levels, const int
     return HSR_OK;
 }
 }  // namespace
+
+extern "C" int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight,
+                                const float* logits, const int64_t* labels, int ignore_index, float* out_level_loss, float* out_grad,
+                                char* scratch, size_t scratch_bytes, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    Levels lv;
+    int rc = parse_levels("loss_tree_ce", K, H, W, num_levels, level_sizes, level_weight, &lv);
+    if (rc != HSR_OK) return rc;
+    if (!logits || !labels || !out_level_loss) {
+        hsr_set_error("loss_tree_ce: NULL logits / labels / out_level_loss");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    const int N = H * W;
+    const int nb = (N + LB - 1) / LB;
+    const size_t part_bytes = align256((size_t)nb * HSR_LOSS_MAX_LEVELS * sizeof(float));
+    rc = check_scratch("loss_tree_ce", scratch, scratch_bytes, 2 * part_bytes + 256);
+    if (rc != HSR_OK) return rc;
+    float* partials = reinterpret_cast<float*>(scratch);
+    unsigned* cparts = reinterpret_cast<unsigned*>(scratch + part_bytes);
+    float* inv = reinterpret_cast<float*>(scratch + 2 * part_bytes);
+    ce_count_kernel<<<nb, LB, 0, stream>>>(labels, N, num_levels, ignore_index, cparts);
+    count_finish_kernel<<<1, LB, 0, stream>>>(cparts, nb, HSR_LOSS_MAX_LEVELS, num_levels, inv);
+    tree_ce_kernel<<<nb, LB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, inv, out_grad, partials);
+    finish_kernel<<<1, LB, 0, stream>>>(partials, nb, HSR_LOSS_MAX_LEVELS, num_levels, inv, 1.0f, out_level_loss);
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}
 
 extern "C" size_t hsr_loss_tree_ce_scratch_bytes(int H, int W)
 {
@@ -1207,23 +1030,19 @@ extern "C" int hsr_loss_leaf_mlp_ce(int K, int C, int H, int W, const float* sem
     const int CT = (C + 15) / 16;
     int nblk = (N + 255) / 256;
     if (nblk > LM_MAX_BLOCKS) nblk = LM_MAX_BLOCKS;
-    const int nb_cnt = (N + LB * L1_ITEMS - 1) / (LB * L1_ITEMS);
-    // scratch: packed weights [CT*16][32] | inv count | count partials | loss partials | dW partials [nblk][CT*16*32]
+    // scratch: packed weights [CT*16][32] | inv count | loss partials | dW partials [nblk][CT*16*32]
     const size_t wt_bytes = align256((size_t)CT * 16 * LM_KP * sizeof(float));
-    const size_t cnt_bytes = align256((size_t)nb_cnt * sizeof(unsigned));
     const size_t loss_bytes = align256((size_t)nblk * sizeof(float));
     const size_t dw_bytes = (size_t)nblk * CT * 16 * LM_KP * sizeof(float);
-    int rc = check_scratch("loss_leaf_mlp_ce", scratch, scratch_bytes, wt_bytes + 256 + cnt_bytes + loss_bytes + dw_bytes);
+    int rc = check_scratch("loss_leaf_mlp_ce", scratch, scratch_bytes, wt_bytes + 256 + loss_bytes + dw_bytes);
     if (rc != HSR_OK) return rc;
     float* wt = reinterpret_cast<float*>(scratch);
     float* inv = reinterpret_cast<float*>(scratch + wt_bytes);
-    unsigned* cparts = reinterpret_cast<unsigned*>(scratch + wt_bytes + 256);
-    float* part_loss = reinterpret_cast<float*>(scratch + wt_bytes + 256 + cnt_bytes);
-    float* part_dw = reinterpret_cast<float*>(scratch + wt_bytes + 256 + cnt_bytes + loss_bytes);
+    float* part_loss = reinterpret_cast<float*>(scratch + wt_bytes + 256);
+    float* part_dw = reinterpret_cast<float*>(scratch + wt_bytes + 256 + loss_bytes);
     leaf_pack_weights_kernel<<<(CT * 16 * LM_KP + 255) / 256, 256, 0, stream>>>(weight, bias, K, C, CT * 16, wt);
     ce_count_kernel<<<(N + LB - 1) / LB, LB, 0, stream>>>(labels, N, 1, ignore_index, reinterpret_cast<unsigned*>(part_dw));
     count_finish_kernel<<<1, LB, 0, stream>>>(reinterpret_cast<unsigned*>(part_dw), (N + LB - 1) / LB, HSR_LOSS_MAX_LEVELS, 1, inv);
-    (void)cparts;
     const int ku = (K + 1 + 3) & ~3;
 #define HSR_LEAF_LAUNCH(KU_, MC_) leaf_mlp_ce_kernel<KU_, MC_><<<nblk, 256, 0, stream>>>(sem, wt, labels, N, K, C, CT, ignore_index, inv, d_sem, part_loss, part_dw)
     if (CT <= 3) {         // <= 48 classes (NYU40 + void)

@@ -204,9 +204,15 @@ def weighted_sum(terms, weights, constant=0.0):
     return _WeightedSum.apply(_weight_cache[key], *terms)
 
 
-class _TrackingLoss(torch.autograd.Function):
+class _MaskedLoss(torch.autograd.Function):
+    """The masked depth and colour terms as one node (include/hsr_losses.h, hsr_loss_tracking_*).  reject: with the reference's
+    ignore_outlier_depth_loss mask (include/ext/hsr_loss_outlier.h): the value pass finds the exact median of the depth error on the device
+    (three histogram passes, no sort, no host read) and sums the masked terms; the gradient pass, when autograd asks, recomputes the mask from
+    the threshold the value pass left in device memory.  No mask tensor.  Returns (total, [depth term, colour term]) and with reject also
+    [median, threshold] and the number of selected pixels."""
+
     @staticmethod
-    def forward(ctx, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, w_depth, w_im, reduction):
+    def forward(ctx, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, w_depth, w_im, reduction, reject):
         d, gd = _chw(depth, "depth"), _chw(gt_depth.detach(), "gt_depth")
         if im is None:      # depth term alone (the mapping branch)
             a = b = None
@@ -215,100 +221,49 @@ class _TrackingLoss(torch.autograd.Function):
             a, b = _chw(im, "im"), _chw(gt_im.detach(), "gt_im")
             Cc, H, W = a.shape
         if (a is not None and b.shape != a.shape) or d.numel() != H * W or gd.numel() != H * W:
-            raise RuntimeError("hsr_utils.losses: tracking_loss wants im / gt_im [C,H,W] and depth / gt_depth [1,H,W] of one size")
+            raise RuntimeError("hsr_utils.losses: the outlier-rejecting loss wants im / gt_im [3,H,W] and depth / gt_depth [1,H,W] of one size" if reject
+                               else "hsr_utils.losses: tracking_loss wants im / gt_im [C,H,W] and depth / gt_depth [1,H,W] of one size")
         s = None
         if use_sil:
             s = _chw(silhouette.detach(), "silhouette")
             if s.numel() != H * W:
                 raise RuntimeError("hsr_utils.losses: silhouette must be [1,H,W] like the depth map")
         dev = d.device
-        out = torch.empty(4, dtype=torch.float32, device=dev)
-        sc = torch.empty(int(_lib.hsr_loss_tracking_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-        _abi.call(_lib.hsr_loss_tracking_value, "hsr_loss_tracking_value", dev, Cc, H, W, None if a is None else a.data_ptr(),
+        head = "hsr_loss_outlier" if reject else "hsr_loss_tracking"      # looked up on _abi.lib at call time
+        out = torch.empty(6 if reject else 4, dtype=torch.float32, device=dev)
+        selected = torch.empty(1, dtype=torch.int32, device=dev) if reject else None
+        sc = torch.empty(int(getattr(_abi.lib, head + "_scratch_bytes")(H, W)), dtype=torch.uint8, device=dev)
+        _abi.call(getattr(_abi.lib, head + "_value"), head + "_value", dev, Cc, H, W, None if a is None else a.data_ptr(),
                   None if b is None else b.data_ptr(), d.data_ptr(), gd.data_ptr(), None if s is None else s.data_ptr(), float(sil_thres),
-                  int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(), sc.data_ptr(), sc.numel())
+                  int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(),
+                  *((selected.data_ptr(),) if reject else ()), sc.data_ptr(), sc.numel())
         ctx.want = (bool(im is not None and im.requires_grad), bool(depth.requires_grad))
         if any(ctx.want):
             e = torch.empty(0, device=dev)
             ctx.save_for_backward(a if a is not None else e, b if b is not None else e, d, gd, s if s is not None else e, out)
             ctx.meta = (Cc, H, W, float(sil_thres), int(bool(use_sil)), float(w_depth), float(w_im), None if im is None else tuple(im.shape),
-                        tuple(depth.shape), int(reduction))
+                        tuple(depth.shape), int(reduction), head)
+        extra = (out[4:6].detach(), selected[0]) if reject else ()
         parts = out[:2].detach()
-        ctx.mark_non_differentiable(parts)
-        return out[2], parts
+        ctx.mark_non_differentiable(parts, *extra)
+        return (out[2], parts) + extra
 
     @staticmethod
-    def backward(ctx, g, _g_parts):
+    def backward(ctx, g, *_g_values):
         if g is None or not any(ctx.want):
-            return (None,) * 10
+            return (None,) * 11
         a, b, d, gd, s, out = ctx.saved_tensors
-        Cc, H, W, sil_thres, use_sil, w_depth, w_im, shape_im, shape_d, reduction = ctx.meta
+        Cc, H, W, sil_thres, use_sil, w_depth, w_im, shape_im, shape_d, reduction, head = ctx.meta
         dev = d.device
         gg = g.to(device=dev, dtype=torch.float32).contiguous()
         d_im = torch.empty_like(a) if ctx.want[0] else None
         d_d = torch.empty_like(d) if ctx.want[1] else None
-        inv_ptr = out.data_ptr() + 12 if reduction == MEAN else None     # &out4[3]: 1 / selected pixels
-        _abi.call(_lib.hsr_loss_tracking_grad, "hsr_loss_tracking_grad", dev, Cc, H, W, a.data_ptr() if Cc else None,
+        inv_ptr = out.data_ptr() + 12 if reduction == MEAN else None     # &out[3]: 1 / selected pixels
+        thr = (out.data_ptr() + 20,) if out.numel() == 6 else ()         # &out6[5]: the threshold of the value pass
+        _abi.call(getattr(_abi.lib, head + "_grad"), head + "_grad", dev, Cc, H, W, a.data_ptr() if Cc else None,
                   b.data_ptr() if Cc else None, d.data_ptr(), gd.data_ptr(), s.data_ptr() if use_sil else None, sil_thres, use_sil, w_depth,
-                  w_im, gg.data_ptr(), inv_ptr, None if d_im is None else d_im.data_ptr(), None if d_d is None else d_d.data_ptr())
-        return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d), None, None, None, None, None, None, None)
-
-
-class _OutlierLoss(torch.autograd.Function):
-    """_TrackingLoss with the reference's ignore_outlier_depth_loss mask (include/ext/hsr_loss_outlier.h): the value pass finds the exact
-    median of the depth error on the device (three histogram passes, no sort, no host read) and sums the masked terms; the gradient pass,
-    when autograd asks, recomputes the mask from the threshold the value pass left in device memory.  No mask tensor."""
-
-    @staticmethod
-    def forward(ctx, im, gt_im, depth, gt_depth, silhouette, sil_thres, use_sil, w_depth, w_im, reduction):
-        d, gd = _chw(depth, "depth"), _chw(gt_depth.detach(), "gt_depth")
-        if im is None:      # depth term alone (the mapping branch)
-            a = b = None
-            Cc, (H, W) = 0, d.shape[-2:]
-        else:
-            a, b = _chw(im, "im"), _chw(gt_im.detach(), "gt_im")
-            Cc, H, W = a.shape
-        if (a is not None and b.shape != a.shape) or d.numel() != H * W or gd.numel() != H * W:
-            raise RuntimeError("hsr_utils.losses: the outlier-rejecting loss wants im / gt_im [3,H,W] and depth / gt_depth [1,H,W] of one size")
-        s = None
-        if use_sil:
-            s = _chw(silhouette.detach(), "silhouette")
-            if s.numel() != H * W:
-                raise RuntimeError("hsr_utils.losses: silhouette must be [1,H,W] like the depth map")
-        dev = d.device
-        out = torch.empty(6, dtype=torch.float32, device=dev)
-        selected = torch.empty(1, dtype=torch.int32, device=dev)
-        sc = torch.empty(int(_lib.hsr_loss_outlier_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-        _abi.call(_abi.lib.hsr_loss_outlier_value, "hsr_loss_outlier_value", dev, Cc, H, W, None if a is None else a.data_ptr(),
-                  None if b is None else b.data_ptr(), d.data_ptr(), gd.data_ptr(), None if s is None else s.data_ptr(), float(sil_thres),
-                  int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(), selected.data_ptr(), sc.data_ptr(),
-                  sc.numel())
-        ctx.want = (bool(im is not None and im.requires_grad), bool(depth.requires_grad))
-        if any(ctx.want):
-            e = torch.empty(0, device=dev)
-            ctx.save_for_backward(a if a is not None else e, b if b is not None else e, d, gd, s if s is not None else e, out)
-            ctx.meta = (Cc, H, W, float(sil_thres), int(bool(use_sil)), float(w_depth), float(w_im), None if im is None else tuple(im.shape),
-                        tuple(depth.shape), int(reduction))
-        parts, stats, count = out[:2].detach(), out[4:6].detach(), selected[0]
-        ctx.mark_non_differentiable(parts, stats, count)
-        return out[2], parts, stats, count
-
-    @staticmethod
-    def backward(ctx, g, _g_parts, _g_stats, _g_count):
-        if g is None or not any(ctx.want):
-            return (None,) * 10
-        a, b, d, gd, s, out = ctx.saved_tensors
-        Cc, H, W, sil_thres, use_sil, w_depth, w_im, shape_im, shape_d, reduction = ctx.meta
-        dev = d.device
-        gg = g.to(device=dev, dtype=torch.float32).contiguous()
-        d_im = torch.empty_like(a) if ctx.want[0] else None
-        d_d = torch.empty_like(d) if ctx.want[1] else None
-        inv_ptr = out.data_ptr() + 12 if reduction == MEAN else None     # &out6[3]: 1 / selected pixels
-        _abi.call(_abi.lib.hsr_loss_outlier_grad, "hsr_loss_outlier_grad", dev, Cc, H, W, a.data_ptr() if Cc else None,
-                  b.data_ptr() if Cc else None, d.data_ptr(), gd.data_ptr(), s.data_ptr() if use_sil else None, sil_thres, use_sil, w_depth,
-                  w_im, out.data_ptr() + 20, gg.data_ptr(), inv_ptr, None if d_im is None else d_im.data_ptr(),
-                  None if d_d is None else d_d.data_ptr())
-        return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d), None, None, None, None, None, None, None)
+                  w_im, *thr, gg.data_ptr(), inv_ptr, None if d_im is None else d_im.data_ptr(), None if d_d is None else d_d.data_ptr())
+        return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d)) + (None,) * 8
 
 
 def depth_error_median(depth, gt_depth):
@@ -342,16 +297,12 @@ def tracking_loss(im, gt_im, depth, gt_depth, silhouette=None, sil_thres=0.99, u
     lw = loss_weights or {"im": 0.5, "depth": 1.0}
     if use_sil_for_loss and silhouette is None:
         raise RuntimeError("hsr_utils.losses: tracking_loss with use_sil_for_loss needs the rendered silhouette / final opacity map")
-    if ignore_outlier_depth_loss:
-        total, parts, _stats, count = _OutlierLoss.apply(im, gt_im, depth, gt_depth, silhouette, float(sil_thres), bool(use_sil_for_loss),
-                                                         float(lw["depth"]), float(lw["im"]), SUM)
-        out = (total,) + ((parts,) if return_parts else ()) + ((count,) if return_selected else ())
-        return out if len(out) > 1 else total
-    if return_selected:
+    if return_selected and not ignore_outlier_depth_loss:
         raise RuntimeError("hsr_utils.losses: tracking_loss counts the selected pixels only with ignore_outlier_depth_loss")
-    total, parts = _TrackingLoss.apply(im, gt_im, depth, gt_depth, silhouette, float(sil_thres), bool(use_sil_for_loss), float(lw["depth"]),
-                                       float(lw["im"]), SUM)
-    return (total, parts) if return_parts else total
+    res = _MaskedLoss.apply(im, gt_im, depth, gt_depth, silhouette, float(sil_thres), bool(use_sil_for_loss), float(lw["depth"]),
+                            float(lw["im"]), SUM, bool(ignore_outlier_depth_loss))
+    out = (res[0],) + ((res[1],) if return_parts else ()) + ((res[3],) if return_selected else ())
+    return out if len(out) > 1 else res[0]
 
 
 def mapping_depth_loss(depth, gt_depth, ignore_outlier_depth_loss=False):
@@ -359,10 +310,7 @@ def mapping_depth_loss(depth, gt_depth, ignore_outlier_depth_loss=False):
     torch.abs(gt_depth - depth)[(gt_depth > 0) & ~isnan(depth)].mean()  — mask, count and mean in one pass, the gradient in a second when
     autograd asks (no mask tensor, no count pre-pass).  ignore_outlier_depth_loss (:910-913): the mask additionally keeps only the pixels
     whose depth error is below 10 times its median (the fused outlier-rejecting head, include/ext/hsr_loss_outlier.h)."""
-    if ignore_outlier_depth_loss:
-        return _OutlierLoss.apply(None, None, depth, gt_depth, None, 0.0, False, 1.0, 0.0, MEAN)[0]
-    total, _parts = _TrackingLoss.apply(None, None, depth, gt_depth, None, 0.0, False, 1.0, 0.0, MEAN)
-    return total
+    return _MaskedLoss.apply(None, None, depth, gt_depth, None, 0.0, False, 1.0, 0.0, MEAN, bool(ignore_outlier_depth_loss))[0]
 
 
 def l1_loss_v1(x, y):

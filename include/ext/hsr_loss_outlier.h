@@ -9,8 +9,8 @@
  * counted set (tests/test_abi.py); this one is bound from a table of its own, diff_gaussian_rasterization/_abi.py
  * SIGNATURES_EXT_LOSS_OUTLIER.  HSR_LOSS_SUM / HSR_LOSS_MEAN are those of hsr_losses.h.
  *
- * ERROR (:911).  e = fabsf(gt - d) * (gt > 0 ? 1.f : 0.f), in fp32, in that order, without contraction (the file is compiled with
- * -ffp-contract=off).  NaN and inf travel as in torch: inf * 0 is NaN, and a NaN depth under a hole (gt <= 0) is still a NaN error.
+ * ERROR (:911).  e = fabsf(gt - d) * (gt > 0 ? 1.f : 0.f), in fp32, in that order, without contraction (csrc/hsr_loss_masked.hip, which
+ * also holds hsr_loss_tracking_* of hsr_losses.h, is compiled with -ffp-contract=off).  NaN and inf travel as in torch: inf * 0 is NaN, and a NaN depth under a hole (gt <= 0) is still a NaN error.
  * fp32 denormals are kept, not flushed.  e is never negative, so its 32 bits order as an unsigned integer.
  *
  * MEDIAN (:912).  torch.median of all n = H * W errors: NaN if any e is NaN; otherwise the element of 0-based rank (n - 1) / 2

@@ -50,7 +50,9 @@ int hsr_loss_l1(int C, int H, int W, const float* pred, const float* gt, const u
  * reduction HSR_LOSS_MEAN: the mapping branch's depth term, torch.abs(gt_depth - depth)[mask].mean() with mask = (gt_depth > 0) &
  * ~isnan(depth) (scripts/hierslam.py:927; use_sil = 0 there, C = 0 skips the colour term: im / gt_im / d_im NULL) — the gradient pass
  * then takes `inv_count` = &out4[3] of the value pass (NULL for sums).
- * im / gt_im: [C,H,W]; depth / gt_depth / silhouette: [H,W].  Scratch: hsr_loss_tracking_scratch_bytes(H, W). */
+ * im / gt_im: [C,H,W]; depth / gt_depth / silhouette: [H,W].  Scratch: hsr_loss_tracking_scratch_bytes(H, W).
+ * These three live in csrc/hsr_loss_masked.hip (compiled with -ffp-contract=off), beside the outlier-rejecting head of
+ * include/ext/hsr_loss_outlier.h, which adds one factor to this mask; every other entry point here is in csrc/hsr_losses.hip. */
 size_t hsr_loss_tracking_scratch_bytes(int H, int W);
 int hsr_loss_tracking_value(int C, int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
                             const float* silhouette, float sil_thres, int use_sil, int reduction, float w_depth, float w_im, float* out4,

@@ -7,6 +7,8 @@ CPU: the oracle of include/ext/hsr_loss_outlier.h (tests/test_loss_outlier_cpu.p
     mask = mask & ~torch.isnan(depth)  [& (silhouette > sil_thres)]                     :909, :916-919
     losses['depth'] = torch.abs(curr_data['depth'] - depth)[mask].sum() | .mean()       :925 (tracking) | :927 (mapping)
     losses['im'] = torch.abs(curr_data['im'] - im)[torch.tile(mask, (3, 1, 1))].sum()   :932-935 (tracking, with the flag on: always masked)
+
+reject=False leaves the factor of :912 out of the mask (median and threshold are still reported): the mask of hsr_loss_tracking_* (include/hsr_losses.h).
 """
 import torch
 
@@ -22,21 +24,23 @@ def rank_rule(values):
     return v.sort().values[(v.numel() - 1) // 2]
 
 
-def outlier_mask(depth, gt_depth, silhouette=None, sil_thres=0.99):
+def outlier_mask(depth, gt_depth, silhouette=None, sil_thres=0.99, reject=True):
     """(median, threshold, mask) of :909-919 for fp32 [H,W] maps; median and threshold are fp32 0-dim tensors as torch computes them"""
     err = torch.abs(gt_depth - depth) * (gt_depth > 0)
     median = err.median()
     threshold = 10 * median
-    mask = (err < threshold) & (gt_depth > 0) & ~torch.isnan(depth)
+    mask = (gt_depth > 0) & ~torch.isnan(depth)
+    if reject:
+        mask = (err < threshold) & mask
     if silhouette is not None:
         mask = mask & (silhouette > sil_thres)
     return median, threshold, mask.detach()
 
 
-def outlier_ref(depth, gt_depth, im=None, gt_im=None, silhouette=None, sil_thres=0.99):
+def outlier_ref(depth, gt_depth, im=None, gt_im=None, silhouette=None, sil_thres=0.99, reject=True):
     """median, threshold, mask, and both terms summed in float64 over that mask (from the fp32 inputs); `count` selected pixels.
     depth / gt_depth / silhouette: [H,W]; im / gt_im: [3,H,W] or None"""
-    median, threshold, mask = outlier_mask(depth, gt_depth, silhouette, sil_thres)
+    median, threshold, mask = outlier_mask(depth, gt_depth, silhouette, sil_thres, reject)
     out = {"median": median, "threshold": threshold, "mask": mask, "count": int(mask.sum()),
            "depth_sum": float((gt_depth.double() - depth.double()).abs()[mask].sum())}
     if im is not None:
@@ -44,20 +48,20 @@ def outlier_ref(depth, gt_depth, im=None, gt_im=None, silhouette=None, sil_thres
     return out
 
 
-def autograd_tracking(depth, gt_depth, im, gt_im, silhouette, sil_thres, upstream):
+def autograd_tracking(depth, gt_depth, im, gt_im, silhouette, sil_thres, upstream, reject=True):
     """torch autograd of the tracking form (:925, :935, weights W_DEPTH / W_IM) in fp32: (d loss / d im, d loss / d depth) of
     upstream * loss.  Where the depth is NaN torch's abs backward gives 0 * sign(NaN) = NaN off the mask; the caller decides."""
     d, a = depth.clone().requires_grad_(True), im.clone().requires_grad_(True)
-    _m, _t, mask = outlier_mask(d.detach(), gt_depth, silhouette, sil_thres)
+    _m, _t, mask = outlier_mask(d.detach(), gt_depth, silhouette, sil_thres, reject)
     loss = W_DEPTH * torch.abs(gt_depth - d)[mask].sum() + W_IM * torch.abs(gt_im - a)[torch.tile(mask[None], (3, 1, 1))].sum()
     (loss * upstream).backward()
     return a.grad, d.grad
 
 
-def autograd_mapping(depth, gt_depth, upstream):
+def autograd_mapping(depth, gt_depth, upstream, reject=True):
     """torch autograd of the mapping form's depth term (:927) in fp32: (mean, d (upstream * mean) / d depth)"""
     d = depth.clone().requires_grad_(True)
-    _m, _t, mask = outlier_mask(d.detach(), gt_depth)
+    _m, _t, mask = outlier_mask(d.detach(), gt_depth, reject=reject)
     loss = torch.abs(gt_depth - d)[mask].mean()
     (loss * upstream).backward()
     return loss.detach(), d.grad

@@ -9,6 +9,9 @@ The oracle of every case is tests/outlier_ref.py (scripts/hierslam.py:909-937 re
     MEAN gradients           within 1 ulp of torch autograd (the head multiplies by 1 / selected, torch divides by selected)
     gradient off the mask    0
 Each case runs in tracking form (C = 3, SUM, silhouette on and off) and in mapping form (C = 0, MEAN), with the upstream gradient 1 and 0.37.
+Each case and form also runs through the plain head (hsr_loss_tracking_*, the keyword off) against the restatement without the factor of
+:912, under the same bounds: the two heads are one set of kernels (hsr_loss_masked.hip).  A reference sum that is not finite (an infinite
+depth on a valid pixel, which only the plain mask selects) must be met by the same non-finite value.
 The cases are the smallest shapes at which the selection can go wrong; they are listed at CASES.  The largest distances of the first MI355X
 run are in profiles/loss_outlier_gpu.log."""
 import functools
@@ -96,8 +99,13 @@ CASES = {
     "129x67": lambda: _noisy(129, 67, seed=8),
     # many workgroups, a non-trivial bin in all three passes
     "340x600": lambda: _noisy(340, 600, seed=9, holes=0.03),
+    # one partial per 1024 pixels; the finish kernel's 256 threads take a second trip from 257 partials on: H * W > 256 * 1024 = 262 144
+    "513x512": lambda: _noisy(513, 512, seed=10),
+    # the outlier head's grid stops at 512 workgroups and strides from H * W > 512 * 1024 = 524 288 on (the plain head's does not stop)
+    "725x724": lambda: _noisy(725, 724, seed=11),
 }
 FORMS = ["tracking_sil", "tracking_nosil", "mapping"]
+PIXELS_PER_PARTIAL, FINISH_THREADS, OUTLIER_GRID_CAP = 1024, 256, 512
 
 
 @functools.lru_cache(maxsize=None)
@@ -114,9 +122,9 @@ def _inputs(case):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(case, use_sil):
+def _reference(case, use_sil, reject=True):
     depth, gt, im, gt_im, sil = _inputs(case)
-    return R.outlier_ref(depth, gt, im, gt_im, sil if use_sil else None, SIL_THRES)
+    return R.outlier_ref(depth, gt, im, gt_im, sil if use_sil else None, SIL_THRES, reject)
 
 
 def _bits(t):
@@ -138,32 +146,38 @@ def _ulps(a, b):
 
 
 def _within(got, ref):
+    """within VAL_TOL of a finite reference; a reference that is not finite must be met by the same value (NaN by NaN)"""
+    if ref != ref or abs(ref) == INF:
+        return got == ref or (got != got and ref != ref)
     return abs(got - ref) <= VAL_TOL * abs(ref)
 
 
-def _raw_value(case, form, scratch=None):
-    """hsr_loss_outlier_value through the C ABI: (out6, selected) as CPU tensors"""
+def _raw_value(case, form, scratch=None, reject=True):
+    """hsr_loss_outlier_value through the C ABI: (out6, selected) as CPU tensors; reject=False: hsr_loss_tracking_value, (out4, None)"""
     from diff_gaussian_rasterization import _abi
     depth, gt, im, gt_im, sil = (t.cuda() for t in _inputs(case))
     H, W = depth.shape
     tracking, use_sil = form != "mapping", form == "tracking_sil"
-    out6 = torch.full((6,), -7.0, device="cuda")
+    head = "hsr_loss_outlier" if reject else "hsr_loss_tracking"
+    out = torch.full((6 if reject else 4,), -7.0, device="cuda")
     sel = torch.full((1,), -7, dtype=torch.int32, device="cuda")
     if scratch is None:
-        scratch = torch.empty(int(_abi.lib.hsr_loss_outlier_scratch_bytes(H, W)), dtype=torch.uint8, device="cuda")
-    _abi.call(_abi.lib.hsr_loss_outlier_value, "hsr_loss_outlier_value", depth.device, 3 if tracking else 0, H, W,
+        scratch = torch.empty(int(getattr(_abi.lib, head + "_scratch_bytes")(H, W)), dtype=torch.uint8, device="cuda")
+    _abi.call(getattr(_abi.lib, head + "_value"), head + "_value", depth.device, 3 if tracking else 0, H, W,
               im.data_ptr() if tracking else None, gt_im.data_ptr() if tracking else None, depth.data_ptr(), gt.data_ptr(),
               sil.data_ptr() if use_sil else None, SIL_THRES, int(use_sil), 0 if tracking else 1, R.W_DEPTH if tracking else 1.0,
-              R.W_IM if tracking else 0.0, out6.data_ptr(), sel.data_ptr(), scratch.data_ptr(), scratch.numel())
+              R.W_IM if tracking else 0.0, out.data_ptr(), *((sel.data_ptr(),) if reject else ()), scratch.data_ptr(), scratch.numel())
     torch.cuda.synchronize()
-    return out6.cpu(), int(sel.cpu())
+    return out.cpu(), int(sel.cpu()) if reject else None
 
 
-def _check_raw(case, form, out6, selected):
-    """the value pass's outputs against the restatement; returns the largest relative distance of the terms"""
-    ref = _reference(case, form == "tracking_sil")
-    assert _same_bits(out6[4], ref["median"]) and _same_bits(out6[5], ref["threshold"]), (case, form, out6[4:], ref["median"], ref["threshold"])
-    assert selected == ref["count"], (case, form, selected, ref["count"])
+def _check_raw(case, form, out6, selected, reject=True):
+    """the value pass's outputs against the restatement; returns the largest relative distance of the terms.  reject=False: out6 is the
+    plain head's out4, which reports neither median nor count (the count is checked through out4[3] = 1 / count, as for both heads)"""
+    ref = _reference(case, form == "tracking_sil", reject)
+    if reject:
+        assert _same_bits(out6[4], ref["median"]) and _same_bits(out6[5], ref["threshold"]), (case, form, out6[4:], ref["median"], ref["threshold"])
+        assert selected == ref["count"], (case, form, selected, ref["count"])
     n = ref["count"]
     if form == "mapping":
         want = [ref["depth_sum"] / n if n else NAN, 0.0]
@@ -177,30 +191,31 @@ def _check_raw(case, form, out6, selected):
             assert got != got, (case, form, k, got)
             continue
         assert _within(got, w), (case, form, k, got, w)
-        worst = max(worst, abs(got - w) / abs(w) if w else 0.0)
+        worst = max(worst, abs(got - w) / abs(w) if w and abs(w) != INF else 0.0)
     inv = float(out6[3])
     assert inv == float(torch.tensor(1.0) / torch.tensor(float(n))) if n else inv == INF
     return worst
 
 
-@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("form,reject", [pytest.param(f, r, id=f if r else f + "_plain") for r in (True, False) for f in FORMS])
 @pytest.mark.parametrize("case", list(CASES))
-def test_value_and_gradients_equal_the_restatement(case, form):
+def test_value_and_gradients_equal_the_restatement(case, form, reject):
+    """reject: the outlier-rejecting head; without it the plain head (the keyword off) against the restatement without the factor of :912"""
     from hsr_utils import losses as L
     depth, gt, im, gt_im, sil = _inputs(case)
     use_sil = form == "tracking_sil"
-    ref = _reference(case, use_sil)
+    ref = _reference(case, use_sil, reject)
     mask = ref["mask"]
-    worst = _check_raw(case, form, *_raw_value(case, form))
+    worst = _check_raw(case, form, *_raw_value(case, form, reject=reject), reject=reject)
     median, threshold = L.depth_error_median(depth.cuda(), gt.cuda())
     assert _same_bits(median, ref["median"]) and _same_bits(threshold, ref["threshold"])
     worst_ulps = 0
     for up in (1.0, 0.37):
         d = depth.cuda().reshape(1, *depth.shape).requires_grad_(True)
         if form == "mapping":
-            got = L.mapping_depth_loss(d, gt.cuda()[None], ignore_outlier_depth_loss=True)
+            got = L.mapping_depth_loss(d, gt.cuda()[None], ignore_outlier_depth_loss=reject)
             (got * up).backward()
-            want_value, want_d = R.autograd_mapping(depth, gt, up)
+            want_value, want_d = R.autograd_mapping(depth, gt, up, reject)
             g_d = d.grad[0].cpu()
             if ref["count"]:
                 assert _within(float(got.detach()), ref["depth_sum"] / ref["count"])
@@ -210,14 +225,17 @@ def test_value_and_gradients_equal_the_restatement(case, form):
                 assert torch.isnan(got) and torch.isnan(want_value)
         else:
             a = im.cuda().requires_grad_(True)
-            got, parts, count = L.tracking_loss(a, gt_im.cuda(), d, gt.cuda()[None], sil.cuda()[None] if use_sil else None, SIL_THRES, use_sil,
-                                                {"depth": R.W_DEPTH, "im": R.W_IM}, return_parts=True, ignore_outlier_depth_loss=True,
-                                                return_selected=True)
+            res = L.tracking_loss(a, gt_im.cuda(), d, gt.cuda()[None], sil.cuda()[None] if use_sil else None, SIL_THRES, use_sil,
+                                  {"depth": R.W_DEPTH, "im": R.W_IM}, return_parts=True, ignore_outlier_depth_loss=reject, return_selected=reject)
+            got, parts = res[:2]
             (got * up).backward()
-            assert int(count) == ref["count"] and count.dtype == torch.int32 and count.dim() == 0
+            if reject:      # the plain head returns no count
+                count = res[2]
+                assert int(count) == ref["count"] and count.dtype == torch.int32 and count.dim() == 0
+            assert len(res) == (3 if reject else 2)
             assert _within(float(parts[0]), ref["depth_sum"]) and _within(float(parts[1]), ref["colour_sum"])
             assert _within(float(got.detach()), R.W_DEPTH * ref["depth_sum"] + R.W_IM * ref["colour_sum"])
-            want_a, want_d = R.autograd_tracking(depth, gt, im, gt_im, sil if use_sil else None, SIL_THRES, up)
+            want_a, want_d = R.autograd_tracking(depth, gt, im, gt_im, sil if use_sil else None, SIL_THRES, up, reject)
             g_d, g_a = d.grad[0].cpu(), a.grad.cpu()
             assert torch.equal(g_a, want_a) and _ulps(g_a, want_a) == 0, (case, form, up)
             assert torch.equal(g_d, torch.nan_to_num(want_d)) and _ulps(g_d, torch.nan_to_num(want_d)) == 0, (case, form, up)
@@ -225,10 +243,9 @@ def test_value_and_gradients_equal_the_restatement(case, form):
             if ref["count"] > 1:
                 assert g_a[:, mask].any()
         assert not torch.isnan(g_d).any() and not g_d[~mask].any()      # 0 off the mask, whatever the pixel holds
-        if ref["count"]:
-            assert (g_d[mask] != 0).all()                                  # no case has an exact zero of the depth error on its mask
-    print("loss_outlier %s %s: median %.9g selected %d of %d; terms off float64 by %.3g (bound %.1g); mean gradient off torch by %d ulp"
-          % (case, form, float(ref["median"]), ref["count"], mask.numel(), worst, VAL_TOL, worst_ulps))
+        assert torch.equal(g_d != 0, mask & (depth != gt))                  # on the mask: 0 only at an exact zero of the depth error
+    print("loss_outlier %s %s%s: median %.9g selected %d of %d; terms off float64 by %.3g (bound %.1g); mean gradient off torch by %d ulp"
+          % (case, form, "" if reject else " (plain head)", float(ref["median"]), ref["count"], mask.numel(), worst, VAL_TOL, worst_ulps))
 
 
 def test_the_cases_are_what_they_claim():
@@ -254,6 +271,15 @@ def test_the_cases_are_what_they_claim():
     m = int(_bits(ref["340x600"]["median"]))
     assert int((bins >> 21 == m >> 21).sum()) > 1000 and int((bins >> 10 == m >> 10).sum()) > 1      # the rank's bin is shared in every pass
     assert 0.8 * 204000 < ref["340x600"]["count"] < 0.97 * 204000
+    # the smallest H x W of these aspect ratios past the two limits: one row or column less stays at or under them
+    partials = {c: -(-_inputs(c)[0].numel() // PIXELS_PER_PARTIAL) for c in CASES}
+    assert 513 * 512 > FINISH_THREADS * PIXELS_PER_PARTIAL >= 512 * 512 and partials["513x512"] == FINISH_THREADS + 1
+    assert 725 * 724 > OUTLIER_GRID_CAP * PIXELS_PER_PARTIAL >= 724 * 724 and partials["725x724"] == OUTLIER_GRID_CAP + 1
+    assert max(n for c, n in partials.items() if c not in ("513x512", "725x724")) <= FINISH_THREADS      # no other case reaches either
+    # the plain mask keeps what the factor of :912 drops: the pixel of infinite depth (its sums are infinite), the 5 % outliers
+    plain = {c: _reference(c, False, False) for c in ("inf_depth_valid_pixel", "340x600")}
+    assert plain["inf_depth_valid_pixel"]["count"] == 15 and plain["inf_depth_valid_pixel"]["depth_sum"] == INF
+    assert plain["340x600"]["count"] > ref["340x600"]["count"] + 0.03 * 204000
 
 
 def test_scratch_reuse_and_repeat():
