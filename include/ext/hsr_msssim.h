@@ -39,7 +39,18 @@ extern "C" {
  * the score of a channel is prod_s v_s^weight_s and the result the mean over the three channels.
  * out: DEVICE double[HSR_EVAL_MSSSIM_OUT]: out[0] the score; out[1 + (s*3 + c)*2 + {0, 1}] the means of cs and ssim of scale s,
  * channel c BEFORE relu.  min(H, W) < HSR_EVAL_MSSSIM_MIN_SIDE returns HSR_ERR_INVALID_ARGUMENT.
- * Scratch (hsr_eval_msssim_scratch_bytes(H, W)): pyramid levels 1..4 of both images and the per-tile partial sums. */
+ * Scratch (hsr_eval_msssim_scratch_bytes(H, W)): pyramid levels 1..4 of both images and the per-tile partial sums.  The layout is
+ * part of the contract (tests/msssim_ref.py scratch_layout restates it, tests/test_gpu_msssim_tiles.py reads it); with level 0 the
+ * frame itself and h_s = (h_{s-1} + 1) / 2, w_s likewise:
+ *   - from byte 0 the pyramid, fp32: for s = 1..4 in turn the x planes [3][h_s][w_s], then the y planes [3][h_s][w_s]; level s + 1
+ *     is the 2x2 pool of level s evaluated as (((a00 + a01) + a10) + a11) * 0.25f, a_rc the window's row r and column c, each
+ *     operation rounded once;
+ *   - from the next 256-byte boundary the partial sums, double: [scale][tile_y * tiles_x + tile_x][channel][cs, ssim], the scales
+ *     one after the other without gaps, with tiles_x = ceil((w_s - 10) / 32) and tiles_y = ceil((h_s - 10) / 32).  Tile (ty, tx)
+ *     holds the sums of the two maps over rows [32 ty, min(32 ty + 32, h_s - 10)) and columns [32 tx, min(32 tx + 32, w_s - 10));
+ *   - the size is that of the partials rounded up to 256 bytes as well.  Every pyramid pixel and every partial is written by each
+ *     call, whatever the scratch held before, and nothing beyond the size is touched.
+ * The means of `out` are the partials of a scale summed in double and divided by (h_s - 10)(w_s - 10). */
 size_t hsr_eval_msssim_scratch_bytes(int H, int W);
 int hsr_eval_msssim(int H, int W, const float* im, const float* gt_im, const float* gt_depth, const float* final_opacity,
                     float sil_thres, double* out, char* scratch, size_t scratch_bytes, void* stream);
