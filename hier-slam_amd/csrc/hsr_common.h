@@ -249,3 +249,19 @@ int hsr_launch_zero_visible_rows(int P, const int* radii, float* grow, int strid
 #define HSR_ERR_HIP (-3)
 #define HSR_ERR_NO_DEVICE (-4)
 #endif
+
+// ---- host helpers of the frame-sized units' entry points ----
+constexpr size_t hsr_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// a frame the kernels cannot index: an empty side, or more pixels than a 32-bit int counts
+inline bool hsr_bad_frame_size(int H, int W) { return H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu; }
+
+// the one scratch check: `who` is the entry point's name as it begins every message of that entry point
+inline int hsr_check_scratch(const char* who, const char* scratch, size_t have, size_t need, unsigned align = 1)
+{
+    if (!scratch || have < need || (reinterpret_cast<uintptr_t>(scratch) & (align - 1)) != 0) {
+        hsr_set_error("%s: scratch too small: %zu bytes needed, %zu given (or NULL, or not %u-byte aligned)", who, need, have, align);
+        return HSR_ERR_BUFFER_TOO_SMALL;
+    }
+    return HSR_OK;
+}

@@ -7,13 +7,12 @@
 //   emit   : emit_points_kernel — order-preserving compaction (block offset + wave ballot rank), back-projection, colours,
 //            log-scales.  Compiled with -ffp-contract=off: the emitted means are what the rasterizer will bin next.
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/hsr_densify.h"
 
 namespace {
 
 constexpr int DB = 256;
-
-__device__ __forceinline__ float depth_error(float gt, float rd) { return fabsf(gt - rd) * (gt > 0.f ? 1.f : 0.f); }
 
 struct SelectState { unsigned prefix, mask, rank; };   // device scratch: bits fixed so far, their mask, remaining rank
 
@@ -33,7 +32,7 @@ __global__ __launch_bounds__(DB) void select_hist_kernel(const float* __restrict
     const unsigned prefix = st->prefix, mask = st->mask;
     for (int i = blockIdx.x * DB * 8 + threadIdx.x, it = 0; it < 8; it++, i += DB) {
         if (i >= N) break;
-        const unsigned bits = __float_as_uint(depth_error(gt[i], rd[i]));
+        const unsigned bits = __float_as_uint(hsr_depth_error(gt[i], rd[i]));
         if ((bits & mask) == prefix) atomicAdd(&s_h[(bits >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(DB) void select_pick_kernel(SelectState* st, unsign
 
 __device__ __forceinline__ bool non_presence(float sil, float rd, float gt, float sil_thres, float thr)
 {
-    const float derr = depth_error(gt, rd);
+    const float derr = hsr_depth_error(gt, rd);
     const bool by_depth = (rd > gt) && (derr > thr);
     return ((sil < sil_thres) || by_depth) && (gt > 0.f);
 }
@@ -75,45 +74,20 @@ __global__ __launch_bounds__(DB) void mask_count_kernel(const float* __restrict_
     const float thr = depth_factor * __uint_as_float(st->prefix);   // 50 * depth_error.median()
     const bool m = i < N && non_presence(sil[i], rd[i], gt[i], sil_thres, thr);
     if (out_mask && i < N) out_mask[i] = m ? 1 : 0;
-    const unsigned long long b = __ballot(m);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (unsigned)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const unsigned n = hsr_block256_count(m, s_w);
+    if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 
 __global__ __launch_bounds__(1024) void scan_counts_kernel(int nblk, unsigned* __restrict__ counts, int* __restrict__ out_count)
 {
     __shared__ unsigned s_w[17];
-    const int per = (nblk + 1023) / 1024, beg = threadIdx.x * per;
-    unsigned local = 0;
-    for (int k = 0; k < per; k++)
-        if (beg + k < nblk) local += counts[beg + k];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned inc = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned run = 0;
-        for (int k = 0; k < 16; k++) { const unsigned v = s_w[k]; s_w[k] = run; run += v; }
-        s_w[16] = run;
-    }
-    __syncthreads();
-    unsigned run = s_w[w] + inc - local;
-    for (int k = 0; k < per; k++)
-        if (beg + k < nblk) { const unsigned v = counts[beg + k]; counts[beg + k] = run; run += v; }
-    if (threadIdx.x == 0) *out_count = (int)s_w[16];
+    const unsigned total = hsr_block1024_exclusive_scan(nblk, counts, s_w);
+    if (threadIdx.x == 0) *out_count = (int)total;
 }
-
-struct Frame { float fx, fy, cx, cy; };
 
 __global__ __launch_bounds__(DB) void emit_points_kernel(const float* __restrict__ sil, const float* __restrict__ rd,
                                                          const float* __restrict__ gt, const float* __restrict__ color, int W, int N,
-                                                         Frame f, const float* __restrict__ c2w, float sil_thres, float depth_factor,
+                                                         hsr_pinhole f, const float* __restrict__ c2w, float sil_thres, float depth_factor,
                                                          const SelectState* __restrict__ st, const unsigned* __restrict__ offsets,
                                                          int capacity, float* __restrict__ out_means, float* __restrict__ out_rgb,
                                                          float* __restrict__ out_log_scales, float* __restrict__ out_msd)
@@ -123,30 +97,19 @@ __global__ __launch_bounds__(DB) void emit_points_kernel(const float* __restrict
     const float thr = depth_factor * __uint_as_float(st->prefix);
     const float z = i < N ? gt[i] : 0.f;
     const bool m = i < N && non_presence(sil[i], rd[i], z, sil_thres, thr);
-    const unsigned long long b = __ballot(m);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) s_w[w] = (unsigned)__popcll(b);
-    __syncthreads();
+    const unsigned rank = hsr_block_rank<4>(m, s_w);   // holds the barrier: no thread returns before it
     if (!m) return;
-    unsigned pos = offsets[blockIdx.x] + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
-    for (int k = 0; k < w; k++) pos += s_w[k];
+    const unsigned pos = offsets[blockIdx.x] + rank;
     if (pos >= (unsigned)capacity) return;
-    // get_pointcloud (scripts/hierslam.py:153-168): xx = (x - CX)/FX, pts_cam = (xx*z, yy*z, z), pts = (c2w @ [pts_cam, 1])[:3]
     const int py = i / W, px = i - py * W;
-    const float xx = ((float)px - f.cx) / f.fx, yy = ((float)py - f.cy) / f.fy;
-    const float pc0 = xx * z, pc1 = yy * z, pc2 = z;
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        out_means[3 * pos + r] = ((c2w[4 * r] * pc0 + c2w[4 * r + 1] * pc1) + c2w[4 * r + 2] * pc2) + c2w[4 * r + 3] * 1.0f;
+    hsr_backproject((float)px, (float)py, z, f, c2w, out_means + 3 * pos);
 #pragma unroll
     for (int c = 0; c < 3; c++) out_rgb[3 * pos + c] = color[(size_t)c * N + i];
-    const float sg = z / ((f.fx + f.fy) / 2.0f);   // :176-177
+    const float sg = hsr_depth_scale(z, f);
     const float msd = sg * sg;
     if (out_msd) out_msd[pos] = msd;
     out_log_scales[pos] = logf(sqrtf(msd));        // :1157
 }
-
-size_t dalign(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---- prune + concat of the map (utils/slam_external.py:121-188) as ONE order-preserving row compaction --------------------
 // keep mask of prune_gaussians (:175-180): to_remove = sigmoid(logit_opacity) < threshold  |  max_c exp(log_scale_c) > big
@@ -167,19 +130,15 @@ __global__ __launch_bounds__(DB) void prune_mask_kernel(int P, int S, const floa
         k = !rem;
         keep[i] = k ? 1 : 0;
     }
-    const unsigned long long b = __ballot(k);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (unsigned)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const unsigned n = hsr_block256_count(k, s_w);
+    if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 __global__ __launch_bounds__(DB) void count_keep_kernel(int P, const uint8_t* __restrict__ keep, unsigned* __restrict__ counts)
 {
     __shared__ unsigned s_w[4];
     const int i = blockIdx.x * DB + threadIdx.x;
-    const unsigned long long b = __ballot(i < P && keep[i] != 0);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = (unsigned)__popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const unsigned n = hsr_block256_count(i < P && keep[i] != 0, s_w);
+    if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 __global__ void add_int_kernel(int* v, int base, int add, int overwrite) { *v = (overwrite ? base : *v) + add; }
 struct RowTables {
@@ -197,13 +156,9 @@ __global__ __launch_bounds__(DB) void compact_append_kernel(int P, int n_append,
     const int nblk_keep = (P + DB - 1) / DB;
     if ((int)blockIdx.x < nblk_keep) {
         const bool k = i < P && (!keep || keep[i] != 0);
-        const unsigned long long b = __ballot(k);
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        if (lane == 0) s_w[w] = (unsigned)__popcll(b);
-        __syncthreads();
+        const unsigned rank = hsr_block_rank<4>(k, s_w);   // holds the barrier: no thread of these blocks returns before it
         if (!k) return;
-        size_t pos = (keep ? offsets[blockIdx.x] : (unsigned)(blockIdx.x * DB)) + (unsigned)__popcll(b & ((1ull << lane) - 1ull));
-        for (int q = 0; q < w; q++) pos += s_w[q];
+        const size_t pos = (size_t)(keep ? offsets[blockIdx.x] : (unsigned)(blockIdx.x * DB)) + rank;
         for (int t = 0; t < tb.n; t++) {
             const int C = tb.t[t].cols;
             const float* src = tb.t[t].src + (size_t)i * C;
@@ -228,7 +183,7 @@ __global__ __launch_bounds__(DB) void compact_append_kernel(int P, int n_append,
 extern "C" size_t hsr_compact_scratch_bytes(int P)
 {
     const size_t nblk = ((size_t)(P > 0 ? P : 1) + DB - 1) / DB;
-    return dalign(nblk * sizeof(unsigned)) + 512;
+    return hsr_align256(nblk * sizeof(unsigned)) + 512;
 }
 
 extern "C" int hsr_prune_mask(int P, int S, const float* logit_opacities, const float* log_scales, float removal_opacity_threshold,
@@ -240,10 +195,7 @@ extern "C" int hsr_prune_mask(int P, int S, const float* logit_opacities, const 
         hsr_set_error("prune_mask: invalid arguments (P=%d S=%d)", P, S);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    if (!scratch || scratch_bytes < hsr_compact_scratch_bytes(P)) {
-        hsr_set_error("prune_mask: scratch too small: %zu bytes needed", hsr_compact_scratch_bytes(P));
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
+    if (int rc = hsr_check_scratch("prune_mask", scratch, scratch_bytes, hsr_compact_scratch_bytes(P))) return rc;
     unsigned* counts = reinterpret_cast<unsigned*>(scratch);
     const int nblk = (P + DB - 1) / DB;
     if (P > 0)
@@ -272,10 +224,7 @@ extern "C" int hsr_compact_append_rows(int P, const uint8_t* keep, int keep_is_s
             return HSR_ERR_INVALID_ARGUMENT;
         }
     }
-    if (!scratch || scratch_bytes < hsr_compact_scratch_bytes(P)) {
-        hsr_set_error("compact_append_rows: scratch too small: %zu bytes needed", hsr_compact_scratch_bytes(P));
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
+    if (int rc = hsr_check_scratch("compact_append_rows", scratch, scratch_bytes, hsr_compact_scratch_bytes(P))) return rc;
     unsigned* counts = reinterpret_cast<unsigned*>(scratch);
     const int nblk = (P + DB - 1) / DB;
     if (keep && !keep_is_scanned) {   // a caller-made mask: count and scan it here
@@ -294,7 +243,7 @@ extern "C" size_t hsr_densify_scratch_bytes(int H, int W)
 {
     if (H < 1 || W < 1) return 4096;
     const size_t nblk = ((size_t)H * W + DB - 1) / DB;
-    return 256 + dalign(256 * sizeof(unsigned)) + dalign(nblk * sizeof(unsigned)) + 1024;
+    return 256 + hsr_align256(256 * sizeof(unsigned)) + hsr_align256(nblk * sizeof(unsigned)) + 1024;
 }
 
 extern "C" int hsr_densify_frame(int H, int W, const float* silhouette, const float* render_depth, const float* gt_depth,
@@ -304,7 +253,7 @@ extern "C" int hsr_densify_frame(int H, int W, const float* silhouette, const fl
                                  size_t scratch_bytes, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !silhouette || !render_depth || !gt_depth || !color || !c2w || !out_count) {
+    if (hsr_bad_frame_size(H, W) || !silhouette || !render_depth || !gt_depth || !color || !c2w || !out_count) {
         hsr_set_error("densify_frame: invalid sizes H=%d W=%d or NULL silhouette/render_depth/gt_depth/color/c2w/out_count", H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -312,15 +261,12 @@ extern "C" int hsr_densify_frame(int H, int W, const float* silhouette, const fl
         hsr_set_error("densify_frame: capacity=%d needs out_means3D, out_rgb and out_log_scales", capacity);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    if (!scratch || scratch_bytes < hsr_densify_scratch_bytes(H, W)) {
-        hsr_set_error("densify_frame: scratch too small: %zu bytes needed", hsr_densify_scratch_bytes(H, W));
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
+    if (int rc = hsr_check_scratch("densify_frame", scratch, scratch_bytes, hsr_densify_scratch_bytes(H, W))) return rc;
     const int N = H * W;
     const int nblk = (N + DB - 1) / DB;
     SelectState* st = reinterpret_cast<SelectState*>(scratch);
     unsigned* hist = reinterpret_cast<unsigned*>(scratch + 256);
-    unsigned* counts = reinterpret_cast<unsigned*>(scratch + 256 + dalign(256 * sizeof(unsigned)));
+    unsigned* counts = reinterpret_cast<unsigned*>(scratch + 256 + hsr_align256(256 * sizeof(unsigned)));
     select_init_kernel<<<1, DB, 0, stream>>>(st, N, hist);
     const int hblk = (N + DB * 8 - 1) / (DB * 8);
     for (int shift = 24; shift >= 0; shift -= 8) {
@@ -330,7 +276,7 @@ extern "C" int hsr_densify_frame(int H, int W, const float* silhouette, const fl
     mask_count_kernel<<<nblk, DB, 0, stream>>>(silhouette, render_depth, gt_depth, N, sil_thres, depth_factor, st, counts, out_mask);
     scan_counts_kernel<<<1, 1024, 0, stream>>>(nblk, counts, out_count);
     if (capacity > 0) {
-        Frame f{fx, fy, cx, cy};
+        hsr_pinhole f{fx, fy, cx, cy};
         emit_points_kernel<<<nblk, DB, 0, stream>>>(silhouette, render_depth, gt_depth, color, W, N, f, c2w, sil_thres, depth_factor, st,
                                                     counts, capacity, out_means3D, out_rgb, out_log_scales, out_mean_sq_dist);
     }

@@ -13,6 +13,7 @@
 //     LDS, row-window uniformity by a scan of the LDS row; column pass: a sliding count of label changes down each column, then
 //     per-block LDS histograms (integers: bit-exact in any order) flushed with 64-bit atomics.
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/hsr_eval.h"
 #include <climits>
 #include <cmath>
@@ -28,27 +29,7 @@ constexpr int COL_R = 16;        // column pass: rows per wave strip (4 waves ->
 constexpr int16_t CI_OUT = -1;   // class index of a label in no class
 constexpr int16_t V_MIXED = -2;  // row window not uniform
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-int check_scratch(const char* what, const char* scratch, size_t have, size_t need)
-{
-    if (!scratch || have < need) {
-        hsr_set_error("%s: scratch of %zu bytes is smaller than the %zu needed", what, have, need);
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
-    return HSR_OK;
-}
-
-bool bad_size(int H, int W) { return H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu; }
-
 // ---------------------------------------------------------------- frame metrics
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(EB) void metrics_kernel(const float* __restrict__ im, const float* __restrict__ gt_im,
                                                      const float* __restrict__ depth, const float* __restrict__ gt_depth,
                                                      const float* __restrict__ opac, float sil_thres, int N, double* __restrict__ partials)
@@ -74,17 +55,10 @@ __global__ __launch_bounds__(EB) void metrics_kernel(const float* __restrict__ i
         acc[4] += sqrtf(e * e) * valid;
         acc[5] += valid;
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double accd[MET_PARTS];
 #pragma unroll
-    for (int k = 0; k < MET_PARTS; k++) {
-        const double s = wave_sum_d((double)acc[k]);
-        if (lane == 0) s_red[wv][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < MET_PARTS) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * MET_PARTS + k] = ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k];
-    }
+    for (int k = 0; k < MET_PARTS; k++) accd[k] = (double)acc[k];
+    hsr_block256_sums(accd, s_red, partials + (size_t)blockIdx.x * MET_PARTS);
 }
 
 __global__ __launch_bounds__(EB) void metrics_finish_kernel(const double* __restrict__ partials, int nblocks, int N, double* __restrict__ out3)
@@ -370,9 +344,9 @@ __global__ __launch_bounds__(EB) void miou_kernel(const long long* __restrict__ 
 // ---------------------------------------------------------------- C ABI
 extern "C" size_t hsr_eval_metrics_scratch_bytes(int H, int W)
 {
-    if (bad_size(H, W)) return 1024;
+    if (hsr_bad_frame_size(H, W)) return 1024;
     const size_t nb = ((size_t)H * W + EB * MET_ITEMS - 1) / (EB * MET_ITEMS);
-    return align256(nb * MET_PARTS * sizeof(double));
+    return hsr_align256(nb * MET_PARTS * sizeof(double));
 }
 
 extern "C" int hsr_eval_frame_metrics(int H, int W, const float* im, const float* gt_im, const float* depth, const float* gt_depth,
@@ -380,11 +354,11 @@ extern "C" int hsr_eval_frame_metrics(int H, int W, const float* im, const float
                                       void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (bad_size(H, W) || !im || !gt_im || !depth || !gt_depth || !out3) {
+    if (hsr_bad_frame_size(H, W) || !im || !gt_im || !depth || !gt_depth || !out3) {
         hsr_set_error("eval_frame_metrics: invalid size H=%d W=%d or NULL im / gt_im / depth / gt_depth / out3", H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    int rc = check_scratch("eval_frame_metrics", scratch, scratch_bytes, hsr_eval_metrics_scratch_bytes(H, W));
+    int rc = hsr_check_scratch("eval_frame_metrics", scratch, scratch_bytes, hsr_eval_metrics_scratch_bytes(H, W));
     if (rc != HSR_OK) return rc;
     const int N = H * W;
     const int nb = (N + EB * MET_ITEMS - 1) / (EB * MET_ITEMS);
@@ -398,7 +372,7 @@ extern "C" int hsr_eval_frame_metrics(int H, int W, const float* im, const float
 extern "C" int hsr_eval_labels_flat(int K, int H, int W, const float* logits, int32_t* out_labels, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (bad_size(H, W) || K < 1 || !logits || !out_labels) {
+    if (hsr_bad_frame_size(H, W) || K < 1 || !logits || !out_labels) {
         hsr_set_error("eval_labels_flat: invalid sizes K=%d H=%d W=%d or NULL logits / out_labels", K, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -412,7 +386,7 @@ extern "C" int hsr_eval_labels_tree(int K, int H, int W, int num_levels, const i
                                     const int32_t* tree_table, int32_t* out_labels, int32_t* out_level_labels, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (bad_size(H, W) || K < 1 || num_levels < 1 || num_levels > HSR_EVAL_MAX_LEVELS || !level_sizes || !logits || !tree_table ||
+    if (hsr_bad_frame_size(H, W) || K < 1 || num_levels < 1 || num_levels > HSR_EVAL_MAX_LEVELS || !level_sizes || !logits || !tree_table ||
         !out_labels) {
         hsr_set_error("eval_labels_tree: invalid sizes K=%d H=%d W=%d levels=%d (1..%d) or NULL level_sizes / logits / tree_table / "
                       "out_labels", K, H, W, num_levels, HSR_EVAL_MAX_LEVELS);
@@ -444,19 +418,19 @@ extern "C" int hsr_eval_labels_tree(int K, int H, int W, int num_levels, const i
 extern "C" size_t hsr_eval_leaf_scratch_bytes(int C)
 {
     if (C < 1) return 256;
-    return align256((size_t)C * (HSR_EVAL_LEAF_MAX_K + 1) * sizeof(float));
+    return hsr_align256((size_t)C * (HSR_EVAL_LEAF_MAX_K + 1) * sizeof(float));
 }
 
 extern "C" int hsr_eval_labels_leaf(int K, int C, int H, int W, const float* sem, const float* weight, const float* bias, int32_t* out_labels,
                                     char* scratch, size_t scratch_bytes, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (bad_size(H, W) || K < 1 || K > HSR_EVAL_LEAF_MAX_K || C < 1 || C > HSR_EVAL_LEAF_MAX_C || !sem || !weight || !bias || !out_labels) {
+    if (hsr_bad_frame_size(H, W) || K < 1 || K > HSR_EVAL_LEAF_MAX_K || C < 1 || C > HSR_EVAL_LEAF_MAX_C || !sem || !weight || !bias || !out_labels) {
         hsr_set_error("eval_labels_leaf: invalid sizes K=%d (1..%d) C=%d (1..%d) H=%d W=%d or NULL sem / weight / bias / out_labels", K,
                       HSR_EVAL_LEAF_MAX_K, C, HSR_EVAL_LEAF_MAX_C, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    int rc = check_scratch("eval_labels_leaf", scratch, scratch_bytes, hsr_eval_leaf_scratch_bytes(C));
+    int rc = hsr_check_scratch("eval_labels_leaf", scratch, scratch_bytes, hsr_eval_leaf_scratch_bytes(C));
     if (rc != HSR_OK) return rc;
     float* wp = reinterpret_cast<float*>(scratch);
     const int np = C * (HSR_EVAL_LEAF_MAX_K + 1);
@@ -469,8 +443,8 @@ extern "C" int hsr_eval_labels_leaf(int K, int C, int H, int W, const float* sem
 
 extern "C" size_t hsr_eval_iou_scratch_bytes(int H, int W)
 {
-    if (bad_size(H, W)) return 1024;
-    return align256(2 * (size_t)H * W * sizeof(int32_t));
+    if (hsr_bad_frame_size(H, W)) return 1024;
+    return hsr_align256(2 * (size_t)H * W * sizeof(int32_t));
 }
 
 extern "C" int hsr_eval_iou_counts(int H, int W, const int32_t* pred, const int32_t* gt, int C, const int32_t* sorted_ids,
@@ -478,13 +452,13 @@ extern "C" int hsr_eval_iou_counts(int H, int W, const int32_t* pred, const int3
                                    void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (bad_size(H, W) || C < 1 || C > HSR_EVAL_MAX_CLASSES || dilation < 1 || dilation > HSR_EVAL_MAX_DILATION || !pred || !gt ||
+    if (hsr_bad_frame_size(H, W) || C < 1 || C > HSR_EVAL_MAX_CLASSES || dilation < 1 || dilation > HSR_EVAL_MAX_DILATION || !pred || !gt ||
         !out_counts || (!sorted_ids) != (!sorted_rows)) {
         hsr_set_error("eval_iou_counts: invalid sizes H=%d W=%d C=%d (1..%d) dilation=%d (1..%d), NULL pred / gt / out_counts, or only "
                       "one of sorted_ids / sorted_rows", H, W, C, HSR_EVAL_MAX_CLASSES, dilation, HSR_EVAL_MAX_DILATION);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    int rc = check_scratch("eval_iou_counts", scratch, scratch_bytes, hsr_eval_iou_scratch_bytes(H, W));
+    int rc = hsr_check_scratch("eval_iou_counts", scratch, scratch_bytes, hsr_eval_iou_scratch_bytes(H, W));
     if (rc != HSR_OK) return rc;
     int32_t* packed = reinterpret_cast<int32_t*>(scratch);
     HSR_HIP_CHECK(hipMemsetAsync(out_counts, 0, (size_t)C * 6 * sizeof(int64_t), stream));

@@ -12,6 +12,7 @@
 // Compiled with -ffp-contract=off: the forward then evaluates exactly the expression tree of the oracle
 // (oracle/frame_prep_oracle.py), which matters because out_means3D feeds the rasterizer's integer decisions.
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/hsr_frame_prep.h"
 
 namespace {
@@ -119,13 +120,6 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_forward_kernel(PrepArgs
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_backward_kernel(
     PrepArgs a, const float* __restrict__ g_means, const float* __restrict__ g_unnorm, const float* __restrict__ g_rot,
     const float* __restrict__ g_opac, const float* __restrict__ g_scales, const float* __restrict__ g_sil, float* __restrict__ d_means3D,
@@ -204,17 +198,7 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_backward_kernel(
             }
         }
     }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < PREP_SUMS; k++) {
-        const float v = wave_sum(sums[k]);
-        if (lane == 0) s_part[wv][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < PREP_SUMS) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * PREP_SUMS + k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];
-    }
+    hsr_block256_sums(sums, s_part, partials + (size_t)blockIdx.x * PREP_SUMS);
 }
 
 // One block: sums the per-block partials in a fixed order (double), then the 3x3 -> quaternion adjoint and the two
@@ -352,10 +336,8 @@ int frame_prep_backward_impl(int P, int S, int transform_rots, int rot_source, c
         hsr_set_error("frame_prep: dL_dout_depth_sil needs w2c");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    if (!scratch || scratch_bytes < hsr_frame_prep_scratch_bytes(P)) {
-        hsr_set_error("frame_prep: scratch too small: %zu bytes needed", hsr_frame_prep_scratch_bytes(P));
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
+    rc = hsr_check_scratch("frame_prep", scratch, scratch_bytes, hsr_frame_prep_scratch_bytes(P));
+    if (rc != HSR_OK) return rc;
     PrepArgs a{P, S, transform_rots != 0, rot_source, num_frames, time_idx, means3D, unnorm_rotations, logit_opacities, log_scales,
                cam_unnorm_rots, cam_trans, w2c};
     float* partials = reinterpret_cast<float*>(scratch);

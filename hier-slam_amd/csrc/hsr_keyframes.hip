@@ -7,6 +7,7 @@
 // Small and latency-bound: 5 launches per selection in place of ~17 per keyframe.  Compiled with -ffp-contract=off: the chains decide
 // integers (the key equality, the five tests), so they are evaluated in the order written, without FMA contraction.
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/hsr_keyframes.h"
 
 namespace {
@@ -19,47 +20,21 @@ __global__ __launch_bounds__(KB) void row_count_kernel(int W, const float* __res
     const float* row = depth + (size_t)blockIdx.x * W;
     int local = 0;
     for (int x = threadIdx.x; x < W; x += KB) local += row[x] > 0.f ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) row_prefix[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const int total = hsr_block256_isum(local, s_w);
+    if (threadIdx.x == 0) row_prefix[blockIdx.x] = total;
 }
 
 // in place: counts[0, H) -> exclusive prefix, total -> counts[H]
 __global__ __launch_bounds__(1024) void row_scan_kernel(int H, int* __restrict__ counts)
 {
     __shared__ int s_w[17];
-    const int per = (H + 1023) / 1024, beg = threadIdx.x * per;
-    int local = 0;
-    for (int k = 0; k < per; k++)
-        if (beg + k < H) local += counts[beg + k];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int k = 0; k < 16; k++) { const int v = s_w[k]; s_w[k] = run; run += v; }
-        s_w[16] = run;
-    }
-    __syncthreads();
-    int run = s_w[w] + inc - local;
-    for (int k = 0; k < per; k++)
-        if (beg + k < H) { const int v = counts[beg + k]; counts[beg + k] = run; run += v; }
-    if (threadIdx.x == 0) counts[H] = s_w[16];
+    const int total = hsr_block1024_exclusive_scan(H, counts, s_w);
+    if (threadIdx.x == 0) counts[H] = total;
 }
-
-struct Frame { float fx, fy, cx, cy; };
 
 // one wave per rank; r and everything derived from it is wave-uniform, so the loops do not diverge
 __global__ __launch_bounds__(KB) void sample_kernel(int H, int W, const float* __restrict__ depth, const int* __restrict__ row_prefix, int n,
-                                                    const int64_t* __restrict__ ranks, Frame f, const float* __restrict__ c2w,
+                                                    const int64_t* __restrict__ ranks, hsr_pinhole f, const float* __restrict__ c2w,
                                                     float* __restrict__ raw_pts, int* __restrict__ out_pixels)
 {
     const int lane = threadIdx.x & 63;
@@ -90,12 +65,7 @@ __global__ __launch_bounds__(KB) void sample_kernel(int H, int W, const float* _
         const int c = __popcll(b);
         if (k >= c) { k -= c; continue; }
         if (v && __popcll(b & ((1ull << lane) - 1ull)) == k) {
-            // get_pointcloud (:17-25)
-            const float xx = ((float)x - f.cx) / f.fx, yy = ((float)row - f.cy) / f.fy;
-            const float pc0 = xx * z, pc1 = yy * z, pc2 = z;
-#pragma unroll
-            for (int q = 0; q < 3; q++)
-                raw_pts[3 * i + q] = ((c2w[4 * q] * pc0 + c2w[4 * q + 1] * pc1) + c2w[4 * q + 2] * pc2) + c2w[4 * q + 3] * 1.0f;
+            hsr_backproject((float)x, (float)row, z, f, c2w, raw_pts + 3 * i);   // get_pointcloud (:17-25)
             out_pixels[2 * i] = row; out_pixels[2 * i + 1] = x;
         }
         return;
@@ -121,12 +91,11 @@ __global__ __launch_bounds__(1024) void dedupe_kernel(int n, const float* __rest
                                                       uint8_t* __restrict__ out_keep, int* __restrict__ out_count)
 {
     __shared__ float s_kx[HSR_KF_MAX_POINTS], s_ky[HSR_KF_MAX_POINTS], s_kz[HSR_KF_MAX_POINTS];
-    __shared__ int s_w[16];
+    __shared__ unsigned s_w[16];
     for (int i = threadIdx.x; i < n; i += 1024) {
         s_kx[i] = round_key(raw_pts[3 * i]); s_ky[i] = round_key(raw_pts[3 * i + 1]); s_kz[i] = round_key(raw_pts[3 * i + 2]);
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int run = 0;   // survivors before this pass: the same in every thread
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x;
@@ -138,14 +107,11 @@ __global__ __launch_bounds__(1024) void dedupe_kernel(int n, const float* __rest
             keep = !rem;
             out_keep[i] = keep ? 1 : 0;
         }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) s_w[w] = __popcll(bal);
-        __syncthreads();
-        int pos = run + __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-        for (int q = 0; q < 16; q++) { const int v = s_w[q]; if (q < w) pos += v; total += v; }
+        unsigned total;
+        const int pos = run + (int)hsr_block_rank<16>(keep, s_w, &total);
         if (keep) { out_pts[3 * pos] = raw_pts[3 * i]; out_pts[3 * pos + 1] = raw_pts[3 * i + 1]; out_pts[3 * pos + 2] = raw_pts[3 * i + 2]; }
-        run += total;
-        __syncthreads();
+        run += (int)total;
+        __syncthreads();   // s_w has been read by every wave before the next pass writes it
     }
     if (threadIdx.x == 0) *out_count = run;
 }
@@ -180,11 +146,8 @@ __global__ __launch_bounds__(KB) void overlap_kernel(int n_cap, const int* __res
         const float u = p0 / zz, v = p1 / zz;                                   // :75-76
         local += (u < p.umax && u > p.edge && v < p.vmax && v > p.edge && zz > 0.f) ? 1 : 0;   // :79-81
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = local;
-    __syncthreads();
-    if (threadIdx.x == 0) out_counts[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const int total = hsr_block256_isum(local, s_w);
+    if (threadIdx.x == 0) out_counts[blockIdx.x] = total;
 }
 
 }  // namespace
@@ -192,7 +155,7 @@ __global__ __launch_bounds__(KB) void overlap_kernel(int n_cap, const int* __res
 extern "C" int hsr_kf_valid_rows(int H, int W, const float* depth, int32_t* row_prefix, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !depth || !row_prefix) {
+    if (hsr_bad_frame_size(H, W) || !depth || !row_prefix) {
         hsr_set_error("kf_valid_rows: invalid sizes H=%d W=%d or NULL depth/row_prefix", H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -212,7 +175,7 @@ extern "C" int hsr_kf_sample_points(int H, int W, const float* depth, const int3
                                     uint8_t* out_keep, int32_t* out_count, char* scratch, size_t scratch_bytes, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || n < 1 || n > HSR_KF_MAX_POINTS) {
+    if (hsr_bad_frame_size(H, W) || n < 1 || n > HSR_KF_MAX_POINTS) {
         hsr_set_error("kf_sample_points: invalid sizes H=%d W=%d n=%d (1 <= n <= %d)", H, W, n, HSR_KF_MAX_POINTS);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -220,12 +183,9 @@ extern "C" int hsr_kf_sample_points(int H, int W, const float* depth, const int3
         hsr_set_error("kf_sample_points: NULL depth/row_prefix/ranks/c2w/out_pts/out_pixels/out_keep/out_count");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    if (!scratch || scratch_bytes < hsr_kf_sample_scratch_bytes(n)) {
-        hsr_set_error("kf_sample_points: scratch too small: %zu bytes needed", hsr_kf_sample_scratch_bytes(n));
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
+    if (int rc = hsr_check_scratch("kf_sample_points", scratch, scratch_bytes, hsr_kf_sample_scratch_bytes(n))) return rc;
     float* raw = reinterpret_cast<float*>(scratch);
-    Frame f{fx, fy, cx, cy};
+    hsr_pinhole f{fx, fy, cx, cy};
     const int per = KB / 64;
     sample_kernel<<<(n + per - 1) / per, KB, 0, stream>>>(H, W, depth, row_prefix, n, ranks, f, c2w, raw, out_pixels);
     dedupe_kernel<<<1, 1024, 0, stream>>>(n, raw, out_pts, out_keep, out_count);

@@ -19,6 +19,7 @@
 // Integer counts throughout the selection, fixed-order float sums: every output is the same bits on every run.
 // Compiled with -ffp-contract=off: error and threshold are computed as written.  Denormals are kept (hipcc's default for fp32 on gfx9).
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/ext/hsr_loss_outlier.h"
 
 namespace {
@@ -30,21 +31,15 @@ constexpr int BINS = 2048;            // 11 bits; the last pass uses 1024 of the
 constexpr int HIST_WORDS = 3 * BINS;  // the three global histograms, then the control words
 constexpr int CTL_NAN = HIST_WORDS;   // number of NaN errors
 constexpr size_t ZERO_BYTES = (size_t)(HIST_WORDS + 4) * sizeof(unsigned);      // 24592: a multiple of 16, from the scratch's start
-constexpr size_t PART_OFF = (ZERO_BYTES + 255) & ~(size_t)255;                  // float partials [MAX_BLOCKS][2]
+constexpr size_t PART_OFF = hsr_align256(ZERO_BYTES);                           // float partials [MAX_BLOCKS][2]
 constexpr size_t COUNT_OFF = PART_OFF + (size_t)MAX_BLOCKS * 2 * sizeof(float); // unsigned selected [MAX_BLOCKS]
 constexpr size_t SCRATCH_BYTES = COUNT_OFF + (size_t)MAX_BLOCKS * sizeof(unsigned);
-
-// scripts/hierslam.py:911, in this order
-__device__ __forceinline__ float depth_error(float gt, float d)
-{
-    return fabsf(gt - d) * (gt > 0.f ? 1.f : 0.f);
-}
 
 // the mask of a pixel; reject: additionally the error below the threshold (strict: a NaN threshold selects nothing).  Not thr = +inf for
 // the plain mask: an infinite depth on a valid pixel has the error inf, inf < inf is false, and the plain mask selects that pixel
 __device__ __forceinline__ bool selected(bool reject, float gt, float d, float thr, float sil, float sil_thres, int use_sil)
 {
-    return (!reject || depth_error(gt, d) < thr) && gt > 0.f && !(d != d) && (!use_sil || sil > sil_thres);
+    return (!reject || hsr_depth_error(gt, d) < thr) && gt > 0.f && !(d != d) && (!use_sil || sil > sil_thres);
 }
 
 struct Rank { unsigned bin, rank; };
@@ -61,12 +56,7 @@ __device__ __forceinline__ Rank find_bin(const unsigned* hist, unsigned rank, un
         c[k] = hist[threadIdx.x * PER + k];
         t += c[k];
     }
-    unsigned incl = t;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += v;
-    }
+    unsigned incl = hsr_wave_inclusive_scan(t, lane);
     if (threadIdx.x == 0) s_res[0] = s_res[1] = 0;
     if (lane == 63) s_wave[wv] = incl;
     __syncthreads();
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(LB) void hist_kernel(const float* __restrict__ dept
     __syncthreads();
     unsigned nan = 0;
     for (unsigned i = blockIdx.x * LB + threadIdx.x; i < N; i += gridDim.x * LB) {      // i + stride < 2^31 + 2^17
-        const float e = depth_error(gt_depth[i], depth[i]);
+        const float e = hsr_depth_error(gt_depth[i], depth[i]);
         const unsigned key = __float_as_uint(e);      // key >> 21 <= 2047 whatever the bits
         if (PASS == 0) {
             nan += e != e ? 1u : 0u;
@@ -129,8 +119,7 @@ __global__ __launch_bounds__(LB) void hist_kernel(const float* __restrict__ dept
         if (c) atomicAdd(&out[b], c);
     }
     if (PASS == 0) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) nan += __shfl_xor(nan, o, 64);
+        nan = hsr_wave_sum(nan);
         if ((threadIdx.x & 63) == 0 && nan) atomicAdd(&hist[CTL_NAN], nan);
     }
 }
@@ -153,17 +142,6 @@ __global__ __launch_bounds__(LB) void median_kernel(const unsigned* hist, unsign
         out2[0] = med;
         out2[1] = 10.0f * med;
     }
-}
-
-__device__ __forceinline__ float block_sum(float v, float* s_red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) s_red[wv] = v;
-    __syncthreads();
-    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
 }
 
 // OUTLIER: the threshold from the finished histograms, one pixel per thread and trip (the grid is capped at MAX_BLOCKS and strides);
@@ -203,17 +181,13 @@ __global__ __launch_bounds__(LB) void value_kernel(const float* __restrict__ im,
                 acc_c += sel ? e : 0.f;
             }
         }
-    const float td = block_sum(acc_d, s_red);
-    const float tc = block_sum(acc_c, s_red);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = n;
-    __syncthreads();
+    const float td = hsr_block256_sum(acc_d, s_red);
+    const float tc = hsr_block256_sum(acc_c, s_red);
+    const unsigned tn = hsr_block256_isum(n, s_wave);   // s_wave is idle: find_bin ends with a barrier
     if (threadIdx.x == 0) {
         partials[2 * (size_t)blockIdx.x] = td;
         partials[2 * (size_t)blockIdx.x + 1] = tc;
-        counts[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        counts[blockIdx.x] = tn;
     }
 }
 
@@ -300,29 +274,20 @@ unsigned blocks_for(unsigned N, unsigned cap)
 size_t tracking_bytes(int H, int W)
 {
     const size_t nb = ((size_t)H * W + LB * ITEMS - 1) / (LB * ITEMS);
-    return (nb * 3 * sizeof(float) + 255) & ~(size_t)255;
+    return hsr_align256(nb * 3 * sizeof(float));
 }
 
 // any_c: the tracking ABI takes every C >= 0, the outlier ABI 0 or 3
 int check_maps(const char* who, bool any_c, int C, int H, int W, const float* im, const float* gt_im, const float* depth,
                const float* gt_depth, const float* sil, int use_sil)
 {
-    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !depth || !gt_depth) {
+    if (hsr_bad_frame_size(H, W) || !depth || !gt_depth) {
         hsr_set_error("%s: invalid sizes H=%d W=%d (H, W >= 1, H * W < 2^31) or NULL depth / gt_depth", who, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
     if (C < 0 || (!any_c && C != 0 && C != 3) || (C > 0 && (!im || !gt_im)) || (use_sil && !sil)) {
         hsr_set_error("%s: C=%d is %s, or NULL im / gt_im / silhouette", who, C, any_c ? "negative" : "neither 0 nor 3");
         return HSR_ERR_INVALID_ARGUMENT;
-    }
-    return HSR_OK;
-}
-
-int check_scratch(const char* who, const char* scratch, size_t have, size_t need, unsigned align)
-{
-    if (!scratch || have < need || (reinterpret_cast<uintptr_t>(scratch) & (align - 1)) != 0) {
-        hsr_set_error("%s: scratch is NULL, not %u-byte aligned or too small: %zu bytes needed, %zu given", who, align, need, have);
-        return HSR_ERR_BUFFER_TOO_SMALL;
     }
     return HSR_OK;
 }
@@ -349,7 +314,7 @@ int masked_value(const char* who, bool reject, int C, int H, int W, const float*
         hsr_set_error("%s: out%s is NULL or reduction is neither HSR_LOSS_SUM nor HSR_LOSS_MEAN", who, reject ? "6 / out_selected" : "4");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    rc = reject ? check_scratch(who, scratch, scratch_bytes, SCRATCH_BYTES, 16) : check_scratch(who, scratch, scratch_bytes, tracking_bytes(H, W), 4);
+    rc = reject ? hsr_check_scratch(who, scratch, scratch_bytes, SCRATCH_BYTES, 16) : hsr_check_scratch(who, scratch, scratch_bytes, tracking_bytes(H, W), 4);
     if (rc != HSR_OK) return rc;
     const unsigned N = (unsigned)H * (unsigned)W;
     const int nb = (int)blocks_for(N, reject ? MAX_BLOCKS : ~0u);
@@ -424,7 +389,7 @@ extern "C" int hsr_loss_outlier_median(int H, int W, const float* depth, const f
         hsr_set_error("loss_outlier_median: out2 is NULL");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    rc = check_scratch("loss_outlier_median", scratch, scratch_bytes, SCRATCH_BYTES, 16);
+    rc = hsr_check_scratch("loss_outlier_median", scratch, scratch_bytes, SCRATCH_BYTES, 16);
     if (rc != HSR_OK) return rc;
     const unsigned N = (unsigned)H * (unsigned)W;
     rc = launch_select(N, (int)blocks_for(N, MAX_BLOCKS), depth, gt_depth, scratch, stream);

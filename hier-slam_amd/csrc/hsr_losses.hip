@@ -16,6 +16,7 @@
 // The tracking loss of include/hsr_losses.h (hsr_loss_tracking_*: mask, both masked sums and their gradients as one head) is not here: it
 // shares its kernels with the outlier-rejecting head in hsr_loss_masked.hip.
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/hsr_losses.h"
 #include <cmath>
 
@@ -26,17 +27,6 @@ constexpr int L1_ITEMS = 8;      // pixels per thread (L1)
 constexpr int SS_T = 32;         // SSIM tile edge (256 threads x 2x2 outputs)
 constexpr int SS_R = 5;          // window radius (11x11)
 constexpr int SS_E = SS_T + 2 * SS_R;
-
-__device__ __forceinline__ float block_sum(float v, float* s_red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) s_red[wv] = v;
-    __syncthreads();
-    return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
 
 // ---------------------------------------------------------------- finish: fixed-order sum of per-block partials
 // out[k] = scale_k * sum_b partials[b * stride + k];  scale: 1, or *inv (device), see `mode`
@@ -89,11 +79,8 @@ __global__ __launch_bounds__(LB) void mask_count_kernel(const uint8_t* __restric
     unsigned c = 0;
     for (int i = blockIdx.x * LB * L1_ITEMS + threadIdx.x, it = 0; it < L1_ITEMS; it++, i += LB)
         if (i < N) c += mask[i] != 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+    const unsigned total = hsr_block256_isum(c, s_red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
 // grid: (blocks over N, C).  scale = host_scale * (inv ? inv[0] : 1)
@@ -113,7 +100,7 @@ __global__ __launch_bounds__(LB) void l1_kernel(const float* __restrict__ pred, 
         acc += sel ? fabsf(d) : 0.f;
         if (grad) grad[plane + i] = sel ? (d > 0.f ? scale : (d < 0.f ? -scale : 0.f)) : 0.f;
     }
-    const float tot = block_sum(acc, s_red);
+    const float tot = hsr_block256_sum(acc, s_red);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -205,7 +192,7 @@ __global__ __launch_bounds__(LB) void ssim_forward_kernel(const float* __restric
         }
         acc += live ? smap : 0.f;
     }
-    const float tot = block_sum(acc, s_red);
+    const float tot = hsr_block256_sum(acc, s_red);
     if (threadIdx.x == 0) partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = tot;
 }
 
@@ -279,13 +266,9 @@ __global__ __launch_bounds__(LB) void ce_count_kernel(const int64_t* __restrict_
     __shared__ unsigned s_red[4];
     const int i = blockIdx.x * LB + threadIdx.x;
     for (int l = 0; l < num_levels; l++) {
-        unsigned c = (i < N && labels[(size_t)l * N + i] != (int64_t)ignore_index) ? 1u : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = c;
-        __syncthreads();
-        if (threadIdx.x == 0) partials[(size_t)blockIdx.x * HSR_LOSS_MAX_LEVELS + l] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+        __syncthreads();   // thread 0 may still be reading the level before
+        const unsigned total = hsr_block256_count(i < N && labels[(size_t)l * N + i] != (int64_t)ignore_index, s_red);
+        if (threadIdx.x == 0) partials[(size_t)blockIdx.x * HSR_LOSS_MAX_LEVELS + l] = total;
     }
 }
 
@@ -323,7 +306,7 @@ __global__ __launch_bounds__(LB) void tree_ce_kernel(const float* __restrict__ l
                 grad[(size_t)(b + c) * N + p] = (sm - (c == lab ? 1.f : 0.f)) * sc;
             }
         }
-        const float tot = block_sum(loss, s_red);
+        const float tot = hsr_block256_sum(loss, s_red);
         if (threadIdx.x == 0) partials[(size_t)blockIdx.x * HSR_LOSS_MAX_LEVELS + l] = tot;
         covered_end = b + n;
     }
@@ -421,12 +404,7 @@ __global__ __launch_bounds__(TB) void tree_ce2_kernel(const float* __restrict__ 
             }
             if (!GRAD) {
                 // the wave's sums of this level, added into the wave's own row (counts are exact in fp32: <= 64 per add, <= 128 per row)
-                float a = loss, cnt = valid ? 1.f : 0.f;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    a += __shfl_xor(a, o, 64);
-                    cnt += __shfl_xor(cnt, o, 64);
-                }
+                const float a = hsr_wave_sum(loss), cnt = hsr_wave_sum(valid ? 1.f : 0.f);
                 if (lane == 0) {
                     s_part[wv][l] += a;
                     s_part[wv][HSR_LOSS_MAX_LEVELS + l] += cnt;
@@ -646,7 +624,7 @@ __global__ void __launch_bounds__(256, 3) leaf_mlp_ce_kernel(const float* __rest
     }
 
     // ---- per-workgroup partials: loss, then d_Wt[c][k] summed over the four waves in a fixed order ----
-    const float tot = block_sum(loss_acc, s_red);
+    const float tot = hsr_block256_sum(loss_acc, s_red);
     if (t == 0) part_loss[blockIdx.x] = tot;
     float* out = part_dw + (size_t)blockIdx.x * (CT * 16 * LM_KP);
 #pragma unroll
@@ -711,17 +689,6 @@ __global__ __launch_bounds__(LFD_T) void leaf_finish_dw_kernel(const float* __re
     else if (d_bias) d_bias[c] = (float)tot;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-int check_scratch(const char* what, char* scratch, size_t have, size_t need)
-{
-    if (!scratch || have < need) {
-        hsr_set_error("%s: scratch too small: %zu bytes needed, %zu given", what, need, have);
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
-    return HSR_OK;
-}
-
 }  // namespace
 
 extern "C" size_t hsr_loss_scratch_bytes(int channels, int H, int W)
@@ -731,12 +698,12 @@ extern "C" size_t hsr_loss_scratch_bytes(int channels, int H, int W)
     const size_t tiles = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T);
     const size_t blocks = (N + LB - 1) / LB + 1;
     // SSIM: three partial-derivative maps + one partial per tile;  CE: MAX_LEVELS partials per block, twice;  L1: small
-    size_t need = align256(3 * (size_t)channels * N * sizeof(float)) + align256((size_t)channels * tiles * sizeof(float));
-    const size_t ce = 2 * align256(blocks * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
-    const size_t l1 = 2 * align256((size_t)channels * blocks * sizeof(float)) + 256;
+    size_t need = hsr_align256(3 * (size_t)channels * N * sizeof(float)) + hsr_align256((size_t)channels * tiles * sizeof(float));
+    const size_t ce = 2 * hsr_align256(blocks * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
+    const size_t l1 = 2 * hsr_align256((size_t)channels * blocks * sizeof(float)) + 256;
     if (ce > need) need = ce;
     if (l1 > need) need = l1;
-    const size_t leaf = (size_t)LM_MAX_BLOCKS * (LM_MAX_CT * 16 * LM_KP + 4) * sizeof(float) + 2 * align256(blocks * sizeof(float)) +
+    const size_t leaf = (size_t)LM_MAX_BLOCKS * (LM_MAX_CT * 16 * LM_KP + 4) * sizeof(float) + 2 * hsr_align256(blocks * sizeof(float)) +
                         (size_t)LM_MAX_CT * 16 * LM_KP * sizeof(float) + 4096;
     if (leaf > need) need = leaf;
     return need + 1024;
@@ -746,7 +713,7 @@ extern "C" int hsr_loss_l1(int C, int H, int W, const float* pred, const float* 
                            float* out_grad, char* scratch, size_t scratch_bytes, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C < 1 || H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !pred || !gt || !out_loss) {
+    if (C < 1 || hsr_bad_frame_size(H, W) || !pred || !gt || !out_loss) {
         hsr_set_error("loss_l1: invalid sizes C=%d H=%d W=%d or NULL pred/gt/out_loss", C, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -756,8 +723,8 @@ extern "C" int hsr_loss_l1(int C, int H, int W, const float* pred, const float* 
     }
     const int N = H * W;
     const int nb = (N + LB * L1_ITEMS - 1) / (LB * L1_ITEMS);
-    const size_t part_bytes = align256((size_t)C * nb * sizeof(float));
-    int rc = check_scratch("loss_l1", scratch, scratch_bytes, 2 * part_bytes + 256);
+    const size_t part_bytes = hsr_align256((size_t)C * nb * sizeof(float));
+    int rc = hsr_check_scratch("loss_l1", scratch, scratch_bytes, 2 * part_bytes + 256);
     if (rc != HSR_OK) return rc;
     float* partials = reinterpret_cast<float*>(scratch);
     unsigned* cparts = reinterpret_cast<unsigned*>(scratch + part_bytes);
@@ -828,8 +795,8 @@ extern "C" int hsr_loss_ssim(int C, int H, int W, const float* img1, const float
         return HSR_ERR_INVALID_ARGUMENT;
     }
     const dim3 grid = ssim_grid(C, H, W);
-    const size_t map_bytes = out_grad ? align256((size_t)C * H * W * sizeof(float) * 3) : 0;
-    int rc = check_scratch("loss_ssim", scratch, scratch_bytes, map_bytes + align256((size_t)grid.x * grid.y * C * sizeof(float)));
+    const size_t map_bytes = out_grad ? hsr_align256((size_t)C * H * W * sizeof(float) * 3) : 0;
+    int rc = hsr_check_scratch("loss_ssim", scratch, scratch_bytes, map_bytes + hsr_align256((size_t)grid.x * grid.y * C * sizeof(float)));
     if (rc != HSR_OK) return rc;
     float* maps = out_grad ? reinterpret_cast<float*>(scratch) : nullptr;
     launch_ssim_value(C, H, W, img1, img2, maps, reinterpret_cast<float*>(scratch + map_bytes), out_ssim, stream);
@@ -848,7 +815,7 @@ extern "C" int hsr_loss_ssim_value(int C, int H, int W, const float* img1, const
         return HSR_ERR_INVALID_ARGUMENT;
     }
     const dim3 grid = ssim_grid(C, H, W);
-    int rc = check_scratch("loss_ssim_value", scratch, scratch_bytes, align256((size_t)grid.x * grid.y * C * sizeof(float)));
+    int rc = hsr_check_scratch("loss_ssim_value", scratch, scratch_bytes, hsr_align256((size_t)grid.x * grid.y * C * sizeof(float)));
     if (rc != HSR_OK) return rc;
     launch_ssim_value(C, H, W, img1, img2, maps, reinterpret_cast<float*>(scratch), out_ssim, (hipStream_t)stream_);
     HSR_HIP_CHECK(hipGetLastError());
@@ -886,7 +853,7 @@ extern "C" int hsr_loss_l1_grad(int C, int H, int W, const float* pred, const fl
                                 const float* upstream, float* out_grad, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (C < 1 || H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !pred || !gt || !out_grad) {
+    if (C < 1 || hsr_bad_frame_size(H, W) || !pred || !gt || !out_grad) {
         hsr_set_error("loss_l1_grad: invalid sizes C=%d H=%d W=%d or NULL pred/gt/out_grad", C, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -905,7 +872,7 @@ extern "C" int hsr_loss_l1_grad(int C, int H, int W, const float* pred, const fl
 namespace {
 int parse_levels(const char* who, int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight, Levels* lv)
 {
-    if (K < 1 || H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !level_sizes) {
+    if (K < 1 || hsr_bad_frame_size(H, W) || !level_sizes) {
         hsr_set_error("%s: invalid sizes K=%d H=%d W=%d or NULL level_sizes", who, K, H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -947,8 +914,8 @@ extern "C" int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* 
     }
     const int N = H * W;
     const int nb = (N + LB - 1) / LB;
-    const size_t part_bytes = align256((size_t)nb * HSR_LOSS_MAX_LEVELS * sizeof(float));
-    rc = check_scratch("loss_tree_ce", scratch, scratch_bytes, 2 * part_bytes + 256);
+    const size_t part_bytes = hsr_align256((size_t)nb * HSR_LOSS_MAX_LEVELS * sizeof(float));
+    rc = hsr_check_scratch("loss_tree_ce", scratch, scratch_bytes, 2 * part_bytes + 256);
     if (rc != HSR_OK) return rc;
     float* partials = reinterpret_cast<float*>(scratch);
     unsigned* cparts = reinterpret_cast<unsigned*>(scratch + part_bytes);
@@ -965,7 +932,7 @@ extern "C" size_t hsr_loss_tree_ce_scratch_bytes(int H, int W)
 {
     if (H < 1 || W < 1) return 1024;
     const size_t nb = ((size_t)H * W + LB - 1) / LB;
-    return align256(nb * 2 * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
+    return hsr_align256(nb * 2 * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
 }
 
 extern "C" int hsr_loss_tree_ce_value(int K, int H, int W, int num_levels, const int* level_sizes, const float* logits,
@@ -983,7 +950,7 @@ extern "C" int hsr_loss_tree_ce_value(int K, int H, int W, int num_levels, const
     const int N = H * W;
     constexpr int VB = 1024;
     const int nb = (N + VB * CE_ITEMS - 1) / (VB * CE_ITEMS);
-    rc = check_scratch("loss_tree_ce_value", scratch, scratch_bytes, hsr_loss_tree_ce_scratch_bytes(H, W) - 256);
+    rc = hsr_check_scratch("loss_tree_ce_value", scratch, scratch_bytes, hsr_loss_tree_ce_scratch_bytes(H, W) - 256);
     if (rc != HSR_OK) return rc;
     float* partials = reinterpret_cast<float*>(scratch);
     tree_ce2_kernel<false, VB><<<nb, VB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, nullptr, nullptr, nullptr, partials, nullptr, nullptr, 0.f);
@@ -1022,7 +989,7 @@ extern "C" int hsr_loss_leaf_mlp_ce(int K, int C, int H, int W, const float* sem
                       16 * LM_MAX_CT, K, C);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    if (H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu || !sem || !weight || !bias || !labels || !out_loss) {
+    if (hsr_bad_frame_size(H, W) || !sem || !weight || !bias || !labels || !out_loss) {
         hsr_set_error("loss_leaf_mlp_ce: invalid sizes H=%d W=%d or NULL sem/weight/bias/labels/out_loss", H, W);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -1031,10 +998,10 @@ extern "C" int hsr_loss_leaf_mlp_ce(int K, int C, int H, int W, const float* sem
     int nblk = (N + 255) / 256;
     if (nblk > LM_MAX_BLOCKS) nblk = LM_MAX_BLOCKS;
     // scratch: packed weights [CT*16][32] | inv count | loss partials | dW partials [nblk][CT*16*32]
-    const size_t wt_bytes = align256((size_t)CT * 16 * LM_KP * sizeof(float));
-    const size_t loss_bytes = align256((size_t)nblk * sizeof(float));
+    const size_t wt_bytes = hsr_align256((size_t)CT * 16 * LM_KP * sizeof(float));
+    const size_t loss_bytes = hsr_align256((size_t)nblk * sizeof(float));
     const size_t dw_bytes = (size_t)nblk * CT * 16 * LM_KP * sizeof(float);
-    int rc = check_scratch("loss_leaf_mlp_ce", scratch, scratch_bytes, wt_bytes + 256 + loss_bytes + dw_bytes);
+    int rc = hsr_check_scratch("loss_leaf_mlp_ce", scratch, scratch_bytes, wt_bytes + 256 + loss_bytes + dw_bytes);
     if (rc != HSR_OK) return rc;
     float* wt = reinterpret_cast<float*>(scratch);
     float* inv = reinterpret_cast<float*>(scratch + wt_bytes);

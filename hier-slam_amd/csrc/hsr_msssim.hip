@@ -17,6 +17,7 @@
 // rounded) changes the cancellation and with it the low-contrast pixels' cs, so every product and sum rounds once, in the order
 // written.
 #include "hsr_common.h"
+#include "hsr_block.h"
 #include "../../include/ext/hsr_msssim.h"
 #include <cmath>
 
@@ -38,11 +39,9 @@ struct Levels {
     long long pyr_floats, part_doubles;
 };
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 bool bad_size(int H, int W)
 {
-    return H < HSR_EVAL_MSSSIM_MIN_SIDE || W < HSR_EVAL_MSSSIM_MIN_SIDE || (size_t)H * W > 0x7fffffffu;
+    return H < HSR_EVAL_MSSSIM_MIN_SIDE || W < HSR_EVAL_MSSSIM_MIN_SIDE || hsr_bad_frame_size(H, W);
 }
 
 Levels levels_of(int H, int W)
@@ -74,13 +73,6 @@ Gauss window()
     }
     for (int x = 0; x < 11; x++) win.g[x] = win.g[x] / sum;
     return win;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // 4 consecutive outputs of the 11-tap filter from a 14-value window, taps in index order, one rounding per product and per sum
@@ -209,8 +201,8 @@ __global__ __launch_bounds__(MB) void scale_kernel(ScaleArgs a, Gauss gw)
         acc_ss += live ? (double)ss : 0.0;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    acc_cs = wave_sum_d(acc_cs);
-    acc_ss = wave_sum_d(acc_ss);
+    acc_cs = hsr_wave_sum(acc_cs);
+    acc_ss = hsr_wave_sum(acc_ss);
     if (lane == 0) { s_red[wv][0] = acc_cs; s_red[wv][1] = acc_ss; }
     __syncthreads();
     if (threadIdx.x < 2) {
@@ -265,7 +257,7 @@ extern "C" size_t hsr_eval_msssim_scratch_bytes(int H, int W)
 {
     if (bad_size(H, W)) return 1024;
     const Levels lv = levels_of(H, W);
-    return align256((size_t)lv.pyr_floats * sizeof(float)) + align256((size_t)lv.part_doubles * sizeof(double));
+    return hsr_align256((size_t)lv.pyr_floats * sizeof(float)) + hsr_align256((size_t)lv.part_doubles * sizeof(double));
 }
 
 extern "C" int hsr_eval_msssim(int H, int W, const float* im, const float* gt_im, const float* gt_depth, const float* final_opacity,
@@ -277,14 +269,10 @@ extern "C" int hsr_eval_msssim(int H, int W, const float* im, const float* gt_im
                       "or NULL im / gt_im / gt_depth / out", H, W, HSR_EVAL_MSSSIM_MIN_SIDE);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const size_t need = hsr_eval_msssim_scratch_bytes(H, W);
-    if (!scratch || scratch_bytes < need) {
-        hsr_set_error("eval_msssim: scratch of %zu bytes is smaller than the %zu needed", scratch_bytes, need);
-        return HSR_ERR_BUFFER_TOO_SMALL;
-    }
+    if (int rc = hsr_check_scratch("eval_msssim", scratch, scratch_bytes, hsr_eval_msssim_scratch_bytes(H, W))) return rc;
     const Levels lv = levels_of(H, W);
     float* pyr = reinterpret_cast<float*>(scratch);
-    double* partials = reinterpret_cast<double*>(scratch + align256((size_t)lv.pyr_floats * sizeof(float)));
+    double* partials = reinterpret_cast<double*>(scratch + hsr_align256((size_t)lv.pyr_floats * sizeof(float)));
     const Gauss gw = window();
     for (int s = 0; s < NS; s++) {
         ScaleArgs a{};

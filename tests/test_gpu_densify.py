@@ -233,6 +233,24 @@ def test_remove_points_with_a_caller_mask_and_bad_input():
     assert p2["means3D"].shape == (0, 3) and v2["timestep"].shape == (0,)
 
 
+def _rank_edge_masks():
+    edges = torch.zeros(257, dtype=torch.bool)
+    edges[[63, 64, 255, 256]] = True     # last lane, first lane of the next wave, last thread, first thread of the next block
+    return [("edges_257", edges), ("all_256", torch.ones(256, dtype=torch.bool)), ("none_256", torch.zeros(256, dtype=torch.bool))]
+
+
+@pytest.mark.parametrize("name,keep", _rank_edge_masks(), ids=[n for n, _ in _rank_edge_masks()])
+def test_compaction_rank_at_wave_and_block_edges(name, keep):
+    """the caller-mask path of remove_points (count, scan, rank) where a rank crosses a wave or a block: rows equal tensor[mask]"""
+    from hsr_utils import slam_external as SE
+    P = keep.shape[0]
+    g = torch.Generator().manual_seed(P)
+    tensors = [torch.rand(P, 3, generator=g), torch.rand(P, generator=g), torch.arange(P, dtype=torch.float32)[:, None].repeat(1, 4)]
+    got = SE.compact_append([t.cuda() for t in tensors], keep=keep.to(torch.uint8).cuda())
+    for t, o in zip(tensors, got):
+        assert o.shape == t[keep].shape and torch.equal(o.cpu(), t[keep])
+
+
 # ---- gradient-driven densification (utils/slam_external.py:191-242; off in the reference's configs).  Pinned by the reference's own outputs at
 # the end of this file (tests/golden/slam_helpers/densify_gradient.npz).  The restatement below (accumulate, clone-concat, split-concat, remove
 # the split originals, prune, reset, written with plain concatenations and boolean indexing) is itself held to that fixture on the CPU

@@ -110,6 +110,19 @@ def test_rank_selection_matches_torch_where(name, depth):
     assert torch.equal(pts[:int(count)], cam[exp_keep])
 
 
+@pytest.mark.parametrize("H,W", [(1025, 3), (2049, 1)])
+def test_row_scan_with_more_rows_than_scan_threads(H, W):
+    """hsr_kf_valid_rows where the single-workgroup scan holds two and three counts per thread: all H + 1 words against numpy.cumsum"""
+    KF = _kf()
+    g = np.random.default_rng(H)
+    depth = (g.random((H, W)) * 4 + 0.5).astype(np.float32)
+    bad = g.random((H, W)) < 0.3
+    depth[bad] = np.where(g.random((H, W)) < 0.5, 0.0, -1.0).astype(np.float32)[bad]      # about 30 % non-positive
+    prefix = KF.valid_row_prefix(torch.tensor(depth).cuda()[None]).cpu().numpy()
+    exp = np.concatenate([[0], np.cumsum((depth > 0).sum(axis=1))])
+    assert prefix.shape == (H + 1,) and np.array_equal(prefix.astype(np.int64), exp)
+
+
 def _rot(axis, angle):
     axis = np.asarray(axis, np.float64) / np.linalg.norm(axis)
     x, y, z = axis
