@@ -1,0 +1,150 @@
+// hsr_frame_ingest.hip — device ingest of one raw sensor frame to one, two or three sizes (gfx950), DESIGN.md §7 row 8.
+// See include/ext/hsr_frame_ingest.h for the three rules, step by step, and the reference lines (basedataset.py:223-227, :248-256,
+// replica.py:241-299, scripts/hierslam.py:1777).
+//   ingest_kernel : one thread per destination pixel over the concatenated pixel ranges of the levels (level 0's pixels first): the
+//                   three colour channels bilinearly in float64 from four interleaved 8-bit taps, then / 255; the depth from one raw
+//                   source word divided by the scale; at level 0 the L + 1 int64 label planes from one raw id and its table row.
+// Memory-bound and small (a 1200x680 frame to itself and two 600x340 levels reads 8 MB and writes 20 MB with 5-level labels); no
+// reuse worth staging in LDS.  Compiled with -ffp-contract=off: the three float64 lerps are evaluated as the header writes them.
+#include <math.h>
+
+#include "hsr_common.h"
+#include "../../include/hsr_eval.h"
+#include "../../include/ext/hsr_frame_resample.h"
+#include "../../include/ext/hsr_frame_ingest.h"
+
+namespace {
+
+constexpr int IB = 256;
+
+struct Levels {
+    hsr_ingest_level l[HSR_INGEST_MAX_LEVELS];
+    long long end[HSR_INGEST_MAX_LEVELS];      // prefix sums of H * W: level k owns [end[k-1], end[k])
+};
+
+// the left tap, the right one and the weight of the right one along one axis: destination index i of nd from ns source samples
+__device__ __forceinline__ void taps(int i, int ns, int nd, int& i0, int& i1, double& f)
+{
+    int n = (2 * i + 1) * ns - nd;      // <= (2 * 16383 + 1) * 16384 < 2^30
+    n = n > 0 ? n : 0;
+    i0 = n / (2 * nd);
+    f = (double)(n - i0 * 2 * nd) / (double)(2 * nd);
+    i1 = i0 + 1 < ns ? i0 + 1 : ns - 1;
+}
+
+template <int DT>
+__device__ __forceinline__ double raw_depth(const void* __restrict__ p, size_t i)
+{
+    if (DT == HSR_INGEST_DEPTH_U16) return (double)static_cast<const uint16_t*>(p)[i];
+    if (DT == HSR_INGEST_DEPTH_I32) return (double)static_cast<const int32_t*>(p)[i];
+    return (double)static_cast<const float*>(p)[i];
+}
+
+template <int DT>
+__global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ color, const void* __restrict__ depth, int Hs, int Ws,
+                                                    double depth_scale, const int* __restrict__ labels, int L,
+                                                    const int* __restrict__ table, int n_ids, Levels lv, long long n_all,
+                                                    long long* __restrict__ out_labels)
+{
+    long long i = (long long)blockIdx.x * IB + threadIdx.x;
+    if (i >= n_all) return;
+    const int k = (i >= lv.end[0]) + (i >= lv.end[1]);      // an absent level ends where the last one does: never selected
+    i -= k == 0 ? 0 : k == 1 ? lv.end[0] : lv.end[1];
+    // selected with constant indices: a dynamically indexed by-value struct would go through scratch memory
+    const int Hd = k == 0 ? lv.l[0].H : k == 1 ? lv.l[1].H : lv.l[2].H;
+    const int Wd = k == 0 ? lv.l[0].W : k == 1 ? lv.l[1].W : lv.l[2].W;
+    float* __restrict__ oc = k == 0 ? lv.l[0].color : k == 1 ? lv.l[1].color : lv.l[2].color;
+    float* __restrict__ od = k == 0 ? lv.l[0].depth : k == 1 ? lv.l[1].depth : lv.l[2].depth;
+    const int y = (int)(i / Wd), x = (int)(i - (long long)y * Wd);      // i < Hd * Wd
+    int x0, x1, y0, y1;
+    double fx, fy;
+    taps(x, Ws, Wd, x0, x1, fx);
+    taps(y, Hs, Hd, y0, y1, fy);
+    const size_t dplane = (size_t)Hd * Wd;
+    const uint8_t* __restrict__ r0 = color + (size_t)y0 * Ws * 3;
+    const uint8_t* __restrict__ r1 = color + (size_t)y1 * Ws * 3;
+    const size_t c0 = (size_t)x0 * 3, c1 = (size_t)x1 * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) {
+        const double a = (double)r0[c0 + ch], b = (double)r0[c1 + ch], c = (double)r1[c0 + ch], d = (double)r1[c1 + ch];
+        const double top = a + fx * (b - a);
+        const double bot = c + fx * (d - c);
+        const double v = top + fy * (bot - top);
+        // float(v) / 255.0f through double: the double quotient of two floats rounds to the correctly rounded fp32 quotient
+        oc[ch * dplane + (size_t)i] = (float)((double)(float)v / 255.0);
+    }
+    const int xs = (x * Ws) / Wd, ys = (y * Hs) / Hd;      // products < 2^28; xs <= Ws - 1, ys <= Hs - 1
+    const size_t s = (size_t)ys * Ws + xs;
+    od[i] = (float)(raw_depth<DT>(depth, s) / depth_scale);
+    if (k == 0 && out_labels) {
+        const int id = labels[s];
+        const bool known = id >= 0 && id < n_ids;
+        const int* __restrict__ row = table + (size_t)(known ? id : 0) * L;      // not read unless known (and L > 0)
+        for (int l = 0; l < L; l++)
+            out_labels[l * dplane + (size_t)i] = known ? row[l] : id;
+        out_labels[L * dplane + (size_t)i] = id;
+    }
+}
+
+bool side_ok(int v) { return v >= 1 && v <= HSR_RESAMPLE_MAX_SIDE; }
+
+}  // namespace
+
+extern "C" int hsr_frame_ingest(int Hs, int Ws, const uint8_t* color_u8, const void* depth_raw, int depth_type, double depth_scale,
+                                const int* labels, int num_levels, const int* tree_table, int n_ids,
+                                int n_out, const hsr_ingest_level* levels, int64_t* out_labels, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_out < 1 || n_out > HSR_INGEST_MAX_LEVELS || !levels) {
+        hsr_set_error("frame_ingest: n_out must be 1..%d with a host array of that many levels; got %d", HSR_INGEST_MAX_LEVELS, n_out);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    bool sides = side_ok(Hs) && side_ok(Ws);
+    for (int k = 0; k < n_out; k++) sides = sides && side_ok(levels[k].H) && side_ok(levels[k].W);
+    if (!sides) {
+        hsr_set_error("frame_ingest: sides must be 1..%d: sensor %dx%d, level 0 %dx%d (of %d levels)", HSR_RESAMPLE_MAX_SIDE, Hs, Ws,
+                      levels[0].H, levels[0].W, n_out);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (depth_type != HSR_INGEST_DEPTH_U16 && depth_type != HSR_INGEST_DEPTH_I32 && depth_type != HSR_INGEST_DEPTH_F32) {
+        hsr_set_error("frame_ingest: depth_type must be HSR_INGEST_DEPTH_U16, _I32 or _F32; got %d", depth_type);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (!isfinite(depth_scale) || depth_scale == 0.0) {
+        hsr_set_error("frame_ingest: depth_scale must be finite and non-zero; got %g", depth_scale);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (num_levels < 0 || num_levels > HSR_EVAL_MAX_LEVELS || (num_levels > 0 && (!tree_table || n_ids < 1))) {
+        hsr_set_error("frame_ingest: num_levels must be 0..%d, and with num_levels > 0 a tree_table of n_ids >= 1 rows; got %d levels, "
+                      "n_ids %d", HSR_EVAL_MAX_LEVELS, num_levels, n_ids);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    bool null = !color_u8 || !depth_raw || ((labels == nullptr) != (out_labels == nullptr));
+    for (int k = 0; k < n_out; k++) null = null || !levels[k].color || !levels[k].depth;
+    if (null) {
+        hsr_set_error("frame_ingest: NULL color_u8 / depth_raw, a NULL output of a requested level, or labels without out_labels (or the reverse)");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    Levels lv{};
+    long long n_all = 0;
+    for (int k = 0; k < HSR_INGEST_MAX_LEVELS; k++) {
+        if (k < n_out) {
+            lv.l[k] = levels[k];
+            n_all += (long long)levels[k].H * levels[k].W;      // <= 3 * 2^28
+        } else {
+            lv.l[k] = hsr_ingest_level{0, 1, nullptr, nullptr};
+        }
+        lv.end[k] = n_all;
+    }
+    const unsigned nblk = (unsigned)((n_all + IB - 1) / IB);
+    long long* ol = reinterpret_cast<long long*>(out_labels);
+    const int n_ids_k = num_levels > 0 ? n_ids : 0;      // without a table no id is "known"
+#define HSR_INGEST_LAUNCH(DT) \
+    ingest_kernel<DT><<<nblk, IB, 0, stream>>>(color_u8, depth_raw, Hs, Ws, depth_scale, labels, num_levels, tree_table, n_ids_k, lv, n_all, ol)
+    if (depth_type == HSR_INGEST_DEPTH_U16) HSR_INGEST_LAUNCH(HSR_INGEST_DEPTH_U16);
+    else if (depth_type == HSR_INGEST_DEPTH_I32) HSR_INGEST_LAUNCH(HSR_INGEST_DEPTH_I32);
+    else HSR_INGEST_LAUNCH(HSR_INGEST_DEPTH_F32);
+#undef HSR_INGEST_LAUNCH
+    HSR_HIP_CHECK(hipGetLastError());
+    return HSR_OK;
+}

@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE and SIGNATURES_EXT_LOSS_OUTLIER against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER and SIGNATURES_EXT_FRAME_INGEST against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -58,6 +58,11 @@ class hsr_row_table(C.Structure):
 class hsr_adam_tensor(C.Structure):
     _fields_ = [("param", vp), ("grad", vp), ("exp_avg", vp), ("exp_avg_sq", vp), ("numel", C.c_int64),
                 ("step_size", cf), ("bc2_sqrt", cf), ("eps", cf), ("one_minus_beta1", cf), ("beta2", cf), ("one_minus_beta2", cf)]
+
+
+class hsr_ingest_level(C.Structure):
+    """one output level of hsr_frame_ingest (include/ext/hsr_frame_ingest.h)"""
+    _fields_ = [("H", ci), ("W", ci), ("color", vp), ("depth", vp)]
 
 
 bp, tk = C.POINTER(hsr_buffer), C.POINTER(hsr_ticket)
@@ -257,6 +262,13 @@ SIGNATURES_EXT_LOSS_OUTLIER = (
                                    vp, vp, vp, vp, vp]),
 )
 
+# include/ext/hsr_frame_ingest.h: a table of its own too (the four above are pinned by their suites)
+SIGNATURES_EXT_FRAME_INGEST = (
+    ("hsr_frame_ingest", ci, [ci, ci, vp, vp, ci, cd,
+                              vp, ci, vp, ci,
+                              ci, C.POINTER(hsr_ingest_level), vp, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -266,7 +278,7 @@ def _load():
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
-                                    + SIGNATURES_EXT_LOSS_OUTLIER):
+                                    + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

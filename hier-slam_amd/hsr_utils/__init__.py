@@ -10,6 +10,8 @@ from .synthetic import make_scene, make_upstream_grads  # noqa: F401
 _KEYFRAMES = ("keyframe_selection_overlap", "overlap_counts", "KeyframePoses", "mapping_window")
 _SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "SlamSession",
          "resample_frame")
+_FRAMES = ("tree_label_table", "ingest_frame")
+_SEQUENCE = ("ReplicaSequence", "tree_annotation")
 
 
 def __getattr__(name):
@@ -20,4 +22,10 @@ def __getattr__(name):
     if name in _SLAM:      # the loop driver binds the library too
         from . import slam
         return getattr(slam, name)
+    if name in _FRAMES:    # so does the ingest of raw sensor frames
+        from . import frames
+        return getattr(frames, name)
+    if name in _SEQUENCE:  # host only (PIL): resolved on first use like the rest
+        from . import sequence
+        return getattr(sequence, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

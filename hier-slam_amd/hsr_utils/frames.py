@@ -1,0 +1,136 @@
+"""Raw sensor frames to the tensors the frame loop takes, on the device (include/ext/hsr_frame_ingest.h): what the
+reference's dataset objects do between a decoded image and scripts/hierslam.py's loop, once per size
+(datasets/gradslam_datasets/basedataset.py:223-227 and scripts/hierslam.py:1777 for the colour image, basedataset.py:248-256 for the
+depth map, replica.py:241-299 and :369 for the labels).
+
+    tree_label_table(label_mapping_tree, num_levels, device)      the class-id -> level-labels table the ingest reads
+    ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_table=None)
+                                                                  ONE launch: every size's colour and depth, level 0's label planes
+
+There is no CPU path for the computation; host inputs are copied to the device once each.  hsr_utils.sequence reads a Replica-layout
+directory into the raw arrays ingest_frame takes; SlamSession.ingest (hsr_utils.slam) builds a frame dict for step() from them.
+"""
+import math
+
+import numpy as np
+import torch
+
+from diff_gaussian_rasterization import _abi
+
+_lib = _abi.lib
+
+INGEST_MAX_LEVELS = 3          # HSR_INGEST_MAX_LEVELS
+INGEST_MAX_SIDE = 16384        # HSR_RESAMPLE_MAX_SIDE
+INGEST_MAX_TREE_LEVELS = 16    # HSR_EVAL_MAX_LEVELS
+DEPTH_U16, DEPTH_I32, DEPTH_F32 = 0, 1, 2      # HSR_INGEST_DEPTH_*
+
+_LABEL_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def tree_label_table(label_mapping_tree, num_levels, device="cuda"):
+    """The dataset's label_mapping_tree ({leaf id (int or str): tuple of per-level labels}, the dict evaluate.tree_lookup_table takes)
+    as an int32 [n_ids, num_levels] device tensor, n_ids = the largest id + 1: row id holds the id's level labels.  A row the dict does
+    not name holds its own id in every column, which is what the ingest writes for an id beyond the table; of two equal keys (3 and
+    "3") the later one wins, as the reference's loop of masked assignments does (replica.py:241-247).  Built once on the host."""
+    L = int(num_levels)
+    if not 1 <= L <= INGEST_MAX_TREE_LEVELS:
+        raise ValueError("hsr_utils.frames: tree_label_table takes 1..%d levels, not %d" % (INGEST_MAX_TREE_LEVELS, L))
+    rows = {}
+    for key, value in label_mapping_tree.items():
+        value = [int(v) for v in value]
+        if len(value) != L:
+            raise RuntimeError("hsr_utils.frames: tree entry %r has %d levels, num_levels is %d" % (key, len(value), L))
+        if int(key) < 0:
+            raise RuntimeError("hsr_utils.frames: tree entry %r: class ids are not negative" % (key,))
+        rows[int(key)] = value
+    if not rows:
+        raise RuntimeError("hsr_utils.frames: an empty label_mapping_tree")
+    n_ids = max(rows) + 1
+    if n_ids > 1 << 24:
+        raise RuntimeError("hsr_utils.frames: a %d-row label table is too large" % n_ids)
+    table = np.repeat(np.arange(n_ids, dtype=np.int64)[:, None], L, axis=1)
+    for key, value in rows.items():
+        table[key] = value
+    if table.min() < -(1 << 31) or table.max() >= 1 << 31:
+        raise RuntimeError("hsr_utils.frames: level labels must fit in int32")
+    return torch.tensor(table.astype(np.int32), device=device)
+
+
+def _as_tensor(x, what):
+    if torch.is_tensor(x):
+        return x
+    if isinstance(x, np.ndarray):
+        if x.dtype == np.uint16:      # torch has no arithmetic on uint16: the bits travel as int16 and are read as uint16
+            x = x.view(np.int16)
+        try:
+            return torch.from_numpy(np.ascontiguousarray(x))
+        except TypeError:
+            raise RuntimeError("hsr_utils.frames: %s has dtype %s, which is not taken" % (what, x.dtype))
+    raise RuntimeError("hsr_utils.frames: %s must be a torch tensor or a numpy array, not %s" % (what, type(x).__name__))
+
+
+def ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_table=None):
+    """hsr_frame_ingest on one raw sensor frame: returns ([(color_i [3,h,w], depth_i [1,h,w]), ...] for the one to three (h, w) of
+    `sizes`, labels_out | None).  color_u8 is uint8 [Hs,Ws,3] as decoders deliver it; depth_raw [Hs,Ws] is uint16 (or int16 bits,
+    read as uint16), int32 or float32, in sensor units of 1 / png_depth_scale metres; labels, when given, is a [Hs,Ws] class-id image
+    of any integer dtype and labels_out is int64 [L + 1, h0, w0] at the FIRST size: one plane per column of tree_table (int32
+    [n_ids, L], tree_label_table; None: flat classes, L = 0), then the id itself.  Colour is float32 in 0..1, bilinear in float64 on
+    the 8-bit values; depth float32 metres, nearest (include/ext/hsr_frame_ingest.h states every step).  Inputs may be device tensors,
+    host tensors or numpy arrays: each host input is copied to the device once (the device of the first device tensor among the
+    inputs, else the current one).  One launch, no host synchronisation; there is no CPU path for the computation."""
+    color, depth = _as_tensor(color_u8, "color_u8"), _as_tensor(depth_raw, "depth_raw")
+    lab = None if labels is None else _as_tensor(labels, "labels")
+    if color.dtype != torch.uint8 or color.dim() != 3 or color.shape[2] != 3:
+        raise RuntimeError("hsr_utils.frames: color_u8 must be uint8 [Hs,Ws,3]; got %s %s" % (color.dtype, tuple(color.shape)))
+    Hs, Ws = int(color.shape[0]), int(color.shape[1])
+    uint16 = getattr(torch, "uint16", None)
+    if depth.dtype == torch.int16 or (uint16 is not None and depth.dtype == uint16):
+        depth_type = DEPTH_U16
+    elif depth.dtype == torch.int32:
+        depth_type = DEPTH_I32
+    elif depth.dtype == torch.float32:
+        depth_type = DEPTH_F32
+    else:
+        raise RuntimeError("hsr_utils.frames: depth_raw must be uint16 (or its bits as int16), int32 or float32; got %s" % depth.dtype)
+    if tuple(depth.shape) != (Hs, Ws):
+        raise RuntimeError("hsr_utils.frames: depth_raw must be [Hs,Ws] = [%d,%d] as the colour image; got %s" % (Hs, Ws, tuple(depth.shape)))
+    if lab is not None and (lab.dtype not in _LABEL_DTYPES or tuple(lab.shape) != (Hs, Ws)):
+        raise RuntimeError("hsr_utils.frames: labels must be an integer [Hs,Ws] = [%d,%d] image; got %s %s" % (Hs, Ws, lab.dtype, tuple(lab.shape)))
+    if tree_table is not None:
+        if lab is None:
+            raise RuntimeError("hsr_utils.frames: a tree_table without labels")
+        if not (torch.is_tensor(tree_table) and tree_table.dtype == torch.int32 and tree_table.dim() == 2 and tree_table.shape[0] >= 1
+                and 1 <= tree_table.shape[1] <= INGEST_MAX_TREE_LEVELS):
+            raise RuntimeError("hsr_utils.frames: tree_table must be an int32 [n_ids, 1..%d] tensor (tree_label_table)" % INGEST_MAX_TREE_LEVELS)
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if not 1 <= len(sizes) <= INGEST_MAX_LEVELS:
+        raise ValueError("hsr_utils.frames: ingest_frame takes one to three sizes, not %d" % len(sizes))
+    for side in (Hs, Ws) + tuple(v for hw in sizes for v in hw):
+        if not 1 <= side <= INGEST_MAX_SIDE:
+            raise ValueError("hsr_utils.frames: ingest_frame sides must be 1..%d; got a frame of %dx%d and sizes %s" % (INGEST_MAX_SIDE, Hs, Ws, sizes))
+    scale = float(png_depth_scale)
+    if not math.isfinite(scale) or scale == 0.0:
+        raise ValueError("hsr_utils.frames: ingest_frame: png_depth_scale must be finite and non-zero, not %r" % (png_depth_scale,))
+    given = [t for t in (color, depth, lab, tree_table) if t is not None]
+    dev = next((t.device for t in given if t.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("hsr_utils.frames: ingest_frame needs a HIP device; there is no CPU path")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    color, depth = color.to(dev).contiguous(), depth.to(dev).contiguous()
+    if lab is not None:
+        lab = lab.to(dev).to(torch.int32).contiguous()
+    L = 0
+    if tree_table is not None:
+        tree_table = tree_table.to(dev).contiguous()
+        L = int(tree_table.shape[1])
+    out = [(torch.empty((3, h, w), dtype=torch.float32, device=dev), torch.empty((1, h, w), dtype=torch.float32, device=dev)) for h, w in sizes]
+    levels = (_abi.hsr_ingest_level * len(sizes))(*[_abi.hsr_ingest_level(h, w, c.data_ptr(), d.data_ptr()) for (h, w), (c, d) in zip(sizes, out)])
+    labels_out = None if lab is None else torch.empty((L + 1,) + sizes[0], dtype=torch.int64, device=dev)
+    _abi.call(_lib.hsr_frame_ingest, "hsr_frame_ingest", dev, Hs, Ws, color.data_ptr(), depth.data_ptr(), depth_type, scale,
+              None if lab is None else lab.data_ptr(), L, None if tree_table is None else tree_table.data_ptr(),
+              0 if tree_table is None else int(tree_table.shape[0]), len(sizes), levels, None if labels_out is None else labels_out.data_ptr())
+    return out, labels_out
+
+
+__all__ = ["tree_label_table", "ingest_frame"]

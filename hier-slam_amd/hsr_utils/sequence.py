@@ -1,0 +1,145 @@
+"""Reading a Replica-layout sequence directory into the raw host arrays hsr_utils.frames.ingest_frame takes (host only: PIL, numpy,
+json; nothing here touches the device or the library).  The layout is the one datasets/gradslam_datasets/replica.py reads (:121-124,
+:331-350):
+
+    <basedir>/<sequence>/results/frame*.jpg          colour, 8 bit
+    <basedir>/<sequence>/results/depth*.png          depth, 16 bit, in units of 1 / png_depth_scale metres
+    <basedir>/<sequence>/traj.txt                    one line of 16 floats per frame: the 4x4 camera-to-world matrix, row by row
+    <semantic_dir>/<sequence>/semantic_class/semantic_class_*.png       optional: one raw class-id image per frame
+    <semantic_dir>/<sequence>/info_semantic_tree.json                   optional: read by tree_annotation
+
+FILE ORDER: the reference sorts its file lists with natsort.  Here the rule is stated: the files of a pattern are ordered by the
+tuple of the integers that the digit runs of their base name spell (frame9.jpg before frame10.jpg, frame000123.jpg after
+frame000099.jpg), ties by the name itself.  For names that differ only in one number, which is every name of this layout, that is
+natsort's order.
+
+    ReplicaSequence(basedir, sequence, start=0, end=-1, stride=1, semantic_dir=None)
+        len(seq), seq[i] -> (color uint8 [H,W,3], depth uint16 [H,W], labels | None, gt_w2c float32 [4,4])
+    tree_annotation(path, num_levels) -> (label_mapping_tree, num_semantic)
+
+Other datasets, undistortion, cropping, image pyramids and embeddings are not read.
+"""
+import glob
+import json
+import os
+import re
+
+import numpy as np
+
+
+def numeric_order(paths):
+    """`paths` ordered by the integers in their base names (module docstring, FILE ORDER)"""
+    return sorted(paths, key=lambda p: (tuple(int(d) for d in re.findall(r"\d+", os.path.basename(p))), os.path.basename(p)))
+
+
+def _read_image(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im)
+
+
+class ReplicaSequence:
+    """The retained frames [start:end:stride] of one sequence (basedataset.py:176-190: end == -1 means all; start < 0 or an end that
+    is neither -1 nor beyond start is a ValueError, as there).  seq[i] decodes frame i of the retained ones and returns raw host
+    arrays: colour uint8 [H,W,3], depth uint16 [H,W], the class-id image (the PNG's own integer dtype) or None without semantic_dir,
+    and gt_w2c, the world-to-camera matrix relative to the first RETAINED frame: inverse(inverse(c2w_first) @ c2w_i), the reference's
+    _preprocess_poses (basedataset.py:258-276) followed by the inverse of scripts/hierslam.py:1775, computed in float64 and returned
+    as float32.  traj.txt has one line per frame of the directory, before [start:end:stride] is taken."""
+
+    def __init__(self, basedir, sequence, start=0, end=-1, stride=1, semantic_dir=None):
+        start, end, stride = int(start), int(end), int(stride)
+        if start < 0:
+            raise ValueError("hsr_utils.sequence: start must not be negative; got %d" % start)
+        if not (end == -1 or end > start):
+            raise ValueError("hsr_utils.sequence: end (%d) must be -1 (all frames) or greater than start (%d)" % (end, start))
+        if stride < 1:
+            raise ValueError("hsr_utils.sequence: stride must be at least 1; got %d" % stride)
+        self.input_folder = os.path.join(basedir, sequence)
+        color = numeric_order(glob.glob(os.path.join(glob.escape(self.input_folder), "results", "frame*.jpg")))
+        depth = numeric_order(glob.glob(os.path.join(glob.escape(self.input_folder), "results", "depth*.png")))
+        if not color or len(color) != len(depth):
+            raise RuntimeError("hsr_utils.sequence: %s/results holds %d frame*.jpg and %d depth*.png files" % (self.input_folder, len(color), len(depth)))
+        with open(os.path.join(self.input_folder, "traj.txt")) as f:
+            lines = [ln for ln in f.read().splitlines() if ln.strip()]
+        if len(lines) < len(color):
+            raise RuntimeError("hsr_utils.sequence: traj.txt has %d poses for %d frames" % (len(lines), len(color)))
+        poses = []
+        for i in range(len(color)):
+            values = [float(v) for v in lines[i].split()]
+            if len(values) != 16:
+                raise RuntimeError("hsr_utils.sequence: traj.txt line %d has %d numbers, not 16" % (i + 1, len(values)))
+            poses.append(np.array(values, dtype=np.float64).reshape(4, 4))
+        semantic = None
+        if semantic_dir is not None:
+            folder = os.path.join(semantic_dir, sequence)
+            semantic = numeric_order(glob.glob(os.path.join(glob.escape(folder), "semantic_class", "semantic_class_*.png")))
+            if len(semantic) != len(color):
+                raise RuntimeError("hsr_utils.sequence: %s/semantic_class holds %d images for %d frames" % (folder, len(semantic), len(color)))
+        stop = len(color) if end == -1 else end
+        pick = slice(start, stop, stride)
+        self.color_paths, self.depth_paths = color[pick], depth[pick]
+        self.semantic_paths = None if semantic is None else semantic[pick]
+        self.retained_inds = list(range(len(color)))[pick]
+        self.c2w = poses[pick]
+        if not self.color_paths:
+            raise RuntimeError("hsr_utils.sequence: no frame of %d left by start=%d, end=%d, stride=%d" % (len(color), start, end, stride))
+        self._first_inv = np.linalg.inv(self.c2w[0])
+
+    def __len__(self):
+        return len(self.color_paths)
+
+    def gt_w2c(self, i):
+        rel_c2w = self._first_inv @ self.c2w[i]
+        return np.linalg.inv(rel_c2w).astype(np.float32)
+
+    def __getitem__(self, i):
+        i = range(len(self))[i]      # negative indices; IndexError beyond the end, so that iteration stops
+        color = _read_image(self.color_paths[i])
+        depth = _read_image(self.depth_paths[i])
+        if color.dtype != np.uint8 or color.ndim != 3 or color.shape[2] != 3:
+            raise RuntimeError("hsr_utils.sequence: %s is not an 8-bit three-channel image (%s %s)" % (self.color_paths[i], color.dtype, color.shape))
+        if depth.ndim != 2 or depth.shape != color.shape[:2]:
+            raise RuntimeError("hsr_utils.sequence: %s is not a one-channel image of the colour image's size (%s)" % (self.depth_paths[i], depth.shape))
+        if depth.dtype != np.uint16:      # PIL decodes a 16-bit grey PNG as int32 ('I') or uint16 ('I;16'), by version; the values are 0..65535
+            if depth.min() < 0 or depth.max() > 65535:
+                raise RuntimeError("hsr_utils.sequence: %s holds values outside 16 bits" % self.depth_paths[i])
+            depth = depth.astype(np.uint16)
+        labels = None
+        if self.semantic_paths is not None:
+            labels = _read_image(self.semantic_paths[i])
+            if labels.ndim != 2 or labels.shape != depth.shape or labels.dtype.kind not in "iu":
+                raise RuntimeError("hsr_utils.sequence: %s is not a one-channel integer image of the frame's size (%s %s)" % (
+                    self.semantic_paths[i], labels.dtype, labels.shape))
+        return np.ascontiguousarray(color), np.ascontiguousarray(depth), labels, self.gt_w2c(i)
+
+
+def tree_annotation(path, num_levels):
+    """info_semantic_tree.json as the reference reads it (replica.py:630-691 with :144-147).  The file is a dict whose keys are
+    "<class id>_<class name>" and whose values list, level by level from the root, one {"<level label>": "<name>"} dict per level
+    the class has.  Returns (label_mapping_tree, num_semantic):
+      label_mapping_tree  {class id as the key's str: tuple of num_levels level labels}, -1 where the class has fewer levels; in the
+                          file's order (what frames.tree_label_table and evaluate.tree_lookup_table take);
+      num_semantic        the classes per level, the largest label of the level + 1, with the number of classes of the file appended
+                          (the reference's find_max_level(flag_add=True) plus len(label_mapping_tree))."""
+    L = int(num_levels)
+    with open(path) as f:
+        annotations = json.load(f)
+    tree = {}
+    for key, item in annotations.items():
+        base_id = key.split("_")[0]
+        int(base_id)      # a key that does not begin with a class id is an error, as in the reference
+        if len(item) > L:
+            raise RuntimeError("hsr_utils.sequence: class %r has %d levels, num_levels is %d" % (key, len(item), L))
+        levels = [-1] * L
+        for i_level, level_info in enumerate(item):
+            for label in level_info:      # one entry per level; of several the last one stays
+                levels[i_level] = int(label)
+        tree[base_id] = tuple(levels)
+    if not tree:
+        raise RuntimeError("hsr_utils.sequence: %s names no class" % path)
+    columns = np.asarray(list(tree.values()), dtype=np.int64)
+    num_semantic = [int(columns[:, i].max()) + 1 for i in range(L)] + [len(tree)]
+    return tree, num_semantic
+
+
+__all__ = ["ReplicaSequence", "tree_annotation", "numeric_order"]

@@ -14,6 +14,7 @@ from the device rows this package already has plus two 
                                the first call (frame id 0) builds the map from the frame and maps it without densification
         track_frame(frame)     :1808-1904      map_frame(frame)     :1927-2083      add_keyframe(frame)     :2107-2124
         tracking_data(frame)   :1792-1799      densify_data(frame)  :1933-1941      {'im', 'depth', 'cam', 'intrinsics'} at that size
+        ingest(time_idx, color_u8, depth_raw, ...)      a frame dict for step() from the raw sensor images (hsr_utils.frames), one launch
 
 `config` is a dict with the reference's key names (configs/*/*.py): tracking / mapping (num_iters, lrs, loss_weights, sil_thres,
 use_sil_for_loss, use_l1, ignore_outlier_depth_loss; tracking: forward_prop, use_gt_poses, use_depth_loss_thres, depth_loss_thres;
@@ -33,9 +34,11 @@ as get_loss(tracking_curr_data) does; map_frame hands the silhouette densificati
 (:1933-1951); the first-frame map is built from the densification frame and intrinsics, scene_radius from its depth (:435-456).
 Keyframe selection, the mapping iterations, the keyframes and render() stay at the frame's own size (:1966, :1986-2075, :2107-2124).
 Both reduced frames come from ONE resample_frame launch per frame (one shared level when the two sizes are equal), cached for the
-current frame.  The reference resamples the SENSOR image to each size; the session resamples the frame it is given: the same thing
-when the frame is at sensor resolution, not when the frame was itself resized — a caller who needs the reference's frames there
-passes 'tracking_im' / 'tracking_depth' / 'densify_im' / 'densify_depth' in the frame, and they are used in place of the resample.
+current frame.  The reference resamples the SENSOR image to each size.  A frame built by ingest() does the same: the frame's own size
+and both reduced sizes come from one hsr_frame_ingest launch on the sensor images, the reduced ones travel in the frame as
+'tracking_im' / 'tracking_depth' / 'densify_im' / 'densify_depth', and nothing is resampled again.  For a frame NOT built by ingest()
+the session resamples the frame it is given: the same thing when that frame is at sensor resolution, not when it was itself resized
+(a caller may pass the four tensors above, and they are used in place of the resample).
 Semantic sessions take the same route: :1949 passes densify_curr_data to the semantic densification and :480-496 is the first-frame
 code, although the reference never constructs the densification dataset for that branch (its own comment at :480: "not run").
 
@@ -368,6 +371,40 @@ class SlamSession:
         """what the silhouette densification and the first-frame map read (:1933-1941, :435-450), at densification size"""
         im, depth = self._level_data(frame)['densify']
         return {'im': im, 'depth': depth, 'cam': self.densify_cam, 'intrinsics': self.densify_intrinsics}
+
+    def ingest(self, time_idx, color_u8, depth_raw, gt_w2c=None, labels=None, tree_table=None, png_depth_scale=None):
+        """A frame dict for step() from the raw sensor images (hsr_utils.frames.ingest_frame; basedataset.py:223-227, :248-256,
+        replica.py:241-299, scripts/hierslam.py:1777): 'id', 'im' and 'depth' at cam.image_height x cam.image_width, 'gt_w2c' and
+        'semantic_label_gt' (int64 [levels + 1, H, W]; tree_table: frames.tree_label_table, None for flat classes) where given, and
+        'tracking_im' / 'tracking_depth' / 'densify_im' / 'densify_depth' for every level whose size differs from the frame's — all
+        from ONE launch on the sensor image (levels of one size share their tensors), so that step() resamples nothing.
+        png_depth_scale defaults to config['data']['png_depth_scale'] (or the same key at the top level); a KeyError without either."""
+        from . import frames
+        if png_depth_scale is None:
+            cfg = self.config
+            data = cfg.get('data') or {}
+            if 'png_depth_scale' in cfg:
+                png_depth_scale = cfg['png_depth_scale']
+            elif 'png_depth_scale' in data:
+                png_depth_scale = data['png_depth_scale']
+            else:
+                raise KeyError("config['data']['png_depth_scale']")
+        sizes, uses = [(self.cam.image_height, self.cam.image_width)], {}
+        for use, cam in (('tracking', self.tracking_cam), ('densify', self.densify_cam)):
+            hw = (cam.image_height, cam.image_width)
+            if cam is not self.cam:
+                if hw not in sizes:
+                    sizes.append(hw)
+                uses[use] = sizes.index(hw)
+        levels, labels_out = frames.ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=labels, tree_table=tree_table)
+        frame = {'id': int(time_idx), 'im': levels[0][0], 'depth': levels[0][1]}
+        if gt_w2c is not None:
+            frame['gt_w2c'] = gt_w2c
+        if labels_out is not None:
+            frame['semantic_label_gt'] = labels_out
+        for use, k in uses.items():
+            frame[use + '_im'], frame[use + '_depth'] = levels[k]
+        return frame
 
     # -- first frame --
     def initialize(self, frame):

@@ -7,10 +7,12 @@
  *
  * RESTATED, NOT PINNED BY cv2: the reference resizes with cv2.resize, which is not available to this project's tests.  Both rules
  * are restated below and checked against two independent float64 restatements (tests/resample_ref.py: torch F.interpolate, and
- * scipy.ndimage.map_coordinates / integer indexing).  The reference resizes the colour image while it is still uint8 (the / 255 of
- * scripts/hierslam.py comes later), and cv2's 8-bit INTER_LINEAR works with fixed-point weights and rounds to a grey level; this
- * kernel interpolates the fp32 image in 0..1 and rounds nothing, so its colours can differ from the reference's by about half a grey
- * level (0.002).  The depth rule copies and has no such difference.
+ * scipy.ndimage.map_coordinates / integer indexing).  The reference resizes the colour image before the / 255 of scripts/hierslam.py,
+ * but not as uint8: it reads the image with dtype=float (basedataset.py:298, replica.py:381), so cv2 interpolates in float64 on the
+ * values 0..255 and rounds to no grey level.  This kernel interpolates the fp32 image in 0..1 with fp32 weights and rounds nothing
+ * either, so its colours differ from the reference's only by fp32 rounding (about 5e-7 of the 0..1 range) — and, when the frame it is
+ * given was itself quantised or resized, by that.  hsr_frame_ingest.h interpolates the 8-bit sensor image in float64 as the reference
+ * does and is the closer of the two.  The depth rule copies and has no such difference.
  *
  * One call is ONE launch and produces up to two levels (H0,W0) and (H1,W1) of the same source frame; H1 == 0 skips level 1 (its
  * two pointers are then not read and nothing is written through them).  Source and destination sides are each 1 .. HSR_RESAMPLE_MAX_SIDE,
