@@ -1,10 +1,11 @@
 // hsr_block.h — workgroup primitives of the frame-sized helper units (internal, not part of the C ABI): wave and block sums, predicate
-// counts, the order-preserving compaction rank, the single-workgroup exclusive scan, and the two fp32 chains several units share
-// (pinhole back-projection, depth error).  Everything is __device__ __forceinline__, so the including file's flags (-ffp-contract=off
+// counts, the order-preserving compaction rank, the single-workgroup exclusive scan, the fp32 chains several units share (pinhole
+// back-projection, depth error) and the SSIM window.  Every device function is __device__ __forceinline__, so the including file's flags (-ffp-contract=off
 // where the Makefile says so) apply to the inlined code.  Waves have 64 lanes; "block256" means exactly 256 threads in x (4 waves),
 // "block1024" exactly 1024 (16 waves).  The rasterizer's hot path has its own tuned reductions (hsr_wave_reduce.h) and does not use these.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 
 // ---- waves -------------------------------------------------------------------------------------------------------------------
 // xor butterfly 32, 16, ..., 1: every lane returns the wave's total (float, double, int, unsigned)
@@ -146,3 +147,22 @@ __device__ __forceinline__ float hsr_depth_scale(float z, const hsr_pinhole& f) 
 
 // scripts/hierslam.py:911, in this order: |gt - d| * (gt > 0)
 __device__ __forceinline__ float hsr_depth_error(float gt, float d) { return fabsf(gt - d) * (gt > 0.f ? 1.f : 0.f); }
+
+// ---- the SSIM window of the loss head and of MS-SSIM ---------------------------------------------------------------------------
+// gaussian(11, 1.5) as float32, normalised in float32 (utils/slam_external.py:54-56); built on the host, passed to the kernels by value.
+// Each unit keeps its own 11-tap blur4 because the two round differently on purpose, and tests pin both: hsr_losses.hip runs an fmaf
+// chain from 0 (the products are never rounded), hsr_msssim.hip is compiled with -ffp-contract=off and rounds every product and every
+// sum once, in tap order, like the restatements its value is pinned against.
+struct hsr_gauss { float g[11]; };
+
+inline hsr_gauss hsr_gauss_window()
+{
+    hsr_gauss win;
+    float sum = 0.f;
+    for (int x = 0; x < 11; x++) {
+        win.g[x] = (float)std::exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
+        sum += win.g[x];
+    }
+    for (int x = 0; x < 11; x++) win.g[x] = win.g[x] / sum;
+    return win;
+}

@@ -11,7 +11,9 @@
 //     11-tap passes with sliding register windows; the forward pass also writes the three partial-derivative maps, the
 //     backward pass is the adjoint correlation of those;
 //   * tree cross-entropy: one thread per pixel walks the levels, channels are read with stride H*W (coalesced across
-//     the wave), online log-sum-exp, then softmax - onehot straight into the planar gradient — no [H*W, n] permute.
+//     the wave); a level of up to 16 channels sits in registers (exact max, then sum), a wider one is streamed with an
+//     online log-sum-exp; the value pass counts the valid labels, the gradient pass writes softmax - onehot straight
+//     into the planar gradient — no [H*W, n] permute.
 // All HBM-bound; algorithmic bytes per pixel: L1 4C*3 (+1 mask), SSIM 4C*(2 + 3) fwd + 4C*(3 + 2 + 1) bwd, CE 4K*3 + 8L.
 // The tracking loss of include/hsr_losses.h (hsr_loss_tracking_*: mask, both masked sums and their gradients as one head) is not here: it
 // shares its kernels with the outlier-rejecting head in hsr_loss_masked.hip.
@@ -109,10 +111,8 @@ __global__ __launch_bounds__(LB) void l1_kernel(const float* __restrict__ pred, 
 // so the 121-tap correlation is evaluated as a horizontal then a vertical 11-tap pass (the two differ from the 2-D form by
 // one fp32 rounding per weight).  Tile = 32x32 outputs, 42x42 inputs in LDS; both passes slide a 14-value register window
 // over 4 consecutive outputs, so a pixel costs ~27 LDS reads and ~130 FMAs instead of 242 and 605.
-struct Gauss { float g[11]; };
-
 template <int NQ>
-__device__ __forceinline__ void blur4(const float (&v)[NQ][14], const Gauss& gw, float (&out)[NQ][4])
+__device__ __forceinline__ void blur4(const float (&v)[NQ][14], const hsr_gauss& gw, float (&out)[NQ][4])
 {
 #pragma unroll
     for (int q = 0; q < NQ; q++)
@@ -127,7 +127,7 @@ __device__ __forceinline__ void blur4(const float (&v)[NQ][14], const Gauss& gw,
 
 // grid (tiles_x, tiles_y, C); block 256
 __global__ __launch_bounds__(LB) void ssim_forward_kernel(const float* __restrict__ img1, const float* __restrict__ img2, int H, int W,
-                                                          Gauss gw, float* __restrict__ d_mu1, float* __restrict__ d_s11,
+                                                          hsr_gauss gw, float* __restrict__ d_mu1, float* __restrict__ d_s11,
                                                           float* __restrict__ d_s12, float* __restrict__ partials)
 {
     __shared__ float s_x[SS_E][SS_E + 1], s_y[SS_E][SS_E + 1];
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(LB) void ssim_forward_kernel(const float* __restric
 // adjoint of the zero-padded correlation with a symmetric window = the same correlation of the three partial-derivative
 // maps (which are zero outside the image)
 __global__ __launch_bounds__(LB) void ssim_backward_kernel(const float* __restrict__ img1, const float* __restrict__ img2, int H, int W,
-                                                           Gauss gw, const float* __restrict__ d_mu1, const float* __restrict__ d_s11,
+                                                           hsr_gauss gw, const float* __restrict__ d_mu1, const float* __restrict__ d_s11,
                                                            const float* __restrict__ d_s12, float inv_n_host, const float* __restrict__ upstream,
                                                            float* __restrict__ grad)
 {
@@ -260,62 +260,18 @@ struct Levels {
     float weight[HSR_LOSS_MAX_LEVELS];
 };
 
-__global__ __launch_bounds__(LB) void ce_count_kernel(const int64_t* __restrict__ labels, int N, int num_levels, int ignore_index,
-                                                      unsigned* __restrict__ partials)
+// valid labels (!= ignore_index) of ONE label plane per block: the leaf head's count (the tree kernel counts in its value pass)
+__global__ __launch_bounds__(LB) void valid_label_count_kernel(const int64_t* __restrict__ labels, int N, int ignore_index,
+                                                               unsigned* __restrict__ partials)
 {
     __shared__ unsigned s_red[4];
     const int i = blockIdx.x * LB + threadIdx.x;
-    for (int l = 0; l < num_levels; l++) {
-        __syncthreads();   // thread 0 may still be reading the level before
-        const unsigned total = hsr_block256_count(i < N && labels[(size_t)l * N + i] != (int64_t)ignore_index, s_red);
-        if (threadIdx.x == 0) partials[(size_t)blockIdx.x * HSR_LOSS_MAX_LEVELS + l] = total;
-    }
+    const unsigned total = hsr_block256_count(i < N && labels[i] != (int64_t)ignore_index, s_red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(LB) void tree_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int N, int K,
-                                                     Levels lv, int ignore_index, const float* __restrict__ inv_count,
-                                                     float* __restrict__ grad, float* __restrict__ partials)
-{
-    __shared__ float s_red[4];
-    const int i = blockIdx.x * LB + threadIdx.x;
-    const bool live = i < N;
-    const size_t p = live ? (size_t)i : 0;
-    int covered_end = 0;
-    for (int l = 0; l < lv.n; l++) {
-        const int b = lv.begin[l], n = lv.size[l];
-        const int64_t lab64 = labels[(size_t)l * N + p];
-        const bool valid = live && lab64 != (int64_t)ignore_index;
-        const int lab = (int)lab64;
-        // online log-sum-exp over the level's channels (stride N: consecutive lanes read consecutive pixels)
-        float m = -INFINITY, s = 0.f, picked = 0.f;
-        for (int c = 0; c < n; c++) {
-            const float z = logits[(size_t)(b + c) * N + p];
-            const float nm = fmaxf(m, z);
-            s = s * expf(m - nm) + expf(z - nm);
-            m = nm;
-            picked = c == lab ? z : picked;
-        }
-        const float lse = m + logf(s);
-        const float loss = valid ? lse - picked : 0.f;
-        if (grad && live) {
-            const float sc = valid ? lv.weight[l] * inv_count[l] : 0.f;
-            const float inv_s = 1.0f / s;
-            for (int c = 0; c < n; c++) {
-                const float z = logits[(size_t)(b + c) * N + p];   // second read comes from L2
-                const float sm = expf(z - m) * inv_s;
-                grad[(size_t)(b + c) * N + p] = (sm - (c == lab ? 1.f : 0.f)) * sc;
-            }
-        }
-        const float tot = hsr_block256_sum(loss, s_red);
-        if (threadIdx.x == 0) partials[(size_t)blockIdx.x * HSR_LOSS_MAX_LEVELS + l] = tot;
-        covered_end = b + n;
-    }
-    if (grad && live)
-        for (int c = covered_end; c < K; c++) grad[(size_t)c * N + p] = 0.f;   // channels behind the last level
-}
-
-// Two-pass form (round 4): the value pass counts the valid labels itself and writes no gradient; the gradient pass runs when autograd
-// asks for it and multiplies by the upstream gradient it reads from device memory — no label pre-pass, no stashed K x H x W gradient, no
+// Two passes: the value pass counts the valid labels itself and writes no gradient; the gradient pass runs when autograd asks for it
+// and multiplies by the upstream gradient it reads from device memory — no label pre-pass, no stashed K x H x W gradient, no
 // `stash * g` multiply afterwards (at 1200 x 680, K = 26: 76 + 35 + 23 us of launches became 2 passes of 118 and 203 MB).
 // A level of at most CE_REG channels is held in registers: all its loads go out together, one expf per channel, no second read.
 constexpr int CE_REG = 16;
@@ -324,11 +280,11 @@ constexpr int CE_ITEMS = 1;   // pixels per thread (2 was measured: 41 + 47 us a
 
 // TB: threads per block — the value pass runs 1 024 (a quarter of the block partials for its one-block finisher), the gradient pass 256
 template <bool GRAD, int TB>
-__global__ __launch_bounds__(TB) void tree_ce2_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int N, int K,
-                                                      Levels lv, int ignore_index, const float* __restrict__ inv_count,
-                                                      const float* __restrict__ upstream, float* __restrict__ grad,
-                                                      float* __restrict__ partials /* [nblk][2 * MAX_LEVELS]: loss sums, then counts */,
-                                                      const float* __restrict__ add_grad, const float* __restrict__ add_scale, float add_host_scale)
+__global__ __launch_bounds__(TB) void tree_ce_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int N, int K,
+                                                     Levels lv, int ignore_index, const float* __restrict__ inv_count,
+                                                     const float* __restrict__ upstream, float* __restrict__ grad,
+                                                     float* __restrict__ partials /* [nblk][2 * MAX_LEVELS]: loss sums, then counts */,
+                                                     const float* __restrict__ add_grad, const float* __restrict__ add_scale, float add_host_scale)
 {
     // GRAD: out = tree part + add_grad * (add_scale[0] * add_host_scale) — another head's stashed gradient of the same map (the leaf head's)
     // joins here instead of costing its own `stash * g` pass and autograd's add of the two K x H x W maps
@@ -697,7 +653,9 @@ extern "C" size_t hsr_loss_scratch_bytes(int channels, int H, int W)
     const size_t N = (size_t)H * W;
     const size_t tiles = (size_t)((W + SS_T - 1) / SS_T) * ((H + SS_T - 1) / SS_T);
     const size_t blocks = (N + LB - 1) / LB + 1;
-    // SSIM: three partial-derivative maps + one partial per tile;  CE: MAX_LEVELS partials per block, twice;  L1: small
+    // SSIM: three partial-derivative maps + one partial per tile;  L1: small;  CE: the term is kept as callers' allocations know it
+    // (MAX_LEVELS partials per 256-pixel block, twice).  hsr_loss_tree_ce needs hsr_loss_tree_ce_scratch_bytes(H, W) = align256(2 x) + 256
+    // with x = (blocks - 1) * MAX_LEVELS floats, and align256(2 x) <= 2 align256(x): the term is ample
     size_t need = hsr_align256(3 * (size_t)channels * N * sizeof(float)) + hsr_align256((size_t)channels * tiles * sizeof(float));
     const size_t ce = 2 * hsr_align256(blocks * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
     const size_t l1 = 2 * hsr_align256((size_t)channels * blocks * sizeof(float)) + 256;
@@ -748,19 +706,6 @@ extern "C" int hsr_loss_l1(int C, int H, int W, const float* pred, const float* 
 }
 
 namespace {
-Gauss ssim_window()
-{
-    // the reference's 1-D window: gaussian(11, 1.5) as float32, normalised in float32 (utils/slam_external.py:54-56)
-    Gauss win;
-    float sum = 0.f;
-    for (int x = 0; x < 11; x++) {
-        win.g[x] = (float)std::exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
-        sum += win.g[x];
-    }
-    for (int x = 0; x < 11; x++) win.g[x] = win.g[x] / sum;
-    return win;
-}
-
 dim3 ssim_grid(int C, int H, int W) { return dim3((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, C); }
 
 float ssim_inv_n(int C, int H, int W) { return (float)(1.0 / ((double)C * (double)((size_t)H * W))); }
@@ -770,7 +715,7 @@ void launch_ssim_value(int C, int H, int W, const float* img1, const float* img2
 {
     const size_t CN = (size_t)C * H * W;
     const dim3 grid = ssim_grid(C, H, W);
-    ssim_forward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, ssim_window(), maps, maps ? maps + CN : nullptr, maps ? maps + 2 * CN : nullptr,
+    ssim_forward_kernel<<<grid, LB, 0, stream>>>(img1, img2, H, W, hsr_gauss_window(), maps, maps ? maps + CN : nullptr, maps ? maps + 2 * CN : nullptr,
                                                  partials);
     finish_kernel<<<1, LB, 0, stream>>>(partials, (int)(grid.x * grid.y * grid.z), 1, 1, nullptr, ssim_inv_n(C, H, W), out_ssim);
 }
@@ -780,7 +725,7 @@ void launch_ssim_grad(int C, int H, int W, const float* img1, const float* img2,
                       hipStream_t stream)
 {
     const size_t CN = (size_t)C * H * W;
-    ssim_backward_kernel<<<ssim_grid(C, H, W), LB, 0, stream>>>(img1, img2, H, W, ssim_window(), maps, maps + CN, maps + 2 * CN, ssim_inv_n(C, H, W),
+    ssim_backward_kernel<<<ssim_grid(C, H, W), LB, 0, stream>>>(img1, img2, H, W, hsr_gauss_window(), maps, maps + CN, maps + 2 * CN, ssim_inv_n(C, H, W),
                                                                 upstream, out_grad);
 }
 }  // namespace
@@ -900,6 +845,36 @@ int parse_levels(const char* who, int K, int H, int W, int num_levels, const int
 }
 }  // namespace
 
+extern "C" size_t hsr_loss_tree_ce_scratch_bytes(int H, int W)
+{
+    if (H < 1 || W < 1) return 1024;
+    const size_t nb = ((size_t)H * W + LB - 1) / LB;
+    return hsr_align256(nb * 2 * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
+}
+
+namespace {
+constexpr int CE_VB = 1024;   // threads per block of the value pass
+
+// level losses (means over the valid labels) and 1 / valid labels per level; partials: hsr_loss_tree_ce_scratch_bytes(H, W) - 256 bytes
+void launch_tree_ce_value(int N, int K, const Levels& lv, const float* logits, const int64_t* labels, int ignore_index, float* partials,
+                          float* out_level_loss, float* out_inv_count, hipStream_t stream)
+{
+    const int nb = (N + CE_VB * CE_ITEMS - 1) / (CE_VB * CE_ITEMS);
+    tree_ce_kernel<false, CE_VB><<<nb, CE_VB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, nullptr, nullptr, nullptr, partials, nullptr, nullptr, 0.f);
+    tree_ce_finish_kernel<<<1, CEF_T, 0, stream>>>(partials, nb, lv.n, out_level_loss, out_inv_count);
+}
+
+// upstream[0] (DEVICE, NULL = 1) * d (sum_l weight_l * loss_l) / d logits + add_grad * add_scale[0] * add_host_scale (add_grad NULL: no join)
+void launch_tree_ce_grad(int N, int K, const Levels& lv, const float* logits, const int64_t* labels, int ignore_index, const float* inv_count,
+                         const float* upstream, const float* add_grad, const float* add_scale, float add_host_scale, float* out_grad,
+                         hipStream_t stream)
+{
+    tree_ce_kernel<true, LB><<<(N + LB * CE_ITEMS - 1) / (LB * CE_ITEMS), LB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, inv_count, upstream, out_grad, nullptr, add_grad,
+                                                               add_scale, add_host_scale);
+}
+}  // namespace
+
+// One call: the value pass and, if out_grad is given, the gradient pass; block partials at the front of the scratch, then 1 / count.
 extern "C" int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight,
                                 const float* logits, const int64_t* labels, int ignore_index, float* out_level_loss, float* out_grad,
                                 char* scratch, size_t scratch_bytes, void* stream_)
@@ -912,34 +887,22 @@ extern "C" int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* 
         hsr_set_error("loss_tree_ce: NULL logits / labels / out_level_loss");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const int N = H * W;
-    const int nb = (N + LB - 1) / LB;
-    const size_t part_bytes = hsr_align256((size_t)nb * HSR_LOSS_MAX_LEVELS * sizeof(float));
-    rc = hsr_check_scratch("loss_tree_ce", scratch, scratch_bytes, 2 * part_bytes + 256);
+    // hsr_loss_tree_ce_scratch_bytes: the value pass's partials and 256 bytes, here the 1 / count vector
+    const size_t part_bytes = hsr_loss_tree_ce_scratch_bytes(H, W) - 256;
+    rc = hsr_check_scratch("loss_tree_ce", scratch, scratch_bytes, part_bytes + 256);
     if (rc != HSR_OK) return rc;
-    float* partials = reinterpret_cast<float*>(scratch);
-    unsigned* cparts = reinterpret_cast<unsigned*>(scratch + part_bytes);
-    float* inv = reinterpret_cast<float*>(scratch + 2 * part_bytes);
-    ce_count_kernel<<<nb, LB, 0, stream>>>(labels, N, num_levels, ignore_index, cparts);
-    count_finish_kernel<<<1, LB, 0, stream>>>(cparts, nb, HSR_LOSS_MAX_LEVELS, num_levels, inv);
-    tree_ce_kernel<<<nb, LB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, inv, out_grad, partials);
-    finish_kernel<<<1, LB, 0, stream>>>(partials, nb, HSR_LOSS_MAX_LEVELS, num_levels, inv, 1.0f, out_level_loss);
+    float* inv = reinterpret_cast<float*>(scratch + part_bytes);
+    launch_tree_ce_value(H * W, K, lv, logits, labels, ignore_index, reinterpret_cast<float*>(scratch), out_level_loss, inv, stream);
+    if (out_grad) launch_tree_ce_grad(H * W, K, lv, logits, labels, ignore_index, inv, nullptr, nullptr, nullptr, 0.f, out_grad, stream);
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
 
-extern "C" size_t hsr_loss_tree_ce_scratch_bytes(int H, int W)
-{
-    if (H < 1 || W < 1) return 1024;
-    const size_t nb = ((size_t)H * W + LB - 1) / LB;
-    return hsr_align256(nb * 2 * HSR_LOSS_MAX_LEVELS * sizeof(float)) + 256;
-}
-
+// The two passes on their own, for an autograd node: the caller keeps out_inv_count until the gradient pass.
 extern "C" int hsr_loss_tree_ce_value(int K, int H, int W, int num_levels, const int* level_sizes, const float* logits,
                                       const int64_t* labels, int ignore_index, float* out_level_loss, float* out_inv_count,
                                       char* scratch, size_t scratch_bytes, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     Levels lv;
     int rc = parse_levels("loss_tree_ce_value", K, H, W, num_levels, level_sizes, nullptr, &lv);
     if (rc != HSR_OK) return rc;
@@ -947,14 +910,10 @@ extern "C" int hsr_loss_tree_ce_value(int K, int H, int W, int num_levels, const
         hsr_set_error("loss_tree_ce_value: NULL logits / labels / out_level_loss / out_inv_count");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const int N = H * W;
-    constexpr int VB = 1024;
-    const int nb = (N + VB * CE_ITEMS - 1) / (VB * CE_ITEMS);
     rc = hsr_check_scratch("loss_tree_ce_value", scratch, scratch_bytes, hsr_loss_tree_ce_scratch_bytes(H, W) - 256);
     if (rc != HSR_OK) return rc;
-    float* partials = reinterpret_cast<float*>(scratch);
-    tree_ce2_kernel<false, VB><<<nb, VB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, nullptr, nullptr, nullptr, partials, nullptr, nullptr, 0.f);
-    tree_ce_finish_kernel<<<1, CEF_T, 0, stream>>>(partials, nb, num_levels, out_level_loss, out_inv_count);
+    launch_tree_ce_value(H * W, K, lv, logits, labels, ignore_index, reinterpret_cast<float*>(scratch), out_level_loss, out_inv_count,
+                         (hipStream_t)stream_);
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
@@ -964,7 +923,6 @@ extern "C" int hsr_loss_tree_ce_grad(int K, int H, int W, int num_levels, const 
                                      const float* upstream, const float* add_grad, const float* add_scale, float add_host_scale,
                                      float* out_grad, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     Levels lv;
     int rc = parse_levels("loss_tree_ce_grad", K, H, W, num_levels, level_sizes, level_weight, &lv);
     if (rc != HSR_OK) return rc;
@@ -972,9 +930,8 @@ extern "C" int hsr_loss_tree_ce_grad(int K, int H, int W, int num_levels, const 
         hsr_set_error("loss_tree_ce_grad: NULL logits / labels / inv_count / out_grad");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    const int N = H * W;
-    tree_ce2_kernel<true, LB><<<(N + LB * CE_ITEMS - 1) / (LB * CE_ITEMS), LB, 0, stream>>>(logits, labels, N, K, lv, ignore_index, inv_count, upstream, out_grad, nullptr, add_grad,
-                                                                add_scale, add_host_scale);
+    launch_tree_ce_grad(H * W, K, lv, logits, labels, ignore_index, inv_count, upstream, add_grad, add_scale, add_host_scale, out_grad,
+                        (hipStream_t)stream_);
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
@@ -1008,8 +965,8 @@ extern "C" int hsr_loss_leaf_mlp_ce(int K, int C, int H, int W, const float* sem
     float* part_loss = reinterpret_cast<float*>(scratch + wt_bytes + 256);
     float* part_dw = reinterpret_cast<float*>(scratch + wt_bytes + 256 + loss_bytes);
     leaf_pack_weights_kernel<<<(CT * 16 * LM_KP + 255) / 256, 256, 0, stream>>>(weight, bias, K, C, CT * 16, wt);
-    ce_count_kernel<<<(N + LB - 1) / LB, LB, 0, stream>>>(labels, N, 1, ignore_index, reinterpret_cast<unsigned*>(part_dw));
-    count_finish_kernel<<<1, LB, 0, stream>>>(reinterpret_cast<unsigned*>(part_dw), (N + LB - 1) / LB, HSR_LOSS_MAX_LEVELS, 1, inv);
+    valid_label_count_kernel<<<(N + LB - 1) / LB, LB, 0, stream>>>(labels, N, ignore_index, reinterpret_cast<unsigned*>(part_dw));
+    count_finish_kernel<<<1, LB, 0, stream>>>(reinterpret_cast<unsigned*>(part_dw), (N + LB - 1) / LB, 1, 1, inv);
     const int ku = (K + 1 + 3) & ~3;
 #define HSR_LEAF_LAUNCH(KU_, MC_) leaf_mlp_ce_kernel<KU_, MC_><<<nblk, 256, 0, stream>>>(sem, wt, labels, N, K, C, CT, ignore_index, inv, d_sem, part_loss, part_dw)
     if (CT <= 3) {         // <= 48 classes (NYU40 + void)

@@ -29,8 +29,6 @@ constexpr int MS_E = MS_T + 10;          // tile: inputs per side
 constexpr int MS_P = MS_E / 2 + 1;       // pooled candidates per side of a tile (the last tile owns up to 42 rows / columns)
 constexpr int NS = HSR_EVAL_MSSSIM_SCALES;
 
-struct Gauss { float g[11]; };
-
 struct Levels {
     int h[NS], w[NS];
     int tiles[NS];               // tiles_x * tiles_y
@@ -62,22 +60,9 @@ Levels levels_of(int H, int W)
     return lv;
 }
 
-// the 1-D window gaussian(11, 1.5) as float32, normalised in float32: the window of hsr_losses.hip
-Gauss window()
-{
-    Gauss win;
-    float sum = 0.f;
-    for (int x = 0; x < 11; x++) {
-        win.g[x] = (float)std::exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5));
-        sum += win.g[x];
-    }
-    for (int x = 0; x < 11; x++) win.g[x] = win.g[x] / sum;
-    return win;
-}
-
 // 4 consecutive outputs of the 11-tap filter from a 14-value window, taps in index order, one rounding per product and per sum
 template <int NQ>
-__device__ __forceinline__ void blur4(const float (&v)[NQ][14], const Gauss& gw, float (&out)[NQ][4])
+__device__ __forceinline__ void blur4(const float (&v)[NQ][14], const hsr_gauss& gw, float (&out)[NQ][4])
 {
 #pragma unroll
     for (int q = 0; q < NQ; q++)
@@ -105,7 +90,7 @@ struct ScaleArgs {
 
 // grid (tiles_x, tiles_y, 3); block 256
 template <bool FIRST>
-__global__ __launch_bounds__(MB) void scale_kernel(ScaleArgs a, Gauss gw)
+__global__ __launch_bounds__(MB) void scale_kernel(ScaleArgs a, hsr_gauss gw)
 {
     __shared__ float s_x[MS_E][MS_E + 1], s_y[MS_E][MS_E + 1];
     __shared__ float s_h[5][MS_E][MS_T + 1];   // horizontally filtered x, y, xx, yy, xy
@@ -273,7 +258,7 @@ extern "C" int hsr_eval_msssim(int H, int W, const float* im, const float* gt_im
     const Levels lv = levels_of(H, W);
     float* pyr = reinterpret_cast<float*>(scratch);
     double* partials = reinterpret_cast<double*>(scratch + hsr_align256((size_t)lv.pyr_floats * sizeof(float)));
-    const Gauss gw = window();
+    const hsr_gauss gw = hsr_gauss_window();
     for (int s = 0; s < NS; s++) {
         ScaleArgs a{};
         a.h = lv.h[s];

@@ -27,16 +27,27 @@ LEAF_MAX_K, LEAF_MAX_C = 31, 128
 _weight_cache = {}
 
 
-def _chw(t, what):
+def _dev(t, what):
+    """float32 on a HIP device, contiguous"""
     if not t.is_cuda:
         raise RuntimeError("hsr_utils.losses: %s must live on a HIP device (got %s); there is no CPU path" % (what, t.device))
     if t.dtype != torch.float32:
         raise RuntimeError("hsr_utils.losses: %s must be float32 (got %s)" % (what, t.dtype))
+    return t.contiguous()
+
+
+def _chw(t, what):
+    t = _dev(t, what)
     if t.dim() == 2:
         t = t.unsqueeze(0)
     if t.dim() != 3:
         raise RuntimeError("hsr_utils.losses: %s must be [C,H,W] or [H,W]" % what)
-    return t.contiguous()
+    return t
+
+
+def _p(t):
+    """the device pointer of an optional tensor"""
+    return None if t is None else t.data_ptr()
 
 
 def _scratch(ch, H, W, dev):
@@ -64,8 +75,8 @@ class _L1(torch.autograd.Function):
         ctx.two_pass = bool(pred.requires_grad) and (int(reduction) == SUM or m is None)
         grad = torch.empty_like(p) if (pred.requires_grad and not ctx.two_pass) else None
         sc = _scratch(Cc, H, W, dev)
-        _abi.call(_lib.hsr_loss_l1, "hsr_loss_l1", dev, Cc, H, W, p.data_ptr(), g.data_ptr(), None if m is None else m.data_ptr(),
-                  int(reduction), out.data_ptr(), None if grad is None else grad.data_ptr(), sc.data_ptr(), sc.numel())
+        _abi.call(_lib.hsr_loss_l1, "hsr_loss_l1", dev, Cc, H, W, p.data_ptr(), g.data_ptr(), _p(m), int(reduction),
+                  out.data_ptr(), _p(grad), sc.data_ptr(), sc.numel())
         ctx.grad = None if grad is None else grad.view(shape)
         if ctx.two_pass:
             ctx.save_for_backward(p, g, m if m is not None else torch.empty(0, device=dev))
@@ -99,8 +110,8 @@ class _SSIM(torch.autograd.Function):
         # value pass now (it leaves the three partial-derivative maps), the adjoint correlation in backward() times the incoming gradient
         maps = torch.empty((3, Cc, H, W), dtype=torch.float32, device=dev) if img1.requires_grad else None
         sc = torch.empty(4096 + 4 * Cc * ((H + 31) // 32) * ((W + 31) // 32), dtype=torch.uint8, device=dev)
-        _abi.call(_lib.hsr_loss_ssim_value, "hsr_loss_ssim_value", dev, Cc, H, W, a.data_ptr(), b.data_ptr(), out.data_ptr(),
-                  None if maps is None else maps.data_ptr(), sc.data_ptr(), sc.numel())
+        _abi.call(_lib.hsr_loss_ssim_value, "hsr_loss_ssim_value", dev, Cc, H, W, a.data_ptr(), b.data_ptr(), out.data_ptr(), _p(maps),
+                  sc.data_ptr(), sc.numel())
         ctx.want = maps is not None
         if ctx.want:
             ctx.save_for_backward(a, b, maps)
@@ -121,30 +132,49 @@ class _SSIM(torch.autograd.Function):
         return grad.view(shape), None
 
 
+def _tree_value(z, labels, level_sizes, ignore_index, with_leaf=False):
+    """The tree value pass (include/hsr_losses.h, hsr_loss_tree_ce_value) over the first len(level_sizes) label planes; with_leaf: one more
+    plane, the leaf labels, must follow them.  Returns (all label planes kept, level sizes as c_int[], level losses, 1 / valid labels)."""
+    K, H, W = z.shape
+    dev = z.device
+    L = len(level_sizes)
+    lab = labels.reshape(-1, H, W)
+    if lab.shape[0] < L + bool(with_leaf):
+        raise RuntimeError(("hsr_utils.losses: %d label planes for %d tree levels + the leaf level" if with_leaf else
+                            "hsr_utils.losses: %d label planes for %d levels") % (lab.shape[0], L))
+    lab = (lab if with_leaf else lab[:L]).to(device=dev, dtype=torch.int64).contiguous()   # the reference calls .long()
+    sizes = (C.c_int * L)(*[int(s) for s in level_sizes])
+    levels = torch.empty(L, dtype=torch.float32, device=dev)
+    inv = torch.empty(L, dtype=torch.float32, device=dev)
+    sc = torch.empty(int(_lib.hsr_loss_tree_ce_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _abi.call(_lib.hsr_loss_tree_ce_value, "hsr_loss_tree_ce_value", dev, K, H, W, L, sizes, z.data_ptr(), lab.data_ptr(), int(ignore_index),
+              levels.data_ptr(), inv.data_ptr(), sc.data_ptr(), sc.numel())
+    return lab, sizes, levels, inv
+
+
+def _tree_grad(z, lab, inv, sizes, weights, ignore_index, g, add_grad=None, add_scale=None, add_host_scale=0.0):
+    """The tree gradient pass (hsr_loss_tree_ce_grad): g * d (sum_l weights[l] * loss_l) / d z, plus add_grad * add_scale * add_host_scale when
+    another head's gradient of the same map joins.  weights: a c_float[] or None (all ones); g, add_scale: 0-dim device tensors."""
+    K, H, W = z.shape
+    grad = torch.empty_like(z)
+    _abi.call(_lib.hsr_loss_tree_ce_grad, "hsr_loss_tree_ce_grad", z.device, K, H, W, len(sizes), sizes, weights, z.data_ptr(), lab.data_ptr(),
+              ignore_index, inv.data_ptr(), g.data_ptr(), _p(add_grad), _p(add_scale), add_host_scale, grad.data_ptr())
+    return grad
+
+
 class _TreeCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, labels, level_sizes, weights, ignore_index):
         z = _chw(logits, "logits")
-        K, H, W = z.shape
         dev = z.device
-        L = len(level_sizes)
-        lab = labels.reshape(-1, H, W)
-        if lab.shape[0] < L:
-            raise RuntimeError("hsr_utils.losses: %d label planes for %d levels" % (lab.shape[0], L))
-        lab = lab[:L].to(device=dev, dtype=torch.int64).contiguous()   # the reference calls .long()
-        sizes = (C.c_int * L)(*[int(s) for s in level_sizes])
-        w = None if weights is None else (C.c_float * L)(*[float(x) for x in weights])
         # value now, gradient when (and if) autograd asks for it — the gradient pass multiplies by the incoming gradient itself, so
         # no K x H x W gradient is stashed and none is multiplied by `g` afterwards (include/hsr_losses.h, hsr_loss_tree_ce_value / _grad)
-        out = torch.empty(L, dtype=torch.float32, device=dev)
-        inv = torch.empty(L, dtype=torch.float32, device=dev)
-        sc = torch.empty(int(_lib.hsr_loss_tree_ce_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-        _abi.call(_lib.hsr_loss_tree_ce_value, "hsr_loss_tree_ce_value", dev, K, H, W, L, sizes, z.data_ptr(), lab.data_ptr(),
-                  int(ignore_index), out.data_ptr(), inv.data_ptr(), sc.data_ptr(), sc.numel())
+        lab, sizes, out, inv = _tree_value(z, labels, level_sizes, ignore_index)
         ctx.want = bool(logits.requires_grad)
         if ctx.want:
             ctx.save_for_backward(z, lab, inv)
-            ctx.meta = (K, H, W, L, sizes, w, int(ignore_index), tuple(logits.shape))
+            w = None if weights is None else (C.c_float * len(sizes))(*[float(x) for x in weights])
+            ctx.meta = (sizes, w, int(ignore_index), tuple(logits.shape))
         ctx.mark_non_differentiable(out)
         if weights is None:
             return out.sum(), out
@@ -159,13 +189,9 @@ class _TreeCE(torch.autograd.Function):
         if not ctx.want or g_total is None:
             return None, None, None, None, None
         z, lab, inv = ctx.saved_tensors
-        K, H, W, L, sizes, w, ignore_index, shape = ctx.meta
-        dev = z.device
-        g = g_total.to(device=dev, dtype=torch.float32).contiguous()
-        grad = torch.empty_like(z)
-        _abi.call(_lib.hsr_loss_tree_ce_grad, "hsr_loss_tree_ce_grad", dev, K, H, W, L, sizes, w, z.data_ptr(), lab.data_ptr(), ignore_index,
-                  inv.data_ptr(), g.data_ptr(), None, None, 0.0, grad.data_ptr())
-        return grad.view(shape), None, None, None, None
+        sizes, w, ignore_index, shape = ctx.meta
+        g = g_total.to(device=z.device, dtype=torch.float32).contiguous()
+        return _tree_grad(z, lab, inv, sizes, w, ignore_index, g).view(shape), None, None, None, None
 
 
 class _WeightedSum(torch.autograd.Function):
@@ -233,9 +259,8 @@ class _MaskedLoss(torch.autograd.Function):
         out = torch.empty(6 if reject else 4, dtype=torch.float32, device=dev)
         selected = torch.empty(1, dtype=torch.int32, device=dev) if reject else None
         sc = torch.empty(int(getattr(_abi.lib, head + "_scratch_bytes")(H, W)), dtype=torch.uint8, device=dev)
-        _abi.call(getattr(_abi.lib, head + "_value"), head + "_value", dev, Cc, H, W, None if a is None else a.data_ptr(),
-                  None if b is None else b.data_ptr(), d.data_ptr(), gd.data_ptr(), None if s is None else s.data_ptr(), float(sil_thres),
-                  int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(),
+        _abi.call(getattr(_abi.lib, head + "_value"), head + "_value", dev, Cc, H, W, _p(a), _p(b), d.data_ptr(),
+                  gd.data_ptr(), _p(s), float(sil_thres), int(bool(use_sil)), int(reduction), float(w_depth), float(w_im), out.data_ptr(),
                   *((selected.data_ptr(),) if reject else ()), sc.data_ptr(), sc.numel())
         ctx.want = (bool(im is not None and im.requires_grad), bool(depth.requires_grad))
         if any(ctx.want):
@@ -262,7 +287,7 @@ class _MaskedLoss(torch.autograd.Function):
         thr = (out.data_ptr() + 20,) if out.numel() == 6 else ()         # &out6[5]: the threshold of the value pass
         _abi.call(getattr(_abi.lib, head + "_grad"), head + "_grad", dev, Cc, H, W, a.data_ptr() if Cc else None,
                   b.data_ptr() if Cc else None, d.data_ptr(), gd.data_ptr(), s.data_ptr() if use_sil else None, sil_thres, use_sil, w_depth,
-                  w_im, *thr, gg.data_ptr(), inv_ptr, None if d_im is None else d_im.data_ptr(), None if d_d is None else d_d.data_ptr())
+                  w_im, *thr, gg.data_ptr(), inv_ptr, _p(d_im), _p(d_d))
         return (None if d_im is None else d_im.view(shape_im), None, None if d_d is None else d_d.view(shape_d)) + (None,) * 8
 
 
@@ -351,29 +376,33 @@ def cross_entropy_planar(logits, labels, ignore_index=-100):
     return tree_cross_entropy(z, labels.reshape(1, z.shape[-2], z.shape[-1]), (z.shape[0],), None, ignore_index)
 
 
+def _leaf_head(z, weight, bias, labels, ignore_index, need):
+    """The fused leaf head (hsr_loss_leaf_mlp_ce) on the checked map z.  need: which of (map, weight, bias) want a gradient.  Returns the loss
+    [1] and d loss / d (z, weight, bias), the last two shaped like their parameters, None where nothing asked."""
+    K, H, W = z.shape
+    dev = z.device
+    w = _dev(weight.reshape(weight.shape[0], -1), "weight")
+    Cc = w.shape[0]
+    if w.shape[1] != K or bias.numel() != Cc:
+        raise RuntimeError("hsr_utils.losses: weight %s / bias %s do not match %d input channels" % (tuple(weight.shape), tuple(bias.shape), K))
+    b = _dev(bias.reshape(-1), "bias")
+    lab = labels.reshape(H, W).to(device=dev, dtype=torch.int64).contiguous()
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    d_sem = torch.empty_like(z) if need[0] else None
+    d_w = torch.empty_like(w) if (need[1] or need[2]) else None
+    d_b = torch.empty_like(b) if (need[1] or need[2]) else None
+    sc = _scratch(K, H, W, dev)
+    _abi.call(_lib.hsr_loss_leaf_mlp_ce, "hsr_loss_leaf_mlp_ce", dev, K, Cc, H, W, z.data_ptr(), w.data_ptr(), b.data_ptr(), lab.data_ptr(),
+              int(ignore_index), out.data_ptr(), _p(d_sem), _p(d_w), _p(d_b), sc.data_ptr(), sc.numel())
+    return out, d_sem, None if d_w is None else d_w.view(weight.shape), None if d_b is None else d_b.view(bias.shape)
+
+
 class _LeafMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sem, weight, bias, labels, ignore_index):
-        z = _chw(sem, "im_semantic")
-        K, H, W = z.shape
-        dev = z.device
-        w = _dev2(weight.reshape(weight.shape[0], -1), "weight")
-        C = w.shape[0]
-        if w.shape[1] != K or bias.numel() != C:
-            raise RuntimeError("hsr_utils.losses: weight %s / bias %s do not match %d input channels" % (tuple(weight.shape), tuple(bias.shape), K))
-        b = _dev2(bias.reshape(-1), "bias")
-        lab = labels.reshape(H, W).to(device=dev, dtype=torch.int64).contiguous()
-        out = torch.empty(1, dtype=torch.float32, device=dev)
         need = (sem.requires_grad, weight.requires_grad, bias.requires_grad)
-        d_sem = torch.empty_like(z) if need[0] else None
-        d_w = torch.empty_like(w) if (need[1] or need[2]) else None
-        d_b = torch.empty_like(b) if (need[1] or need[2]) else None
-        sc = _scratch(K, H, W, dev)
-        _abi.call(_lib.hsr_loss_leaf_mlp_ce, "hsr_loss_leaf_mlp_ce", dev, K, C, H, W, z.data_ptr(), w.data_ptr(), b.data_ptr(), lab.data_ptr(),
-                  int(ignore_index), out.data_ptr(), None if d_sem is None else d_sem.data_ptr(), None if d_w is None else d_w.data_ptr(),
-                  None if d_b is None else d_b.data_ptr(), sc.data_ptr(), sc.numel())
-        ctx.grads = (None if d_sem is None else d_sem.view(sem.shape), None if d_w is None else d_w.view(weight.shape),
-                     None if d_b is None else d_b.view(bias.shape))
+        out, d_sem, d_w, d_b = _leaf_head(_chw(sem, "im_semantic"), weight, bias, labels, ignore_index, need)
+        ctx.grads = (None if d_sem is None else d_sem.view(sem.shape), d_w, d_b)
         return out[0]
 
     @staticmethod
@@ -392,59 +421,31 @@ class _SemanticHeads(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sem, weight, bias, labels, level_sizes, w_tree, w_leaf, ignore_index):
         z = _chw(sem, "im_semantic")
-        K, H, W = z.shape
-        dev = z.device
         L = len(level_sizes)
-        lab = labels.reshape(-1, H, W)
-        if lab.shape[0] < L + 1:
-            raise RuntimeError("hsr_utils.losses: %d label planes for %d tree levels + the leaf level" % (lab.shape[0], L))
-        lab = lab.to(device=dev, dtype=torch.int64).contiguous()
-        tree_lab, leaf_lab = lab[:L], lab[-1]
-        wt = _dev2(weight.reshape(weight.shape[0], -1), "weight")
-        Cc = wt.shape[0]
-        if wt.shape[1] != K or bias.numel() != Cc:
-            raise RuntimeError("hsr_utils.losses: weight %s / bias %s do not match %d input channels" % (tuple(weight.shape), tuple(bias.shape), K))
-        b = _dev2(bias.reshape(-1), "bias")
-        sizes = (C.c_int * L)(*[int(s) for s in level_sizes])
-        levels = torch.empty(L, dtype=torch.float32, device=dev)
-        inv = torch.empty(L, dtype=torch.float32, device=dev)
-        leaf = torch.empty(1, dtype=torch.float32, device=dev)
         need = (sem.requires_grad, weight.requires_grad, bias.requires_grad)
-        d_sem = torch.empty_like(z) if need[0] else None
-        d_w = torch.empty_like(wt) if (need[1] or need[2]) else None
-        d_b = torch.empty_like(b) if (need[1] or need[2]) else None
-        sc1 = torch.empty(int(_lib.hsr_loss_tree_ce_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
-        sc2 = _scratch(K, H, W, dev)
-        _abi.call(_lib.hsr_loss_tree_ce_value, "hsr_loss_tree_ce_value", dev, K, H, W, L, sizes, z.data_ptr(), tree_lab.data_ptr(),
-                  int(ignore_index), levels.data_ptr(), inv.data_ptr(), sc1.data_ptr(), sc1.numel())
-        _abi.call(_lib.hsr_loss_leaf_mlp_ce, "hsr_loss_leaf_mlp_ce", dev, K, Cc, H, W, z.data_ptr(), wt.data_ptr(), b.data_ptr(),
-                  leaf_lab.data_ptr(), int(ignore_index), leaf.data_ptr(), None if d_sem is None else d_sem.data_ptr(),
-                  None if d_w is None else d_w.data_ptr(), None if d_b is None else d_b.data_ptr(), sc2.data_ptr(), sc2.numel())
+        lab, sizes, levels, inv = _tree_value(z, labels, level_sizes, ignore_index, with_leaf=True)
+        leaf, d_sem, d_w, d_b = _leaf_head(z, weight, bias, lab[-1], ignore_index, need)
         ctx.want = need
         if need[0]:
-            ctx.save_for_backward(z, tree_lab, inv)
-        ctx.meta = (K, H, W, L, sizes, float(w_tree), float(w_leaf), int(ignore_index), tuple(sem.shape))
-        ctx.stash = (d_sem, None if d_w is None else d_w.view(weight.shape), None if d_b is None else d_b.view(bias.shape))
+            ctx.save_for_backward(z, lab[:L], inv)
+        ctx.meta = (sizes, float(w_tree), float(w_leaf), int(ignore_index), tuple(sem.shape))
+        ctx.stash = (d_sem, d_w, d_b)
         ctx.mark_non_differentiable(levels)
         total = levels.sum() * float(w_tree) + leaf[0] * float(w_leaf)
         return total, levels, leaf[0].detach()
 
     @staticmethod
     def backward(ctx, g, _g_levels, _g_leaf):
-        K, H, W, L, sizes, w_tree, w_leaf, ignore_index, shape = ctx.meta
+        sizes, w_tree, w_leaf, ignore_index, shape = ctx.meta
         d_sem, d_w, d_b = ctx.stash
         if g is None:
             return (None,) * 8
         out_sem = None
         if ctx.want[0]:
             z, tree_lab, inv = ctx.saved_tensors
-            dev = z.device
-            gg = g.to(device=dev, dtype=torch.float32).contiguous()
-            wl = (C.c_float * L)(*([w_tree] * L))
-            grad = torch.empty_like(z)
-            _abi.call(_lib.hsr_loss_tree_ce_grad, "hsr_loss_tree_ce_grad", dev, K, H, W, L, sizes, wl, z.data_ptr(), tree_lab.data_ptr(),
-                      ignore_index, inv.data_ptr(), gg.data_ptr(), d_sem.data_ptr(), gg.data_ptr(), w_leaf, grad.data_ptr())
-            out_sem = grad.view(shape)
+            gg = g.to(device=z.device, dtype=torch.float32).contiguous()
+            wl = (C.c_float * len(sizes))(*([w_tree] * len(sizes)))
+            out_sem = _tree_grad(z, tree_lab, inv, sizes, wl, ignore_index, gg, d_sem, gg, w_leaf).view(shape)
         gl = g * w_leaf
         return (out_sem, None if (d_w is None or not ctx.want[1]) else d_w * gl, None if (d_b is None or not ctx.want[2]) else d_b * gl,
                 None, None, None, None, None)
@@ -468,14 +469,6 @@ def semantic_loss_mlp(im_semantic, labels, num_semantic, mlp, weight_sem=(1.0, 1
     total, levels, leaf = _SemanticHeads.apply(im_semantic, weight, bias, labels, tuple(num_semantic), float(weight_sem[0]), float(weight_sem[1]),
                                                ignore_index)
     return (total, levels, leaf) if return_parts else total
-
-
-def _dev2(t, what):
-    if not t.is_cuda:
-        raise RuntimeError("hsr_utils.losses: %s must live on a HIP device (got %s); there is no CPU path" % (what, t.device))
-    if t.dtype != torch.float32:
-        raise RuntimeError("hsr_utils.losses: %s must be float32 (got %s)" % (what, t.dtype))
-    return t.contiguous()
 
 
 def leaf_mlp_cross_entropy(im_semantic, mlp, labels, ignore_index=-100):

@@ -8,7 +8,7 @@
  *   calc_ssim                         11x11 Gaussian window, zero padding, mean      utils/slam_external.py:54-97
  *   multi-level cross-entropy         CrossEntropyLoss per tree level over channel   scripts/hierslam.py:963-974, :993-1003,
  *                                     ranges of the K logit planes                   transfer_tree_rendered_labelmap :91-111
- * Every entry point computes the loss value AND d loss / d input in the same call (one read of the maps): the value
+ * Every one-call entry point computes the loss value AND d loss / d input in the same call: the value
  * goes to a device scalar, the gradient to a caller-owned plane set.  The 1x1-conv leaf MLP (scripts/hierslam.py:1756)
  * stays a torch Conv2d; its logits go through hsr_loss_tree_ce with one level.
  *
@@ -85,7 +85,10 @@ int hsr_loss_ssim_grad(int C, int H, int W, const float* img1, const float* img2
  * outside every level get 0.  `level_sizes` and `level_weight` are HOST arrays of num_levels entries; level_weight == NULL
  * means all ones.  Labels must lie in [0, level_sizes[l]) or equal ignore_index (torch asserts this; here an out-of-range
  * label is treated as matching no class: its pixel contributes the log-sum-exp and gets the plain softmax as its gradient,
- * and such a pixel still counts toward the mean).  hsr_loss_leaf_mlp_ce follows the same rule. */
+ * and such a pixel still counts toward the mean).  hsr_loss_leaf_mlp_ce follows the same rule.
+ * This entry point is the two passes below run back to back — hsr_loss_tree_ce_value, then (if out_grad is given) hsr_loss_tree_ce_grad with
+ * upstream = NULL and no add_grad, the block partials and 1 / count in `scratch` — and returns bit for bit what they return.
+ * Scratch: hsr_loss_scratch_bytes(K, H, W), or hsr_loss_tree_ce_scratch_bytes(H, W), which is what it needs. */
 int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight, const float* logits,
                      const int64_t* labels, int ignore_index, float* out_level_loss, float* out_grad, char* scratch,
                      size_t scratch_bytes, void* stream);
@@ -97,7 +100,7 @@ int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* level_sizes
  * another head's gradient with respect to the same map (the leaf head's stashed d loss / d sem) joins in the same pass,
  * out_grad += add_grad * add_scale[0] * add_host_scale (`add_scale`: DEVICE float or NULL = 1) — instead of a `stash * g` pass of its own and
  * autograd's add of two K x H x W maps.  Scratch (value pass):
- * hsr_loss_tree_ce_scratch_bytes(H, W) — block partials only, a few hundred KB. */
+ * hsr_loss_tree_ce_scratch_bytes(H, W) — block partials (and room for the one-call entry's 1 / count), a few hundred KB. */
 size_t hsr_loss_tree_ce_scratch_bytes(int H, int W);
 int hsr_loss_tree_ce_value(int K, int H, int W, int num_levels, const int* level_sizes, const float* logits, const int64_t* labels,
                            int ignore_index, float* out_level_loss, float* out_inv_count, char* scratch, size_t scratch_bytes,

@@ -275,15 +275,18 @@ def test_leaf_mlp_head_wide_falls_back_to_conv_plus_fused_ce():
     assert abs(float(loss) - float(ref)) < 1e-5 and sem.grad is not None and mlp.weight.grad is not None
 
 
-def test_tree_ce_two_pass_form_matches_the_one_pass_entry_point_and_scales_by_the_upstream_gradient():
-    """hsr_loss_tree_ce_value / _grad (what the autograd node calls since round 4) against hsr_loss_tree_ce (value and gradient in one
-    pass, still exported): same level losses, same gradient; an upstream gradient g != 1 scales it inside the gradient pass; a level
-    wider than the 16 channels the kernel holds in registers takes its streaming path."""
+def test_tree_ce_one_call_entry_is_bit_for_bit_the_value_and_gradient_passes_and_the_upstream_gradient_scales():
+    """hsr_loss_tree_ce is hsr_loss_tree_ce_value and hsr_loss_tree_ce_grad run back to back: the autograd node's level losses and a direct
+    value / gradient call pair equal its outputs bit for bit (same NaN pattern); an upstream gradient g != 1 scales the gradient inside the
+    gradient pass; a level wider than the 16 channels the kernel holds in registers takes its streaming path.  So that the equalities are
+    not all there is, the one-call outputs are also held to the float64 oracle at this file's bounds."""
     import ctypes as C
+    import loss_oracle as LO
     from hsr_utils import losses as L
     g = np.random.default_rng(17)
     for sizes, K, H, W in (([2, 4, 6, 6, 8], 26, 37, 61), ([3, 21, 5], 31, 19, 33)):   # second: a 21-channel level
-        z = torch.tensor(g.normal(0, 3, (K, H, W)).astype(np.float32), device="cuda")
+        z_np = g.normal(0, 3, (K, H, W)).astype(np.float32)
+        z = torch.tensor(z_np, device="cuda")
         lab_np = np.stack([g.integers(0, n, (H, W)) for n in sizes]).astype(np.int64)
         lab_np[1, :3] = -100
         lab = torch.tensor(lab_np, device="cuda")
@@ -295,12 +298,29 @@ def test_tree_ce_two_pass_form_matches_the_one_pass_entry_point_and_scales_by_th
         s = torch.cuda.current_stream().cuda_stream
         assert L._lib.hsr_loss_tree_ce(K, H, W, n, csz, cw, z.data_ptr(), lab.data_ptr(), -100, out1.data_ptr(), grad1.data_ptr(),
                                        sc.data_ptr(), sc.numel(), s) == 0
+        # the two entry points called directly: same weights, no upstream gradient, no join
+        out2, inv2, grad2 = torch.empty(n, device="cuda"), torch.empty(n, device="cuda"), torch.empty_like(z)
+        sc2 = torch.empty(int(L._lib.hsr_loss_tree_ce_scratch_bytes(H, W)), dtype=torch.uint8, device="cuda")
+        assert L._lib.hsr_loss_tree_ce_value(K, H, W, n, csz, z.data_ptr(), lab.data_ptr(), -100, out2.data_ptr(), inv2.data_ptr(),
+                                             sc2.data_ptr(), sc2.numel(), s) == 0
+        assert L._lib.hsr_loss_tree_ce_grad(K, H, W, n, csz, cw, z.data_ptr(), lab.data_ptr(), -100, inv2.data_ptr(), None, None, None, 0.0,
+                                            grad2.data_ptr(), s) == 0
         zz = z.clone().requires_grad_(True)
         total, levels = L.tree_cross_entropy(zz, lab, sizes, weights=w, return_levels=True)
         (3.5 * total).backward()
         torch.cuda.synchronize()
-        np.testing.assert_allclose(levels.cpu().numpy(), out1.cpu().numpy(), rtol=2e-6)
+        nan1 = torch.isnan(out1)
+        for lv in (levels, out2):
+            assert torch.equal(torch.isnan(lv), nan1) and torch.equal(lv[~nan1], out1[~nan1])
+        assert torch.equal(grad2, grad1)
         assert _relmax(zz.grad.cpu().numpy(), 3.5 * grad1.cpu().numpy()) < GRAD_TOL
+        lo, go = LO.tree_cross_entropy(z_np, lab_np, sizes)
+        np.testing.assert_allclose(out1.cpu().numpy(), lo, rtol=3e-6)
+        gw, b0 = go.copy(), 0
+        for nl, wl in zip(sizes, w):
+            gw[b0:b0 + nl] *= wl
+            b0 += nl
+        assert _relmax(grad1.cpu().numpy(), gw) < GRAD_TOL
 
 
 def test_weighted_sum_is_the_python_arithmetic_it_replaces():
