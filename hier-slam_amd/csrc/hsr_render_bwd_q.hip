@@ -38,7 +38,9 @@
 //   * with K > 0 the kernel is bound by its gradient atomics, not by any of this: three 64-byte lines per (splat, quadrant) row,
 //     4.57 M requests at the headline = 0.225 ms at the memory side's rate, 0.28 measured with or without the instruction savings.
 //     What helps there is fewer LINES: compact rows (hsr_tile_common.h) make K = 0 one line instead of two and 12 <= K <= 20 two
-//     instead of three; K = 26 needs 36 floats and stays at three.
+//     instead of three; K = 26 needs 36 floats and stays at three.  Or fewer ROWS: a splat that reaches a tile reaches 1.66 of its quadrants,
+//     so with three-line rows line 0 is summed over the tile in LDS and sent once per (splat, tile) (MERGE in the kernel; EXPERIMENTS.md §10h):
+//     4.59 M -> 3.99 M requests, 0.277 -> 0.262 ms.
 #include "hsr_bwd_tile.h"
 
 #ifdef HSR_TRACE
@@ -95,6 +97,11 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
     constexpr int NCH = GEO ? 0 : KC + 5;          // sem[KC], r, g, b, depth, opacity(direct)
     constexpr int NG = GEO ? 0 : (NCH + 15) / 16;  // 16-channel groups
     constexpr int NGA = NG > 0 ? NG : 1;
+    // Two channel groups with classic rows (K = 21..27, three 64-byte lines per row): line 0 of a splat's row — columns 0..6 — leaves ONCE
+    // per (splat, tile) instead of once per (splat, quadrant).  The quadrants' flushes add their seven sums into a per-batch table in LDS
+    // (two LDS-atomic wave-instructions per chunk), the median-depth gradient goes into its column 6, and the workgroup sends each slot's
+    // line when the batch is over ("line 0 of a finished batch" below).  Lines 1 and 2 leave per quadrant, as everywhere else.
+    constexpr bool MERGE = NG == 2 && !CL;
     static_assert(NG <= 2, "at most 32 direct channels per launch");
     static_assert(BATCH <= 256 && (BATCH + 1) * ENTB < 65536, "batch slots are bytes, record offsets 16 bits");
     // one 48-byte record per staged splat { x, y, A', B' | r, g, b, depth | C', opacity, B'/2, - }; record BATCH is the dummy
@@ -109,7 +116,8 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
     __shared__ uint2 s_ord[4][4][Q_ORD];               // per (wave, group): { record offset, segment byte offset } of the entries the group visits: no decoding in the loop
     __shared__ uint32_t s_rowent[4][Q_ROWS];           // record offset of each chunk row
     __shared__ __attribute__((aligned(16))) uint32_t s_cid[4][Q_ROWS];   // packed-row offset (Gaussian id x row stride) of each chunk row
-    __shared__ float s_medj[BATCH];                    // median-depth gradient of each staged splat: see "median" below
+    __shared__ float s_medj[MERGE ? 1 : BATCH];        // median-depth gradient of each staged splat: see "median" below (MERGE: column 6 of s_l0)
+    __shared__ __attribute__((aligned(16))) float s_l0[MERGE ? BATCH : 1][8];   // MERGE: columns 0..6 of each staged splat's row, summed over the tile
     __shared__ uint8_t s_segtab[4][Q_ROWS][4];         // segment of each (row, group) pair of the chunk, Q_SEG_ZERO where the group does not visit the row
 
     const int tile = hsr_block_tile(blockIdx.x, hsr_num_tiles(a.W, a.H));
@@ -281,7 +289,7 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
         }
         const uint32_t eo = s_rowent[wv][l16];
         // median: whatever has been added for this row's splat so far, by any wave — taken (exchanged with zero), so that it is emitted once
-        if (!SEMA && gq == 0 && eo < (uint32_t)(BATCH * ENTB)) medsum = atomicExch(&s_medj[eo / ENTB], 0.f);
+        if (!SEMA && !MERGE && gq == 0 && eo < (uint32_t)(BATCH * ENTB)) medsum = atomicExch(&s_medj[eo / ENTB], 0.f);
         const float4* ent = reinterpret_cast<const float4*>(entb + eo);
         const float4 e0 = ent[0], e2 = ent[2];
         float s0[4], s1[4], s2[4];
@@ -379,6 +387,8 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             }
         } else {
             // columns 0..6: two wave-instructions of 8 rows x 7 values, so that each row's line is ONE request
+            // MERGE: the same two wave-instructions add into the batch table, slot of the row's splat (cid: the row's record offset, i.e.
+            // slot x ENTB, instead of its packed-row offset); the line leaves when the batch is over
             const int vi = lane & 7;
             float4 sa[2];
             uint32_t cid[2];
@@ -386,18 +396,51 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             for (int pass = 0; pass < 2; pass++) {
                 const int row = (lane >> 3) + 8 * pass;
                 sa[pass] = *reinterpret_cast<const float4*>(tb + row * Q_TB + vi * 4);
-                cid[pass] = s_cid[wv][row];
+                cid[pass] = MERGE ? s_rowent[wv][row] : s_cid[wv][row];
             }
             asm volatile("" : "+v"(sa[0].x), "+v"(sa[1].x), "+v"(cid[0]), "+v"(cid[1]));
 #pragma unroll
             for (int pass = 0; pass < 2; pass++) {
                 const int row = (lane >> 3) + 8 * pass;
                 const float val = (sa[pass].x + sa[pass].y) + (sa[pass].z + sa[pass].w);
-                if (vi < 7 && row < nrows && val != 0.f)
-                    atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(a.grow) + 4u * (cid[pass] + (uint32_t)vi)), val);
+                if (vi < 7 && row < nrows && val != 0.f) {
+                    if (MERGE) atomicAdd(&s_l0[MERGE ? cid[pass] / (uint32_t)ENTB : 0u][vi], val);
+                    else atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(a.grow) + 4u * (cid[pass] + (uint32_t)vi)), val);
+                }
             }
         }
         wave_lds_fence();
+    };
+
+    // MERGE — line 0 of a finished batch: slots [0, n) of s_l0 -> columns 0..6 of their splats' rows, 8 rows x 7 values per wave-instruction
+    // so that each row's line is ONE request; a value of 0 stays predicated off, so a slot nobody added to sends nothing.  Called after a
+    // barrier every wave's flushes of that batch precede (a wave that skipped the batch added nothing and is merely early at it).  Wave w
+    // sends slots [64 w, 64 w + 64): exactly the slots its own threads stage next, and a wave's LDS accesses execute in order, so the
+    // staging stores that follow need no further barrier.  Every LDS read first and unconditional (clamped), as in the flush.
+    auto emit_line0 = [&](int n) {
+        // (the lane's indices from an opaque copy of t: hipcc otherwise forms the two call sites' addresses once, in the prologue, and keeps
+        // them live — in scratch — through the whole visit loop)
+        int tt = t;
+        asm volatile("" : "+v"(tt));
+        const int vi = tt & 7, slot0 = (tt & ~63) + ((tt & 63) >> 3);
+#pragma unroll
+        for (int half = 0; half < 2; half++) {   // four passes' reads in flight at a time: registers
+            float val[4];
+            uint32_t rid[4];
+#pragma unroll
+            for (int pass = 0; pass < 4; pass++) {
+                const int slot = min(slot0 + 32 * half + 8 * pass, BATCH - 1);
+                val[pass] = s_l0[MERGE ? slot : 0][vi];
+                rid[pass] = (uint32_t)s_id[slot] * (uint32_t)a.grow_stride;
+            }
+            asm volatile("" : "+v"(val[0]), "+v"(val[1]), "+v"(val[2]), "+v"(val[3]), "+v"(rid[0]), "+v"(rid[1]), "+v"(rid[2]), "+v"(rid[3]));
+#pragma unroll
+            for (int pass = 0; pass < 4; pass++) {
+                const int slot = slot0 + 32 * half + 8 * pass;
+                if (slot < n && vi < 7 && val[pass] != 0.f)
+                    atomicAdd(reinterpret_cast<float*>(reinterpret_cast<char*>(a.grow) + 4u * (rid[pass] + (uint32_t)vi)), val[pass]);
+            }
+        }
     };
 
     for (int hi = hi_all; hi > 0; hi -= BATCH) {
@@ -407,13 +450,17 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
         const long long ts = TR_NOW();
         (void)ts;
         __syncthreads();
+        if (MERGE && hi != hi_all) emit_line0(BATCH);   // the batch before this one (a full one); its s_id and s_l0 are overwritten just below
         uint32_t qmask = 0u;
         if (t < cnt) {
             const uint32_t mask = p_mask;
             qmask = quadrant_bits(mask);
             s_mask[t] = (uint16_t)mask;
             s_id[t] = id_cur;
-            s_medj[t] = 0.f;
+            if (MERGE) {
+                *reinterpret_cast<float4*>(&s_l0[MERGE ? t : 0][0]) = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(&s_l0[MERGE ? t : 0][4]) = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else s_medj[t] = 0.f;
             HSR_BWD_STORE_RECORD(s_ent, REC4 * t);
             if (SEMA) {   // the splat's features of this pass's channels (zero past K); read here, once per staged splat
                 const float* f = a.semantics + (size_t)id_cur * (size_t)a.K;
@@ -437,9 +484,10 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
         // with zero) what its splat's slot holds.  The splat reaches the pixel's quadrant, so the pixel's own wave has it as a row of a
         // chunk AFTER this add (LDS operations of a wave execute in order): every contribution is emitted exactly once, whichever wave's
         // flush picks it up — the destination (column 6 of the splat's row) is the same.  Nothing of this is left in the visit loop.
+        // MERGE: the add goes straight into column 6 of the slot's line-0 sums and leaves with them when the batch is over.
         {
             const int jm = hi - 1 - median_at;
-            if (jm >= 0 && jm < cnt && dpm != 0.f) atomicAdd(&s_medj[jm], dpm);
+            if (jm >= 0 && jm < cnt && dpm != 0.f) atomicAdd(MERGE ? &s_l0[MERGE ? jm : 0][6] : &s_medj[MERGE ? 0 : jm], dpm);
         }
         HSR_BWD_STAGING_ADVANCE(hi, BATCH);
         TR_ADD(tr_stage, ts);
@@ -589,6 +637,10 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             }
         }
         TR_ADD(tr_loop, tl);
+    }
+    if (MERGE && hi_all > 0) {   // the last batch
+        __syncthreads();
+        emit_line0((hi_all - 1) % BATCH + 1);
     }
 #ifdef HSR_TRACE
     if (lane == 0) {
