@@ -735,7 +735,7 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     }
     {
         StageTimer tm(HSR_STAGE_BWD_PREPROCESS, stream);
-        hsr_launch_preprocess_backward(pb, stream);
+        if ((rc = hsr_launch_preprocess_backward(pb, stream)) != HSR_OK) return rc;
     }
     HSR_LAUNCH_CHECK(in.debug, stream);
     return HSR_OK;

@@ -131,6 +131,24 @@ __global__ void __launch_bounds__(256) zero_visible_rows_kernel(int P, const int
     }
 }
 
+// Packed mode stages the gradient rows in LDS: HSR_UNPACK_LDS_FLOATS floats per workgroup, rows padded by 4 floats (one ds_read_b128
+// per row and lane then falls on 16 distinct 16-byte slots for every stride that is a multiple of 16 floats).  28 KB: the four workgroups
+// per CU that the kernel's registers allow keep 113 KB of the CU's 160 KB; 14 KB measured the same, 40 KB and 56 KB (three and two
+// workgroups per CU) slower (EXPERIMENTS.md §10i).
+#define HSR_UNPACK_LDS_FLOATS 7168
+#define HSR_UNPACK_PAD 4
+// rows of one pass over a block's 256: as many as the LDS holds, the passes of equal length, a multiple of 4 rows where that is possible
+// (a pass's [rows, K] piece of dL_dsemantics then starts 16-byte aligned whenever the tensor does); 0: not even one row fits
+__host__ __device__ inline int hsr_unpack_rows(int stride)
+{
+    const int fit = HSR_UNPACK_LDS_FLOATS / (stride + HSR_UNPACK_PAD);
+    if (fit >= 256) return 256;
+    if (fit < 4) return fit;
+    const int npass = (256 + fit - 1) / fit;
+    const int rows = (((256 + npass - 1) / npass) + 3) & ~3;
+    return rows <= fit ? rows : (fit & ~3);
+}
+
 // packed mode (a.grow): unpacks each Gaussian's accumulated row; legacy mode: the sums are already in dL_dmean2D / dL_dconic / dL_ddepth.
 __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdArgs a)
 {
@@ -138,68 +156,122 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdArgs a)
     // packed mode: rows of culled Gaussians (radii <= 0) were neither zero-filled nor added into (zero_visible_rows_kernel): they
     // are not read either — their gradients are the zeros written below
     __shared__ uint8_t s_vis[256];
-    if (a.grow) {
-        s_vis[threadIdx.x] = idx < a.P && a.radii[idx] > 0;
+    __shared__ float4 s_rows4[HSR_UNPACK_LDS_FLOATS / 4];
+    float4 l0 = make_float4(0.f, 0.f, 0.f, 0.f), l1 = l0;               // line 0, columns 0..7 of this lane's row (zeros: culled)
+    float d_r = 0.f, d_g = 0.f, d_b = 0.f, d_dep = 0.f, d_op = 0.f;     // the direct sums: channel columns K .. K + 4
+    const bool vis = idx < a.P && a.radii[idx] > 0;                    // radii: read once, for both modes
+    if (a.grow && !(a.K > 0 && a.out_semantics)) {
+        // no semantic columns to unpack (K = 0, the geometry-only rows): a row's lines have one reader, its own lane, which takes them from
+        // global memory; a culled Gaussian's lane re-reads the first row of the block's slab (unconditional loads, values discarded)
+        const size_t row = vis ? (size_t)idx : (size_t)blockIdx.x * 256;
+        const float4* r = reinterpret_cast<const float4*>(a.grow + row * a.grow_stride);
+        const float4 x0 = r[0], x1 = r[1];
+        if (vis) { l0 = x0; l1 = x1; }
+        if (!a.geo) {
+            // r, g, b, depth, opacity (direct): channel columns K .. K + 4, five consecutive row columns under either layout
+            const float* dr = a.grow + row * a.grow_stride + hsr_grow_col(a.grow_layout, a.K, a.K);
+            const float y0 = dr[0], y1 = dr[1], y2 = dr[2], y3 = dr[3], y4 = dr[4];
+            if (vis) { d_r = y0; d_g = y1; d_b = y2; d_dep = y3; d_op = y4; }
+        }
+    } else if (a.grow) {
+        // Each 64-byte line of a visible row is requested once: the block's 256 rows are one contiguous slab of 256 * stride floats,
+        // brought into LDS in passes of `rows` whole rows with 16-byte loads (consecutive lanes, consecutive 16 bytes).  Both consumers
+        // read the LDS copy: the [rows, K] piece of dL_dsemantics, contiguous in the output and written 16 bytes per lane where it is
+        // 16-byte aligned (a gradient sink may hand out a view at any 4-byte offset: dword stores then), and each lane's own columns.
+        s_vis[threadIdx.x] = vis;
         __syncthreads();
-    }
-    if (a.grow && a.K > 0 && a.out_semantics) {
-        // packed mode: the block unpacks the semantic columns of its 256 rows cooperatively — consecutive
-        // lanes read consecutive floats of a row and write one contiguous [256, K] slab of dL_dsemantics
-        // (row, column) of element e advance incrementally — no division in the loop — and four loads are in flight per lane
+        float* s_rows = reinterpret_cast<float*>(s_rows4);
         const int g0 = blockIdx.x * 256;
         const int ng = min(256, a.P - g0);
-        const int K = a.K, total = ng * K;
-        const int dgi = 256 / K, dc = 256 - dgi * K;          // e += 256: row += dgi, column += dc (then one carry)
-        int gi = (int)threadIdx.x / K, c = (int)threadIdx.x - gi * K;
-        const float* src = a.grow + (size_t)g0 * a.grow_stride;   // + the column of channel c: hsr_grow_col
-        float* dst = a.out_semantics + (size_t)g0 * K;
-        int e = threadIdx.x;
-        for (; e + 768 < total; e += 1024) {
-            float v[4];
+        const int S = a.grow_stride, SP = S + HSR_UNPACK_PAD, q = S >> 2;
+        const int rows = hsr_unpack_rows(S);
+        const int K = a.K;
+        const int nfar = a.grow_layout ? K + 5 - hsr_grow_nl0(K) : K + 5;   // hsr_grow_col: channel columns below nfar sit at 16 + ch, the others at 7 + ch - nfar
+        const int dcol0 = hsr_grow_col(a.grow_layout, K, K);
+        const int drow = 256 / q, dq = 256 - drow * q;                      // float4 i += 256: row += drow, piece += dq (then one carry)
+        const int row_t = (int)threadIdx.x / q, pc_t = (int)threadIdx.x - row_t * q;
+        for (int r0 = 0; r0 < ng; r0 += rows) {
+            const int nr = min(rows, ng - r0);
+            const float4* src = reinterpret_cast<const float4*>(a.grow + (size_t)(g0 + r0) * S);
+            const int n4 = nr * q;
+            int row = row_t, pc = pc_t;
+            for (int i0 = 0; i0 < n4; i0 += 1024) {
+                float4 v[4];
+                int at[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-                // unconditional load (a culled Gaussian's lanes re-read the slab's first word, value discarded): a load under a
-                // divergent condition would be waited for where it is issued instead of four being in flight
-                const bool vs = s_vis[gi];
-                const float x = src[vs ? (size_t)gi * a.grow_stride + hsr_grow_col(a.grow_layout, K, c) : (size_t)0];
-                v[u] = vs ? x : 0.f;
-                gi += dgi; c += dc;
-                if (c >= K) { c -= K; gi++; }
+                for (int u = 0; u < 4; u++) {
+                    // unconditional load (a culled row's lanes re-read the pass's first 16 bytes, value discarded): a load under a
+                    // divergent condition would be waited for where it is issued instead of four being in flight
+                    const int i = i0 + 256 * u + (int)threadIdx.x;
+                    const bool in = i < n4;
+                    const bool vs = in && s_vis[r0 + row];
+                    const float4 x = src[vs ? i : 0];
+                    v[u] = vs ? x : make_float4(0.f, 0.f, 0.f, 0.f);
+                    at[u] = in ? row * SP + 4 * pc : -1;
+                    row += drow; pc += dq;
+                    if (pc >= q) { pc -= q; row++; }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++)
+                    if (at[u] >= 0) *reinterpret_cast<float4*>(s_rows + at[u]) = v[u];
             }
+            __syncthreads();
+            {
+                float* dst = a.out_semantics + (size_t)(g0 + r0) * K;
+                const int total = nr * K;
+                if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+                    const int n4o = total >> 2;
+                    const int dgi = 1024 / K, dc = 1024 - dgi * K;          // element e += 1024: row += dgi, column += dc (then one carry)
+                    int gi = (4 * (int)threadIdx.x) / K, c = 4 * (int)threadIdx.x - gi * K;
+                    for (int j = threadIdx.x; j < n4o; j += 256) {
+                        float o[4];
+                        int g = gi, cc = c;
 #pragma unroll
-            for (int u = 0; u < 4; u++) dst[e + 256 * u] = v[u];
-        }
-        for (; e < total; e += 256) {
-            const bool vs = s_vis[gi];
-            const float x = src[vs ? (size_t)gi * a.grow_stride + hsr_grow_col(a.grow_layout, K, c) : (size_t)0];
-            dst[e] = vs ? x : 0.f;
-            gi += dgi; c += dc;
-            if (c >= K) { c -= K; gi++; }
+                        for (int u = 0; u < 4; u++) {
+                            o[u] = s_rows[g * SP + (cc < nfar ? HSR_GROW_SEM0 + cc : 7 + cc - nfar)];
+                            if (++cc == K) { cc = 0; g++; }
+                        }
+                        reinterpret_cast<float4*>(dst)[j] = make_float4(o[0], o[1], o[2], o[3]);
+                        gi += dgi; c += dc;
+                        if (c >= K) { c -= K; gi++; }
+                    }
+                    const int e = 4 * n4o + (int)threadIdx.x;               // the last, partial block: up to three floats behind the last whole piece
+                    if (e < total) {
+                        const int g = e / K, cc = e - g * K;
+                        dst[e] = s_rows[g * SP + (cc < nfar ? HSR_GROW_SEM0 + cc : 7 + cc - nfar)];
+                    }
+                } else {
+                    const int dgi = 256 / K, dc = 256 - dgi * K;            // e += 256: row += dgi, column += dc (then one carry)
+                    int gi = (int)threadIdx.x / K, c = (int)threadIdx.x - gi * K;
+                    for (int e = threadIdx.x; e < total; e += 256) {
+                        dst[e] = s_rows[gi * SP + (c < nfar ? HSR_GROW_SEM0 + c : 7 + c - nfar)];
+                        gi += dgi; c += dc;
+                        if (c >= K) { c -= K; gi++; }
+                    }
+                }
+            }
+            const int lr = (int)threadIdx.x - r0;
+            if (lr >= 0 && lr < nr) {
+                const float* mine = s_rows + lr * SP;
+                l0 = *reinterpret_cast<const float4*>(mine);
+                l1 = *reinterpret_cast<const float4*>(mine + 4);
+                if (!a.geo) {
+                    // r, g, b, depth, opacity (direct): five consecutive row columns under either layout
+                    d_r = mine[dcol0]; d_g = mine[dcol0 + 1]; d_b = mine[dcol0 + 2]; d_dep = mine[dcol0 + 3]; d_op = mine[dcol0 + 4];
+                }
+            }
+            if (r0 + rows < ng) __syncthreads();                            // the next pass overwrites the staged rows
         }
     }
     if (idx >= a.P) return;
     float g_m2x = 0, g_m2y = 0, g_cx = 0, g_cy = 0, g_cw = 0, g_depth = 0;
     if (a.grow) {
-        // packed mode: unpack this Gaussian's atomically accumulated row into the reference's arrays
-        // a culled Gaussian's lane re-reads the first row of the block's slab (unconditional loads, values discarded)
-        const bool vis = s_vis[threadIdx.x];
-        const size_t row = vis ? (size_t)idx : (size_t)blockIdx.x * 256;
-        const float4* r = reinterpret_cast<const float4*>(a.grow + row * a.grow_stride);
-        const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float4 l0 = r[0], l1 = r[1];
-        const float4 r0 = vis ? l0 : zero4, r1 = vis ? l1 : zero4;
-        float d_r = 0.f, d_g = 0.f, d_b = 0.f, d_dep = 0.f, d_op = 0.f;
-        if (!a.geo) {
-            // r, g, b, depth, opacity (direct): channel columns K .. K + 4, five consecutive row columns under either layout
-            const float* dr = a.grow + row * a.grow_stride + hsr_grow_col(a.grow_layout, a.K, a.K);
-            const float x0 = dr[0], x1 = dr[1], x2 = dr[2], x3 = dr[3], x4 = dr[4];
-            if (vis) { d_r = x0; d_g = x1; d_b = x2; d_dep = x3; d_op = x4; }
-        }
-        g_m2x = r0.x; g_m2y = r0.y; g_cx = r0.z; g_cy = r0.w; g_cw = r1.x;
-        g_depth = r1.z + d_dep;
+        // packed mode: unpack this Gaussian's atomically accumulated row into the reference's arrays (a culled Gaussian's: zeros)
+        g_m2x = l0.x; g_m2y = l0.y; g_cx = l0.z; g_cy = l0.w; g_cw = l1.x;
+        g_depth = l1.z + d_dep;
         a.out_mean2D[3 * idx] = g_m2x; a.out_mean2D[3 * idx + 1] = g_m2y; a.out_mean2D[3 * idx + 2] = 0.f;
         if (a.out_conic) reinterpret_cast<float4*>(a.out_conic)[idx] = make_float4(g_cx, g_cy, 0.f, g_cw);
-        if (a.out_opacity) a.out_opacity[idx] = r1.y + d_op;
+        if (a.out_opacity) a.out_opacity[idx] = l1.y + d_op;
         if (a.out_color) { a.out_color[3 * idx] = d_r; a.out_color[3 * idx + 1] = d_g; a.out_color[3 * idx + 2] = d_b; }
         if (a.out_depth) a.out_depth[idx] = g_depth;
     } else {
@@ -211,8 +283,7 @@ __global__ void __launch_bounds__(256) preprocess_backward_kernel(PreBwdArgs a)
     float dcov[6] = {0, 0, 0, 0, 0, 0};
     float dsc[3] = {0, 0, 0};
     float dq[4] = {0, 0, 0, 0};
-    const bool visible = a.radii[idx] > 0;
-    if (visible) {
+    if (vis) {
         const float mx = a.means3D[3 * idx], my = a.means3D[3 * idx + 1], mz = a.means3D[3 * idx + 2];
         const float* vm = a.viewmatrix;
         const float* proj = a.projmatrix;
@@ -362,6 +433,10 @@ int hsr_launch_zero_visible_rows(int P, const int* radii, float* grow, int strid
 int hsr_launch_preprocess_backward(const PreBwdArgs& a, hipStream_t stream)
 {
     if (a.P <= 0) return HSR_OK;
+    if (a.grow && hsr_unpack_rows(a.grow_stride) < 1) {
+        hsr_set_error("preprocess backward: a packed row of %d floats does not fit the kernel's LDS", a.grow_stride);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
     const dim3 grid((a.P + 255) / 256), block(256);
     preprocess_backward_kernel<<<grid, block, 0, stream>>>(a);
     return HSR_OK;
