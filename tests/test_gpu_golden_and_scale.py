@@ -74,6 +74,8 @@ def test_full_size_properties(P, W, H, K):
     # num_rendered = sum of tile counts; keys sorted; key = (tile << 32) | depth bits of its Gaussian
     assert int(touched.sum()) == R and int((radii > 0).sum()) == int((touched > 0).sum())
     assert bool((keys[1:] >= keys[:-1]).all())
+    # entries of equal (tile, depth) keys stand in ascending Gaussian order: the stable sort's rule
+    assert bool(((keys[1:] != keys[:-1]) | (vals[1:] > vals[:-1])).all())
     tiles = keys >> 32
     assert int(tiles.min()) >= 0 and int(tiles.max()) < T
     assert bool(((keys & 0xFFFFFFFF).int() == depths[vals.long()].view(torch.int32)).all())

@@ -50,22 +50,31 @@ TIE_BOUNDED = []   # comparisons that needed the oracle's tie bound (reported at
 CONDITIONED = []   # comparisons settled against the truth build: HIP within twice the fp32 noise floor of that gradient (ditto)
 
 
-def _compare(cam, sc, up, semantic, variant, extra=None, grad_rtol=1e-4):
-    out_g, gr_g, st_g = run_gpu(cam, sc, up, semantic=semantic, variant=variant, extra=extra)
-    out_o, gr_o, st_o = run_oracle(cam, sc, up, semantic=semantic, variant=variant, extra=extra)
-    # ---- integer outputs: bit-exact ----
+def _compare_integers(out_g, st_g, out_o, st_o):
+    """the integer state of one forward, HIP against the oracle, bit for bit: radii, counts, offsets, the sorted lists and tile ranges,
+    and the per-Gaussian fp32 state that feeds them"""
     assert np.array_equal(out_g["radii"], out_o["radii"]), "radii"
     assert st_g["num_rendered"] == out_o["num_rendered"], "num_rendered"
     assert np.array_equal(st_g["tiles_touched"], st_o.field("tiles_touched")), "tiles_touched"
     assert np.array_equal(st_g["point_offsets"], st_o.field("point_offsets")), "point_offsets"
     assert np.array_equal(st_g["keys"], st_o.field("keys")), "sorted keys"
     assert np.array_equal(st_g["vals"], st_o.field("vals")), "sorted values"
+    # on the device's own lists, no oracle needed: entries of equal (tile, depth) keys stand in ascending Gaussian order — the stable
+    # sort's rule, which alone decides the blend order on maps whose splats share depths (tests/test_gpu_depth_ties.py)
+    scenes.assert_ties_in_index_order(st_g["keys"], st_g["vals"])
     assert np.array_equal(st_g["ranges"], st_o.field("ranges")), "tile ranges"
     vis = out_o["radii"] > 0
     # per-Gaussian fp32 state feeding integer outputs: identical bits by construction (no contraction)
     assert np.array_equal(st_g["depths"][vis], st_o.field("depths")[vis]), "depths"
     assert np.array_equal(st_g["means2D"][vis], st_o.field("means2D")[vis]), "means2D"
     assert np.array_equal(st_g["conic_opacity"][vis], st_o.field("conic_opacity")[vis]), "conic_opacity"
+
+
+def _compare(cam, sc, up, semantic, variant, extra=None, grad_rtol=1e-4):
+    out_g, gr_g, st_g = run_gpu(cam, sc, up, semantic=semantic, variant=variant, extra=extra)
+    out_o, gr_o, st_o = run_oracle(cam, sc, up, semantic=semantic, variant=variant, extra=extra)
+    # ---- integer outputs: bit-exact ----
+    _compare_integers(out_g, st_g, out_o, st_o)
     # ---- thresholded integers: budgeted ----
     npix = out_o["color"].shape[1] * out_o["color"].shape[2]
     nmis = int((st_g["n_contrib"] != st_o.field("n_contrib")).sum())
