@@ -16,7 +16,8 @@
 //     point_list -> record global round trips hide behind compute instead of serialising the tile.
 //   * each 16-lane group of a wave owns a 4x4 sub-block and walks a compacted per-sub-block list built at
 //     staging time from the splats' alpha>=1/255 regions (subblock_mask, hsr_tile_common.h), so splats that
-//     cannot touch the sub-block cost it nothing; the wave iterates to the longest of its four lists, and a
+//     cannot touch the sub-block cost it nothing; the wave iterates to the longest of its four lists (a shorter
+//     group visits a dummy entry of opacity 0 meanwhile: no validity predicate in the loop), and a
 //     visit that no lane accepts costs only the alpha test (wave ballot).  A wave whose 64 pixels are all
 //     terminated stops blending but keeps staging.
 //   * records are staged pre-scaled (log2(e) and the -0.5 folded into the conic) so alpha costs one
@@ -151,8 +152,13 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     constexpr bool QS = PF && KC > 0;
     constexpr int NGF = QS ? RW / 16 : 0;            // full 16-channel groups
     constexpr int REM = QS ? (RW % 16) / 4 : 0;      // words per lane of the partial group
-    __shared__ float4 s_rec[BATCH * 2];
-    __shared__ float4 s_row[BATCH * (RW / 4)];
+    // The per-lane kernels (not QS) stage one entry more than a batch holds: slot BATCH is the DUMMY, a record of opacity 0 (alpha = 0:
+    // it never contributes) and a feature row of zeros, written once per workgroup.  A group pads its list with it up to the wave's
+    // iteration count, so the blend loop visits a real staged entry on every trip and carries no "is this visit mine" predicate.
+    constexpr int NSLOT = BATCH + (QS ? 0 : 1);
+    static_assert(NSLOT <= 256, "list entries are bytes");
+    __shared__ float4 s_rec[NSLOT * 2];
+    __shared__ float4 s_row[NSLOT * (RW / 4)];
     __shared__ uint8_t s_sublist[16 * HSR_SUB_LSTRIDE];
     __shared__ uint8_t s_subcnt[4][16];
     __shared__ int s_wdone[4];
@@ -186,7 +192,11 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     const uint2 range = a.ranges[tile];
     const int n = (int)(range.y - range.x);
 
-    float T = 1.0f;
+    // Per-lane kernels: a finished pixel is a pixel whose RUNNING transmittance T is 0 — from then on alpha * T and T * (1 - alpha) are 0
+    // and every later entry "finishes" it again, so the loop carries no done mask; T_out is the transmittance the pixel outputs (it
+    // follows T while the pixel is live and stays where it was when the pixel finished).  A pixel outside the image starts finished.
+    // The QS kernels keep T and the done flag.
+    float T = (QS || inside) ? 1.0f : 0.0f, T_out = 1.0f;
     uint32_t last_contributor = 0;
     float C0 = 0, C1 = 0, C2 = 0, Dd = 0, Mm = 0;
     uint32_t median_at = 0;   // 1 + list position of the splat at which T crossed 0.5 (ImgState::median_pos)
@@ -210,6 +220,11 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     for (int c = 0; c < NPF; c++) pf_t[c] = 0.f;
     float pf_sink = 0.f;
     int id_cur = 0;            // id of the splat whose record sits in p_* (PF: its row is fetched when it is staged)
+
+    if constexpr (!QS) {   // the dummy entry; the first barrier of the batch loop publishes it
+        if (t < 2) s_rec[2 * BATCH + t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t < RW / 4) s_row[BATCH * (RW / 4) + t] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
 
     // Staging loads are UNCONDITIONAL (clamped indices; lanes past the end of the list fetch a duplicate they never stage) and the
     // id of batch b+2 is requested BEFORE the records of batch b+1: a load inside a divergent `if` lands in a temporary that is
@@ -272,7 +287,7 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
 
 
     for (int start = 0; start < n; start += BATCH) {
-        const bool wave_done = __ballot(!done) == 0ull;
+        const bool wave_done = __ballot(QS ? !done : T != 0.0f) == 0ull;
         if ((t & 63) == 0) s_wdone[wv] = wave_done;
         const long long tb0 = TRF_NOW();
         (void)tb0;
@@ -374,14 +389,18 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
         const int m = __builtin_amdgcn_readfirstlane(max(max(__builtin_amdgcn_readlane(total, 0), __builtin_amdgcn_readlane(total, 16)),
                                                          max(__builtin_amdgcn_readlane(total, 32), __builtin_amdgcn_readlane(total, 48))));
         const uint8_t* list = s_sublist + sb * HSR_SUB_LSTRIDE;
-        // a group past the end of its list keeps re-reading its last entry, with weight 0 (an empty list is given the always
-        // staged slot 0 as its only entry): an unconditional clamped read instead of a masked one
-        if (total == 0 && (lane & 15) == 0) s_sublist[sb * HSR_SUB_LSTRIDE] = 0;
+        if constexpr (QS) {
+            // a group past the end of its list keeps re-reading its last entry, with weight 0 (an empty list is given the always
+            // staged slot 0 as its only entry): an unconditional clamped read instead of a masked one
+            if (total == 0 && (lane & 15) == 0) s_sublist[sb * HSR_SUB_LSTRIDE] = 0;
+        } else {
+            pad_sublist(sb, lane, s_sublist, total, m, BATCH);
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int last = max(total - 1, 0);
         if constexpr (QS) {
+            const int last = max(total - 1, 0);
             constexpr int NW = 4 * NGF + REM;
             constexpr int NCH = KC + (BASE ? 2 : 0);   // channels that are accumulated: features, then blue, depth
             int j_next = (int)list[0];
@@ -448,25 +467,33 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
 #endif
             }
         } else {
-            int j_next = (int)list[0];
+            // The visit loop, on the pattern of the backward's (hsr_render_bwd_q.hip): every trip visits a staged entry — the group's own
+            // or the dummy — so nothing in it asks whether the visit counts; a lane that does not contribute multiplies by w = 0.
+            // The median crossing and the last contributor are recorded as the entry's SLOT in registers that hold "list position -
+            // (start + 1)" for the length of the batch (negative: set in an earlier batch, or never), and are turned back after it.
+            const int base1 = start + 1;
+            int last_rel = (int)last_contributor - base1, med_rel = (int)median_at - base1;
+            int j = (int)list[0];
             for (int k = 0; k < m; k++) {
-                const int j = j_next;
-                const bool valid = k < total;
-                j_next = (int)list[min(k + 1, last)];
+                const int j_next = (int)list[k + 1];   // list[m] is padding too
                 const float4 g = s_rec[2 * j];
                 const float4 h4 = s_rec[2 * j + 1];
                 const float2 co = make_float2(h4.x, h4.y);
                 const float dx = g.x - pfx, dy = g.y - pfy;
                 const float power2 = fmaf(co.x, dy * dy, fmaf(g.w, dx * dy, g.z * (dx * dx)));
                 const float alpha = fminf(0.99f, co.y * __builtin_amdgcn_exp2f(power2));
-                bool contrib = valid && !done && power2 <= 0.0f && alpha >= 1.0f / 255.0f;
+                const bool reach = power2 <= 0.0f && alpha >= 1.0f / 255.0f;
                 const float test_T = T * (1.0f - alpha);
-                if (contrib && test_T < 0.0001f) {
-                    done = true;
-                    contrib = false;
-                }
-                if (__ballot(contrib) == 0ull) continue;
+                const bool low = test_T < 0.0001f;
+                const bool contrib = reach && !low;   // never on a finished pixel: its test_T is 0
                 const float w = contrib ? alpha * T : 0.f;
+                // no lane contributes (2 % of the trips at the headline workload): the rows are not read.  The test is one scalar branch on
+                // the mask the select above already has; a lane that finishes here still has its T cleared.
+                if (__ballot(contrib) == 0ull) {
+                    T = reach ? 0.0f : T;
+                    j = j_next;
+                    continue;
+                }
                 if (BASE) {
                     C0 = fmaf(h4.z, w, C0);
                     C1 = fmaf(h4.w, w, C1);
@@ -483,24 +510,27 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
                             const int c = 4 * q + i;
                             if (c < KC) S[c < KC ? c : 0] = fmaf(fv[i], w, S[c < KC ? c : 0]);
                             else if (BASE && c == KC) C2 = fmaf(fv[i], w, C2);
-                            else if (BASE && c == KC + 1) {
-                                Dd = fmaf(fv[i], w, Dd);
-                                if (contrib && T > 0.5f && test_T < 0.5f) median_at = (uint32_t)(start + j + 1);   // its depth: epilogue
-                            }
+                            else if (BASE && c == KC + 1) Dd = fmaf(fv[i], w, Dd);
                         }
                     }
                 }
-                if (contrib) {
-                    T = test_T;
-                    last_contributor = (uint32_t)(start + j + 1);
-                }
+                // T_out moves only when the lane contributes, so "contributes, T > 0.5 before, < 0.5 after" needs no third term
+                const float T_was = T_out;
+                T_out = contrib ? test_T : T_out;
+                if (BASE) med_rel = (T_was > 0.5f && T_out < 0.5f) ? j : med_rel;
+                last_rel = contrib ? j : last_rel;
+                T = reach ? (low ? 0.0f : test_T) : T;   // contributes: goes on; finishes (again): 0
+                j = j_next;
 #ifdef HSR_TRACE
                 tr_iters++;
 #endif
             }
+            last_contributor = (uint32_t)(last_rel + base1);
+            median_at = (uint32_t)(med_rel + base1);
+            if (BASE && med_rel >= 0) median_D = reinterpret_cast<const float*>(s_row)[med_rel * RW + KC + 1];   // crossed in this batch
         }
         TRF_ADD(tr_blend, tl0);
-        resolve_median(start);
+        if constexpr (QS) resolve_median(start);
         continue;   // not redundant: without it hipcc lays the batch loop out differently (16 more instructions in the kernels without PF)
     }
 
@@ -511,7 +541,8 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     if (inside) {
         const size_t pix_id = (size_t)a.W * (size_t)(int)pfy + (size_t)(int)pfx;
         if (BASE) {
-            a.final_T[pix_id] = T;
+            const float T_fin = QS ? T : T_out;
+            a.final_T[pix_id] = T_fin;
             a.n_contrib[pix_id] = last_contributor;
             a.median_pos[pix_id] = median_at;
             a.out_color[pix_id] = C0;
@@ -519,7 +550,7 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
             a.out_color[2 * N + pix_id] = C2;
             a.out_depth[pix_id] = Dd;
             a.out_median_depth[pix_id] = median_D;   // resolve_median()
-            a.out_opacity[pix_id] = 1.0f - T;
+            a.out_opacity[pix_id] = 1.0f - T_fin;
             if (MASK) a.out_mask[pix_id] = Mm;
         }
         if (KC > 0) {
