@@ -25,7 +25,8 @@ __device__ __forceinline__ void wave_lds_fence()
 
 // ---- software-pipelined staging of a batch's splats ----
 // Thread t holds, in registers, the splat it will stage in the NEXT batch (the inputs of its 48-byte record and its sub-block mask) and
-// the id of the one after that: each was requested a whole batch of blending before it is used.
+// the id of the one after that: each was requested a whole batch of blending before it is used, and is waited for once, at the top of
+// the batch that stages it (HSR_SETTLE_STAGING).
 //
 // These are macros, not functions: the two kernels sit at a register step, and hipcc schedules and allocates them differently as soon as
 // any of this text is reached through a call — even a force-inlined one, even a bare struct of these registers (the early
@@ -69,7 +70,8 @@ __device__ __forceinline__ void wave_lds_fence()
 // requested a whole batch ago)
 #define HSR_BWD_STAGING_ADVANCE(hi, BATCH)                                                                                                 \
     {                                                                                                                                      \
-        const int id_use = id_next;                                                                                                        \
+        int id_use = id_next;                                                                                                              \
+        asm volatile("" : "+v"(id_use));                                                                                                   \
         id_next = fetch_id(hi - 2 * BATCH);                                                                                                \
         load_record(id_use);                                                                                                               \
         p_mask = fetch_mask(hi - BATCH);                                                                                                   \
@@ -79,9 +81,17 @@ __device__ __forceinline__ void wave_lds_fence()
     s_ent[(i)] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);                                             \
     s_ent[(i) + 1] = make_float4(p_r, p_g, p_b, p_d);                                                                                        \
     s_ent[(i) + 2] = make_float4((-0.5f * HSR_LOG2E) * p_co.z, p_co.w, (-0.5f * HSR_LOG2E) * p_co.y, 0.f)
-// Makes the staging registers of the next batch "used" BEFORE the first atomics of this batch are issued: hipcc then waits for their
-// loads here — they were issued a chunk of blending ago and have landed — instead of at the next batch's staging, where the same
-// s_waitcnt would also have to sit out every atomic issued in between (loads, stores and atomics retire through one in-order counter).
+// Makes the staging registers "used": hipcc waits for their loads where this stands.  It stands ONCE per batch, right behind the batch's
+// top barrier and in front of everything that issues an atomic there (loads, stores and atomics retire through one in-order counter:
+// a wait placed behind fresh atomics sits them out too).  What the wait does cover is the wave's own last flush of the batch before,
+// whose atomics have had the barrier to retire in.
+// It used to stand inside the chunk loop, in front of the first flush, so that the wait would cover no atomic at all.  hipcc does not
+// leave it there: a loop that holds atomics but no loads and uses a register whose load is pending gets the counter flushed in its
+// PREHEADER (the waitcnt pass's rule for such loops), i.e. every wave waited for the gathers a few dozen instructions after it had
+// requested them, once per batch, and blended nothing meanwhile.  Hence no staging register may be touched between
+// HSR_BWD_STAGING_ADVANCE and the next batch's top barrier — not by a copy either, which is why ADVANCE hands the id over through an
+// opaque copy: without it the register allocator rotates id_next with a move at the head of the batch loop, in front of the barrier,
+// and that move waits for all but the last four atomics of the batch.
 #define HSR_SETTLE_STAGING()                                                                                                   \
     asm volatile("" ::"v"(id_next), "v"(p_xy.x), "v"(p_xy.y), "v"(p_co.x), "v"(p_co.y), "v"(p_co.z), "v"(p_co.w), "v"(p_r), "v"(p_g), \
                  "v"(p_b), "v"(p_d), "v"(p_mask))

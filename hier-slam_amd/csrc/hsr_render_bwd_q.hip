@@ -450,6 +450,8 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
         const long long ts = TR_NOW();
         (void)ts;
         __syncthreads();
+        // this batch's staged registers are waited for HERE, once, in front of the atomics of emit_line0: see HSR_SETTLE_STAGING
+        HSR_SETTLE_STAGING();
         if (MERGE && hi != hi_all) emit_line0(BATCH);   // the batch before this one (a full one); its s_id and s_l0 are overwritten just below
         uint32_t qmask = 0u;
         if (t < cnt) {
@@ -491,15 +493,11 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
         }
         HSR_BWD_STAGING_ADVANCE(hi, BATCH);
         TR_ADD(tr_stage, ts);
-        if (hi - cnt >= wmax) {   // this wave's pixels all stopped in front of this batch
-            HSR_SETTLE_STAGING();
-            continue;
-        }
+        if (hi - cnt >= wmax) continue;   // this wave's pixels all stopped in front of this batch
         const long long tl = TR_NOW();
         (void)tl;
 
         const int total = build_flat_list(wv, lane, s_list, s_lcnt, s_flat);
-        if (total == 0) HSR_SETTLE_STAGING();
         int nrows = 0;
         for (int c0 = 0; c0 < total; c0 += nrows) {
             nrows = min(Q_ROWS, total - c0);
@@ -628,7 +626,6 @@ __global__ void __launch_bounds__(256, (SEMA || (!GEO && KC + 5 > 16)) ? 3 : 4) 
             {
                 const long long tf = TR_NOW();
                 (void)tf;
-                if (c0 == 0) HSR_SETTLE_STAGING();
                 flush(nrows);
                 TR_ADD(tr_flush, tf);
 #ifdef HSR_TRACE

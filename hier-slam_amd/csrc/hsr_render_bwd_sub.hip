@@ -277,6 +277,7 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
         // list position of batch slot j is hi - 1 - j: "behind the last contributor" and "the median splat" as slot tests, per batch
         const int j_first = hi - last_contributor, j_median = hi - 1 - median_at;
         __syncthreads();
+        HSR_SETTLE_STAGING();   // the one wait for this batch's staged registers
         uint32_t qmask = 0u;
         if (t < cnt) {
             const uint32_t mask = p_mask;
@@ -288,13 +289,9 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
         publish_quadrant_lists(qmask, t, s_list, s_lcnt);
         __syncthreads();
         HSR_BWD_STAGING_ADVANCE(hi, BATCH);
-        if (hi - cnt >= wmax) {   // this wave's pixels all stopped in front of this batch
-            HSR_SETTLE_STAGING();
-            continue;
-        }
+        if (hi - cnt >= wmax) continue;   // this wave's pixels all stopped in front of this batch
 
         const int total = build_flat_list(wv, lane, s_list, s_lcnt, s_flat);
-        if (total == 0) HSR_SETTLE_STAGING();
         for (int c0 = 0; c0 < total; c0 += SB_SLOTS) {
             const int nrows = min(SB_SLOTS, total - c0);
             // lane (group gq, row l16): does chunk entry l16 touch sub-block (wv, gq)?
@@ -366,7 +363,6 @@ __global__ void __launch_bounds__(256, NG <= 2 ? 4 : (NG == 3 ? 3 : 2)) render_b
                 const float total7 = row_reduce_transpose7(v, lane);
                 if (myv_on && valid) u7[r * 32 + myv * 4 + gq] = total7;
             }
-            if (c0 == 0) HSR_SETTLE_STAGING();
             flush(nrows);
         }
     }

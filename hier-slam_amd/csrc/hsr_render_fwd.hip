@@ -111,6 +111,10 @@ __device__ __forceinline__ void quad_fma_words(float (&s)[16], const float (&x)[
     }
 }
 
+// a word of the tile lists as the kernel addresses it: in the global address space, or (false) with the address space left to hipcc
+template <bool GLOBAL> struct list_word { typedef __attribute__((address_space(1))) uint32_t type; };
+template <> struct list_word<false> { typedef uint32_t type; };
+
 // KC: semantic channels handled by this launch (0 = none).  BASE: also produce colour/depth/median/
 // opacity/final_T/n_contrib.  MASK: non-semantic variant, writes mask = sum(alpha*T).
 // ALIGNED: the launch covers whole feature rows of an even K (c0 == 0, KC == K): rows are 8-byte
@@ -175,6 +179,16 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
         a.point_list = bs.vals;
         a.masks = bs.vals_unsorted;
     }
+    // The list and the mask array are read and written through pointers QUALIFIED as global.  On the speculative path they are carved out
+    // of an integer (hsr_bin_resolve), so hipcc knows no address space for them and the id of batch b + 2 went out as a FLAT load —
+    // and while a FLAT load is pending hipcc counts nothing: every later wait, whatever it is for, waits for all loads in flight.
+    // (PIPE: not in the 48-channel instantiation, which sits exactly at its 128 registers and spills one with either half of this, and
+    // not beyond 80 channels, where two waves per SIMD gained nothing from it — K = 102 measured 0.4 % slower, inside its spread: they
+    // keep the code they had)
+    constexpr bool PIPE = !(PF && (KC == 48 || KC > 80));
+    typedef typename list_word<PIPE>::type g_u32;
+    const g_u32* const list_g = (const g_u32*)a.point_list;
+    g_u32* const masks_g = (g_u32*)a.masks;
     const TileGeom tg = tile_geom_sub(tile, a.W, a.H, t);
     const bool inside = tg.inside;
     const size_t N = (size_t)a.W * a.H;
@@ -231,7 +245,11 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     // copied into the loop-carried register at the end of the branch, and that copy — like a load that overwrites the register the
     // previous loads took their addresses from — makes hipcc wait for everything in flight right there, i.e. the "pipelined" gathers
     // were waited for where they were issued (round 1 and most of round 2: s_waitcnt vmcnt(0) 30 instructions after the loads).
-    auto fetch_id = [&](int start) -> int { return (int)a.point_list[range.x + min(max(start + t, 0), n - 1)]; };
+    auto fetch_id = [&](int start) -> int {
+        const uint32_t at = range.x + min(max(start + t, 0), n - 1);
+        if constexpr (PIPE) return (int)list_g[at];
+        else return (int)a.point_list[at];
+    };
     auto load_record = [&](int id_of) {
         const size_t id = (size_t)id_of;
         id_cur = id_of;
@@ -267,6 +285,20 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
             }
         }
     };
+    // Makes every staging register "used": hipcc waits for the gathers where this stands.  It stands once per batch, behind the first
+    // barrier and in front of the staging block, on EVERY path (the block itself is skipped by a wave whose 64 threads are past the end
+    // of the batch: on that path the loads used to stay pending, and the first instruction of the next gather that reused one of their
+    // registers waited for them — in the middle of the gather, in front of the row requests).
+    auto settle_staging = [&]() {
+        if constexpr (PIPE) {
+            asm volatile("" ::"v"(id_next), "v"(id_cur), "v"(p_xy.x), "v"(p_xy.y), "v"(p_co.x), "v"(p_co.y), "v"(p_co.z), "v"(p_co.w), "v"(p_r),
+                         "v"(p_g), "v"(p_b), "v"(p_d));
+#pragma unroll
+            for (int c = 0; c < ((KC > 0 && !PF) ? KC : 1); c++) asm volatile("" ::"v"(p_sem[c]));
+#pragma unroll
+            for (int c = 0; c < NPF; c++) asm volatile("" ::"v"(pf_t[c]));
+        }
+    };
     if (n > 0) {
         const int id0 = fetch_id(0);
         id_next = fetch_id(BATCH);
@@ -298,10 +330,12 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
         (void)ts0;
         if (s_wdone[0] & s_wdone[1] & s_wdone[2] & s_wdone[3]) break;
         const int cnt = min(BATCH, n - start);
+        if constexpr (PIPE) settle_staging();   // the one wait of a batch for its gathers
         uint32_t mask16 = 0u;
         if (t < cnt) {
             mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0);
-            a.masks[range.x + start + t] = mask16;   // the backward stages the same entries: it reads the mask instead of deriving it again
+            if constexpr (PIPE) masks_g[range.x + start + t] = mask16;
+            else a.masks[range.x + start + t] = mask16;   // the backward stages the same entries: it reads the mask instead of deriving it again
             s_rec[2 * t] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);
             s_rec[2 * t + 1] = make_float4((-0.5f * HSR_LOG2E) * p_co.z, p_co.w, p_r, p_g);
             float4* row = &s_row[t * (RW / 4)];
