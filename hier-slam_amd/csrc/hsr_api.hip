@@ -1,5 +1,5 @@
-// hsr_api.hip — the C ABI of libhsr_rast.so (see include/hsr_rasterizer.h): argument validation,
-// state-buffer carving and stage orchestration.  Host code only; kernels live in the other units.
+// hsr_api.hip — the C ABI of libhsr_rast.so (include/hsr_rasterizer.h): argument validation — all of it in front of the first acquire,
+// memset or launch — and stage orchestration.  Host code only; kernels live in the other units, the state buffers' layouts in hsr_state.hip.
 //
 // Stage order of one forward (reference Rasterizer::forward[_semantic], rasterizer_impl.cu:198-345,
 // :460-610):   preprocess (+ per-block tile-count sums) -> scan of the block sums -> 4-byte D2H of
@@ -17,7 +17,6 @@
 #include <string.h>
 
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/hsr_rasterizer.h"
@@ -26,14 +25,6 @@
 namespace {
 
 thread_local char g_err[512] = "";
-
-template <typename T>
-inline void take(char*& p, T*& out, size_t count)
-{
-    uintptr_t a = (reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255;
-    out = reinterpret_cast<T*>(a);
-    p = reinterpret_cast<char*>(out + count);
-}
 
 uint32_t higher_msb(uint32_t n)  // reference getHigherMsb, rasterizer_impl.cu:35-50
 {
@@ -149,10 +140,6 @@ struct PinnedCounter {
 constexpr int HSR_MAX_DEVICES = 64;
 thread_local PinnedCounter g_counters_by_device[HSR_MAX_DEVICES];
 thread_local PinnedCounter* g_pc = nullptr;      // the current call's slot (set by counter_buffer())
-#define g_pinned (g_pc->host)
-#define g_pinned_dev (g_pc->dev)
-#define g_counter_seq (g_pc->seq)
-#define g_counter_event (g_pc->event)
 
 // Non-blocking forward (hsr_forward_arm_async): the count lands in a slot of a per-device ring of host-mapped words that is
 // process-wide — the ticket may be resolved on another thread (autograd's backward thread) than the one that called the forward.
@@ -221,10 +208,10 @@ int counter_buffer()
         return HSR_ERR_INVALID_ARGUMENT;
     }
     g_pc = &g_counters_by_device[d];
-    if (!g_pinned) {
-        HSR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_pinned), 64, hipHostMallocPortable | hipHostMallocMapped));
-        g_pinned[0] = g_pinned[1] = g_pinned[2] = 0;
-        HSR_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g_pinned_dev), g_pinned, 0));
+    if (!g_pc->host) {
+        HSR_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_pc->host), 64, hipHostMallocPortable | hipHostMallocMapped));
+        g_pc->host[0] = g_pc->host[1] = g_pc->host[2] = 0;
+        HSR_HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g_pc->dev), g_pc->host, 0));
     }
     return HSR_OK;
 }
@@ -232,10 +219,10 @@ int read_counter_begin(const uint32_t* dev, hipStream_t stream)
 {
     int rc;
     if ((rc = counter_buffer()) != HSR_OK) return rc;
-    if (!g_counter_event) HSR_HIP_CHECK(hipEventCreateWithFlags(&g_counter_event, hipEventDisableTiming));
-    HSR_HIP_CHECK(hipMemcpyAsync(g_pinned, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HSR_HIP_CHECK(hipMemcpyAsync(g_pinned + 2, dev + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));   // prefilter flag
-    HSR_HIP_CHECK(hipEventRecord(g_counter_event, stream));
+    if (!g_pc->event) HSR_HIP_CHECK(hipEventCreateWithFlags(&g_pc->event, hipEventDisableTiming));
+    HSR_HIP_CHECK(hipMemcpyAsync(g_pc->host, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HSR_HIP_CHECK(hipMemcpyAsync(g_pc->host + 2, dev + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));   // prefilter flag
+    HSR_HIP_CHECK(hipEventRecord(g_pc->event, stream));
     return HSR_OK;
 }
 thread_local double g_host_wait_ms = 0.0;
@@ -243,9 +230,9 @@ thread_local int g_last_per_tile = 0;   // num_rendered / tiles of this thread's
 int read_counter_end(uint32_t* host_out)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    HSR_HIP_CHECK(hipEventSynchronize(g_counter_event));
+    HSR_HIP_CHECK(hipEventSynchronize(g_pc->event));
     g_host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    *host_out = g_pinned[0];
+    *host_out = g_pc->host[0];
     return HSR_OK;
 }
 // Direct-binning path: bin_hist_kernel's last workgroup stores {num_rendered, seq} into the host-mapped buffer itself (no copy
@@ -286,18 +273,18 @@ int poll_counter(uint32_t seq, hipStream_t stream, uint32_t* host_out, volatile 
     // a few hundred microseconds in a training loop — and a `pause` loop would hold a core at 100 % for all of it.  Sleep
     // through the first half of the recently observed wait (an average over the last calls), then poll; short waits (< 0.15
     // ms: the count is already there or nearly) are polled from the start.
-    if (g_pc->wait_ema_us > 150.0 && __atomic_load_n(&g_pinned[1], __ATOMIC_ACQUIRE) != seq) {
+    if (g_pc->wait_ema_us > 150.0 && __atomic_load_n(&g_pc->host[1], __ATOMIC_ACQUIRE) != seq) {
         timespec ts{0, (long)(g_pc->wait_ema_us * 0.5 * 1000.0)};
         if (ts.tv_nsec > 2000000L) ts.tv_nsec = 2000000L;
         nanosleep(&ts, nullptr);
     }
     unsigned spins = 0;
-    while (__atomic_load_n(&g_pinned[1], __ATOMIC_ACQUIRE) != seq) {
+    while (__atomic_load_n(&g_pc->host[1], __ATOMIC_ACQUIRE) != seq) {
         if ((++spins & 0xFFFu) == 0) {
             const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             if (el > 10.0) {
                 const hipError_t e = hipStreamSynchronize(stream);
-                if (e != hipSuccess || __atomic_load_n(&g_pinned[1], __ATOMIC_ACQUIRE) != seq) {
+                if (e != hipSuccess || __atomic_load_n(&g_pc->host[1], __ATOMIC_ACQUIRE) != seq) {
                     hsr_set_error("num_rendered never arrived (%s)", hipGetErrorString(e));
                     return HSR_ERR_HIP;
                 }
@@ -310,17 +297,25 @@ int poll_counter(uint32_t seq, hipStream_t stream, uint32_t* host_out, volatile 
     const double waited_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     g_host_wait_ms += waited_ms;
     g_pc->wait_ema_us = 0.75 * g_pc->wait_ema_us + 0.25 * waited_ms * 1000.0;
-    *host_out = __atomic_load_n(&g_pinned[0], __ATOMIC_RELAXED);
+    *host_out = __atomic_load_n(&g_pc->host[0], __ATOMIC_RELAXED);
     return HSR_OK;
 }
 
+// One forward call's arguments, in the order of hsr_forward_semantic's parameters and then what hsr_forward has instead: each entry
+// point states them as ONE initialiser list that reads against its prototype; whatever a list leaves out is zero.
 struct FwdIn {
-    int P, D, M, K, semantic, W, H, prefiltered, debug;
-    const float *background, *means3D, *shs, *colors_precomp, *semantics, *opacities, *scales, *rotations, *cov3D_precomp,
-        *viewmatrix, *projmatrix, *cam_pos;
-    float scale_modifier, tan_fovx, tan_fovy;
-    float *out_color, *out_semantic, *out_depth, *out_median, *out_opacity, *out_mask;
+    int P, D, M, K;
+    const float* background;
+    int W, H;
+    const float *means3D, *shs, *colors_precomp, *semantics, *opacities, *scales;
+    float scale_modifier;
+    const float *rotations, *cov3D_precomp, *viewmatrix, *projmatrix, *cam_pos;
+    float tan_fovx, tan_fovy;
+    int prefiltered;
+    float *out_color, *out_semantic, *out_depth, *out_median, *out_opacity;
     int* radii;
+    int debug, semantic;
+    float* out_mask;
 };
 
 // a slot of the device's ring for one non-blocking forward
@@ -343,6 +338,23 @@ int ring_slot(uint32_t* seq_out, volatile uint32_t** host_out, uint32_t** dev_ou
     if (s == 0) s = ++r.seq;
     const uint32_t idx = s % HSR_ASYNC_SLOTS;
     *seq_out = s; *host_out = r.host + 4 * idx; *dev_out = r.dev + 4 * idx; *device_out = d;
+    return HSR_OK;
+}
+
+// The checks on a count freshly read from its slot {num_rendered, seq, prefilter flag}, for the blocking call and for a ticket alike.
+// rendered (may be NULL) receives a count that fits an int, whatever the prefilter flag says.
+int check_count(uint32_t R32, int prefiltered, const volatile uint32_t* slot, int32_t* rendered)
+{
+    if (R32 > 0x7fffffffu) {
+        hsr_set_error("num_rendered %u overflows int", R32);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (rendered) *rendered = (int32_t)R32;
+    if (prefiltered && __atomic_load_n(&slot[2], __ATOMIC_RELAXED) != 0) {
+        // the reference's device-side message and __trap() (auxiliary.h:156-160), as an error return instead of a dead queue
+        hsr_set_error("Point is filtered although prefiltered is set. This shouldn't happen!");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
     return HSR_OK;
 }
 
@@ -395,14 +407,17 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
         hsr_set_error("SH degree %d needs M >= %d coefficients (got %d)", in.D, (in.D + 1) * (in.D + 1), in.M);
         return HSR_ERR_INVALID_ARGUMENT;
     }
+    if (!in.semantic && !in.out_mask) {
+        hsr_set_error("out_mask is NULL");
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
 
     int rc;
-    char* gptr;
-    char* iptr;
+    char *gptr, *iptr;
     if ((rc = acquire(geometry, hsr_required_geometry_bytes(P), "geometry", &gptr)) != HSR_OK) return rc;
     if ((rc = acquire(image, hsr_required_image_bytes(W, H), "image", &iptr)) != HSR_OK) return rc;
-    GeomState g;
-    ImgState im;
+    GeomState g{};
+    ImgState im{};
     hsr_carve_geom(gptr, P, &g);
     hsr_carve_img(iptr, W, H, &im);
 
@@ -410,7 +425,7 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
     const int T = tiles_x * tiles_y;
     int* radii = in.radii ? in.radii : g.radii;
 
-    PreprocessArgs pa;
+    PreprocessArgs pa{};
     pa.P = P; pa.D = in.D; pa.M = in.M; pa.W = W; pa.H = H;
     pa.means3D = in.means3D; pa.scales = in.scales; pa.scale_modifier = in.scale_modifier; pa.rotations = in.rotations;
     pa.opacities = in.opacities; pa.shs = in.shs; pa.cov3D_precomp = in.cov3D_precomp; pa.colors_precomp = in.colors_precomp;
@@ -449,9 +464,9 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
             if ((rc = ring_slot(&seq, &slot_host, &slot_dev, &slot_device)) != HSR_OK) return rc;
         } else {
             if ((rc = counter_buffer()) != HSR_OK) return rc;
-            seq = ++g_counter_seq;
-            if (seq == 0) seq = ++g_counter_seq;
-            slot_dev = g_pinned_dev;
+            seq = ++g_pc->seq;
+            if (seq == 0) seq = ++g_pc->seq;
+            slot_dev = g_pc->dev;
         }
         StageTimer tm(HSR_STAGE_FWD_DUPLICATE, stream);
         hsr_launch_bin_count(plan, P, radii, tiles_x, tiles_y, g, bin_scratch, im.ranges, stream, slot_dev, seq);
@@ -463,19 +478,57 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
 
     if (!binned && (rc = read_counter_begin(g.counters, stream)) != HSR_OK) return rc;
 
-    RenderFwdArgs ra;
+    RenderFwdArgs ra{};   // point_list, masks and bin: filled in by the tail
     ra.W = W; ra.H = H; ra.K = in.semantic ? in.K : 0; ra.semantic = in.semantic;
-    ra.ranges = im.ranges; ra.point_list = nullptr; ra.masks = nullptr; ra.means2D = g.means2D; ra.conic_opacity = g.conic_opacity;
+    ra.ranges = im.ranges; ra.means2D = g.means2D; ra.conic_opacity = g.conic_opacity;
     ra.depths = g.depths; ra.colors = in.colors_precomp ? in.colors_precomp : g.rgb; ra.semantics = in.semantics;
     ra.rec = g.rec;
     ra.final_T = im.final_T; ra.n_contrib = im.n_contrib; ra.median_pos = im.median_pos;
     ra.out_color = in.out_color; ra.out_semantic = in.out_semantic; ra.out_depth = in.out_depth;
     ra.out_median_depth = in.out_median; ra.out_opacity = in.out_opacity; ra.out_mask = in.out_mask;
-    ra.bin = BinDevRef{nullptr, nullptr, 0};
-    if (!in.semantic && !in.out_mask) {
-        hsr_set_error("out_mask is NULL");
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
+
+    // The tail, the stages behind the count, stated once: instance emission -> sort -> tile render.  The lists lie in b, carved
+    // for R instances — or, ref given, where the kernels themselves resolve them from the device-side count (the speculative form
+    // of the direct-binning path: b all NULL, R unknown; debug is off there, so its one launch check asks for launch errors only).
+    const auto enqueue_tail = [&](BinState b, int R, const BinDevRef* ref, int per_tile_hint) -> int {
+        if (binned) {
+            {   // also when R == 0: its first workgroup writes the tile ranges
+                StageTimer tm(HSR_STAGE_FWD_DUPLICATE, stream);
+                hsr_launch_bin_emit(plan, P, radii, tiles_x, tiles_y, g, bin_scratch, im.ranges, b.keys, stream, ref);
+            }
+            if (!ref) HSR_LAUNCH_CHECK(in.debug, stream);
+            StageTimer tm(HSR_STAGE_FWD_SORT, stream);
+            if (ref || R > 0) hsr_launch_tile_sort(b, T, P, im.ranges, stream, ref, per_tile_hint);
+        } else {
+            // emit into the buffer pair from which the sort's ping-pong passes end in (keys, vals)
+            const bool emit_sorted = hsr_sort_emit_into_sorted_buffers(end_bit);
+            {
+                StageTimer tm(HSR_STAGE_FWD_DUPLICATE, stream);
+                BinState be = b;
+                be.keys_unsorted = emit_sorted ? b.keys : b.keys_unsorted;
+                be.vals_unsorted = emit_sorted ? b.vals : b.vals_unsorted;
+                hsr_launch_duplicate(P, radii, tiles_x, tiles_y, g, be, im.ranges, stream);
+            }
+            HSR_LAUNCH_CHECK(in.debug, stream);
+            // tile-bit radix passes -> tile ranges -> per-tile depth sort (ranges are a by-product of the sort)
+            StageTimer tm(HSR_STAGE_FWD_SORT, stream);
+            if ((rc = hsr_launch_sort_pairs(b, R, end_bit, T, im.ranges, stream)) != HSR_OK) return rc;
+        }
+        if (!ref) HSR_LAUNCH_CHECK(in.debug, stream);
+        RenderFwdArgs r = ra;
+        if (ref) {
+            r.bin = *ref;
+        } else {
+            r.point_list = b.vals;
+            r.masks = b.vals_unsorted;   // free after the sort: the staging phase leaves the sub-block masks there for the backward
+        }
+        {
+            StageTimer tm(HSR_STAGE_FWD_RENDER, stream);
+            hsr_launch_render_forward(r, stream);
+        }
+        HSR_LAUNCH_CHECK(in.debug, stream);
+        return HSR_OK;
+    };
 
     // Speculative tail: when the caller's binning buffer already has room (diff_gaussian_rasterization sizes it from the
     // previous frame), the emit, per-tile sort and render kernels are enqueued BEFORE the host reads num_rendered back; they
@@ -483,25 +536,9 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
     // The host then waits on an event that completed long ago instead of idling the stream while it wakes up and launches
     // the rest — the reference stalls here on every frame (rasterizer_impl.cu:285), and with a 0.65 ms render the host
     // side (~0.45 ms per fwd+bwd through Python) would otherwise be on the critical path.
-    bool speculated = false;
     if (will_speculate) {
         const BinDevRef ref{static_cast<char*>(binning->ptr), reinterpret_cast<const uint32_t*>(g.counters), binning->capacity};
-        BinState none{nullptr, nullptr, nullptr, nullptr, nullptr};
-        {
-            StageTimer tm(HSR_STAGE_FWD_DUPLICATE, stream);
-            hsr_launch_bin_emit(plan, P, radii, tiles_x, tiles_y, g, bin_scratch, im.ranges, nullptr, stream, &ref);
-        }
-        {
-            StageTimer tm(HSR_STAGE_FWD_SORT, stream);
-            hsr_launch_tile_sort(none, T, P, im.ranges, stream, &ref, g_last_per_tile);
-        }
-        ra.bin = ref;
-        {
-            StageTimer tm(HSR_STAGE_FWD_RENDER, stream);
-            hsr_launch_render_forward(ra, stream);
-        }
-        HSR_HIP_CHECK(hipGetLastError());
-        speculated = true;
+        if ((rc = enqueue_tail(BinState{}, 0, &ref, g_last_per_tile)) != HSR_OK) return rc;
     }
     if (go_async) {
         // everything is enqueued; the count is read by hsr_forward_end (typically from the backward, when it has long arrived)
@@ -516,74 +553,35 @@ int forward_impl(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, c
 
     uint32_t R32 = 0;
     if ((rc = binned ? poll_counter(seq, stream, &R32) : read_counter_end(&R32)) != HSR_OK) return rc;
-    if (R32 > 0x7fffffffu) {
-        hsr_set_error("num_rendered %u overflows int", R32);
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
+    if ((rc = check_count(R32, in.prefiltered, g_pc->host, nullptr)) != HSR_OK) return rc;
     const int R = (int)R32;
-    if (in.prefiltered && __atomic_load_n(&g_pinned[2], __ATOMIC_RELAXED) != 0) {
-        // the reference's device-side message and __trap() (auxiliary.h:156-160), as an error return instead of a dead queue
-        hsr_set_error("Point is filtered although prefiltered is set. This shouldn't happen!");
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    if (speculated) {
-        BinState chk;
+    const int per_tile = R / (T > 0 ? T : 1);
+    if (will_speculate) {
+        BinState chk{};
         const BinDevRef ref{static_cast<char*>(binning->ptr), nullptr, binning->capacity};
-        g_last_per_tile = R / (T > 0 ? T : 1);
+        g_last_per_tile = per_tile;
         if (hsr_bin_resolve(ref, R32, &chk)) return R;   // the kernels found the same layout: done
         // too small after all: the speculative kernels returned at once; the render kernel's final_T (= the count table)
         // was not touched either, but recount anyway to keep this rare path independent of that
-        hsr_launch_bin_count(plan, P, radii, tiles_x, tiles_y, g, bin_scratch, im.ranges, stream, g_pinned_dev, seq);
-        ra.bin = BinDevRef{nullptr, nullptr, 0};
+        hsr_launch_bin_count(plan, P, radii, tiles_x, tiles_y, g, bin_scratch, im.ranges, stream, g_pc->dev, seq);
     }
 
     char* bptr;
     if ((rc = acquire(binning, hsr_required_binning_bytes(R), "binning", &bptr)) != HSR_OK) return rc;
-    BinState b;
+    BinState b{};
     hsr_carve_bin(bptr, R, &b);
-
-    if (binned) {   // also when R == 0: its first workgroup writes the tile ranges
-        StageTimer tm(HSR_STAGE_FWD_DUPLICATE, stream);
-        hsr_launch_bin_emit(plan, P, radii, tiles_x, tiles_y, g, bin_scratch, im.ranges, b.keys, stream);
-    }
-    if (binned) {
-        HSR_LAUNCH_CHECK(in.debug, stream);
-        StageTimer tm(HSR_STAGE_FWD_SORT, stream);
-        if (R > 0) hsr_launch_tile_sort(b, T, P, im.ranges, stream, nullptr, R / (T > 0 ? T : 1));
-    } else {
-        // emit into the buffer pair from which the sort's ping-pong passes end in (keys, vals)
-        const bool emit_sorted = hsr_sort_emit_into_sorted_buffers(end_bit);
-        uint64_t* emit_k = emit_sorted ? b.keys : b.keys_unsorted;
-        uint32_t* emit_v = emit_sorted ? b.vals : b.vals_unsorted;
-        {
-            StageTimer tm(HSR_STAGE_FWD_DUPLICATE, stream);
-            BinState be = b;
-            be.keys_unsorted = emit_k;
-            be.vals_unsorted = emit_v;
-            hsr_launch_duplicate(P, radii, tiles_x, tiles_y, g, be, im.ranges, stream);
-        }
-        HSR_LAUNCH_CHECK(in.debug, stream);
-        // tile-bit radix passes -> tile ranges -> per-tile depth sort (ranges are a by-product of the sort)
-        StageTimer tm(HSR_STAGE_FWD_SORT, stream);
-        if ((rc = hsr_launch_sort_pairs(b, R, end_bit, T, im.ranges, stream)) != HSR_OK) return rc;
-    }
-    HSR_LAUNCH_CHECK(in.debug, stream);
-
-    ra.point_list = b.vals;
-    ra.masks = b.vals_unsorted;   // free after the sort: the staging phase leaves the sub-block masks there for the backward
-    {
-        StageTimer tm(HSR_STAGE_FWD_RENDER, stream);
-        hsr_launch_render_forward(ra, stream);
-    }
-    HSR_LAUNCH_CHECK(in.debug, stream);
+    if ((rc = enqueue_tail(b, R, nullptr, per_tile)) != HSR_OK) return rc;
     return R;
 }
 
-struct BwdIn {
-    int P, D, M, K, semantic, R, W, H, debug;
-    const float *background, *means3D, *shs, *colors_precomp, *semantics, *scales, *rotations, *cov3D_precomp, *viewmatrix,
-        *projmatrix, *campos;
-    float scale_modifier, tan_fovx, tan_fovy;
+struct BwdIn {   // in the order of hsr_backward_semantic's parameters (see FwdIn)
+    int P, D, M, K, R;
+    const float* background;
+    int W, H;
+    const float *means3D, *shs, *colors_precomp, *semantics, *scales;
+    float scale_modifier;
+    const float *rotations, *cov3D_precomp, *viewmatrix, *projmatrix, *campos;
+    float tan_fovx, tan_fovy;
     const int* radii;
     const char *geom, *binning, *img;
     const float *dL_dpix, *dL_dpix_sem, *dL_dpix_depth, *dL_dpix_median, *dL_dpix_opacity;
@@ -591,20 +589,26 @@ struct BwdIn {
         *dL_dscale, *dL_drot;
     char* scratch;
     size_t scratch_bytes;
+    int debug, semantic;
 };
 
-// the sums the tile kernel accumulates atomically start from zero (the reference relies on the
-// caller's torch::zeros, rasterize_points.cu:378-388)
-int zero_accumulators(const BwdIn& in, int K, hipStream_t stream)
+// The sums the tile kernel accumulates atomically start from zero (the reference relies on the caller's torch::zeros,
+// rasterize_points.cu:378-388): the packed rows (grow) of visible Gaussians (radii > 0) only — nothing else is added into or read back
+// (hsr_backward_pre.hip) — or, grow NULL, the legacy mode's six output arrays.
+int zero_accumulators(const BwdIn& in, int K, const int* radii, float* grow, int row_stride, hipStream_t stream)
 {
     StageTimer tm(HSR_STAGE_BWD_ZERO, stream);
     const size_t P = (size_t)in.P;
-    HSR_HIP_CHECK(hipMemsetAsync(in.dL_dmean2D, 0, sizeof(float) * 3 * P, stream));
-    HSR_HIP_CHECK(hipMemsetAsync(in.dL_dconic, 0, sizeof(float) * 4 * P, stream));
-    HSR_HIP_CHECK(hipMemsetAsync(in.dL_dopacity, 0, sizeof(float) * P, stream));
-    HSR_HIP_CHECK(hipMemsetAsync(in.dL_dcolor, 0, sizeof(float) * 3 * P, stream));
-    HSR_HIP_CHECK(hipMemsetAsync(in.dL_ddepth, 0, sizeof(float) * P, stream));
-    if (K > 0) HSR_HIP_CHECK(hipMemsetAsync(in.dL_dsemantics, 0, sizeof(float) * (size_t)K * P, stream));
+    if (grow) {
+        hsr_launch_zero_visible_rows(in.P, radii, grow, row_stride, stream);
+    } else {
+        HSR_HIP_CHECK(hipMemsetAsync(in.dL_dmean2D, 0, sizeof(float) * 3 * P, stream));
+        HSR_HIP_CHECK(hipMemsetAsync(in.dL_dconic, 0, sizeof(float) * 4 * P, stream));
+        HSR_HIP_CHECK(hipMemsetAsync(in.dL_dopacity, 0, sizeof(float) * P, stream));
+        HSR_HIP_CHECK(hipMemsetAsync(in.dL_dcolor, 0, sizeof(float) * 3 * P, stream));
+        HSR_HIP_CHECK(hipMemsetAsync(in.dL_ddepth, 0, sizeof(float) * P, stream));
+        if (K > 0) HSR_HIP_CHECK(hipMemsetAsync(in.dL_dsemantics, 0, sizeof(float) * (size_t)K * P, stream));
+    }
     // SH coefficients above the active degree (and those of culled Gaussians) receive no gradient
     if (!in.colors_precomp && in.shs && in.dL_dsh && in.M > 0)
         HSR_HIP_CHECK(hipMemsetAsync(in.dL_dsh, 0, sizeof(float) * 3 * (size_t)in.M * P, stream));
@@ -646,9 +650,9 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
         hsr_set_error("background is NULL");
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    GeomState g;
-    ImgState im;
-    BinState b;
+    GeomState g{};
+    ImgState im{};
+    BinState b{};
     hsr_carve_geom(const_cast<char*>(in.geom), P, &g);
     hsr_carve_img(const_cast<char*>(in.img), W, H, &im);
     hsr_carve_bin(const_cast<char*>(in.binning), in.R, &b);
@@ -679,21 +683,16 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
             return HSR_ERR_INVALID_ARGUMENT;
         }
     }
-    float* grow = nullptr;
-    if (use_packed) {
-        char* sp = in.scratch;
-        take(sp, grow, (size_t)P * plan.row_stride);
-        StageTimer tm(HSR_STAGE_BWD_ZERO, stream);
-        // only the rows of visible Gaussians (radii > 0): nothing else is added into or read back (hsr_backward_pre.hip)
-        hsr_launch_zero_visible_rows(P, radii, grow, plan.row_stride, stream);
-        if (!in.colors_precomp && in.shs && in.dL_dsh && in.M > 0)
-            HSR_HIP_CHECK(hipMemsetAsync(in.dL_dsh, 0, sizeof(float) * 3 * (size_t)in.M * (size_t)P, stream));
-    } else {
-        if ((rc = zero_accumulators(in, K, stream)) != HSR_OK) return rc;
+    const float* shs = in.colors_precomp ? nullptr : in.shs;
+    if (shs && (!in.dL_dsh || !in.campos)) {
+        hsr_set_error("shs given without dL_dsh / campos");
+        return HSR_ERR_INVALID_ARGUMENT;
     }
+    float* grow = use_packed ? reinterpret_cast<float*>(hsr_align256(reinterpret_cast<uintptr_t>(in.scratch))) : nullptr;   // rows: 256-aligned
+    if ((rc = zero_accumulators(in, K, radii, grow, plan.row_stride, stream)) != HSR_OK) return rc;
 
     if (in.R > 0) {
-        RenderBwdArgs ra;
+        RenderBwdArgs ra{};
         ra.W = W; ra.H = H; ra.K = K; ra.semantic = in.semantic; ra.P = P;
         ra.bg = in.background; ra.ranges = im.ranges; ra.point_list = b.vals; ra.masks = b.vals_unsorted; ra.means2D = g.means2D;
         ra.conic_opacity = g.conic_opacity; ra.depths = g.depths; ra.colors = in.colors_precomp ? in.colors_precomp : g.rgb;
@@ -715,9 +714,9 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     }
     HSR_LAUNCH_CHECK(in.debug, stream);
 
-    PreBwdArgs pb;
+    PreBwdArgs pb{};
     pb.P = P; pb.D = in.D; pb.M = in.M; pb.means3D = in.means3D; pb.radii = radii;
-    pb.shs = in.colors_precomp ? nullptr : in.shs; pb.clamped = g.clamped; pb.scales = in.scales; pb.rotations = in.rotations;
+    pb.shs = shs; pb.clamped = g.clamped; pb.scales = in.scales; pb.rotations = in.rotations;
     pb.scale_modifier = in.scale_modifier; pb.cov3Ds = in.cov3D_precomp ? in.cov3D_precomp : g.cov3D;
     pb.viewmatrix = in.viewmatrix; pb.projmatrix = in.projmatrix;
     pb.focal_y = H / (2.0f * in.tan_fovy); pb.focal_x = W / (2.0f * in.tan_fovx);
@@ -729,10 +728,6 @@ int backward_impl(const BwdIn& in, hipStream_t stream)
     pb.out_mean2D = in.dL_dmean2D; pb.out_conic = in.dL_dconic; pb.out_opacity = in.dL_dopacity; pb.out_color = in.dL_dcolor;
     pb.out_semantics = in.dL_dsemantics; pb.out_depth = in.dL_ddepth;
     pb.grow = grow; pb.grow_stride = plan.row_stride; pb.grow_layout = plan.row_layout; pb.geo = plan.geometry_only;
-    if (pb.shs && (!in.dL_dsh || !in.campos)) {
-        hsr_set_error("shs given without dL_dsh / campos");
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
     {
         StageTimer tm(HSR_STAGE_BWD_PREPROCESS, stream);
         if ((rc = hsr_launch_preprocess_backward(pb, stream)) != HSR_OK) return rc;
@@ -751,62 +746,8 @@ void hsr_set_error(const char* fmt, ...)
     va_end(ap);
 }
 
-size_t hsr_carve_geom(char* base, int P, GeomState* out)
-{
-    char* p = base;
-    GeomState g;
-    const size_t Pn = (size_t)(P > 0 ? P : 1);
-    take(p, g.depths, Pn);
-    take(p, g.means2D, Pn);
-    take(p, g.conic_opacity, Pn);
-    take(p, g.cov3D, Pn * 6);
-    take(p, g.rgb, Pn * 3);
-    take(p, g.clamped, Pn * 3);
-    take(p, g.tiles_touched, Pn);
-    take(p, g.point_offsets, Pn);
-    take(p, g.radii, Pn);
-    take(p, g.block_sums, (Pn + 255) / 256 + 1);
-    take(p, g.counters, 8);
-    take(p, g.rec, Pn * 4);
-    if (out) *out = g;
-    return (size_t)(p - base);
-}
-size_t hsr_carve_img(char* base, int W, int H, ImgState* out)
-{
-    char* p = base;
-    ImgState s;
-    const size_t N = (size_t)W * H;
-    const size_t T = (size_t)hsr_num_tiles(W, H);
-    take(p, s.ranges, T);
-    take(p, s.final_T, N);
-    take(p, s.n_contrib, N);
-    take(p, s.median_pos, N);
-    if (out) *out = s;
-    return (size_t)(p - base);
-}
-size_t hsr_carve_bin(char* base, int R, BinState* out)
-{
-    // ONE layout rule for the binning buffer: hsr_bin_resolve (hsr_common.h), which the speculative kernels also evaluate on the
-    // device from num_rendered.  It aligns each array from the real address, so the size query runs it from a 256-aligned origin.
-    BinState b;
-    char* origin = base ? base : reinterpret_cast<char*>(uintptr_t(256));
-    const BinDevRef ref{origin, nullptr, ~size_t(0) >> 1};
-    hsr_bin_resolve(ref, (uint32_t)(R > 0 ? R : 0), &b);
-    const uint32_t Rn = (uint32_t)(R > 0 ? R : 0);
-    const size_t bytes = (size_t)(reinterpret_cast<char*>(b.hist + hsr_sort_hist_entries_inline(Rn)) - origin);
-    if (!base) {   // layout query: offsets from a NULL base, as hsr_get_state_layout reports them
-        auto rebase = [&](auto*& q) { q = reinterpret_cast<std::remove_reference_t<decltype(q)>>(reinterpret_cast<char*>(q) - 256); };
-        rebase(b.keys_unsorted); rebase(b.keys); rebase(b.vals_unsorted); rebase(b.vals); rebase(b.hist);
-    }
-    if (out) *out = b;
-    return bytes;
-}
-
 extern "C" {
 
-size_t hsr_required_geometry_bytes(int P) { return hsr_carve_geom(nullptr, P, nullptr) + 256; }
-size_t hsr_required_image_bytes(int width, int height) { return hsr_carve_img(nullptr, width, height, nullptr) + 256; }
-size_t hsr_required_binning_bytes(int num_rendered) { return hsr_carve_bin(nullptr, num_rendered, nullptr) + 256; }
 size_t hsr_backward_scratch_bytes(int P, int K, int num_rendered)
 {
     if (P <= 0 || K < 0) return 0;
@@ -899,27 +840,6 @@ const char* hsr_stage_name(int stage)
 }
 const char* hsr_version(void) { return "hsr_rast 0.1 gfx950"; }
 
-int hsr_get_state_layout(int P, int width, int height, int num_rendered, hsr_state_layout* out)
-{
-    if (!out) return HSR_ERR_INVALID_ARGUMENT;
-    GeomState g;
-    ImgState im;
-    BinState b;
-    hsr_carve_geom(nullptr, P, &g);
-    hsr_carve_img(nullptr, width, height, &im);
-    hsr_carve_bin(nullptr, num_rendered, &b);
-#define OFF(p) ((size_t) reinterpret_cast<uintptr_t>(p))
-    out->geom_depths = OFF(g.depths); out->geom_means2D = OFF(g.means2D); out->geom_conic_opacity = OFF(g.conic_opacity);
-    out->geom_cov3D = OFF(g.cov3D); out->geom_rgb = OFF(g.rgb); out->geom_clamped = OFF(g.clamped);
-    out->geom_tiles_touched = OFF(g.tiles_touched); out->geom_point_offsets = OFF(g.point_offsets); out->geom_radii = OFF(g.radii);
-    out->bin_keys_unsorted = OFF(b.keys_unsorted); out->bin_keys = OFF(b.keys); out->bin_vals_unsorted = OFF(b.vals_unsorted);
-    out->bin_vals = OFF(b.vals);
-    out->img_ranges = OFF(im.ranges); out->img_final_T = OFF(im.final_T); out->img_n_contrib = OFF(im.n_contrib);
-    out->img_median_pos = OFF(im.median_pos);
-#undef OFF
-    return HSR_OK;
-}
-
 int hsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix, uint8_t* present,
                      void* stream)
 {
@@ -956,16 +876,8 @@ int hsr_forward_end(hsr_ticket* ticket, int block, void* stream)
     uint32_t R32 = 0;
     int rc;
     if ((rc = poll_counter(ticket->seq, static_cast<hipStream_t>(stream), &R32, ticket->slot)) != HSR_OK) return rc;
-    if (R32 > 0x7fffffffu) {
-        hsr_set_error("num_rendered %u overflows int", R32);
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    ticket->rendered = (int32_t)R32;
-    if (ticket->prefiltered && __atomic_load_n(&ticket->slot[2], __ATOMIC_RELAXED) != 0) {
-        hsr_set_error("Point is filtered although prefiltered is set. This shouldn't happen!");
-        return HSR_ERR_INVALID_ARGUMENT;
-    }
-    BinState chk;
+    if ((rc = check_count(R32, ticket->prefiltered, ticket->slot, &ticket->rendered)) != HSR_OK) return rc;
+    BinState chk{};
     const BinDevRef ref{ticket->binning_base, nullptr, ticket->binning_capacity};
     if (!hsr_bin_resolve(ref, R32, &chk)) {
         hsr_set_error("non-blocking forward: num_rendered = %u does not fit the binning buffer (%zu bytes, %zu needed): the output images of "
@@ -983,14 +895,9 @@ int hsr_forward(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* image, in
                 float tan_fovx, float tan_fovy, int prefiltered, float* out_color, float* out_depth, float* out_median_depth,
                 float* out_opacity, float* out_mask, int* radii, int debug, void* stream)
 {
-    FwdIn in;
-    in.P = P; in.D = D; in.M = M; in.K = 0; in.semantic = 0; in.W = width; in.H = height; in.prefiltered = prefiltered; in.debug = debug;
-    in.background = background; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.semantics = nullptr;
-    in.opacities = opacities; in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp;
-    in.viewmatrix = viewmatrix; in.projmatrix = projmatrix; in.cam_pos = cam_pos;
-    in.scale_modifier = scale_modifier; in.tan_fovx = tan_fovx; in.tan_fovy = tan_fovy;
-    in.out_color = out_color; in.out_semantic = nullptr; in.out_depth = out_depth; in.out_median = out_median_depth;
-    in.out_opacity = out_opacity; in.out_mask = out_mask; in.radii = radii;
+    const FwdIn in{P, D, M, /*K*/ 0, background, width, height, means3D, shs, colors_precomp, /*semantics*/ nullptr, opacities, scales,
+                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                   /*out_semantic*/ nullptr, out_depth, out_median_depth, out_opacity, radii, debug, /*semantic*/ 0, out_mask};
     return forward_impl(geometry, binning, image, in, static_cast<hipStream_t>(stream));
 }
 
@@ -1002,14 +909,9 @@ int hsr_forward_semantic(hsr_buffer* geometry, hsr_buffer* binning, hsr_buffer* 
                          float tan_fovy, int prefiltered, float* out_color, float* out_semantic, float* out_depth,
                          float* out_median_depth, float* out_opacity, int* radii, int debug, void* stream)
 {
-    FwdIn in;
-    in.P = P; in.D = D; in.M = M; in.K = K; in.semantic = 1; in.W = width; in.H = height; in.prefiltered = prefiltered; in.debug = debug;
-    in.background = background; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.semantics = semantics_precomp;
-    in.opacities = opacities; in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp;
-    in.viewmatrix = viewmatrix; in.projmatrix = projmatrix; in.cam_pos = cam_pos;
-    in.scale_modifier = scale_modifier; in.tan_fovx = tan_fovx; in.tan_fovy = tan_fovy;
-    in.out_color = out_color; in.out_semantic = out_semantic; in.out_depth = out_depth; in.out_median = out_median_depth;
-    in.out_opacity = out_opacity; in.out_mask = nullptr; in.radii = radii;
+    const FwdIn in{P, D, M, K, background, width, height, means3D, shs, colors_precomp, semantics_precomp, opacities, scales,
+                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, prefiltered, out_color,
+                   out_semantic, out_depth, out_median_depth, out_opacity, radii, debug, /*semantic*/ 1};   // no out_mask
     return forward_impl(geometry, binning, image, in, static_cast<hipStream_t>(stream));
 }
 
@@ -1022,18 +924,11 @@ int hsr_backward(int P, int D, int M, int R, const float* background, int width,
                  float* dL_dopacity, float* dL_dcolor, float* dL_ddepth, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh,
                  float* dL_dscale, float* dL_drot, char* scratch, size_t scratch_bytes, int debug, void* stream)
 {
-    BwdIn in;
-    in.scratch = scratch; in.scratch_bytes = scratch_bytes;
-    in.P = P; in.D = D; in.M = M; in.K = 0; in.semantic = 0; in.R = R; in.W = width; in.H = height; in.debug = debug;
-    in.background = background; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.semantics = nullptr;
-    in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp; in.viewmatrix = viewmatrix;
-    in.projmatrix = projmatrix; in.campos = campos; in.scale_modifier = scale_modifier; in.tan_fovx = tan_fovx; in.tan_fovy = tan_fovy;
-    in.radii = radii; in.geom = geom_buffer; in.binning = binning_buffer; in.img = img_buffer;
-    in.dL_dpix = dL_dpix; in.dL_dpix_sem = nullptr; in.dL_dpix_depth = dL_dpix_depth; in.dL_dpix_median = dL_dpix_median_depth;
-    in.dL_dpix_opacity = dL_dpix_final_opacity;
-    in.dL_dmean2D = dL_dmean2D; in.dL_dconic = dL_dconic; in.dL_dopacity = dL_dopacity; in.dL_dcolor = dL_dcolor;
-    in.dL_dsemantics = nullptr; in.dL_ddepth = dL_ddepth; in.dL_dmean3D = dL_dmean3D; in.dL_dcov3D = dL_dcov3D; in.dL_dsh = dL_dsh;
-    in.dL_dscale = dL_dscale; in.dL_drot = dL_drot;
+    const BwdIn in{P, D, M, /*K*/ 0, R, background, width, height, means3D, shs, colors_precomp, /*semantics*/ nullptr, scales,
+                   scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
+                   binning_buffer, img_buffer, dL_dpix, /*dL_dpix_sem*/ nullptr, dL_dpix_depth, dL_dpix_median_depth,
+                   dL_dpix_final_opacity, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, /*dL_dsemantics*/ nullptr, dL_ddepth, dL_dmean3D,
+                   dL_dcov3D, dL_dsh, dL_dscale, dL_drot, scratch, scratch_bytes, debug, /*semantic*/ 0};
     return backward_impl(in, static_cast<hipStream_t>(stream));
 }
 
@@ -1048,18 +943,11 @@ int hsr_backward_semantic(int P, int D, int M, int K, int R, const float* backgr
                           float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot,
                           char* scratch, size_t scratch_bytes, int debug, void* stream)
 {
-    BwdIn in;
-    in.scratch = scratch; in.scratch_bytes = scratch_bytes;
-    in.P = P; in.D = D; in.M = M; in.K = K; in.semantic = 1; in.R = R; in.W = width; in.H = height; in.debug = debug;
-    in.background = background; in.means3D = means3D; in.shs = shs; in.colors_precomp = colors_precomp; in.semantics = semantics_precomp;
-    in.scales = scales; in.rotations = rotations; in.cov3D_precomp = cov3D_precomp; in.viewmatrix = viewmatrix;
-    in.projmatrix = projmatrix; in.campos = campos; in.scale_modifier = scale_modifier; in.tan_fovx = tan_fovx; in.tan_fovy = tan_fovy;
-    in.radii = radii; in.geom = geom_buffer; in.binning = binning_buffer; in.img = img_buffer;
-    in.dL_dpix = dL_dpix; in.dL_dpix_sem = dL_dpix_semantic; in.dL_dpix_depth = dL_dpix_depth; in.dL_dpix_median = dL_dpix_median_depth;
-    in.dL_dpix_opacity = dL_dpix_final_opacity;
-    in.dL_dmean2D = dL_dmean2D; in.dL_dconic = dL_dconic; in.dL_dopacity = dL_dopacity; in.dL_dcolor = dL_dcolor;
-    in.dL_dsemantics = dL_dsemantics; in.dL_ddepth = dL_ddepth; in.dL_dmean3D = dL_dmean3D; in.dL_dcov3D = dL_dcov3D; in.dL_dsh = dL_dsh;
-    in.dL_dscale = dL_dscale; in.dL_drot = dL_drot;
+    const BwdIn in{P, D, M, K, R, background, width, height, means3D, shs, colors_precomp, semantics_precomp, scales, scale_modifier,
+                   rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer, binning_buffer,
+                   img_buffer, dL_dpix, dL_dpix_semantic, dL_dpix_depth, dL_dpix_median_depth, dL_dpix_final_opacity, dL_dmean2D,
+                   dL_dconic, dL_dopacity, dL_dcolor, dL_dsemantics, dL_ddepth, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                   scratch, scratch_bytes, debug, /*semantic*/ 1};
     return backward_impl(in, static_cast<hipStream_t>(stream));
 }
 

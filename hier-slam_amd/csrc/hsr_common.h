@@ -60,22 +60,47 @@ __host__ __device__ inline uint32_t hsr_sort_hist_entries_inline(uint32_t R)
     const uint32_t nblocks = (R + HSR_SORT_TILE - 1) / HSR_SORT_TILE;
     return 256u * (nblocks > 0 ? nblocks : 1u) + 256u;
 }
-// same arithmetic as hsr_carve_bin (each array 256-byte aligned); false when the buffer is too small for R instances
-__host__ __device__ inline bool hsr_bin_resolve(const BinDevRef& ref, uint32_t R, BinState* out)
+
+// ---- layouts of the three state buffers, stated once each (hsr_state.hip; the binning buffer's here, for the device): the byte
+// offset of every array from a 256-aligned origin, every array 256-aligned, and `end`, the bytes used from that origin.  Integers
+// only.  A carve aligns the real base up to 256 and adds the offsets; a size query is `end` plus 256 bytes for that alignment.
+constexpr size_t hsr_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct GeomLayout { size_t depths, means2D, conic_opacity, cov3D, rgb, clamped, tiles_touched, point_offsets, radii, block_sums, counters, rec, end; };
+struct ImgLayout { size_t ranges, final_T, n_contrib, median_pos, end; };
+struct BinLayout { size_t keys_unsorted, keys, vals_unsorted, vals, hist, end; };
+GeomLayout hsr_geom_layout(int P);
+ImgLayout hsr_img_layout(int W, int H);
+// the ONE rule of the binning buffer, counted from `origin`: 0 for offsets (a 256-aligned base), or an address as an integer, which
+// is how the speculative kernels resolve their arrays from the device-side num_rendered (hsr_bin_resolve)
+__host__ __device__ inline BinLayout hsr_bin_layout(size_t origin, uint32_t R)
 {
     const size_t Rn = R > 0 ? R : 1;
-    uintptr_t p = reinterpret_cast<uintptr_t>(ref.base);
-    p = (p + 255) & ~(uintptr_t)255; out->keys_unsorted = reinterpret_cast<uint64_t*>(p); p += 8 * Rn;
-    p = (p + 255) & ~(uintptr_t)255; out->keys = reinterpret_cast<uint64_t*>(p); p += 8 * Rn;
-    p = (p + 255) & ~(uintptr_t)255; out->vals_unsorted = reinterpret_cast<uint32_t*>(p); p += 4 * Rn;
-    p = (p + 255) & ~(uintptr_t)255; out->vals = reinterpret_cast<uint32_t*>(p); p += 4 * Rn;
-    p = (p + 255) & ~(uintptr_t)255; out->hist = reinterpret_cast<uint32_t*>(p); p += 4 * (size_t)hsr_sort_hist_entries_inline(R);
-    return p - reinterpret_cast<uintptr_t>(ref.base) <= ref.capacity && R <= 0x7fffffffu;
+    BinLayout l;
+    size_t p = origin;
+    p = (p + 255) & ~(size_t)255; l.keys_unsorted = p; p += 8 * Rn;
+    p = (p + 255) & ~(size_t)255; l.keys = p; p += 8 * Rn;
+    p = (p + 255) & ~(size_t)255; l.vals_unsorted = p; p += 4 * Rn;
+    p = (p + 255) & ~(size_t)255; l.vals = p; p += 4 * Rn;
+    p = (p + 255) & ~(size_t)255; l.hist = p; p += 4 * (size_t)hsr_sort_hist_entries_inline(R);
+    l.end = p;
+    return l;
+}
+// the arrays of R instances in the buffer at ref.base; false when it is too small for them
+__host__ __device__ inline bool hsr_bin_resolve(const BinDevRef& ref, uint32_t R, BinState* out)
+{
+    const size_t base = reinterpret_cast<uintptr_t>(ref.base);
+    const BinLayout l = hsr_bin_layout(base, R);
+    out->keys_unsorted = reinterpret_cast<uint64_t*>(l.keys_unsorted);
+    out->keys = reinterpret_cast<uint64_t*>(l.keys);
+    out->vals_unsorted = reinterpret_cast<uint32_t*>(l.vals_unsorted);
+    out->vals = reinterpret_cast<uint32_t*>(l.vals);
+    out->hist = reinterpret_cast<uint32_t*>(l.hist);
+    return l.end - base <= ref.capacity && R <= 0x7fffffffu;
 }
 
-size_t hsr_carve_geom(char* base, int P, GeomState* out);
-size_t hsr_carve_img(char* base, int W, int H, ImgState* out);
-size_t hsr_carve_bin(char* base, int R, BinState* out);
+void hsr_carve_geom(char* base, int P, GeomState* out);
+void hsr_carve_img(char* base, int W, int H, ImgState* out);
+void hsr_carve_bin(char* base, int R, BinState* out);   // R < 0 counts as 0
 
 void hsr_set_error(const char* fmt, ...);
 
@@ -251,8 +276,6 @@ int hsr_launch_zero_visible_rows(int P, const int* radii, float* grow, int strid
 #endif
 
 // ---- host helpers of the frame-sized units' entry points ----
-constexpr size_t hsr_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // a frame the kernels cannot index: an empty side, or more pixels than a 32-bit int counts
 inline bool hsr_bad_frame_size(int H, int W) { return H < 1 || W < 1 || (size_t)H * W > 0x7fffffffu; }
 

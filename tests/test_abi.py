@@ -210,6 +210,16 @@ def test_argument_validation_without_gpu():
     from hsr_utils import densify  # sets the argtypes of the densification entry points
     assert densify._lib.hsr_densify_scratch_bytes(680, 1200) > 680 * 1200 // 256 * 4
     assert lib.hsr_densify_frame(0, 8, *([null] * 4), 1.0, 1.0, 0.0, 0.0, null, 0.5, 50.0, 0, *([null] * 7), null, 0, null) == -1
+    # two refusals that depend on the arguments alone, in otherwise plausible calls: `d` stands for device memory and is never
+    # followed.  The buffer descriptors are NULL, so a call that got as far as acquiring one would say so instead.
+    dummy = C.create_string_buffer(256)
+    d = C.addressof(dummy)
+    rc = lib.hsr_forward(None, None, None, 10, 0, 0, d, 32, 16, d, null, d, d, d, 1.0, d, null, d, d, d, 1.0, 1.0, 0,
+                         d, d, d, d, null, null, 0, null)                                        # out_mask NULL
+    assert rc == -1 and lib.hsr_last_error() == b"out_mask is NULL"
+    rc = lib.hsr_backward(10, 0, 1, 100, d, 32, 16, d, d, null, d, 1.0, d, null, d, d, d, 1.0, 1.0, null, d, d, d,
+                          d, d, d, d, d, d, d, d, d, d, null, null, d, d, null, 0, 0, null)       # shs given, dL_dsh NULL
+    assert rc == -1 and lib.hsr_last_error() == b"shs given without dL_dsh / campos"
 
 
 def test_no_cpu_fallback_and_reference_error_messages():

@@ -21,7 +21,9 @@ def short(name):
 
 
 def kernels(obj):
-    """{demangled name: (size, [instruction lines])} of the functions in a device object"""
+    """{demangled name: (size, [instruction lines])} of the functions in a device object; none for a unit that side does not have"""
+    if not os.path.exists(obj):
+        return {}
     sizes = {}
     for line in subprocess.check_output([OBJDUMP, "-t", "-C", obj], text=True).splitlines():
         m = re.match(r"^[0-9a-f]+ [gl ].{6} \.text\s+([0-9a-f]+) (?:\.protected |\.hidden )?(.+)$", line)
