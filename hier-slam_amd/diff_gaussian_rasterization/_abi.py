@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER and SIGNATURES_EXT_FRAME_INGEST against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST and SIGNATURES_EXT_FRAME_EXPORT against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -63,6 +63,12 @@ class hsr_adam_tensor(C.Structure):
 class hsr_ingest_level(C.Structure):
     """one output level of hsr_frame_ingest (include/ext/hsr_frame_ingest.h)"""
     _fields_ = [("H", ci), ("W", ci), ("color", vp), ("depth", vp)]
+
+
+class hsr_export_job(C.Structure):
+    """one picture of hsr_frame_export (include/ext/hsr_frame_export.h)"""
+    _fields_ = [("kind", ci), ("src", vp), ("table", vp), ("n", ci), ("K", ci), ("L", ci), ("sizes", ci * 16), ("lo", cf), ("hi", cf),
+                ("out", vp)]
 
 
 bp, tk = C.POINTER(hsr_buffer), C.POINTER(hsr_ticket)
@@ -269,6 +275,11 @@ SIGNATURES_EXT_FRAME_INGEST = (
                               ci, C.POINTER(hsr_ingest_level), vp, vp]),
 )
 
+# include/ext/hsr_frame_export.h: and one more of its own (the five above are pinned by their suites)
+SIGNATURES_EXT_FRAME_EXPORT = (
+    ("hsr_frame_export", ci, [ci, ci, ci, C.POINTER(hsr_export_job), vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -278,7 +289,7 @@ def _load():
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
-                                    + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST):
+                                    + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

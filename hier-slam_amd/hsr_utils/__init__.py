@@ -12,6 +12,7 @@ _SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", 
          "resample_frame")
 _FRAMES = ("tree_label_table", "ingest_frame")
 _SEQUENCE = ("ReplicaSequence", "tree_annotation")
+_EXPORT = ("export_frame", "jet_colormap", "label_colormap", "tuple_colour_table", "write_png")
 
 
 def __getattr__(name):
@@ -28,4 +29,7 @@ def __getattr__(name):
     if name in _SEQUENCE:  # host only (PIL): resolved on first use like the rest
         from . import sequence
         return getattr(sequence, name)
+    if name in _EXPORT:    # the pictures of an evaluated frame: binds the library as well
+        from . import export
+        return getattr(export, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

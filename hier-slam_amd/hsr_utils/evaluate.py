@@ -11,6 +11,9 @@
     frame_miou(counts)                                                             mean IoU / boundary IoU of a frame :1487-1498
     evaluate_frame(...)                                                            the per-frame body of eval_semantic_tree_newrender
     trajectory_ate(gt_w2c_list, est_w2c_list)                                      evaluate_ate + align :218-275, :1555-1577 (numpy)
+    evaluate_sequence(params, frames, cam, eval_dir, ...)                          the loop of eval_semantic_tree_newrender / eval_newrender:
+                                                                                    scores per frame, the txt files, the pictures
+                                                                                    (hsr_utils.export, include/ext/hsr_frame_export.h)
 
 Every per-frame call runs on the current stream and returns device tensors without a host synchronisation: score all frames, read
 the numbers once at the end.  Frame averages are plain means over frames (:1590-1600).  There is no CPU path.
@@ -249,6 +252,13 @@ def evaluate_frame(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, *, 
     semantic rasterizer returns them; gt_labels: the leaf label map ([H,W], int; label_gt[-1] for tree datasets).  `mode` and its
     arguments as semantic_labels; num_classes / class_ids as iou_counts.  With ms_ssim=True the dict is without LPIPS only: it gains
     the key ms_ssim (float64, the function ms_ssim of this module on the same images and masks).  No host synchronisation."""
+    return _frame_scores(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, final_opacity, sil_thres, level_sizes, tree_table, mlp,
+                         num_classes, class_ids, dilation_ratio, ms_ssim)[0]
+
+
+def _frame_scores(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, final_opacity, sil_thres, level_sizes, tree_table, mlp,
+                  num_classes, class_ids, dilation_ratio, ms_ssim):
+    """evaluate_frame's body: (its dict, the predicted int32 [H,W] label map, which evaluate_sequence's pictures reuse)"""
     m = frame_metrics(im, gt_im, depth, gt_depth, final_opacity, sil_thres)
     lab = semantic_labels(im_semantic, mode, level_sizes=level_sizes, tree_table=tree_table, mlp=mlp)
     if mode == "tree":
@@ -261,7 +271,7 @@ def evaluate_frame(im, gt_im, depth, gt_depth, im_semantic, gt_labels, mode, *, 
     scores = {"psnr": m[0], "depth_l1": m[1], "depth_rmse": m[2], "miou": s[0], "mbiou": s[1]}
     if ms_ssim:
         scores["ms_ssim"] = _ms_ssim(im, gt_im, gt_depth, final_opacity, sil_thres)
-    return scores
+    return scores, lab
 
 
 def _align(model, data):
@@ -304,5 +314,122 @@ def trajectory_ate(gt_w2c_list, est_w2c_list, first_frame_w2c=None):
     return float(err.mean())
 
 
+SEQUENCE_FILES = {"psnr": "psnr.txt", "depth_rmse": "rmse.txt", "depth_l1": "l1.txt", "ms_ssim": "ssim.txt", "miou": "miou.txt",
+                  "mbiou": "mbiou.txt"}
+
+
+def evaluate_sequence(params, frames, cam, eval_dir=None, *, eval_every=1, sil_thres, mapping_iters, add_new_gaussians, mode,
+                      save_frames=False, level_sizes=None, tree_table=None, mlp=None, num_classes=None, class_ids=None,
+                      dilation_ratio=0.02, tuple_table=None, label_table=None, depth_table=None, depth_range=(0.0, 6.0), ms_ssim=True):
+    """The loop of eval_semantic_tree_newrender (utils/eval_helpers.py:1145-1646; scripts/hierslam.py:2181-2230) over a finished map:
+    with mode=None, and then without semantic planes, scores or pictures, the loop of eval_newrender (:645-).
+
+    params: the final map and poses (SlamSession.params, or map_io's).  frames: any iterable of the session's frame dicts ('id', 'im',
+    'depth', optional 'gt_w2c' and 'semantic_label_gt' [levels + 1 leaf, H, W]), read once and in order, so a generator over
+    session.ingest(...) works.  cam: the camera of the frames' size.  Every frame's gt pose is kept for the ATE; a frame is rendered
+    and scored when its id is 0 or (id + 1) % eval_every == 0 (:1233).  It is rendered from `params` at its estimated pose as
+    SlamSession.render does (slam.render_params) and scored by evaluate_frame with mode, level_sizes, tree_table, mlp, num_classes,
+    class_ids and dilation_ratio as there; the silhouette mask (final opacity > sil_thres) enters the scores when mapping_iters == 0
+    and not add_new_gaussians (:1264-1275).  With mode=None the scores are frame_metrics' and ms_ssim's alone.
+
+    With save_frames (and eval_dir) one hsr_utils.export.export_frame launch per scored frame makes all of the frame's pictures, written
+    under the reference's names: rendered_rgb/gs_%04d.png, rendered_depth/gs_%04d.png, rgb/gt_%04d.png, depth/gt_%04d.png (depth_table,
+    depth_range as export_frame's) and, with a mode, rendered_semantic/sem_%04d_multilevel.png (mode "tree": the rendered map's level
+    labels coloured by tuple_table) or rendered_semantic/sem_%04d.png (modes "leaf" and "flat": the predicted classes coloured by
+    label_table) and rendered_semantic/gt_%04d.png (the ground-truth level planes by tuple_table where it is given, else the
+    ground-truth classes by label_table).  A saved picture costs one device-to-host copy.
+
+    The scores stay on the device and are read once after the last frame.  With eval_dir: psnr.txt, rmse.txt, l1.txt, ssim.txt (with
+    ms_ssim), miou.txt and mbiou.txt (with a mode) via np.savetxt, one row per scored frame, and summary.txt with the reference's
+    summary line.  Returns a dict: 'frame_ids', the lists 'psnr', 'depth_l1', 'depth_rmse', 'ms_ssim', 'miou', 'mbiou' (float64 arrays)
+    and their plain means 'avg_psnr', ... (:1587-1600), and 'ate_rmse' (trajectory_ate over the frames read, :1554-1584; None when no
+    frame carries a gt pose).
+
+    Not built: LPIPS (no weights here; lpips.txt is left out), the matplotlib plots, wandb, and the gt_transfer branch."""
+    import os
+    from . import slam
+    if save_frames and eval_dir is None:
+        raise RuntimeError("hsr_utils.evaluate: save_frames needs eval_dir")
+    if int(eval_every) < 1:
+        raise ValueError("hsr_utils.evaluate: eval_every must be >= 1, not %r" % (eval_every,))
+    if mode not in (None, "flat", "tree", "leaf"):
+        raise RuntimeError("hsr_utils.evaluate: mode must be None, 'flat', 'tree' or 'leaf' (got %r)" % (mode,))
+    use_sil = int(mapping_iters) == 0 and not add_new_gaussians
+    dirs = {}
+    if eval_dir is not None:
+        os.makedirs(eval_dir, exist_ok=True)
+    if save_frames:
+        from . import export
+        for name in ("rendered_rgb", "rendered_depth", "rgb", "depth") + (("rendered_semantic",) if mode is not None else ()):
+            dirs[name] = os.path.join(eval_dir, name)
+            os.makedirs(dirs[name], exist_ok=True)
+    gt_w2c_list, ids, rows = [], [], []
+    for frame in frames:
+        time_idx = int(frame['id'])
+        gt_w2c_list.append(frame.get('gt_w2c'))
+        if time_idx != 0 and (time_idx + 1) % int(eval_every) != 0:
+            continue
+        with torch.no_grad():
+            _rv, im, _radius, sem, depth, opac = slam.render_params(params, time_idx, cam, mode is not None)
+        op, thres = (opac, sil_thres) if use_sil else (None, None)
+        lab = label_gt = None
+        if mode is None:
+            m = frame_metrics(im, frame['im'], depth, frame['depth'], op, thres)
+            scores = {"psnr": m[0], "depth_l1": m[1], "depth_rmse": m[2]}
+            if ms_ssim:
+                scores["ms_ssim"] = _ms_ssim(im, frame['im'], frame['depth'], op, thres)
+        else:
+            label_gt = frame['semantic_label_gt']
+            scores, lab = _frame_scores(im, frame['im'], depth, frame['depth'], sem, label_gt[-1], mode, op, thres, level_sizes, tree_table,
+                                        mlp, num_classes, class_ids, dilation_ratio, ms_ssim)
+        ids.append(time_idx)
+        rows.append(scores)
+        if save_frames:
+            want = dict(im=im, gt_im=frame['im'], depth=depth, gt_depth=frame['depth'])
+            names = dict(im=("rendered_rgb", "gs_%04d.png"), depth=("rendered_depth", "gs_%04d.png"), gt_im=("rgb", "gt_%04d.png"),
+                         gt_depth=("depth", "gt_%04d.png"))
+            if mode == "tree":
+                want["im_semantic"] = sem
+                names["im_semantic"] = ("rendered_semantic", "sem_%04d_multilevel.png")
+            elif mode is not None:
+                want["labels"] = lab
+                names["labels"] = ("rendered_semantic", "sem_%04d.png")
+            if mode is not None:
+                if tuple_table is not None:
+                    gl = label_gt[:-1]
+                    want["gt_levels"] = gl if gl.dtype == torch.int64 else gl.to(torch.int64)
+                    names["gt_levels"] = ("rendered_semantic", "gt_%04d.png")
+                else:
+                    want["gt_labels"] = label_gt[-1]
+                    names["gt_labels"] = ("rendered_semantic", "gt_%04d.png")
+            pictures = export.export_frame(depth_table=depth_table, depth_range=depth_range, level_sizes=level_sizes, tuple_table=tuple_table,
+                                           label_table=label_table, **want)
+            for key, (sub, pattern) in names.items():
+                export.write_png(os.path.join(dirs[sub], pattern % time_idx), pictures[key])
+    if not rows:
+        raise RuntimeError("hsr_utils.evaluate: evaluate_sequence got no frame to score")
+    keys = [k for k in SEQUENCE_FILES if k in rows[0]]
+    table = torch.stack([torch.stack([r[k].to(torch.float64) for k in keys]) for r in rows]).cpu().numpy()      # the one read
+    result = {"frame_ids": ids}
+    for col, k in enumerate(keys):
+        result[k] = table[:, col].copy()
+        result["avg_" + k] = float(result[k].mean())
+    n = min(len(gt_w2c_list), int(params['cam_unnorm_rots'].shape[-1]))
+    result["ate_rmse"] = None
+    if gt_w2c_list[0] is not None and all(g is not None for g in gt_w2c_list[:n]):
+        result["ate_rmse"] = trajectory_ate(gt_w2c_list[:n], [slam.frame_w2c(params, t) for t in range(n)])
+    if eval_dir is not None:
+        for k in keys:
+            np.savetxt(os.path.join(eval_dir, SEQUENCE_FILES[k]), result[k])
+        cols = [("ATE RMSE", None if result["ate_rmse"] is None else result["ate_rmse"] * 100)] + [
+            (title, result["avg_" + k] * scale) for k, title, scale in (
+                ("psnr", "PSNR", 1.0), ("ms_ssim", "MS-SSIM", 1.0), ("depth_l1", "Depth L1", 100.0), ("depth_rmse", "Depth RMSE", 100.0),
+                ("miou", "miou%", 100.0), ("mbiou", "mbiou%", 100.0)) if k in keys]
+        with open(os.path.join(eval_dir, "summary.txt"), "w") as f:
+            f.write(" ".join("[%s]" % title for title, _v in cols) + "\n")
+            f.write("\t".join("nan" if v is None else "%.3f" % v for _t, v in cols) + "\n")
+    return result
+
+
 __all__ = ["frame_metrics", "ms_ssim", "semantic_labels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
-           "dilation_pixels"]
+           "dilation_pixels", "evaluate_sequence"]

@@ -288,6 +288,27 @@ def normalize_config(config):
     return cfg
 
 
+def render_params(params, time_idx, cam, semantic, gaussians_grad=False, camera_grad=False, retain_means2D=False):
+    """(rendervar, im, radius, semantic map | None, depth, final opacity) of the map `params` from the estimated pose of frame time_idx
+    with camera `cam`: the semantic rasterizer when `semantic`, else the plain one.  What SlamSession renders with, as a function of
+    the parameters alone, so that a finished map (hsr_utils.map_io) can be rendered without a session (evaluate.evaluate_sequence)."""
+    from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic
+    from . import slam_helpers as SH
+    tg = SH.transform_to_frame(params, time_idx, gaussians_grad=gaussians_grad, camera_grad=camera_grad)
+    if semantic:
+        rv = SH.transformed_params2rendervar_semantic(params, tg)
+        if retain_means2D:
+            rv['means2D'].retain_grad()
+        im, radius, sem, depth, _median, opac = GaussianRasterizer_semantic(raster_settings=cam)(**rv)
+    else:
+        rv = SH.transformed_params2rendervar(params, tg)
+        if retain_means2D:
+            rv['means2D'].retain_grad()
+        im, radius, depth, _median, opac, _mask = GaussianRasterizer(raster_settings=cam)(**rv)
+        sem = None
+    return rv, im, radius, sem, depth, opac
+
+
 def _param_groups(params, lrs):
     """initialize_optimizer's groups (scripts/hierslam.py:411-417): one named group per parameter"""
     return [{'params': [v], 'name': k, 'lr': lrs[k]} for k, v in params.items()]
@@ -421,22 +442,8 @@ class SlamSession:
 
     # -- rendering and losses --
     def _render(self, time_idx, gaussians_grad, camera_grad, retain_means2D=False, cam=None):
-        from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic
-        from . import slam_helpers as SH
-        cam = self.cam if cam is None else cam
-        tg = SH.transform_to_frame(self.params, time_idx, gaussians_grad=gaussians_grad, camera_grad=camera_grad)
-        if self.flag_use_semantic:
-            rv = SH.transformed_params2rendervar_semantic(self.params, tg)
-            if retain_means2D:
-                rv['means2D'].retain_grad()
-            im, radius, sem, depth, _median, opac = GaussianRasterizer_semantic(raster_settings=cam)(**rv)
-        else:
-            rv = SH.transformed_params2rendervar(self.params, tg)
-            if retain_means2D:
-                rv['means2D'].retain_grad()
-            im, radius, depth, _median, opac, _mask = GaussianRasterizer(raster_settings=cam)(**rv)
-            sem = None
-        return rv, im, radius, sem, depth, opac
+        return render_params(self.params, time_idx, self.cam if cam is None else cam, self.flag_use_semantic, gaussians_grad, camera_grad,
+                             retain_means2D)
 
     def render(self, time_idx):
         """(im, depth, final opacity, semantic | None) of the map from the estimated pose of frame time_idx, without gradients"""
@@ -637,4 +644,4 @@ class SlamSession:
 
 
 __all__ = ["initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "is_mapping_frame",
-           "normalize_config", "map_init_frame", "resample_frame", "frame_w2c", "SlamSession"]
+           "normalize_config", "map_init_frame", "resample_frame", "frame_w2c", "render_params", "SlamSession"]
