@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST and SIGNATURES_EXT_FRAME_EXPORT against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT and SIGNATURES_EXT_FRAME_INGEST_PLANES against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -280,6 +280,15 @@ SIGNATURES_EXT_FRAME_EXPORT = (
     ("hsr_frame_export", ci, [ci, ci, ci, C.POINTER(hsr_export_job), vp]),
 )
 
+# include/ext/hsr_frame_ingest_planes.h: the ingest with a source size per image (SIGNATURES_EXT_FRAME_INGEST is pinned to one name)
+SIGNATURES_EXT_FRAME_INGEST_PLANES = (
+    ("hsr_frame_ingest_planes", ci, [ci, ci, vp,
+                                     ci, ci, vp, ci, cd,
+                                     ci, ci, vp,
+                                     ci, vp, ci, ci,
+                                     ci, C.POINTER(hsr_ingest_level), vp, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -289,7 +298,8 @@ def _load():
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
-                                    + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT):
+                                    + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT
+                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

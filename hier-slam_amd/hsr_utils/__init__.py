@@ -10,8 +10,8 @@ from .synthetic import make_scene, make_upstream_grads  # noqa: F401
 _KEYFRAMES = ("keyframe_selection_overlap", "overlap_counts", "KeyframePoses", "mapping_window")
 _SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "SlamSession",
          "resample_frame")
-_FRAMES = ("tree_label_table", "ingest_frame")
-_SEQUENCE = ("ReplicaSequence", "tree_annotation")
+_FRAMES = ("tree_label_table", "ingest_frame", "ingest_frame_planes", "composed_label_table")
+_SEQUENCE = ("ReplicaSequence", "tree_annotation", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation")
 _EXPORT = ("export_frame", "jet_colormap", "label_colormap", "tuple_colour_table", "write_png")
 
 

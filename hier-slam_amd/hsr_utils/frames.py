@@ -133,4 +133,130 @@ def ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_
     return out, labels_out
 
 
-__all__ = ["tree_label_table", "ingest_frame"]
+def _int_keys(mapping, what):
+    """{int(key): value} of a dict keyed by ints or their strings; of two equal keys the later one wins; no negative key"""
+    out = {}
+    for key, value in mapping.items():
+        if int(key) < 0:
+            raise RuntimeError("hsr_utils.frames: %s entry %r: class ids are not negative" % (what, key))
+        out[int(key)] = value
+    return out
+
+
+def composed_label_table(class_mapping, label_mapping_tree, num_levels, device="cuda"):
+    """The table ingest_frame_planes(..., leaf_column=True) reads: int32 [n_ids, num_levels + 1], row r holding the level labels of
+    label_mapping_tree[leaf] and then leaf itself, with leaf = class_mapping.get(r, r); n_ids is the largest key of either dict + 1.
+
+    This is the composition of the reference's two loops of masked assignments on a ScanNet id image: raw id -> NYU40 id
+    (datasets/gradslam_datasets/scannet.py:288-290, class_mapping = sequence.scannet_class_mapping), then NYU40 id -> the tree's
+    levels (:302-307 for four levels, :325-330 for five, label_mapping_tree = sequence.scannet_tree_annotation), the NYU40 image
+    staying as the last plane (:313, :337).  Both loops take their masks from an UNCHANGED copy of the image (semantic_raw in the
+    first, semantic_raw_nyu in the second) and write into another, so neither chains: an id that is both a key and another key's
+    value is mapped once.  Each loop is therefore a pure lookup, and so is their composition.  A leaf the tree does not name keeps
+    the leaf in every level column (the level copies start as the NYU40 image); an id no row holds keeps its raw value on every
+    plane, which is what the ingest writes for an id beyond the table.
+
+    class_mapping None is the identity (the reference's "ab" modes, :285-286).  label_mapping_tree None with num_levels 0 gives the
+    one-column flat remap (the 'nyu40' mode).  Keys may be ints or their strings, the later of two equal keys wins, and ids and
+    labels must fit in int32, as in tree_label_table.  Built once on the host."""
+    L = int(num_levels)
+    if not 0 <= L <= INGEST_MAX_TREE_LEVELS:
+        raise ValueError("hsr_utils.frames: composed_label_table takes 0..%d levels, not %d" % (INGEST_MAX_TREE_LEVELS, L))
+    if (label_mapping_tree is None) != (L == 0):
+        raise ValueError("hsr_utils.frames: composed_label_table: a label_mapping_tree goes with num_levels >= 1, None with num_levels 0")
+    classes = {k: int(v) for k, v in _int_keys(class_mapping or {}, "class_mapping").items()}
+    tree = {}
+    for key, value in _int_keys(label_mapping_tree or {}, "tree").items():
+        value = [int(v) for v in value]
+        if len(value) != L:
+            raise RuntimeError("hsr_utils.frames: tree entry %r has %d levels, num_levels is %d" % (key, len(value), L))
+        tree[key] = value
+    if not classes and not tree:
+        raise RuntimeError("hsr_utils.frames: an empty class_mapping and an empty label_mapping_tree")
+    n_ids = max(list(classes) + list(tree)) + 1
+    if n_ids > 1 << 24:
+        raise RuntimeError("hsr_utils.frames: a %d-row label table is too large" % n_ids)
+    table = np.empty((n_ids, L + 1), dtype=np.int64)
+    for r in range(n_ids):
+        leaf = classes.get(r, r)
+        table[r, :L] = tree.get(leaf, [leaf] * L)
+        table[r, L] = leaf
+    if table.min() < -(1 << 31) or table.max() >= 1 << 31:
+        raise RuntimeError("hsr_utils.frames: class ids and level labels must fit in int32")
+    return torch.tensor(table.astype(np.int32), device=device)
+
+
+def ingest_frame_planes(color_u8, depth_raw, sizes, png_depth_scale, labels=None, label_table=None, leaf_column=False):
+    """hsr_frame_ingest_planes: ingest_frame for a frame whose depth and label images have sizes of their own (a ScanNet frame: colour
+    and labels 968x1296, depth 480x640).  Returns what ingest_frame returns, ([(color_i [3,h,w], depth_i [1,h,w]), ...] for the one
+    to three (h, w) of `sizes`, labels_out | None), from the same kinds of inputs; depth_raw and labels may each be any 2-D shape.
+    label_table is int32 [n_ids, L] (tree_label_table) with leaf_column False: L level planes, then the raw id, as ingest_frame.  With
+    leaf_column True it is int32 [n_ids, L + 1] (composed_label_table) and the last plane is the row's last column for an id the
+    table holds; L may then be 0 (a flat remap, one plane).  Colour is bilinear from its own size, depth and labels nearest from
+    theirs (include/ext/hsr_frame_ingest_planes.h states every step).  One launch, no host synchronisation; no CPU path."""
+    color, depth = _as_tensor(color_u8, "color_u8"), _as_tensor(depth_raw, "depth_raw")
+    lab = None if labels is None else _as_tensor(labels, "labels")
+    leaf = bool(leaf_column)
+    if color.dtype != torch.uint8 or color.dim() != 3 or color.shape[2] != 3:
+        raise RuntimeError("hsr_utils.frames: color_u8 must be uint8 [Hc,Wc,3]; got %s %s" % (color.dtype, tuple(color.shape)))
+    uint16 = getattr(torch, "uint16", None)
+    if depth.dtype == torch.int16 or (uint16 is not None and depth.dtype == uint16):
+        depth_type = DEPTH_U16
+    elif depth.dtype == torch.int32:
+        depth_type = DEPTH_I32
+    elif depth.dtype == torch.float32:
+        depth_type = DEPTH_F32
+    else:
+        raise RuntimeError("hsr_utils.frames: depth_raw must be uint16 (or its bits as int16), int32 or float32; got %s" % depth.dtype)
+    if depth.dim() != 2:
+        raise RuntimeError("hsr_utils.frames: depth_raw must be a 2-D [Hd,Wd] image; got %s" % (tuple(depth.shape),))
+    if lab is not None and (lab.dtype not in _LABEL_DTYPES or lab.dim() != 2):
+        raise RuntimeError("hsr_utils.frames: labels must be an integer 2-D [Hl,Wl] image; got %s %s" % (lab.dtype, tuple(lab.shape)))
+    if label_table is None:
+        if leaf:
+            raise RuntimeError("hsr_utils.frames: leaf_column without a label_table")
+    else:
+        if lab is None:
+            raise RuntimeError("hsr_utils.frames: a label_table without labels")
+        if not (torch.is_tensor(label_table) and label_table.dtype == torch.int32 and label_table.dim() == 2 and label_table.shape[0] >= 1):
+            raise RuntimeError("hsr_utils.frames: label_table must be an int32 2-D [n_ids, columns] tensor (tree_label_table, composed_label_table)")
+        L = int(label_table.shape[1]) - int(leaf)
+        if L > INGEST_MAX_TREE_LEVELS or L < (0 if leaf else 1):
+            raise RuntimeError("hsr_utils.frames: label_table has %d level columns%s; %d..%d are taken" % (
+                L, " before its leaf column" if leaf else "", 0 if leaf else 1, INGEST_MAX_TREE_LEVELS))
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    if not 1 <= len(sizes) <= INGEST_MAX_LEVELS:
+        raise ValueError("hsr_utils.frames: ingest_frame_planes takes one to three sizes, not %d" % len(sizes))
+    sources = [tuple(int(v) for v in t.shape[:2]) for t in (color, depth, lab) if t is not None]
+    for side in tuple(v for hw in sources + sizes for v in hw):
+        if not 1 <= side <= INGEST_MAX_SIDE:
+            raise ValueError("hsr_utils.frames: ingest_frame_planes sides must be 1..%d; got images of %s and sizes %s" % (INGEST_MAX_SIDE, sources, sizes))
+    scale = float(png_depth_scale)
+    if not math.isfinite(scale) or scale == 0.0:
+        raise ValueError("hsr_utils.frames: ingest_frame_planes: png_depth_scale must be finite and non-zero, not %r" % (png_depth_scale,))
+    given = [t for t in (color, depth, lab, label_table) if t is not None]
+    dev = next((t.device for t in given if t.is_cuda), None)
+    if dev is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("hsr_utils.frames: ingest_frame_planes needs a HIP device; there is no CPU path")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    color, depth = color.to(dev).contiguous(), depth.to(dev).contiguous()
+    Hl = Wl = 0
+    if lab is not None:
+        lab = lab.to(dev).to(torch.int32).contiguous()
+        Hl, Wl = sources[2]
+    L = 0
+    if label_table is not None:
+        label_table = label_table.to(dev).contiguous()
+        L = int(label_table.shape[1]) - int(leaf)
+    out = [(torch.empty((3, h, w), dtype=torch.float32, device=dev), torch.empty((1, h, w), dtype=torch.float32, device=dev)) for h, w in sizes]
+    levels = (_abi.hsr_ingest_level * len(sizes))(*[_abi.hsr_ingest_level(h, w, c.data_ptr(), d.data_ptr()) for (h, w), (c, d) in zip(sizes, out)])
+    labels_out = None if lab is None else torch.empty((L + 1,) + sizes[0], dtype=torch.int64, device=dev)
+    _abi.call(_lib.hsr_frame_ingest_planes, "hsr_frame_ingest_planes", dev, sources[0][0], sources[0][1], color.data_ptr(),
+              sources[1][0], sources[1][1], depth.data_ptr(), depth_type, scale, Hl, Wl, None if lab is None else lab.data_ptr(),
+              L, None if label_table is None else label_table.data_ptr(), 0 if label_table is None else int(label_table.shape[0]), int(leaf),
+              len(sizes), levels, None if labels_out is None else labels_out.data_ptr())
+    return out, labels_out
+
+
+__all__ = ["tree_label_table", "ingest_frame", "composed_label_table", "ingest_frame_planes"]

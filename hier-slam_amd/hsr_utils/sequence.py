@@ -17,8 +17,19 @@ natsort's order.
         len(seq), seq[i] -> (color uint8 [H,W,3], depth uint16 [H,W], labels | None, gt_w2c float32 [4,4])
     tree_annotation(path, num_levels) -> (label_mapping_tree, num_semantic)
 
+and the ScanNet layout of datasets/gradslam_datasets/scannet.py (:404-418, :114), whose three images have sizes of their own
+(hsr_utils.frames.ingest_frame_planes):
+
+    <basedir>/<sequence>/color/*.jpg, depth/*.png, pose/*.txt, label-filt/*.png
+
+    ScanNetSequence(basedir, sequence, start=0, end=-1, stride=1, labels=True)
+        len(seq), seq[i] -> (color uint8 [Hc,Wc,3], depth uint16 [Hd,Wd], labels int32 [Hl,Wl] | None, gt_w2c float32 [4,4])
+    scannet_class_mapping(tsv_path, column=4) -> {raw id: NYU40 id}
+    scannet_tree_annotation(tsv_path, num_levels, key_column) -> (label_mapping_tree, num_semantic)
+
 Other datasets, undistortion, cropping, image pyramids and embeddings are not read.
 """
+import csv
 import glob
 import json
 import os
@@ -48,12 +59,7 @@ class ReplicaSequence:
 
     def __init__(self, basedir, sequence, start=0, end=-1, stride=1, semantic_dir=None):
         start, end, stride = int(start), int(end), int(stride)
-        if start < 0:
-            raise ValueError("hsr_utils.sequence: start must not be negative; got %d" % start)
-        if not (end == -1 or end > start):
-            raise ValueError("hsr_utils.sequence: end (%d) must be -1 (all frames) or greater than start (%d)" % (end, start))
-        if stride < 1:
-            raise ValueError("hsr_utils.sequence: stride must be at least 1; got %d" % stride)
+        _check_range(start, end, stride)
         self.input_folder = os.path.join(basedir, sequence)
         color = numeric_order(glob.glob(os.path.join(glob.escape(self.input_folder), "results", "frame*.jpg")))
         depth = numeric_order(glob.glob(os.path.join(glob.escape(self.input_folder), "results", "depth*.png")))
@@ -142,4 +148,145 @@ def tree_annotation(path, num_levels):
     return tree, num_semantic
 
 
-__all__ = ["ReplicaSequence", "tree_annotation", "numeric_order"]
+def _check_range(start, end, stride):
+    """the [start:end:stride] rules of ReplicaSequence (basedataset.py:176-190)"""
+    if start < 0:
+        raise ValueError("hsr_utils.sequence: start must not be negative; got %d" % start)
+    if not (end == -1 or end > start):
+        raise ValueError("hsr_utils.sequence: end (%d) must be -1 (all frames) or greater than start (%d)" % (end, start))
+    if stride < 1:
+        raise ValueError("hsr_utils.sequence: stride must be at least 1; got %d" % stride)
+
+
+def _as_uint16(image, path):
+    """PIL decodes a 16-bit grey PNG as int32 ('I') or uint16 ('I;16'), by version; the values are 0..65535"""
+    if image.dtype != np.uint16:
+        if image.dtype.kind not in "iu" or image.min() < 0 or image.max() > 65535:
+            raise RuntimeError("hsr_utils.sequence: %s holds values outside 16 bits" % path)
+        image = image.astype(np.uint16)
+    return image
+
+
+class ScanNetSequence:
+    """The retained frames [start:end:stride] of one ScanNet-layout sequence, as datasets/gradslam_datasets/scannet.py reads it
+    (:404-418, :114), in numeric_order:
+
+        <basedir>/<sequence>/color/*.jpg          colour, 8 bit (968x1296 in the dataset)
+        <basedir>/<sequence>/depth/*.png          depth, 16 bit, in millimetres (480x640; png_depth_scale 1000)
+        <basedir>/<sequence>/pose/*.txt           one 4x4 camera-to-world matrix per file, row by row
+        <basedir>/<sequence>/label-filt/*.png     raw ScanNet class ids, 16 bit (968x1296); read unless labels=False
+
+    seq[i] decodes frame i of the retained ones and returns raw host arrays: colour uint8 [Hc,Wc,3], depth uint16 [Hd,Wd], the
+    class-id image int32 [Hl,Wl] (None with labels=False) and gt_w2c float32 [4,4].  The three images may differ in size: they are what
+    frames.ingest_frame_planes and SlamSession.ingest take.  The start / end / stride rules, the errors and `retained_inds` are
+    ReplicaSequence's, and gt_w2c is, as there, relative to the first RETAINED frame: inverse(inverse(c2w_first) @ c2w_i) in float64,
+    returned as float32.  ScanNet marks a frame whose pose was lost with a matrix of -inf: a pose file that holds a non-finite number
+    gives its frame a gt_w2c full of NaN, and SlamSession.step keeps such a frame out of the keyframes, as the reference's check at
+    scripts/hierslam.py:2108-2109 does.  A non-finite FIRST retained pose (every other pose is relative to it) is a RuntimeError
+    naming the file.  Undistortion, pyramids and embeddings are not read."""
+
+    def __init__(self, basedir, sequence, start=0, end=-1, stride=1, labels=True):
+        start, end, stride = int(start), int(end), int(stride)
+        _check_range(start, end, stride)
+        self.input_folder = os.path.join(basedir, sequence)
+        folder = glob.escape(self.input_folder)
+        color = numeric_order(glob.glob(os.path.join(folder, "color", "*.jpg")))
+        depth = numeric_order(glob.glob(os.path.join(folder, "depth", "*.png")))
+        pose = numeric_order(glob.glob(os.path.join(folder, "pose", "*.txt")))
+        if not color or len(color) != len(depth):
+            raise RuntimeError("hsr_utils.sequence: %s holds %d color/*.jpg and %d depth/*.png files" % (self.input_folder, len(color), len(depth)))
+        if len(pose) < len(color):
+            raise RuntimeError("hsr_utils.sequence: %s/pose has %d poses for %d frames" % (self.input_folder, len(pose), len(color)))
+        semantic = None
+        if labels:
+            semantic = numeric_order(glob.glob(os.path.join(folder, "label-filt", "*.png")))
+            if len(semantic) != len(color):
+                raise RuntimeError("hsr_utils.sequence: %s/label-filt holds %d images for %d frames" % (self.input_folder, len(semantic), len(color)))
+        stop = len(color) if end == -1 else end
+        pick = slice(start, stop, stride)
+        self.color_paths, self.depth_paths, self.pose_paths = color[pick], depth[pick], pose[:len(color)][pick]
+        self.label_paths = None if semantic is None else semantic[pick]
+        self.retained_inds = list(range(len(color)))[pick]
+        if not self.color_paths:
+            raise RuntimeError("hsr_utils.sequence: no frame of %d left by start=%d, end=%d, stride=%d" % (len(color), start, end, stride))
+        self.c2w = []
+        for path in self.pose_paths:
+            with open(path) as f:
+                values = [float(v) for v in f.read().split()]
+            if len(values) != 16:
+                raise RuntimeError("hsr_utils.sequence: %s has %d numbers, not 16" % (path, len(values)))
+            self.c2w.append(np.array(values, dtype=np.float64).reshape(4, 4))
+        if not np.isfinite(self.c2w[0]).all():
+            raise RuntimeError("hsr_utils.sequence: %s, the first retained pose, is not finite; every other pose is relative to it" % self.pose_paths[0])
+        self._first_inv = np.linalg.inv(self.c2w[0])
+
+    def __len__(self):
+        return len(self.color_paths)
+
+    def gt_w2c(self, i):
+        if not np.isfinite(self.c2w[i]).all():
+            return np.full((4, 4), np.nan, dtype=np.float32)
+        return np.linalg.inv(self._first_inv @ self.c2w[i]).astype(np.float32)
+
+    def __getitem__(self, i):
+        i = range(len(self))[i]      # negative indices; IndexError beyond the end, so that iteration stops
+        color = _read_image(self.color_paths[i])
+        depth = _read_image(self.depth_paths[i])
+        if color.dtype != np.uint8 or color.ndim != 3 or color.shape[2] != 3:
+            raise RuntimeError("hsr_utils.sequence: %s is not an 8-bit three-channel image (%s %s)" % (self.color_paths[i], color.dtype, color.shape))
+        if depth.ndim != 2:
+            raise RuntimeError("hsr_utils.sequence: %s is not a one-channel image (%s)" % (self.depth_paths[i], depth.shape))
+        depth = _as_uint16(depth, self.depth_paths[i])
+        labels = None
+        if self.label_paths is not None:
+            labels = _read_image(self.label_paths[i])
+            if labels.ndim != 2 or labels.dtype.kind not in "iu":
+                raise RuntimeError("hsr_utils.sequence: %s is not a one-channel integer image (%s %s)" % (self.label_paths[i], labels.dtype, labels.shape))
+            labels = np.ascontiguousarray(labels.astype(np.int32))
+        return np.ascontiguousarray(color), np.ascontiguousarray(depth), labels, self.gt_w2c(i)
+
+
+def _tsv_rows(tsv_path):
+    """the tab-separated cells of every line after the header line"""
+    with open(tsv_path, newline="") as f:
+        return [row for i, row in enumerate(csv.reader(f, delimiter="\t")) if i > 0 and row]
+
+
+def scannet_class_mapping(tsv_path, column=4):
+    """scannetv2-labels.combined.tsv as the reference's load_scannet_nyu40_mapping reads it (scannet.py:575-599): the header line is
+    skipped and every other line gives {int(cell 0): int(cell `column`)} — the raw ScanNet id to the NYU40 id with column 4.  Of two
+    lines with one id the later wins.  What frames.composed_label_table takes as class_mapping."""
+    mapping = {}
+    for n, row in enumerate(_tsv_rows(tsv_path)):
+        if len(row) <= column:
+            raise RuntimeError("hsr_utils.sequence: %s line %d has %d cells, column %d is wanted" % (tsv_path, n + 2, len(row), column))
+        mapping[int(row[0])] = int(row[column])
+    return mapping
+
+
+def scannet_tree_annotation(tsv_path, num_levels, key_column):
+    """The tree tsv of the reference's ScanNet configs.  RESTATED, NOT PINNED BY A FILE OF THE DATASET: no tree tsv file is among this
+    project's fixtures, and the format is taken from the reference's two readers, scannet.py:734-795 (key_column=4, the NYU40 id;
+    four levels) and :890-966 (key_column=0, the raw id; five levels).  The header line is skipped.  On every other line the key is int(cell key_column) and
+    level l's label is int(cell 17 + 2l), the cell after it holding the level's name; an empty cell, or one the line is too short
+    to have, is -1 (the reference keeps None there).  Of two lines with one key the later wins.  Returns (label_mapping_tree,
+    num_semantic) shaped like tree_annotation's: {key: tuple of num_levels labels} in ascending key order (the reference sorts), and
+    the largest label of each level + 1 followed by the number of keys."""
+    L = int(num_levels)
+    if L < 1:
+        raise ValueError("hsr_utils.sequence: scannet_tree_annotation takes at least one level, not %d" % L)
+    tree = {}
+    for n, row in enumerate(_tsv_rows(tsv_path)):
+        if len(row) <= key_column:
+            raise RuntimeError("hsr_utils.sequence: %s line %d has %d cells, key column %d is wanted" % (tsv_path, n + 2, len(row), key_column))
+        cells = [row[17 + 2 * l] if 17 + 2 * l < len(row) else "" for l in range(L)]
+        tree[int(row[key_column])] = tuple(int(c) if c != "" else -1 for c in cells)
+    if not tree:
+        raise RuntimeError("hsr_utils.sequence: %s names no class" % tsv_path)
+    tree = dict(sorted(tree.items()))
+    columns = np.asarray(list(tree.values()), dtype=np.int64)
+    num_semantic = [int(columns[:, i].max()) + 1 for i in range(L)] + [len(tree)]
+    return tree, num_semantic
+
+
+__all__ = ["ReplicaSequence", "tree_annotation", "numeric_order", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation"]

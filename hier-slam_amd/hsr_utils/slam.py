@@ -393,13 +393,16 @@ class SlamSession:
         im, depth = self._level_data(frame)['densify']
         return {'im': im, 'depth': depth, 'cam': self.densify_cam, 'intrinsics': self.densify_intrinsics}
 
-    def ingest(self, time_idx, color_u8, depth_raw, gt_w2c=None, labels=None, tree_table=None, png_depth_scale=None):
+    def ingest(self, time_idx, color_u8, depth_raw, gt_w2c=None, labels=None, tree_table=None, png_depth_scale=None, leaf_column=False):
         """A frame dict for step() from the raw sensor images (hsr_utils.frames.ingest_frame; basedataset.py:223-227, :248-256,
         replica.py:241-299, scripts/hierslam.py:1777): 'id', 'im' and 'depth' at cam.image_height x cam.image_width, 'gt_w2c' and
         'semantic_label_gt' (int64 [levels + 1, H, W]; tree_table: frames.tree_label_table, None for flat classes) where given, and
         'tracking_im' / 'tracking_depth' / 'densify_im' / 'densify_depth' for every level whose size differs from the frame's — all
         from ONE launch on the sensor image (levels of one size share their tensors), so that step() resamples nothing.
-        png_depth_scale defaults to config['data']['png_depth_scale'] (or the same key at the top level); a KeyError without either."""
+        png_depth_scale defaults to config['data']['png_depth_scale'] (or the same key at the top level); a KeyError without either.
+        A depth or label image of another size than the colour image (a ScanNet frame: 968x1296 colour and labels, 480x640 depth), or
+        leaf_column=True (tree_table: frames.composed_label_table, whose last column becomes the last label plane: scannet.py:284-339),
+        goes through frames.ingest_frame_planes instead: still one launch, each image resampled once per size from its own."""
         from . import frames
         if png_depth_scale is None:
             cfg = self.config
@@ -417,7 +420,16 @@ class SlamSession:
                 if hw not in sizes:
                     sizes.append(hw)
                 uses[use] = sizes.index(hw)
-        levels, labels_out = frames.ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=labels, tree_table=tree_table)
+        shape = tuple(getattr(color_u8, 'shape', ()))[:2]      # only shapes that can be read: malformed inputs are ingest_frame's to refuse
+
+        def own_size(image):
+            other = tuple(getattr(image, 'shape', ()))
+            return len(other) == 2 and other != shape
+        if leaf_column or own_size(depth_raw) or own_size(labels):
+            levels, labels_out = frames.ingest_frame_planes(color_u8, depth_raw, sizes, png_depth_scale, labels=labels, label_table=tree_table,
+                                                            leaf_column=leaf_column)
+        else:
+            levels, labels_out = frames.ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=labels, tree_table=tree_table)
         frame = {'id': int(time_idx), 'im': levels[0][0], 'depth': levels[0][1]}
         if gt_w2c is not None:
             frame['gt_w2c'] = gt_w2c

@@ -7,7 +7,7 @@
  * diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_FRAME_INGEST.
  *
  * One call is ONE launch: an 8-bit interleaved colour image, a raw depth image and, optionally, a raw class-id image, all at the
- * sensor size Hs x Ws, become n_out (1 .. HSR_INGEST_MAX_LEVELS) levels of float32 planar colour in 0..1 and float32 depth in
+ * sensor size Hs x Ws (hsr_frame_ingest_planes.h: the same with a size per image, and a leaf column in the label table), become n_out (1 .. HSR_INGEST_MAX_LEVELS) levels of float32 planar colour in 0..1 and float32 depth in
  * metres, plus, at level 0's size only, one int64 label plane per tree level and one for the raw id.  No scratch, no allocation, no
  * host synchronisation.  Sides (the sensor's and every level's) are 1 .. HSR_RESAMPLE_MAX_SIDE (16384, hsr_frame_resample.h).
  * HSR_ERR_INVALID_ARGUMENT, and nothing launched, for: a side outside that range, n_out outside 1..3, depth_type not one of the
