@@ -17,6 +17,7 @@
 //               mask, and per-wave running digit counters live in LDS.  Order (wave, round, lane) =
 //               input order, so the scatter is stable.
 #include "hsr_common.h"
+#include "hsr_sort_net.h"
 
 namespace {
 
@@ -165,7 +166,7 @@ __global__ void __launch_bounds__(SORT_THREADS) sort_scatter_kernel(const uint64
 //                 segment of the two global buffer pairs (segments of different tiles are disjoint).
 constexpr int TS_MAX = 2048;
 
-__device__ __forceinline__ void ts_block_radix(uint64_t* ka, uint32_t* va, uint64_t* kb, uint32_t* vb, int r0, int n,
+__device__ __forceinline__ void ts_block_radix(sg_u64* ka, sg_u32* va, sg_u64* kb, sg_u32* vb, int r0, int n,
                                                uint32_t* hist /*[256]*/, uint32_t (*wcnt)[256], int gid_passes)
 {
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -229,8 +230,8 @@ __device__ __forceinline__ void ts_block_radix(uint64_t* ka, uint32_t* va, uint6
             for (int i2 = 0; i2 < 4; i2++) wcnt[i2][t] = 0;
             __syncthreads();
         }
-        uint64_t* tk = ka; ka = kb; kb = tk;
-        uint32_t* tv = va; va = vb; vb = tv;
+        sg_u64* tk = ka; ka = kb; kb = tk;
+        sg_u32* tv = va; va = vb; vb = tv;
         __threadfence_block();
     }
     if (npass & 1) {  // an odd number of passes ends in the alternate pair: bring the segment home
@@ -248,74 +249,27 @@ __device__ __forceinline__ void ts_block_radix(uint64_t* ka, uint32_t* va, uint6
 // SIMD's issue rate with a dependent LDS round trip in 21 of the steps — lasts as long as one wave does (27.8 us; waves average 19 us of
 // life, profiles/r02_h_final.json).  Two waves per tile halve the elements per lane (E = 4 for 257..512 entries: 128 lanes x 4), so every
 // step is half as long and twice as many waves hide each other's LDS round trips.  Thread = tid128 of the pair, element e = E * tid128 + r;
-// a step with stride j >= E exchanges with thread tid128 ^ (j / E): inside the wave for j / E < 64 (wave-level fence), and across the two
-// waves for exactly ONE step of the whole network (k = N, j = N / 2), bracketed by two workgroup barriers (partner's stores visible;
+// a step with stride j >= E exchanges with thread tid128 ^ (j / E): inside the wave for j / E < 64 (lane exchange, TS_XCH below), and across
+// the two waves for exactly ONE step of the whole network (k = N, j = N / 2), bracketed by two workgroup barriers (partner's stores visible;
 // partner's loads done before the next step overwrites the slots).  Two pairs = two tiles per 256-thread workgroup; every pair
 // passes exactly those two barriers whatever its tile holds.  16 KB of exchange buffers: all 1 613 workgroups of the headline resident.
 // Tiles above TP_MAX entries are left to the whole workgroup afterwards (block_sort_tile).
 constexpr int TP_MAX = 1024;   // E = 8
 constexpr int TQ_MAX = 2048;   // four waves, E = 8: tiles of 1025..2048 entries (block_sort_tile)
-
-// NT threads (2 or 4 waves) sort N = NT * E composites held E per thread; buf: E / 2 rows of NT x 16 bytes.
-template <int E, int NT>
-__device__ __forceinline__ void net_bitonic(uint64_t (&x)[E], int tid, ulonglong2* buf)
-{
-    constexpr int N = NT * E;
-#pragma unroll
-    for (int k = 2; k <= N; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j < E) {
-#pragma unroll
-                for (int r = 0; r < E; r++) {
-                    if ((r & j) == 0) {
-                        const bool up = k < E ? ((r & k) == 0) : (((E * tid) & k) == 0);
-                        const uint64_t a = x[r], b = x[r + j];
-                        const bool sw = (a > b) == up;
-                        x[r] = sw ? b : a;
-                        x[r + j] = sw ? a : b;
-                    }
-                }
-            } else {
-                const int m = j / E;                   // partner thread = tid ^ m
-                const bool cross = m >= 64;            // partner in another wave: one step of the network at two waves, three at four
-#pragma unroll
-                for (int q = 0; q < E / 2; q++) buf[q * NT + tid] = make_ulonglong2(x[2 * q], x[2 * q + 1]);
-                if (cross) {
-                    __syncthreads();
-                } else {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                }
-                const bool keep_min = ((tid & m) == 0) == (((E * tid) & k) == 0);
-#pragma unroll
-                for (int q = 0; q < E / 2; q++) {
-                    const ulonglong2 y = buf[q * NT + (tid ^ m)];
-                    const uint64_t a0 = x[2 * q], a1 = x[2 * q + 1];
-                    x[2 * q] = keep_min ? (a0 < y.x ? a0 : y.x) : (a0 > y.x ? a0 : y.x);
-                    x[2 * q + 1] = keep_min ? (a1 < y.y ? a1 : y.y) : (a1 > y.y ? a1 : y.y);
-                }
-                // the next exchange's stores stay behind these loads
-                if (cross) {
-                    __syncthreads();
-                } else {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                }
-            }
-        }
-    }
-}
+// Steps whose partner is in the same wave take the partner's composites with ds_swizzle_b32 (partner lane ^ 1..16) and
+// v_permlane32_swap (lane ^ 32) instead of two 16-byte rows through the exchange buffer with a fence on either side.  Measured with
+// tools/micro/sort_net.hip (profiles/micro_sort_net.log), launch of 3 225 tiles: E = 4 on two waves 23.0 -> 18.9 us, E = 8 on four waves
+// 77.6 -> 62.5 us; __shfl_xor (ds_bpermute_b32) 26.9 / 95.4 us, slower than the buffer; DPP moves and v_permlane16_swap instead of every
+// swizzle 21.2 / 70.6 us; DPP for lane ^ 1 and ^ 2 alone 18.8 / 61.1 us, inside the spread of this form.  The step across waves keeps the buffer.
+constexpr int TS_XCH = SN_SWIZZLE;
 
 // One tile, the whole workgroup (256 threads).  comp / hist / wcnt: the workgroup's LDS scratch.
-__device__ __forceinline__ void block_sort_tile(int tile, const uint2* __restrict__ ranges, uint64_t* __restrict__ keys,
-                                                uint32_t* __restrict__ vals, uint64_t* __restrict__ keys_alt,
-                                                uint32_t* __restrict__ vals_alt, int gid_passes, int composite_in, uint64_t* comp,
+__device__ __forceinline__ void block_sort_tile(int tile, const sg_u32x2* __restrict__ ranges, sg_u64* __restrict__ keys,
+                                                sg_u32* __restrict__ vals, sg_u64* __restrict__ keys_alt,
+                                                sg_u32* __restrict__ vals_alt, int gid_passes, int composite_in, uint64_t* comp,
                                                 uint32_t* hist, uint32_t (*wcnt)[256])
 {
-    const uint2 rg = ranges[tile];
+    const sn_u32x2 rg = ranges[tile];
     const int r0 = (int)rg.x, n = (int)(rg.y - rg.x);
     const int t = threadIdx.x;
     // composite_in (direct binning): keys[] holds (depth bits << 32) | index per instance, the tile is given
@@ -342,21 +296,15 @@ __device__ __forceinline__ void block_sort_tile(int tile, const uint2* __restric
         // exchange through LDS in 3 of the 66 steps — instead of the LDS network below (16 bytes read and written per compare-exchange,
         // a workgroup barrier at every stride >= 128: 0.141 ms of that workload's 1.86 ms step)
         static_assert(TQ_MAX == TS_MAX && TS_MAX * 8 >= 4 * 256 * 16, "exchange buffer = the LDS network's key array");
+        // the thread index opaque to the compiler: tile_sort_pair_kernel calls this in a loop over its two tiles, and hipcc otherwise hoists
+        // the network's ~35 lane masks (which half of a step keeps the minimum) out of that loop and spills them, with the kernel's
+        // long-lived scalars, to VGPR lanes — also on the path of the workgroups that have no large tile at all
+        int tq = t;
+        asm volatile("" : "+v"(tq));
         uint64_t x[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int e = 8 * t + r;
-            x[r] = e < n ? keys[r0 + e] : ~0ull;
-        }
-        net_bitonic<8, 256>(x, t, reinterpret_cast<ulonglong2*>(comp));
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int e = 8 * t + r;
-            if (e < n) {
-                keys[r0 + e] = my_tile_hi | (x[r] >> 32);
-                vals[r0 + e] = (uint32_t)x[r];
-            }
-        }
+        sn_load_run<8>(keys + r0, (r0 & 1) == 0, 8 * tq, n, x);
+        net_bitonic<8, 256, TS_XCH>(x, tq, reinterpret_cast<ulonglong2*>(comp));
+        sn_store_run<8>(keys + r0, vals + r0, r0, 8 * tq, n, my_tile_hi, x);
         return;
     }
     int N = 64;
@@ -404,36 +352,28 @@ __global__ void __launch_bounds__(256) tile_sort_kernel(const uint2* __restrict_
         if (!hsr_bin_resolve(ref, *ref.R_dev, &bs)) return;
         keys = bs.keys; vals = bs.vals; keys_alt = bs.keys_unsorted; vals_alt = bs.vals_unsorted;
     }
+    // every array through a pointer qualified as global (hsr_sort_net.h): no FLAT access, on the speculative path or the plain one
+    const sg_u32x2* const ranges_g = (const sg_u32x2*)ranges;
     __shared__ uint64_t comp[TS_MAX];
     __shared__ uint32_t hist[256];
     __shared__ uint32_t wcnt[4][256];
     if (composite_in == 2) {   // direct binning, tiles of at most TP_MAX entries belong to tile_sort_pair_kernel
-        const uint2 rg = ranges[blockIdx.x];
+        const sn_u32x2 rg = ranges_g[blockIdx.x];
         if (rg.y - rg.x <= (uint32_t)TP_MAX) return;
         composite_in = 1;
     }
-    block_sort_tile((int)blockIdx.x, ranges, keys, vals, keys_alt, vals_alt, gid_passes, composite_in, comp, hist, wcnt);
+    block_sort_tile((int)blockIdx.x, ranges_g, (sg_u64*)keys, (sg_u32*)vals, (sg_u64*)keys_alt, (sg_u32*)vals_alt, gid_passes, composite_in,
+                    comp, hist, wcnt);
 }
 
 template <int E>
-__device__ __forceinline__ void pair_sort_tile(int r0, int n, int tid, uint64_t tile_hi, uint64_t* __restrict__ keys,
-                                               uint32_t* __restrict__ vals, ulonglong2* buf)
+__device__ __forceinline__ void pair_sort_tile(int r0, int n, int tid, uint64_t tile_hi, sg_u64* __restrict__ keys,
+                                               sg_u32* __restrict__ vals, ulonglong2* buf)
 {
     uint64_t x[E];
-#pragma unroll
-    for (int r = 0; r < E; r++) {
-        const int e = E * tid + r;
-        x[r] = e < n ? keys[r0 + e] : ~0ull;
-    }
-    net_bitonic<E, 128>(x, tid, buf);
-#pragma unroll
-    for (int r = 0; r < E; r++) {
-        const int e = E * tid + r;
-        if (e < n) {
-            keys[r0 + e] = tile_hi | (x[r] >> 32);
-            vals[r0 + e] = (uint32_t)x[r];
-        }
-    }
+    sn_load_run<E>(keys + r0, (r0 & 1) == 0, E * tid, n, x);
+    net_bitonic<E, 128, TS_XCH>(x, tid, buf);
+    sn_store_run<E>(keys + r0, vals + r0, r0, E * tid, n, tile_hi, x);
 }
 
 __global__ void __launch_bounds__(256, 7) tile_sort_pair_kernel(int T, const uint2* __restrict__ ranges, uint64_t* __restrict__ keys,
@@ -450,11 +390,15 @@ __global__ void __launch_bounds__(256, 7) tile_sort_pair_kernel(int T, const uin
         if (!hsr_bin_resolve(ref, *ref.R_dev, &bs)) return;
         keys = bs.keys; vals = bs.vals; keys_alt = bs.keys_unsorted; vals_alt = bs.vals_unsorted;
     }
+    // every array through a pointer qualified as global (hsr_sort_net.h): no FLAT access, on the speculative path or the plain one
+    const sg_u32x2* const ranges_g = (const sg_u32x2*)ranges;
+    sg_u64* const keys_g = (sg_u64*)keys;
+    sg_u32* const vals_g = (sg_u32*)vals;
     const int pair = threadIdx.x >> 7, tid = threadIdx.x & 127;
     const int tile = blockIdx.x * 2 + pair;
     int n = 0, r0 = 0;
     if (tile < T) {
-        const uint2 rg = ranges[tile];
+        const sn_u32x2 rg = ranges_g[tile];
         r0 = (int)rg.x;
         n = (int)(rg.y - rg.x);
     }
@@ -463,9 +407,9 @@ __global__ void __launch_bounds__(256, 7) tile_sort_pair_kernel(int T, const uin
         ulonglong2* buf = reinterpret_cast<ulonglong2*>(s_raw) + pair * (4 * 128);
         const uint64_t tile_hi = (uint64_t)tile << 32;
         // every pair passes exactly two workgroup barriers here (inside the network, or the bare ones of a pair with nothing to sort)
-        if (n > 0 && n <= 256) pair_sort_tile<2>(r0, n, tid, tile_hi, keys, vals, buf);
-        else if (n > 256 && n <= 512) pair_sort_tile<4>(r0, n, tid, tile_hi, keys, vals, buf);
-        else if (n > 512 && n <= TP_MAX) pair_sort_tile<8>(r0, n, tid, tile_hi, keys, vals, buf);
+        if (n > 0 && n <= 256) pair_sort_tile<2>(r0, n, tid, tile_hi, keys_g, vals_g, buf);
+        else if (n > 256 && n <= 512) pair_sort_tile<4>(r0, n, tid, tile_hi, keys_g, vals_g, buf);
+        else if (n > 512 && n <= TP_MAX) pair_sort_tile<8>(r0, n, tid, tile_hi, keys_g, vals_g, buf);
         else { __syncthreads(); __syncthreads(); }
     }
     if (!big_too) return;   // the larger tiles have a launch of their own (one workgroup per tile)
@@ -475,7 +419,7 @@ __global__ void __launch_bounds__(256, 7) tile_sort_pair_kernel(int T, const uin
     uint32_t (*wcnt)[256] = reinterpret_cast<uint32_t (*)[256]>(s_raw + TS_MAX * 8 + 256 * 4);
     for (int w = 0; w < 2; w++) {
         if (!s_big[w]) continue;
-        block_sort_tile(blockIdx.x * 2 + w, ranges, keys, vals, keys_alt, vals_alt, gid_passes, 1, comp, hist, wcnt);
+        block_sort_tile(blockIdx.x * 2 + w, ranges_g, keys_g, vals_g, (sg_u64*)keys_alt, (sg_u32*)vals_alt, gid_passes, 1, comp, hist, wcnt);
         __syncthreads();
     }
 }
