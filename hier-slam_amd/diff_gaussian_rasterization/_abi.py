@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT and SIGNATURES_EXT_FRAME_INGEST_PLANES against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES and SIGNATURES_EXT_MAP_EXPORT against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -69,6 +69,13 @@ class hsr_export_job(C.Structure):
     """one picture of hsr_frame_export (include/ext/hsr_frame_export.h)"""
     _fields_ = [("kind", ci), ("src", vp), ("table", vp), ("n", ci), ("K", ci), ("L", ci), ("sizes", ci * 16), ("lo", cf), ("hi", cf),
                 ("out", vp)]
+
+
+class hsr_map_export_job(C.Structure):
+    """the one job of hsr_map_export (include/ext/hsr_map_export.h)"""
+    _fields_ = [("P", ci), ("S", ci), ("record", ci), ("colour", ci), ("means3D", vp), ("rgb_colors", vp), ("unnorm_rotations", vp),
+                ("logit_opacities", vp), ("log_scales", vp), ("normals", vp), ("colours", vp), ("labels", vp), ("semantic", vp),
+                ("table", vp), ("n", ci), ("K", ci), ("L", ci), ("sizes", ci * 16), ("out", vp), ("out_labels", vp)]
 
 
 bp, tk = C.POINTER(hsr_buffer), C.POINTER(hsr_ticket)
@@ -289,6 +296,11 @@ SIGNATURES_EXT_FRAME_INGEST_PLANES = (
                                      ci, C.POINTER(hsr_ingest_level), vp, vp]),
 )
 
+# include/ext/hsr_map_export.h: the map as PLY records; a table of its own like the rest
+SIGNATURES_EXT_MAP_EXPORT = (
+    ("hsr_map_export", ci, [C.POINTER(hsr_map_export_job), vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -299,7 +311,7 @@ def _load():
     loaded = C.CDLL(LIB_PATH)
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
                                     + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT
-                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES):
+                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

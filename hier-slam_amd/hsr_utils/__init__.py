@@ -13,6 +13,8 @@ _SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", 
 _FRAMES = ("tree_label_table", "ingest_frame", "ingest_frame_planes", "composed_label_table")
 _SEQUENCE = ("ReplicaSequence", "tree_annotation", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation")
 _EXPORT = ("export_frame", "jet_colormap", "label_colormap", "tuple_colour_table", "write_png")
+_MAP_EXPORT = ("export_map", "gaussian_tree_labels", "level_prefix_colour_table", "leaf_head_labels", "save_map_ply",
+               "save_map_ply_semantic")
 
 
 def __getattr__(name):
@@ -32,4 +34,7 @@ def __getattr__(name):
     if name in _EXPORT:    # the pictures of an evaluated frame: binds the library as well
         from . import export
         return getattr(export, name)
+    if name in _MAP_EXPORT:      # and the map as PLY records
+        from . import map_export
+        return getattr(map_export, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -637,6 +637,14 @@ class SlamSession:
         """the estimated world-to-camera of every frame seen so far, as a list of [4,4] device tensors"""
         return [frame_w2c(self.params, t) for t in range(len(self.gt_w2c_all_frames))]
 
+    def export_map(self, path, **kw):
+        """the map as it stands as a PLY file: hsr_utils.map_export.save_map_ply(path, self.params, **kw) — the SH records by default,
+        colour="given" | "labels" | "tree" with their arguments for the coloured ones; returns the path"""
+        from . import map_export
+        if self.params is None:
+            raise RuntimeError("hsr_utils.slam: export_map before the first frame: there is no map yet")
+        return map_export.save_map_ply(path, self.params, **kw)
+
     def step(self, frame):
         """one pass of the frame loop (scripts/hierslam.py:1762-2124) for frame['id'] = the number of frames stepped so far"""
         time_idx = int(frame['id'])
