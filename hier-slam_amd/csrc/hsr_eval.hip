@@ -14,6 +14,7 @@
 //     per-block LDS histograms (integers: bit-exact in any order) flushed with 64-bit atomics.
 #include "hsr_common.h"
 #include "hsr_block.h"
+#include "hsr_tree.h"
 #include "../../include/hsr_eval.h"
 #include <climits>
 #include <cmath>
@@ -87,42 +88,16 @@ __global__ __launch_bounds__(EB) void metrics_finish_kernel(const double* __rest
 }
 
 // ---------------------------------------------------------------- labels
-// The largest probability is fl(1 / sum): the maximal logit has expf(0) = 1, every other expf(x_i - max) <= 1, and rounding is
-// monotone.  fl(e / sum) can equal it only when e >= 1 - 4 eps (below, e / sum is more than one rounding step under 1 / sum), which
-// needs x_i - max > -1e-6 with expf's few-ulp error: other classes are skipped without changing the result.
-__device__ __forceinline__ bool may_tie_max(float t) { return t >= -1e-6f; }
-
-// argmax(softmax(x)) over n planes of stride N starting at `x`: max, sum of expf(x - max) in index order, then the first index whose
-// expf(x_i - max) / sum equals the largest probability.  The second and third reads of the planes hit the caches (a block's 256
-// pixels x n planes).  All-NaN or infinite inputs give 0.
-__device__ __forceinline__ int softmax_argmax(const float* __restrict__ x, int n, int N)
-{
-    float m = -INFINITY;
-    for (int i = 0; i < n; i++) m = fmaxf(m, x[(size_t)i * N]);
-    float s = 0.f;
-    for (int i = 0; i < n; i++) s += expf(x[(size_t)i * N] - m);
-    const float pmax = 1.0f / s;
-    for (int i = 0; i < n; i++) {
-        const float t = x[(size_t)i * N] - m;
-        if (may_tie_max(t) && expf(t) / s == pmax) return i;
-    }
-    return 0;
-}
-
+// argmax(softmax(.)) is hsr_tree.h's rule.  The planes are read twice (the second read hits the caches: a block's 256 pixels x n planes).
 __global__ __launch_bounds__(EB) void labels_flat_kernel(const float* __restrict__ logits, int K, int N, int32_t* __restrict__ out)
 {
     const int i = blockIdx.x * EB + threadIdx.x;
     if (i >= N) return;
-    out[i] = softmax_argmax(logits + i, K, N);
+    const float* __restrict__ x = logits + i;
+    out[i] = hsr_softmax_argmax([&](int k) { return x[(size_t)k * N]; }, K);
 }
 
-struct TreeLevels {
-    int n;
-    int size[HSR_EVAL_MAX_LEVELS];
-    int begin[HSR_EVAL_MAX_LEVELS];
-};
-
-__global__ __launch_bounds__(EB) void labels_tree_kernel(const float* __restrict__ logits, TreeLevels lv, int N,
+__global__ __launch_bounds__(EB) void labels_tree_kernel(const float* __restrict__ logits, hsr_tree_levels lv, int N,
                                                          const int32_t* __restrict__ table, int32_t* __restrict__ out,
                                                          int32_t* __restrict__ out_levels)
 {
@@ -130,7 +105,8 @@ __global__ __launch_bounds__(EB) void labels_tree_kernel(const float* __restrict
     if (i >= N) return;
     int idx = 0;
     for (int l = 0; l < lv.n; l++) {
-        const int lab = softmax_argmax(logits + (size_t)lv.begin[l] * N + i, lv.size[l], N);
+        const float* __restrict__ x = logits + (size_t)lv.begin[l] * N + i;
+        const int lab = hsr_softmax_argmax([&](int k) { return x[(size_t)k * N]; }, lv.size[l]);
         if (out_levels) out_levels[(size_t)l * N + i] = lab;
         idx = idx * lv.size[l] + lab;     // mixed radix, level 0 most significant (hsr_utils/evaluate.py tree_lookup_table)
     }
@@ -152,7 +128,7 @@ __global__ __launch_bounds__(EB) void leaf_pack_kernel(const float* __restrict__
     }
 }
 
-// one wave per block; LDS: the block's C x 64 logits ([c][lane]: conflict-free), computed once, read by the sum and argmax passes
+// one wave per block; LDS: the block's C x 64 logits ([c][lane]: conflict-free), computed once, read by the passes of the label rule
 __global__ __launch_bounds__(64) void labels_leaf_kernel(const float* __restrict__ sem, int K, int C, int N, const float* __restrict__ wp,
                                                          int32_t* __restrict__ out)
 {
@@ -164,7 +140,6 @@ __global__ __launch_bounds__(64) void labels_leaf_kernel(const float* __restrict
 #pragma unroll
     for (int k = 0; k < HSR_EVAL_LEAF_MAX_K; k++) x[k] = (live && k < K) ? sem[(size_t)k * N + i] : 0.f;
     const float* __restrict__ bias = wp + (size_t)C * HSR_EVAL_LEAF_MAX_K;
-    float m = -INFINITY;
     // unrolled: the scalar loads of the weights of four classes issue together instead of one class's latency per trip
 #pragma unroll 4
     for (int c = 0; c < C; c++) {
@@ -174,16 +149,8 @@ __global__ __launch_bounds__(64) void labels_leaf_kernel(const float* __restrict
         for (int k = 0; k < HSR_EVAL_LEAF_MAX_K; k++) z = fmaf(wc[k], x[k], z);
         z += bias[c];
         s_z[c * 64 + lane] = z;
-        m = fmaxf(m, z);
     }
-    float s = 0.f;
-    for (int c = 0; c < C; c++) s += expf(s_z[c * 64 + lane] - m);
-    const float pmax = 1.0f / s;
-    int best = 0;
-    for (int c = 0; c < C; c++) {
-        const float t = s_z[c * 64 + lane] - m;
-        if (may_tie_max(t) && expf(t) / s == pmax) { best = c; break; }
-    }
+    const int best = hsr_softmax_argmax([&](int c) { return s_z[c * 64 + lane]; }, C);
     if (live) out[i] = best;
 }
 
@@ -392,22 +359,15 @@ extern "C" int hsr_eval_labels_tree(int K, int H, int W, int num_levels, const i
                       "out_labels", K, H, W, num_levels, HSR_EVAL_MAX_LEVELS);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    TreeLevels lv{};
-    lv.n = num_levels;
-    long long begin = 0, entries = 1;
-    for (int l = 0; l < num_levels; l++) {
-        if (level_sizes[l] < 1) {
-            hsr_set_error("eval_labels_tree: level %d has %d classes", l, level_sizes[l]);
-            return HSR_ERR_INVALID_ARGUMENT;
-        }
-        lv.size[l] = level_sizes[l];
-        lv.begin[l] = (int)begin;
-        begin += level_sizes[l];
-        entries *= level_sizes[l];
-        if (begin > K || entries > 0x7fffffffLL) {
-            hsr_set_error("eval_labels_tree: the levels need %lld of %d planes and a %lld-entry table", begin, K, entries);
-            return HSR_ERR_INVALID_ARGUMENT;
-        }
+    hsr_tree_levels lv;
+    const hsr_tree_extent e = hsr_parse_tree_levels(num_levels, level_sizes, &lv);
+    if (e.bad_level >= 0) {
+        hsr_set_error("eval_labels_tree: level %d has %d classes", e.bad_level, level_sizes[e.bad_level]);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (e.sum > K || e.prod > INT_MAX) {
+        hsr_set_error("eval_labels_tree: the levels need %lld of %d planes and a %lld-entry table", e.sum, K, e.prod);
+        return HSR_ERR_INVALID_ARGUMENT;
     }
     const int N = H * W;
     labels_tree_kernel<<<(N + EB - 1) / EB, EB, 0, stream>>>(logits, lv, N, tree_table, out_labels, out_level_labels);

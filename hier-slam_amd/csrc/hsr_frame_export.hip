@@ -9,11 +9,12 @@
 // A plane of H * W % 4 != 0 floats puts the next plane off 16 bytes: the 16-byte accesses are declared 4-byte (8-byte for int64)
 // aligned, which global memory takes at any dword.  Streaming, bound by bytes: a 1200x680 frame with K = 26 logits and 4 levels reads
 // 85 MB per LOGITS picture and writes 2.4 MB per picture; nothing is reused across lanes, so nothing is staged in LDS.  The LOGITS
-// labels read each plane of a level once for the maximum and once for the sum (the second read hits the caches).
+// labels (hsr_tree.h's rule) read each plane of a level once for the maximum and once for the sum (the second read hits the caches).
 // Compiled with -ffp-contract=off: no rule of the header has a fused multiply-add.
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_tree.h"
 #include "../../include/hsr_eval.h"
 #include "../../include/ext/hsr_frame_resample.h"
 #include "../../include/ext/hsr_frame_export.h"
@@ -90,75 +91,6 @@ __device__ __forceinline__ void lookup(const uint8_t* __restrict__ table, const 
 
 __device__ __forceinline__ float clamp01(float x) { return x > 0.f ? (x < 1.f ? x : 1.f) : 0.f; }      // a NaN fails x > 0
 
-// hsr_eval.hip's may_tie_max: expf(t) / s can equal 1.0f / s only for t >= -1e-6
-__device__ __forceinline__ bool may_tie_max(float t) { return t >= -1e-6f; }
-
-// hsr_eval.hip's softmax_argmax on V pixels at once (restated: that one reads one pixel with scalar loads): the maximum and the sum in
-// index order, then the lowest i with expf(x_i - m) / s == 1.0f / s.  Both passes take the planes four at a time, the four loads issued
-// before the first is used: with 4 pixels per lane a frame has few waves, and one load in flight per wave leaves the kernel waiting on
-// latency (34.5 us for the 1200x680 K = 26 picture on an MI355X, profiles/export_bench.log).  The search for that lowest i starts at
-// the first index that passes may_tie_max, found while summing — the indices before it fail the test that the original makes first.
-// Where that index holds the maximum itself (the difference is 0, expf(0) = 1 and 1.0f / s == 1.0f / s unless s is a NaN) it is the
-// answer and nothing is read again; only a near tie in front of the maximum is searched.
-constexpr int XU = 4;
-
-template <int V>
-__device__ __forceinline__ void softmax_argmax(const float* __restrict__ x, int n, size_t N, int (&lab)[V])
-{
-    float m[V], s[V], dfirst[V], t[XU][V];
-    int first[V];
-#pragma unroll
-    for (int v = 0; v < V; v++) { m[v] = -INFINITY; s[v] = 0.f; first[v] = -1; dfirst[v] = 0.f; }
-    int i = 0;
-    for (; i + XU <= n; i += XU) {
-#pragma unroll
-        for (int u = 0; u < XU; u++) load<V>(x + (size_t)(i + u) * N, t[u]);
-#pragma unroll
-        for (int u = 0; u < XU; u++)
-#pragma unroll
-            for (int v = 0; v < V; v++) m[v] = fmaxf(m[v], t[u][v]);
-    }
-    for (; i < n; i++) {
-        load<V>(x + (size_t)i * N, t[0]);
-#pragma unroll
-        for (int v = 0; v < V; v++) m[v] = fmaxf(m[v], t[0][v]);
-    }
-    auto sum = [&](int at, const float (&tv)[V]) {
-#pragma unroll
-        for (int v = 0; v < V; v++) {
-            const float d = tv[v] - m[v];
-            s[v] += expf(d);
-            const bool hit = first[v] < 0 && may_tie_max(d);
-            first[v] = hit ? at : first[v];
-            dfirst[v] = hit ? d : dfirst[v];
-        }
-    };
-    for (i = 0; i + XU <= n; i += XU) {
-#pragma unroll
-        for (int u = 0; u < XU; u++) load<V>(x + (size_t)(i + u) * N, t[u]);
-#pragma unroll
-        for (int u = 0; u < XU; u++) sum(i + u, t[u]);
-    }
-    for (; i < n; i++) {
-        load<V>(x + (size_t)i * N, t[0]);
-        sum(i, t[0]);
-    }
-#pragma unroll
-    for (int v = 0; v < V; v++) {
-        const float pmax = 1.0f / s[v];
-        lab[v] = 0;
-        if (first[v] < 0) continue;      // every difference a NaN or below the bound: the original finds nothing either
-        if (dfirst[v] == 0.f) {          // the maximum itself
-            lab[v] = s[v] == s[v] ? first[v] : 0;
-            continue;
-        }
-        for (int k = first[v]; k < n; k++) {
-            const float d = x[(size_t)k * N + v] - m[v];
-            if (may_tie_max(d) && expf(d) / s[v] == pmax) { lab[v] = k; break; }
-        }
-    }
-}
-
 // V pixels of picture `job` from flat index i on; N = H * W
 template <int V>
 __device__ __forceinline__ void export_pixels(const hsr_export_job& job, size_t i, size_t N)
@@ -214,7 +146,9 @@ __device__ __forceinline__ void export_pixels(const hsr_export_job& job, size_t 
             for (int l = 0; l < job.L; l++) {
                 int lab[V];
                 const int size = job.sizes[l];
-                softmax_argmax<V>(src + (size_t)begin * N, size, N, lab);
+                const float* __restrict__ x = src + (size_t)begin * N;      // hsr_tree.h's rule on V pixels: a 16-byte load per plane
+                hsr_softmax_argmax<V>([&](int k, float (&t)[V]) { load<V>(x + (size_t)k * N, t); },
+                                      [&](int k, int v) { return x[(size_t)k * N + v]; }, size, lab);
 #pragma unroll
                 for (int v = 0; v < V; v++) idx[v] = idx[v] * size + lab[v];
                 begin += size;
@@ -278,21 +212,17 @@ extern "C" int hsr_frame_export(int H, int W, int n_jobs, const hsr_export_job* 
                 hsr_set_error("frame_export: job %d: L must be 1..%d; got %d", k, HSR_EVAL_MAX_LEVELS, j.L);
                 return HSR_ERR_INVALID_ARGUMENT;
             }
-            long long sum = 0, prod = 1;
-            for (int l = 0; l < j.L; l++) {
-                if (j.sizes[l] < 1) {
-                    hsr_set_error("frame_export: job %d: level %d has %d classes", k, l, j.sizes[l]);
-                    return HSR_ERR_INVALID_ARGUMENT;
-                }
-                sum += j.sizes[l];
-                prod = prod > 0x7fffffffLL ? prod : prod * j.sizes[l];      // stays above every int once it is
-            }
-            if (j.kind == HSR_EXPORT_LOGITS && sum > j.K) {
-                hsr_set_error("frame_export: job %d: the levels need %lld planes, K is %d", k, sum, j.K);
+            const hsr_tree_extent e = hsr_parse_tree_levels(j.L, j.sizes, nullptr);
+            if (e.bad_level >= 0) {
+                hsr_set_error("frame_export: job %d: level %d has %d classes", k, e.bad_level, j.sizes[e.bad_level]);
                 return HSR_ERR_INVALID_ARGUMENT;
             }
-            if (prod != j.n) {
-                hsr_set_error("frame_export: job %d: the levels need a table of %lld rows, n is %d", k, prod, j.n);
+            if (j.kind == HSR_EXPORT_LOGITS && e.sum > j.K) {
+                hsr_set_error("frame_export: job %d: the levels need %lld planes, K is %d", k, e.sum, j.K);
+                return HSR_ERR_INVALID_ARGUMENT;
+            }
+            if (e.prod != j.n) {
+                hsr_set_error("frame_export: job %d: the levels need a table of %lld rows, n is %d", k, e.prod, j.n);
                 return HSR_ERR_INVALID_ARGUMENT;
             }
         }

@@ -19,6 +19,7 @@
 // shares its kernels with the outlier-rejecting head in hsr_loss_masked.hip.
 #include "hsr_common.h"
 #include "hsr_block.h"
+#include "hsr_tree.h"
 #include "../../include/hsr_losses.h"
 #include <cmath>
 
@@ -254,9 +255,7 @@ __global__ __launch_bounds__(LB) void ssim_backward_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------- tree cross-entropy
-struct Levels {
-    int n;
-    int begin[HSR_LOSS_MAX_LEVELS], size[HSR_LOSS_MAX_LEVELS];
+struct Levels : hsr_tree_levels {
     float weight[HSR_LOSS_MAX_LEVELS];
 };
 
@@ -815,7 +814,8 @@ extern "C" int hsr_loss_l1_grad(int C, int H, int W, const float* pred, const fl
 }
 
 namespace {
-int parse_levels(const char* who, int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight, Levels* lv)
+// the checks of the three tree cross-entropy entry points, and their levels with the weights (NULL: 1)
+int tree_ce_levels(const char* who, int K, int H, int W, int num_levels, const int* level_sizes, const float* level_weight, Levels* lv)
 {
     if (K < 1 || hsr_bad_frame_size(H, W) || !level_sizes) {
         hsr_set_error("%s: invalid sizes K=%d H=%d W=%d or NULL level_sizes", who, K, H, W);
@@ -825,22 +825,16 @@ int parse_levels(const char* who, int K, int H, int W, int num_levels, const int
         hsr_set_error("%s: num_levels=%d outside [1, %d]", who, num_levels, HSR_LOSS_MAX_LEVELS);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    lv->n = num_levels;
-    int begin = 0;
-    for (int l = 0; l < num_levels; l++) {
-        if (level_sizes[l] < 1) {
-            hsr_set_error("%s: level %d has %d classes", who, l, level_sizes[l]);
-            return HSR_ERR_INVALID_ARGUMENT;
-        }
-        lv->begin[l] = begin;
-        lv->size[l] = level_sizes[l];
-        lv->weight[l] = level_weight ? level_weight[l] : 1.0f;
-        begin += level_sizes[l];
-    }
-    if (begin > K) {
-        hsr_set_error("%s: levels cover %d channels but the map has K=%d", who, begin, K);
+    const hsr_tree_extent e = hsr_parse_tree_levels(num_levels, level_sizes, lv);
+    if (e.bad_level >= 0) {
+        hsr_set_error("%s: level %d has %d classes", who, e.bad_level, level_sizes[e.bad_level]);
         return HSR_ERR_INVALID_ARGUMENT;
     }
+    if (e.sum > K) {
+        hsr_set_error("%s: levels cover %d channels but the map has K=%d", who, (int)(e.sum > INT_MAX ? INT_MAX : e.sum), K);
+        return HSR_ERR_INVALID_ARGUMENT;
+    }
+    for (int l = 0; l < num_levels; l++) lv->weight[l] = level_weight ? level_weight[l] : 1.0f;
     return HSR_OK;
 }
 }  // namespace
@@ -881,7 +875,7 @@ extern "C" int hsr_loss_tree_ce(int K, int H, int W, int num_levels, const int* 
 {
     hipStream_t stream = (hipStream_t)stream_;
     Levels lv;
-    int rc = parse_levels("loss_tree_ce", K, H, W, num_levels, level_sizes, level_weight, &lv);
+    int rc = tree_ce_levels("loss_tree_ce", K, H, W, num_levels, level_sizes, level_weight, &lv);
     if (rc != HSR_OK) return rc;
     if (!logits || !labels || !out_level_loss) {
         hsr_set_error("loss_tree_ce: NULL logits / labels / out_level_loss");
@@ -904,7 +898,7 @@ extern "C" int hsr_loss_tree_ce_value(int K, int H, int W, int num_levels, const
                                       char* scratch, size_t scratch_bytes, void* stream_)
 {
     Levels lv;
-    int rc = parse_levels("loss_tree_ce_value", K, H, W, num_levels, level_sizes, nullptr, &lv);
+    int rc = tree_ce_levels("loss_tree_ce_value", K, H, W, num_levels, level_sizes, nullptr, &lv);
     if (rc != HSR_OK) return rc;
     if (!logits || !labels || !out_level_loss || !out_inv_count) {
         hsr_set_error("loss_tree_ce_value: NULL logits / labels / out_level_loss / out_inv_count");
@@ -924,7 +918,7 @@ extern "C" int hsr_loss_tree_ce_grad(int K, int H, int W, int num_levels, const 
                                      float* out_grad, void* stream_)
 {
     Levels lv;
-    int rc = parse_levels("loss_tree_ce_grad", K, H, W, num_levels, level_sizes, level_weight, &lv);
+    int rc = tree_ce_levels("loss_tree_ce_grad", K, H, W, num_levels, level_sizes, level_weight, &lv);
     if (rc != HSR_OK) return rc;
     if (!logits || !labels || !inv_count || !out_grad) {
         hsr_set_error("loss_tree_ce_grad: NULL logits / labels / inv_count / out_grad");

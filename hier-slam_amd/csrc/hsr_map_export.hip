@@ -11,7 +11,7 @@
 //       tree the [P,K] logits are the largest input.  A wave stages the contiguous span of its 64 rows (64 K floats, 16 bytes per lane,
 //            sixteen loads in flight) into LDS rows of pitch K | 1 dwords: odd, so that lane r reading its own row r * pitch + c hits
 //            bank (r * pitch + c) % 32, distinct over the 32 lanes of a half wave.  Every lane then runs the passes of the label rule
-//            (softmax_argmax below) on its row in LDS.  A SIMD spends four cycles on a wave's instruction however few lanes are live,
+//            (hsr_tree.h's hsr_softmax_argmax) on its row in LDS.  A SIMD spends four cycles on a wave's instruction however few lanes are live,
 //            so the rows are never dealt to fewer lanes: the workgroup shrinks instead, to the most of 4, 2 and 1 waves
 //            whose records and 64 rows each fit in 64 KB (beside 59-byte records K <= 48, K <= 112 — K = 102 runs two waves — and
 //            K <= 240).  Longer rows are not staged: each lane reads its own from global memory, a run of 964 bytes or more.
@@ -24,6 +24,7 @@
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_tree.h"
 #include "../../include/hsr_eval.h"
 #include "../../include/ext/hsr_map_export.h"
 
@@ -88,54 +89,6 @@ template <bool WIDE, class F> __device__ __forceinline__ void scatter(const Fetc
     }
 }
 
-// hsr_eval.hip's may_tie_max: expf(t) / s can equal 1.0f / s only for t >= -1e-6
-__device__ __forceinline__ bool may_tie_max(float t) { return t >= -1e-6f; }
-
-// hsr_eval.hip's softmax_argmax, restated over an accessor: the maximum and the sum in index order, then the lowest i with
-// expf(x_i - m) / s == 1.0f / s.  Both passes take the values four at a time, the four reads issued before the first is used: a lane
-// walking its row one dependent LDS read at a time waits out the read's latency per value.  The search for that lowest i starts at the
-// first index that passes may_tie_max, found while summing — the indices before it fail the test that the original makes first.  Where
-// that index holds the maximum itself (the difference is 0, expf(0) = 1 and 1.0f / s == 1.0f / s unless s is a NaN) it is the answer
-// and nothing is read again; only a near tie in front of the maximum is searched.  (hsr_frame_export.hip's form of the same rule.)
-constexpr int XU = 4;
-
-template <class At> __device__ __forceinline__ int softmax_argmax(At at, int n)
-{
-    float m = -INFINITY, v[XU];
-    int i = 0;
-    for (; i + XU <= n; i += XU) {
-#pragma unroll
-        for (int u = 0; u < XU; u++) v[u] = at(i + u);
-#pragma unroll
-        for (int u = 0; u < XU; u++) m = fmaxf(m, v[u]);
-    }
-    for (; i < n; i++) m = fmaxf(m, at(i));
-    float s = 0.f, dfirst = 0.f;
-    int first = -1;
-    auto sum = [&](int k, float x) {
-        const float d = x - m;
-        s += expf(d);
-        const bool hit = first < 0 && may_tie_max(d);
-        first = hit ? k : first;
-        dfirst = hit ? d : dfirst;
-    };
-    for (i = 0; i + XU <= n; i += XU) {
-#pragma unroll
-        for (int u = 0; u < XU; u++) v[u] = at(i + u);
-#pragma unroll
-        for (int u = 0; u < XU; u++) sum(i + u, v[u]);
-    }
-    for (; i < n; i++) sum(i, at(i));
-    if (first < 0) return 0;      // every difference a NaN or below the bound: the original finds nothing either
-    if (dfirst == 0.f) return s == s ? first : 0;      // the maximum itself
-    const float pmax = 1.0f / s;
-    for (int k = first; k < n; k++) {
-        const float d = at(k) - m;
-        if (may_tie_max(d) && expf(d) / s == pmax) return k;
-    }
-    return 0;
-}
-
 // the per-level labels of Gaussian g (its logits behind `at`), out_labels, and the tuple's colour into record `local`
 template <int REC, class At>
 __device__ __forceinline__ void tree_gaussian(const hsr_map_export_job& job, At at, int g, int local, unsigned char* rec)
@@ -143,7 +96,7 @@ __device__ __forceinline__ void tree_gaussian(const hsr_map_export_job& job, At 
     int idx = 0, begin = 0;
     for (int l = 0; l < job.L; l++) {
         const int size = job.sizes[l];      // a wave-uniform index into the kernel arguments: scalar loads, no scratch
-        const int lab = softmax_argmax([&](int i) { return at(begin + i); }, size);
+        const int lab = hsr_softmax_argmax([&](int i) { return at(begin + i); }, size);
         if (job.out_labels) job.out_labels[(size_t)l * job.P + g] = lab;
         idx = idx * size + lab;
         begin += size;
@@ -419,21 +372,17 @@ extern "C" int hsr_map_export(const hsr_map_export_job* job_, void* stream_)
             hsr_set_error("map_export: L must be 1..%d; got %d", HSR_EVAL_MAX_LEVELS, j.L);
             return HSR_ERR_INVALID_ARGUMENT;
         }
-        long long sum = 0, prod = 1;
-        for (int l = 0; l < j.L; l++) {
-            if (j.sizes[l] < 1) {
-                hsr_set_error("map_export: level %d has %d classes", l, j.sizes[l]);
-                return HSR_ERR_INVALID_ARGUMENT;
-            }
-            sum += j.sizes[l];
-            prod = prod > 0x7fffffffLL ? prod : prod * j.sizes[l];      // stays above every int once it is
-        }
-        if (sum > j.K) {
-            hsr_set_error("map_export: the levels need %lld columns, K is %d", sum, j.K);
+        const hsr_tree_extent e = hsr_parse_tree_levels(j.L, j.sizes, nullptr);
+        if (e.bad_level >= 0) {
+            hsr_set_error("map_export: level %d has %d classes", e.bad_level, j.sizes[e.bad_level]);
             return HSR_ERR_INVALID_ARGUMENT;
         }
-        if (records && prod != j.n) {
-            hsr_set_error("map_export: the levels need a table of %lld rows, n is %d", prod, j.n);
+        if (e.sum > j.K) {
+            hsr_set_error("map_export: the levels need %lld columns, K is %d", e.sum, j.K);
+            return HSR_ERR_INVALID_ARGUMENT;
+        }
+        if (records && e.prod != j.n) {
+            hsr_set_error("map_export: the levels need a table of %lld rows, n is %d", e.prod, j.n);
             return HSR_ERR_INVALID_ARGUMENT;
         }
         wide = wide && aligned16(j.semantic);

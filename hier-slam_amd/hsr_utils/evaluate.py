@@ -4,6 +4,7 @@
                                                                                     utils/eval_helpers.py:1258-1295
     semantic_labels(im_semantic, mode, level_sizes=, tree_table=, mlp=)            argmax(softmax): flat :974-983, tree :187-204 +
                                                                                     :135-156, leaf MLP :1251-1255
+    tree_levels(level_sizes)                                                       the one check of a level_sizes list: (sizes, tuples)
     tree_lookup_table(label_mapping_tree, level_sizes)                             the dict of transfer_tree_2_label as a dense table
     iou_counts(pred, gt, num_classes=, class_ids=, dilation_ratio=0.02)            calculate_iou :83-90, boundary_iou :37-81, per class
     ms_ssim(im, gt_im, gt_depth, final_opacity=None, sil_thres=None, details=False) MS-SSIM :722, :946, :1272; restated, not pinned
@@ -19,6 +20,7 @@ Every per-frame call runs on the current stream and returns device tensors witho
 the numbers once at the end.  Frame averages are plain means over frames (:1590-1600).  There is no CPU path.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -107,18 +109,26 @@ def ms_ssim(im, gt_im, gt_depth, final_opacity=None, sil_thres=None, details=Fal
 _ms_ssim = ms_ssim      # evaluate_frame's flag carries the function's name
 
 
+def tree_levels(level_sizes):
+    """(sizes, n): the level sizes of the dataset's num_semantic — level_sizes without its last entry, the leaf count — and the
+    number n = prod(sizes) of label tuples, the rows of a table over the mixed-radix tuple index.  The one check of a level_sizes
+    list for every function of hsr_utils that takes one: 1..MAX_LEVELS levels of at least one class, at most 2^26 tuples."""
+    sizes = [int(s) for s in level_sizes][:-1]
+    if not 1 <= len(sizes) <= MAX_LEVELS or min(sizes) < 1:
+        raise RuntimeError("hsr_utils.evaluate: level_sizes must list 1..%d level sizes >= 1 plus the leaf count" % MAX_LEVELS)
+    n = math.prod(sizes)
+    if n > 1 << 26:
+        raise RuntimeError("hsr_utils.evaluate: a %d-entry table of the level tuples is too large" % n)
+    return sizes, n
+
+
 def tree_lookup_table(label_mapping_tree, level_sizes, device="cuda"):
     """The dataset's label_mapping_tree ({leaf id (int or str): tuple of per-level labels}) as a dense int32 table over the mixed-radix
     index of the level labels (level 0 most significant), for the levels level_sizes[:-1] (the dataset's num_semantic, whose last
     entry is the leaf count; datasets/gradslam_datasets/replica.py:144-147).  A tuple not in the dict maps to -1; of two keys with one
     tuple the later entry wins, as transfer_tree_2_label's loop of masked assignments does (utils/eval_helpers.py:135-156).  Tuples
     with a label outside its level's range are never produced by the argmax and are left out.  Built once on the host."""
-    sizes = [int(s) for s in level_sizes][:-1]
-    if not 1 <= len(sizes) <= MAX_LEVELS or min(sizes) < 1:
-        raise RuntimeError("hsr_utils.evaluate: level_sizes must list 1..%d level sizes >= 1 plus the leaf count" % MAX_LEVELS)
-    n = int(np.prod(sizes))
-    if n > 1 << 26:
-        raise RuntimeError("hsr_utils.evaluate: a %d-entry tree table is too large" % n)
+    sizes, n = tree_levels(level_sizes)
     table = np.full(n, -1, dtype=np.int64)
     for key, value in label_mapping_tree.items():
         value = [int(v) for v in value]
@@ -158,13 +168,13 @@ def semantic_labels(im_semantic, mode, *, level_sizes=None, tree_table=None, mlp
     if mode == "tree":
         if level_sizes is None or tree_table is None:
             raise RuntimeError("hsr_utils.evaluate: mode 'tree' needs level_sizes and tree_table")
-        sizes = [int(s) for s in level_sizes][:-1]
+        sizes, n = tree_levels(level_sizes)
         L = len(sizes)
-        if not 1 <= L <= MAX_LEVELS or sum(sizes) > K or min(sizes) < 1:
+        if sum(sizes) > K:
             raise RuntimeError("hsr_utils.evaluate: level_sizes %s (levels + leaf count) do not fit %d planes" % (list(level_sizes), K))
         table = _dev(tree_table, "tree_table", torch.int32)
-        if table.numel() != int(np.prod(sizes)):
-            raise RuntimeError("hsr_utils.evaluate: tree_table has %d entries, the levels %s need %d" % (table.numel(), sizes, int(np.prod(sizes))))
+        if table.numel() != n:
+            raise RuntimeError("hsr_utils.evaluate: tree_table has %d entries, the levels %s need %d" % (table.numel(), sizes, n))
         levels = torch.empty((L, H, W), dtype=torch.int32, device=dev)
         _abi.call(_lib.hsr_eval_labels_tree, "hsr_eval_labels_tree", dev, K, H, W, L, (C.c_int * L)(*sizes), z.data_ptr(), table.data_ptr(),
                   out.data_ptr(), levels.data_ptr())
@@ -431,5 +441,5 @@ def evaluate_sequence(params, frames, cam, eval_dir=None, *, eval_every=1, sil_t
     return result
 
 
-__all__ = ["frame_metrics", "ms_ssim", "semantic_labels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
+__all__ = ["frame_metrics", "ms_ssim", "semantic_labels", "tree_levels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
            "dilation_pixels", "evaluate_sequence"]

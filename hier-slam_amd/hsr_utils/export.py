@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from diff_gaussian_rasterization import _abi
-from .evaluate import MAX_LEVELS, _dev, _plane
+from .evaluate import _dev, _plane, tree_levels
 
 _lib = _abi.lib
 
@@ -59,18 +59,6 @@ def label_colormap(n, device="cuda"):
     return torch.tensor(table.astype(np.uint8), device=device)
 
 
-def _level_sizes(level_sizes):
-    sizes = [int(s) for s in level_sizes][:-1]
-    if not 1 <= len(sizes) <= MAX_LEVELS or min(sizes) < 1:
-        raise RuntimeError("hsr_utils.export: level_sizes must list 1..%d level sizes >= 1 plus the leaf count" % MAX_LEVELS)
-    n = 1
-    for s in sizes:
-        n *= s
-    if n > 1 << 26:
-        raise RuntimeError("hsr_utils.export: a %d-entry tuple table is too large" % n)
-    return sizes, n
-
-
 def tuple_colour_table(colour_map_level, level_sizes, wildcard, device="cuda"):
     """The dataset's colour_map_np_level ({tuple of per-level labels: (r, g, b)}) as a dense uint8 [prod(sizes), 3] table over the
     mixed-radix index of evaluate.tree_lookup_table (level 0 most significant), sizes = level_sizes[:-1] as there (the dataset's
@@ -79,7 +67,7 @@ def tuple_colour_table(colour_map_level, level_sizes, wildcard, device="cuda"):
     key matches every label of that level (a key of -1 alone matches every tuple).  wildcard=False is semantic_label_vis (:100-117,
     ScanNet): a key holding -1 matches nothing, since no label is -1.  A key with a label outside its level's range matches nothing;
     rows no key names are black.  Keys may be tuples, lists, arrays or tensors.  Built once on the host."""
-    sizes, n = _level_sizes(level_sizes)
+    sizes, n = tree_levels(level_sizes)
     strides = [int(np.prod(sizes[l + 1:], dtype=np.int64)) for l in range(len(sizes))]
     table = np.zeros((n, 3), dtype=np.uint8)
     for key, value in colour_map_level.items():
@@ -137,7 +125,7 @@ def export_frame(*, im=None, gt_im=None, depth=None, gt_depth=None, im_semantic=
     if im_semantic is not None or gt_levels is not None:
         if level_sizes is None or tuple_table is None:
             raise RuntimeError("hsr_utils.export: im_semantic and gt_levels need level_sizes and tuple_table")
-        sizes, n_tuples = _level_sizes(level_sizes)
+        sizes, n_tuples = tree_levels(level_sizes)
         tuple_table = _table(tuple_table, "tuple_table", n_tuples)
     if labels is not None or gt_labels is not None:
         if label_table is None:

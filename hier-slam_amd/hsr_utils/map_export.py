@@ -20,7 +20,7 @@ import torch
 
 from diff_gaussian_rasterization import _abi
 from . import export
-from .evaluate import _dev
+from .evaluate import _dev, tree_levels
 
 _lib = _abi.lib
 
@@ -50,7 +50,7 @@ def _array(t, what, cols, P=None, dtype=torch.float32):
 
 
 def _tree_job(job, semantic, level_sizes, P=None):
-    sizes, n = export._level_sizes(level_sizes)
+    sizes, n = tree_levels(level_sizes)
     sem = _dev(semantic.detach() if isinstance(semantic, torch.Tensor) else semantic, "semantic")
     if sem.dim() != 2 or sem.shape[1] < sum(sizes) or (P is not None and sem.shape[0] != P):
         raise RuntimeError("hsr_utils.map_export: semantic must be [%s,K] with K >= %d, the levels %s (got %s)"
@@ -159,7 +159,7 @@ def level_prefix_colour_table(tree_id_classes_map_level, level_sizes, i_level, d
     leaves it at -1, which numpy wraps to the LAST colour of the map — deliberately not copied.  level_sizes is the dataset's
     num_semantic (the leaf count last).  Exporting level i is then colour="tree" with this table and the first i + 1 level sizes (plus
     any last entry, which is dropped): save_map_ply_semantic(i_level=...) does both."""
-    sizes = [int(s) for s in level_sizes][:-1]
+    sizes, _n = tree_levels(level_sizes)
     i_level = int(i_level)
     if not 0 <= i_level < len(sizes):
         raise ValueError("hsr_utils.map_export: i_level must be 0..%d (got %d)" % (len(sizes) - 1, i_level))

@@ -49,7 +49,7 @@
  *
  * LOGITS (:1314-1327) — src float32 [K,H,W], sizes[L], table [n,3] with n = prod(sizes).  Level l owns the planes
  * begin_l .. begin_l + sizes[l] - 1, begin_l = sizes[0] + .. + sizes[l-1]; planes from sum(sizes) on are not read.  The label of a
- * level is that of hsr_eval_labels_tree (hsr_eval.h), bit for bit: with m the largest x_i of the level's planes (fmaxf from -inf, in
+ * level is that of hsr_eval_labels_tree (hsr_eval.h), bit for bit (one definition, csrc/hsr_tree.h): with m the largest x_i of the level's planes (fmaxf from -inf, in
  * index order) and s the fp32 sum of expf(x_i - m) in index order, the lowest i with expf(x_i - m) / s == 1.0f / s; 0 when there is
  * none (a NaN or an infinity among the level's values).  Then as LEVELS (such labels are never out of range).
  *

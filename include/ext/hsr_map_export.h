@@ -39,7 +39,7 @@
  *   HSR_MAP_COLOUR_TREE    semantic float32 [P,K] row-major, row stride K; sizes[L]; table uint8 [n,3], n = prod(sizes).  Level l owns
  *                          the columns begin_l .. begin_l + sizes[l] - 1, begin_l = sizes[0] + .. + sizes[l-1]; columns from sum(sizes)
  *                          on are not used (they may hold anything).  The label of a level is that of hsr_eval_labels_tree (hsr_eval.h)
- *                          and of hsr_frame_export.h's LOGITS, bit for bit: with m the largest x_i of the level's columns (fmaxf from
+ *                          and of hsr_frame_export.h's LOGITS, bit for bit (one definition, csrc/hsr_tree.h): with m the largest x_i of the level's columns (fmaxf from
  *                          -inf, in index order) and s the fp32 sum of expf(x_i - m) in index order, the lowest i with
  *                          expf(x_i - m) / s == 1.0f / s; 0 when there is none (a NaN or +inf among the level's values: s is then a
  *                          NaN; a -inf beside finite values is a value like any other and never wins).  The
