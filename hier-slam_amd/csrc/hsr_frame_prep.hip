@@ -13,6 +13,7 @@
 // (oracle/frame_prep_oracle.py), which matters because out_means3D feeds the rasterizer's integer decisions.
 #include "hsr_common.h"
 #include "hsr_block.h"
+#include "hsr_quat.h"
 #include "../../include/hsr_frame_prep.h"
 
 namespace {
@@ -50,31 +51,11 @@ __device__ __forceinline__ Pose load_pose(const float* cam_unnorm_rots, const fl
     return p;
 }
 
-__device__ __forceinline__ float4 quat_mult(const float* a, float4 b)  // slam_helpers.py:21-28, a = q1, b = q2 (w, x, y, z)
-{
-    float4 o;
-    o.x = ((a[0] * b.x - a[1] * b.y) - a[2] * b.z) - a[3] * b.w;
-    o.y = ((a[0] * b.y + a[1] * b.x) + a[2] * b.w) - a[3] * b.z;
-    o.z = ((a[0] * b.z - a[1] * b.w) + a[2] * b.x) + a[3] * b.y;
-    o.w = ((a[0] * b.w + a[1] * b.z) - a[2] * b.y) + a[3] * b.x;
-    return o;
-}
-
-__device__ __forceinline__ float norm4(float4 v) { return sqrtf(((v.x * v.x + v.y * v.y) + v.z * v.z) + v.w * v.w); }
-
-__device__ __forceinline__ float4 normalize4(float4 v, float* n_out = nullptr)
-{
-    const float n = norm4(v);
-    if (n_out) *n_out = n;
-    const float d = fmaxf(n, 1e-12f);
-    return make_float4(v.x / d, v.y / d, v.z / d, v.w / d);
-}
-
 // adjoint of y = v / max(|v|, eps), F.normalize as torch.autograd differentiates it: (g - y (y.g)) / |v| where |v| >= eps; below eps the
 // clamp has no gradient, the divisor is the constant eps and the projection term is gone: g / eps (finite at |v| = 0 too)
 __device__ __forceinline__ float4 normalize_adjoint(float4 v, float4 g)
 {
-    const float nv = norm4(v);
+    const float nv = hsr_norm4(v);
     const float n = fmaxf(nv, 1e-12f);
     if (nv < 1e-12f) return make_float4(g.x / n, g.y / n, g.z / n, g.w / n);
     const float4 y = make_float4(v.x / n, v.y / n, v.z / n, v.w / n);
@@ -103,9 +84,9 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_forward_kernel(PrepArgs
     out_means3D[3 * p] = m[0]; out_means3D[3 * p + 1] = m[1]; out_means3D[3 * p + 2] = m[2];
     const float4 u = reinterpret_cast<const float4*>(a.unnorm_rotations)[p];
     float4 tr = u;
-    if (a.transform_rots) tr = quat_mult(ps.q, normalize4(u));
+    if (a.transform_rots) tr = hsr_quat_mult(ps.q, hsr_normalize4(u));
     if (out_unnorm_rot) reinterpret_cast<float4*>(out_unnorm_rot)[p] = tr;
-    reinterpret_cast<float4*>(out_rotations)[p] = normalize4(a.rot_source == HSR_PREP_ROT_PARAMS ? u : tr);
+    reinterpret_cast<float4*>(out_rotations)[p] = hsr_normalize4(a.rot_source == HSR_PREP_ROT_PARAMS ? u : tr);
     out_opacities[p] = 1.0f / (1.0f + expf(-a.logit_opacities[p]));
     if (a.S == 1) {
         const float e = expf(a.log_scales[p]);
@@ -161,11 +142,11 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_backward_kernel(
         float4 gtr = g_unnorm ? reinterpret_cast<const float4*>(g_unnorm)[p] : zero4;
         float4 gu = zero4;
         float4 un = zero4;
-        if (a.transform_rots) un = normalize4(u);
+        if (a.transform_rots) un = hsr_normalize4(u);
         if (a.rot_source == HSR_PREP_ROT_PARAMS) {
             gu = normalize_adjoint(u, gr);
         } else {
-            const float4 tr = a.transform_rots ? quat_mult(ps.q, un) : u;
+            const float4 tr = a.transform_rots ? hsr_quat_mult(ps.q, un) : u;
             const float4 t4 = normalize_adjoint(tr, gr);
             gtr.x += t4.x; gtr.y += t4.y; gtr.z += t4.z; gtr.w += t4.w;
         }

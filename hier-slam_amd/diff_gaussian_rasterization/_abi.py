@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES and SIGNATURES_EXT_MAP_EXPORT against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES, SIGNATURES_EXT_MAP_EXPORT and SIGNATURES_EXT_VIEW against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -301,6 +301,19 @@ SIGNATURES_EXT_MAP_EXPORT = (
     ("hsr_map_export", ci, [C.POINTER(hsr_map_export_job), vp]),
 )
 
+# include/ext/hsr_view.h: rasterizer inputs from a given world-to-camera matrix and a view's hole counts; a table of its own like the rest
+SIGNATURES_EXT_VIEW = (
+    ("hsr_view_prep", ci, [ci, ci, ci, ci,
+                           vp, vp,
+                           vp, vp,
+                           vp,
+                           vp, vp, vp,
+                           vp, vp, vp]),
+    ("hsr_view_holes_scratch_bytes", sz, [ci, ci]),
+    ("hsr_view_holes", ci, [ci, ci, vp, vp, cf,
+                            vp, vp, sz, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -311,7 +324,7 @@ def _load():
     loaded = C.CDLL(LIB_PATH)
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
                                     + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT
-                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT):
+                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT + SIGNATURES_EXT_VIEW):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

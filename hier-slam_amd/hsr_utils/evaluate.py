@@ -15,6 +15,11 @@
     evaluate_sequence(params, frames, cam, eval_dir, ...)                          the loop of eval_semantic_tree_newrender / eval_newrender:
                                                                                     scores per frame, the txt files, the pictures
                                                                                     (hsr_utils.export, include/ext/hsr_frame_export.h)
+    view_holes(final_opacity, gt_depth, sil_thres)                                 the hole count of a novel view :1726-1734
+                                                                                    (include/ext/hsr_view.h)
+    view_percent_holes(holes, numel)                                               percent_holes and the validity rule :1734-1738 (host)
+    evaluate_novel_views(params, frames, cam, eval_dir, ...)                       the loop of eval_nvs :1648-1863: the map rendered from
+                                                                                    given poses, scored over the valid views
 
 Every per-frame call runs on the current stream and returns device tensors without a host synchronisation: score all frames, read
 the numbers once at the end.  Frame averages are plain means over frames (:1590-1600).  There is no CPU path.
@@ -441,5 +446,122 @@ def evaluate_sequence(params, frames, cam, eval_dir=None, *, eval_every=1, sil_t
     return result
 
 
+# ---- novel views -------------------------------------------------------------------------------------------------------------------------
+VALID_MAX_PERCENT_HOLES = np.float32(0.1)      # utils/eval_helpers.py:1735, the Python 0.1 beside a float32 tensor
+
+
+def view_holes(final_opacity, gt_depth, sil_thres):
+    """int64 [2] on the device: [the pixels with !(final_opacity > sil_thres) and gt_depth > 0, the pixels with gt_depth > 0] of one
+    rendered view — the ~(presence_sil_mask | ~valid_depth_mask).sum() of eval_nvs (utils/eval_helpers.py:1726-1734) and the number of
+    valid-depth pixels.  A NaN opacity is a hole.  final_opacity / gt_depth: [1,H,W] or [H,W], float32.  Two small launches
+    (hsr_view_holes), no host synchronisation: count every view, read once."""
+    op = _dev(final_opacity, "final_opacity")
+    if op.dim() < 2:
+        raise RuntimeError("hsr_utils.evaluate: final_opacity must be [H,W] or [1,H,W] (got %s)" % (tuple(op.shape),))
+    H, W = (int(v) for v in op.shape[-2:])
+    op, gd = _plane(op, "final_opacity", H, W), _plane(gt_depth, "gt_depth", H, W)
+    dev = op.device
+    out = torch.empty(2, dtype=torch.int64, device=dev)
+    sc = torch.empty(int(_lib.hsr_view_holes_scratch_bytes(H, W)), dtype=torch.uint8, device=dev)
+    _abi.call(_lib.hsr_view_holes, "hsr_view_holes", dev, H, W, op.data_ptr(), gd.data_ptr(), float(sil_thres), out.data_ptr(), sc.data_ptr(),
+              sc.numel())
+    return out
+
+
+def view_percent_holes(holes, numel):
+    """(percent_holes float32, valid bool) from integer hole counts (an int or an integer array) and the pixel count of the frame, as
+    torch evaluates eval_nvs's `(~m).sum() / m.numel() * 100 > 0.1` (utils/eval_helpers.py:1734-1738): the int64 sum and numel become
+    float32, one float32 division, one float32 product with 100, and the comparison against 0.1 rounded to float32.  A view is valid
+    when percent_holes <= 0.1.  Host numpy."""
+    pct = np.asarray(holes, dtype=np.int64).astype(np.float32) / np.float32(numel) * np.float32(100)
+    return pct, ~(pct > VALID_MAX_PERCENT_HOLES)
+
+
+NVS_FILES = {"psnr": "psnr.txt", "depth_rmse": "rmse.txt", "depth_l1": "l1.txt", "ms_ssim": "ssim.txt"}
+
+
+def evaluate_novel_views(params, frames, cam, eval_dir=None, *, eval_every=1, sil_thres, mapping_iters, add_new_gaussians, save_frames=False,
+                         depth_table=None, depth_range=(0.0, 6.0), ms_ssim=True):
+    """The loop of eval_nvs (utils/eval_helpers.py:1648-1863; scripts/eval_novel_view.py): the finished map `params` rendered from
+    held-out poses and scored against their images.
+
+    frames: what the reference's NVS dataset delivers (hsr_utils.sequence.ReplicaV2Sequence(use_train_split=False) once ingested): any
+    iterable of dicts with 'im' [3,H,W], 'depth' [1,H,W] (float32, on the device) and 'gt_w2c' [4,4] relative to the first training
+    frame, read once and in order.  The FIRST item is the first training frame and is skipped (:1679-1685); the item at position i >= 1
+    is test view test_time_idx = i - 1, scored when test_time_idx == 0 or (test_time_idx + 1) % eval_every == 0 (:1688-1690).  A scored
+    view without 'gt_w2c' is a RuntimeError.  cam: the camera of the frames' size (setup_camera on the first frame's pose, :1683).
+
+    Per scored view: one slam.render_view call from gt_w2c with the plain rasterizer, whose depth and final opacity stand for the
+    reference's separate depth-and-silhouette render (as in evaluate_sequence); view_holes; frame_metrics and (with ms_ssim) ms_ssim,
+    with the silhouette mask only when mapping_iters == 0 and not add_new_gaussians (:1742-1773).  With save_frames (and eval_dir) one
+    hsr_utils.export.export_frame launch writes rendered_rgb/render_%04d.png, rendered_depth/render_%04d.png, rgb/gt_%04d.png and
+    depth/gt_%04d.png, numbered by test_time_idx (:1786-1796; depth_table, depth_range as export_frame's).
+
+    Scores and counts stay on the device and are read once after the last view.  A view is valid when percent_holes <= 0.1
+    (view_percent_holes, :1734-1738).  With eval_dir: psnr.txt, rmse.txt, l1.txt, ssim.txt (with ms_ssim) via np.savetxt, one row per
+    scored view, and valid_nvs_frames.npy.  Returns a dict: 'frame_ids' (the test_time_idx of the scored views), the arrays 'psnr',
+    'depth_l1', 'depth_rmse', 'ms_ssim' (float64), 'holes' and 'valid_depth' (int64, view_holes' two counts), 'percent_holes' (float32)
+    and 'valid_nvs_frames' (bool), and 'avg_psnr', ... the means over the VALID views only (:1820-1824): NaN when none is valid.
+
+    Not built: LPIPS (no weights here; lpips.txt is left out), the per-view plots, metrics.png and wandb."""
+    import os
+    from . import slam
+    if save_frames and eval_dir is None:
+        raise RuntimeError("hsr_utils.evaluate: save_frames needs eval_dir")
+    if int(eval_every) < 1:
+        raise ValueError("hsr_utils.evaluate: eval_every must be >= 1, not %r" % (eval_every,))
+    use_sil = int(mapping_iters) == 0 and not add_new_gaussians
+    dirs = {}
+    if eval_dir is not None:
+        os.makedirs(eval_dir, exist_ok=True)
+    if save_frames:
+        from . import export
+        for name in ("rendered_rgb", "rendered_depth", "rgb", "depth"):
+            dirs[name] = os.path.join(eval_dir, name)
+            os.makedirs(dirs[name], exist_ok=True)
+    keys = ["psnr", "depth_l1", "depth_rmse"] + (["ms_ssim"] if ms_ssim else [])
+    ids, rows, numel = [], [], []
+    for position, frame in enumerate(frames):
+        if position == 0:      # the first training frame: it fixes the camera in the reference and is not scored
+            continue
+        test_time_idx = position - 1
+        if test_time_idx != 0 and (test_time_idx + 1) % int(eval_every) != 0:
+            continue
+        if frame.get('gt_w2c') is None:
+            raise RuntimeError("hsr_utils.evaluate: novel view %d carries no 'gt_w2c'" % test_time_idx)
+        _rv, im, _radius, _sem, depth, opac = slam.render_view(params, frame['gt_w2c'], cam, False)
+        holes = view_holes(opac, frame['depth'], sil_thres)
+        op, thres = (opac, sil_thres) if use_sil else (None, None)
+        scores = list(frame_metrics(im, frame['im'], depth, frame['depth'], op, thres))
+        if ms_ssim:
+            scores.append(_ms_ssim(im, frame['im'], frame['depth'], op, thres))
+        ids.append(test_time_idx)
+        numel.append(int(opac.numel()))
+        rows.append(torch.cat([torch.stack(scores), holes.to(torch.float64)]))      # counts below 2^31 are exact in float64
+        if save_frames:
+            pictures = export.export_frame(im=im, gt_im=frame['im'], depth=depth, gt_depth=frame['depth'], depth_table=depth_table,
+                                           depth_range=depth_range)
+            for key, (sub, pattern) in dict(im=("rendered_rgb", "render_%04d.png"), depth=("rendered_depth", "render_%04d.png"),
+                                            gt_im=("rgb", "gt_%04d.png"), gt_depth=("depth", "gt_%04d.png")).items():
+                export.write_png(os.path.join(dirs[sub], pattern % test_time_idx), pictures[key])
+    if not rows:
+        raise RuntimeError("hsr_utils.evaluate: evaluate_novel_views got no view to score")
+    table = torch.stack(rows).cpu().numpy()      # the one read
+    result = {"frame_ids": ids}
+    for col, k in enumerate(keys):
+        result[k] = table[:, col].copy()
+    result["holes"] = table[:, len(keys)].astype(np.int64)
+    result["valid_depth"] = table[:, len(keys) + 1].astype(np.int64)
+    result["percent_holes"], valid = view_percent_holes(result["holes"], np.asarray(numel, dtype=np.int64))
+    result["valid_nvs_frames"] = valid
+    for k in keys:
+        result["avg_" + k] = float(result[k][valid].mean()) if valid.any() else float("nan")
+    if eval_dir is not None:
+        for k in keys:
+            np.savetxt(os.path.join(eval_dir, NVS_FILES[k]), result[k])
+        np.save(os.path.join(eval_dir, "valid_nvs_frames.npy"), valid)
+    return result
+
+
 __all__ = ["frame_metrics", "ms_ssim", "semantic_labels", "tree_levels", "tree_lookup_table", "iou_counts", "frame_miou", "evaluate_frame", "trajectory_ate",
-           "dilation_pixels", "evaluate_sequence"]
+           "dilation_pixels", "evaluate_sequence", "view_holes", "view_percent_holes", "evaluate_novel_views"]

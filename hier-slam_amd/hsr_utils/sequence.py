@@ -17,6 +17,15 @@ natsort's order.
         len(seq), seq[i] -> (color uint8 [H,W,3], depth uint16 [H,W], labels | None, gt_w2c float32 [4,4])
     tree_annotation(path, num_levels) -> (label_mapping_tree, num_semantic)
 
+the Replica-V2 layout of the same file's ReplicaV2Dataset (:439-514), whose second trajectory is the held-out split of the
+novel-view evaluation (hsr_utils.evaluate.evaluate_novel_views):
+
+    <basedir>/<sequence>/imap/00/rgb/rgb_*.png, depth/depth_*.png, traj_w_c.txt      the training trajectory
+    <basedir>/<sequence>/imap/01/...                                                 the test trajectory, same layout
+
+    ReplicaV2Sequence(basedir, sequence, use_train_split=True, start=0, end=-1, stride=1)
+        len(seq), seq[i] -> (color uint8 [H,W,3], depth uint16 [H,W], None, gt_w2c float32 [4,4])
+
 and the ScanNet layout of datasets/gradslam_datasets/scannet.py (:404-418, :114), whose three images have sizes of their own
 (hsr_utils.frames.ingest_frame_planes):
 
@@ -49,6 +58,21 @@ def _read_image(path):
         return np.asarray(im)
 
 
+def _pose_lines(path, count):
+    """the first `count` lines of a trajectory file as float64 [4,4] camera-to-world matrices, row by row"""
+    with open(path) as f:
+        lines = [ln for ln in f.read().splitlines() if ln.strip()]
+    if len(lines) < count:
+        raise RuntimeError("hsr_utils.sequence: %s has %d poses for %d frames" % (path, len(lines), count))
+    poses = []
+    for i in range(count):
+        values = [float(v) for v in lines[i].split()]
+        if len(values) != 16:
+            raise RuntimeError("hsr_utils.sequence: %s line %d has %d numbers, not 16" % (path, i + 1, len(values)))
+        poses.append(np.array(values, dtype=np.float64).reshape(4, 4))
+    return poses
+
+
 class ReplicaSequence:
     """The retained frames [start:end:stride] of one sequence (basedataset.py:176-190: end == -1 means all; start < 0 or an end that
     is neither -1 nor beyond start is a ValueError, as there).  seq[i] decodes frame i of the retained ones and returns raw host
@@ -65,16 +89,7 @@ class ReplicaSequence:
         depth = numeric_order(glob.glob(os.path.join(glob.escape(self.input_folder), "results", "depth*.png")))
         if not color or len(color) != len(depth):
             raise RuntimeError("hsr_utils.sequence: %s/results holds %d frame*.jpg and %d depth*.png files" % (self.input_folder, len(color), len(depth)))
-        with open(os.path.join(self.input_folder, "traj.txt")) as f:
-            lines = [ln for ln in f.read().splitlines() if ln.strip()]
-        if len(lines) < len(color):
-            raise RuntimeError("hsr_utils.sequence: traj.txt has %d poses for %d frames" % (len(lines), len(color)))
-        poses = []
-        for i in range(len(color)):
-            values = [float(v) for v in lines[i].split()]
-            if len(values) != 16:
-                raise RuntimeError("hsr_utils.sequence: traj.txt line %d has %d numbers, not 16" % (i + 1, len(values)))
-            poses.append(np.array(values, dtype=np.float64).reshape(4, 4))
+        poses = _pose_lines(os.path.join(self.input_folder, "traj.txt"), len(color))
         semantic = None
         if semantic_dir is not None:
             folder = os.path.join(semantic_dir, sequence)
@@ -117,6 +132,52 @@ class ReplicaSequence:
                 raise RuntimeError("hsr_utils.sequence: %s is not a one-channel integer image of the frame's size (%s %s)" % (
                     self.semantic_paths[i], labels.dtype, labels.shape))
         return np.ascontiguousarray(color), np.ascontiguousarray(depth), labels, self.gt_w2c(i)
+
+
+class ReplicaV2Sequence(ReplicaSequence):
+    """The retained frames [start:end:stride] of one Replica-V2 sequence, as the reference's ReplicaV2Dataset reads it
+    (datasets/gradslam_datasets/replica.py:439-514), in numeric_order:
+
+        use_train_split=True    <basedir>/<sequence>/imap/00/rgb/rgb_*.png, depth/depth_*.png and traj_w_c.txt (one line of 16 floats per
+                                frame: the camera-to-world matrix, row by row)
+        use_train_split=False   the same from imap/01, with the FIRST TRAINING FRAME (imap/00/rgb/rgb_0.png, depth/depth_0.png and line 1
+                                of imap/00/traj_w_c.txt) put in front (:483-486, :494-500): item 0 is that frame, item i >= 1 is test view
+                                i - 1, which is the order hsr_utils.evaluate.evaluate_novel_views reads.  [start:end:stride] is taken of
+                                that list, as the reference's base class does.
+
+    Items, checks and errors are ReplicaSequence's: raw host arrays (colour uint8 [H,W,3], depth uint16 [H,W], None for the labels,
+    which this layout does not have) and gt_w2c relative to the first RETAINED frame, inverse(inverse(c2w_first) @ c2w_i) in float64,
+    returned as float32 — for the test split with start=0 that is relative to the first training frame, the frame the map's poses are
+    relative to."""
+
+    def __init__(self, basedir, sequence, use_train_split=True, start=0, end=-1, stride=1):
+        start, end, stride = int(start), int(end), int(stride)
+        _check_range(start, end, stride)
+        self.use_train_split = bool(use_train_split)
+        train_folder = os.path.join(basedir, sequence, "imap", "00")
+        self.input_folder = train_folder if self.use_train_split else os.path.join(basedir, sequence, "imap", "01")
+        folder = glob.escape(self.input_folder)
+        color = numeric_order(glob.glob(os.path.join(folder, "rgb", "rgb_*.png")))
+        depth = numeric_order(glob.glob(os.path.join(folder, "depth", "depth_*.png")))
+        if not color or len(color) != len(depth):
+            raise RuntimeError("hsr_utils.sequence: %s holds %d rgb/rgb_*.png and %d depth/depth_*.png files" % (self.input_folder, len(color), len(depth)))
+        poses = _pose_lines(os.path.join(self.input_folder, "traj_w_c.txt"), len(color))
+        if not self.use_train_split:
+            first = (os.path.join(train_folder, "rgb", "rgb_0.png"), os.path.join(train_folder, "depth", "depth_0.png"))
+            for path in first:
+                if not os.path.exists(path):
+                    raise RuntimeError("hsr_utils.sequence: %s, the first training frame, is missing" % path)
+            color, depth = [first[0]] + color, [first[1]] + depth
+            poses = _pose_lines(os.path.join(train_folder, "traj_w_c.txt"), 1) + poses
+        stop = len(color) if end == -1 else end
+        pick = slice(start, stop, stride)
+        self.color_paths, self.depth_paths = color[pick], depth[pick]
+        self.semantic_paths = None
+        self.retained_inds = list(range(len(color)))[pick]
+        self.c2w = poses[pick]
+        if not self.color_paths:
+            raise RuntimeError("hsr_utils.sequence: no frame of %d left by start=%d, end=%d, stride=%d" % (len(color), start, end, stride))
+        self._first_inv = np.linalg.inv(self.c2w[0])
 
 
 def tree_annotation(path, num_levels):
@@ -289,4 +350,4 @@ def scannet_tree_annotation(tsv_path, num_levels, key_column):
     return tree, num_semantic
 
 
-__all__ = ["ReplicaSequence", "tree_annotation", "numeric_order", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation"]
+__all__ = ["ReplicaSequence", "ReplicaV2Sequence", "tree_annotation", "numeric_order", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation"]

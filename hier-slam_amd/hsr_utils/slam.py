@@ -8,6 +8,9 @@ from the device rows this package already has plus two 
     initialize_camera_pose(params, curr_time_idx, forward_prop)                :1354-1373
     update_poses(params, sliding_window_kf)                                    :57-70
     matrix_to_quaternion(matrix)                                               what the use_gt_poses branch needs (:1895-1904)
+    render_params(params, time_idx, cam, semantic, ...)                        the map from the estimated pose of a frame
+    render_view(params, w2c, cam, semantic)                                    the map from a given world-to-camera matrix (eval_nvs,
+                                                                               utils/eval_helpers.py:1692-1741; the viz scripts)
     is_keyframe(time_idx, num_frames, keyframe_every, gt_w2c=None)             the rule of :2108-2109
     SlamSession(config, intrinsics, first_frame_w2c, cam)                      the body of the frame loop, :1762-2124:
         step(frame)            pose seeding, track_frame, map_frame (every map_every frames), add_keyframe, in the reference's order;
@@ -309,6 +312,25 @@ def render_params(params, time_idx, cam, semantic, gaussians_grad=False, camera_
     return rv, im, radius, sem, depth, opac
 
 
+def render_view(params, w2c, cam, semantic):
+    """render_params with a world-to-camera matrix in place of time_idx: (rendervar, im, radius, semantic map | None, depth, final
+    opacity) of the map `params` seen from `w2c` ([4,4], relative to the first frame like the pose parameters; on the device or the
+    host, slam_helpers.transform_to_view) with camera `cam`, under torch.no_grad().  One hsr_view_prep launch in front of the
+    rasterizer; nothing of params['cam_unnorm_rots'] / ['cam_trans'] is read, so the view needs no pose column."""
+    from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic
+    from . import slam_helpers as SH
+    with torch.no_grad():
+        tg = SH.transform_to_view(params, w2c)
+        if semantic:
+            rv = SH.transformed_params2rendervar_semantic(params, tg)
+            im, radius, sem, depth, _median, opac = GaussianRasterizer_semantic(raster_settings=cam)(**rv)
+        else:
+            rv = SH.transformed_params2rendervar(params, tg)
+            im, radius, depth, _median, opac, _mask = GaussianRasterizer(raster_settings=cam)(**rv)
+            sem = None
+    return rv, im, radius, sem, depth, opac
+
+
 def _param_groups(params, lrs):
     """initialize_optimizer's groups (scripts/hierslam.py:411-417): one named group per parameter"""
     return [{'params': [v], 'name': k, 'lr': lrs[k]} for k, v in params.items()]
@@ -461,6 +483,14 @@ class SlamSession:
         """(im, depth, final opacity, semantic | None) of the map from the estimated pose of frame time_idx, without gradients"""
         with torch.no_grad():
             _rv, im, _radius, sem, depth, opac = self._render(time_idx, False, False)
+        return im, depth, opac, sem
+
+    def render_view(self, w2c):
+        """(im, depth, final opacity, semantic | None) of the map from the world-to-camera matrix `w2c` ([4,4], relative to the first
+        frame), without gradients: render() for a pose that is no frame's (module function render_view)"""
+        if self.params is None:
+            raise RuntimeError("hsr_utils.slam: render_view before the first frame: there is no map yet")
+        _rv, im, _radius, sem, depth, opac = render_view(self.params, w2c, self.cam, self.flag_use_semantic)
         return im, depth, opac, sem
 
     def _note_seen(self, rv, radius):
@@ -664,4 +694,4 @@ class SlamSession:
 
 
 __all__ = ["initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "is_mapping_frame",
-           "normalize_config", "map_init_frame", "resample_frame", "frame_w2c", "render_params", "SlamSession"]
+           "normalize_config", "map_init_frame", "resample_frame", "frame_w2c", "render_params", "render_view", "SlamSession"]

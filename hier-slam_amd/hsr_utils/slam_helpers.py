@@ -7,6 +7,10 @@ Mirror of the four caller-side helpers scripts/hierslam.py runs right before eve
     transformed_params2rendervar_semantic(params, transformed_gaussians)       utils/slam_helpers.py:195-219
     transformed_params2depthplussilhouette(params, w2c, transformed_gaussians) utils/slam_helpers.py:260-275
 
+and one entry of this package's own, for a view that is no column of the pose parameters (a held-out test pose, a viewer's camera):
+
+    transform_to_view(params, w2c)                                             utils/eval_helpers.py:1692-1712 (eval_nvs)
+
 Same names, arguments, dictionary keys, shapes and gradient flow (`gaussians_grad` / `camera_grad` detach exactly what
 the reference detaches).  In the reference each is a chain of small torch kernels (about 12 launches forward, 25
 backward, per iteration); here `transform_to_frame` returns a lazy dictionary and the `…2rendervar…` call that follows
@@ -205,6 +209,69 @@ def transform_to_frame(params, time_idx, gaussians_grad, camera_grad):
     """World -> camera frame for frame `time_idx` (slam_helpers.py:278-330).  Returns a dictionary with 'means3D' and
     'unnorm_rotations' (lazy, see TransformedGaussians)."""
     return TransformedGaussians(params, time_idx, gaussians_grad, camera_grad)
+
+
+def _view_matrix(w2c, dev):
+    """`w2c` as a float32 [4,4] tensor on `dev`: a device tensor as it is, a host tensor or array copied once without blocking"""
+    if not torch.is_tensor(w2c):
+        w2c = torch.as_tensor(w2c)
+    if w2c.dtype != torch.float32:
+        w2c = w2c.to(torch.float32)
+    if w2c.device != dev:
+        w2c = w2c.to(dev, non_blocking=True)
+    return w2c.detach().contiguous()
+
+
+class ViewGaussians(TransformedGaussians):
+    """What transform_to_view returns: TransformedGaussians with the world-to-camera matrix given instead of read from a pose column.
+    One hsr_view_prep launch (include/ext/hsr_view.h) per rendervar variant, without autograd: a novel view is never optimised."""
+
+    def __init__(self, params, w2c):
+        super().__init__(params, None, False, False)
+        self._w2c = w2c
+
+    def _run(self, rot_source, w2c=None):
+        if w2c is not None:
+            raise RuntimeError("hsr_utils.slam_helpers: transform_to_view has no depth-plus-silhouette colours; the depth and final "
+                               "opacity of a novel view come from the plain rasterizer (hsr_utils.slam.render_view)")
+        p = self._params
+        with torch.no_grad():
+            means3D = _dev_f32(p['means3D'].detach(), "means3D")
+            dev = means3D.device
+            unnorm_rotations = _dev_f32(p['unnorm_rotations'].detach(), "unnorm_rotations")
+            logit_opacities = _dev_f32(p['logit_opacities'].detach(), "logit_opacities")
+            log_scales = _dev_f32(p['log_scales'].detach(), "log_scales")
+            P = int(means3D.shape[0])
+            if means3D.dim() != 2 or means3D.shape[1] != 3:
+                raise RuntimeError("means3D must have dimensions (num_points, 3)")
+            if tuple(unnorm_rotations.shape) != (P, 4) or logit_opacities.numel() != P or log_scales.dim() != 2 or log_scales.shape[0] != P:
+                raise RuntimeError("unnorm_rotations [P,4], logit_opacities [P,1] and log_scales [P,1|3] must match means3D")
+            S = int(log_scales.shape[1])
+            self._w2c = view = _view_matrix(self._w2c, dev)      # kept: a second variant does not copy again
+            o = dict(dtype=torch.float32, device=dev)
+            out_means, out_tr, out_rot = torch.empty((P, 3), **o), torch.empty((P, 4), **o), torch.empty((P, 4), **o)
+            out_op, out_sc = torch.empty_like(logit_opacities), torch.empty((P, 3), **o)
+            _abi.call(_lib.hsr_view_prep, "hsr_view_prep", dev, P, S, int(S != 1), int(rot_source), _p(means3D), _p(unnorm_rotations),
+                      _p(logit_opacities), _p(log_scales), view.data_ptr(), _p(out_means), _p(out_tr), _p(out_rot), _p(out_op), _p(out_sc))
+        bundle = {"means3D": out_means, "unnorm_rotations": out_tr, "rotations": out_rot, "opacities": out_op, "scales": out_sc,
+                  "depth_sil": None, "rot_source": rot_source, "has_sil": False, "w2c_key": None}
+        if self._bundle is None:
+            self._bundle = bundle
+            dict.__setitem__(self, 'means3D', out_means)
+            dict.__setitem__(self, 'unnorm_rotations', out_tr)
+        return bundle
+
+
+def transform_to_view(params, w2c):
+    """World -> camera frame for a GIVEN world-to-camera matrix: what eval_nvs does per view (utils/eval_helpers.py:1692-1712) and the
+    viz scripts' get_rendervars(params, w2c, ...).  Returns the dictionary transform_to_frame returns ('means3D', 'unnorm_rotations',
+    lazy), which transformed_params2rendervar / _semantic take; computed by hsr_view_prep without autograd.  w2c: a [4,4] tensor or
+    array — a device tensor is used as it is (a pose computed on the device costs no copy), a host one is copied once without
+    blocking, another dtype is converted to float32.  Any other shape is a RuntimeError."""
+    shape = tuple(w2c.shape) if hasattr(w2c, "shape") else tuple(torch.as_tensor(w2c).shape)
+    if shape != (4, 4):
+        raise RuntimeError("hsr_utils.slam_helpers: w2c must be [4,4] (got %s)" % (shape,))
+    return ViewGaussians(params, w2c)
 
 
 def _bundle_of(params, transformed_gaussians, rot_source, w2c=None):
