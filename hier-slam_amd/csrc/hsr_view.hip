@@ -11,11 +11,11 @@
 // camera quaternion is computed by every thread from the 9 floats of the matrix (uniform loads, a few dozen VALU operations against
 // ~100 B of traffic).  Compiled with -ffp-contract=off: out_means3D feeds the rasterizer's integer decisions and must be bit-equal to
 // hsr_frame_prep_forward's for equal matrices.
+// The per-row arithmetic is csrc/hsr_view_row.h's view_row(), which hsr_replay.hip runs as well with a selected row's rank as the destination.
 // The hole counts are integers: a grid-stride pass with hsr_block.h's block sums, then a one-workgroup finish.
 #include "hsr_common.h"
 #include "hsr_block.h"
-#include "hsr_quat.h"
-#include "../../include/hsr_frame_prep.h"
+#include "hsr_view_row.h"
 #include "../../include/ext/hsr_view.h"
 
 namespace {
@@ -24,57 +24,13 @@ constexpr int VIEW_BLOCK = 256;
 constexpr int HOLES_ITEMS = 4;         // pixels per thread and grid pass
 constexpr int HOLES_MAX_BLOCKS = 96;   // workgroups of the pass: a frame of more than 96 * 1024 pixels takes further grid passes
 
-struct ViewArgs {
-    int P, S, transform_rots, rot_source;
-    const float *means3D, *unnorm_rotations, *logit_opacities, *log_scales, *w2c;
-};
-
-// F.normalize(matrix_to_quaternion(w2c[:3,:3])): hsr_utils/slam.py matrix_to_quaternion, then eval_helpers.py:1708
-__device__ __forceinline__ void view_quaternion(const float* __restrict__ m, float* q)
-{
-    const float m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[4], m11 = m[5], m12 = m[6], m20 = m[8], m21 = m[9], m22 = m[10];
-    const float p0 = ((1.0f + m00) + m11) + m22, p1 = ((1.0f + m00) - m11) - m22;
-    const float p2 = ((1.0f - m00) + m11) - m22, p3 = ((1.0f - m00) - m11) + m22;
-    // argmax: the largest pivot, the first on ties
-    float pv = p0;
-    float4 r = make_float4(p0, m21 - m12, m02 - m20, m10 - m01);
-    if (p1 > pv) { pv = p1; r = make_float4(m21 - m12, p1, m10 + m01, m02 + m20); }
-    if (p2 > pv) { pv = p2; r = make_float4(m02 - m20, m10 + m01, p2, m21 + m12); }
-    if (p3 > pv) { pv = p3; r = make_float4(m10 - m01, m02 + m20, m21 + m12, p3); }
-    const float d = 2.0f * sqrtf(fmaxf(pv, 1e-12f));
-    r = make_float4(r.x / d, r.y / d, r.z / d, r.w / d);
-    if (r.x < 0.0f) r = make_float4(-r.x, -r.y, -r.z, -r.w);
-    r = hsr_normalize4(r);
-    q[0] = r.x; q[1] = r.y; q[2] = r.z; q[3] = r.w;
-}
-
 __global__ __launch_bounds__(VIEW_BLOCK) void view_prep_kernel(ViewArgs a, float* __restrict__ out_means3D, float* __restrict__ out_unnorm_rot,
                                                                float* __restrict__ out_rotations, float* __restrict__ out_opacities,
                                                                float* __restrict__ out_scales)
 {
     const int p = blockIdx.x * VIEW_BLOCK + threadIdx.x;
     if (p >= a.P) return;
-    const float x0 = a.means3D[3 * p], x1 = a.means3D[3 * p + 1], x2 = a.means3D[3 * p + 2];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-        out_means3D[3 * p + i] = ((x0 * a.w2c[4 * i] + x1 * a.w2c[4 * i + 1]) + x2 * a.w2c[4 * i + 2]) + a.w2c[4 * i + 3];
-    const float4 u = reinterpret_cast<const float4*>(a.unnorm_rotations)[p];
-    float4 tr = u;
-    if (a.transform_rots) {
-        float q[4];
-        view_quaternion(a.w2c, q);
-        tr = hsr_quat_mult(q, hsr_normalize4(u));
-    }
-    if (out_unnorm_rot) reinterpret_cast<float4*>(out_unnorm_rot)[p] = tr;
-    reinterpret_cast<float4*>(out_rotations)[p] = hsr_normalize4(a.rot_source == HSR_PREP_ROT_PARAMS ? u : tr);
-    out_opacities[p] = 1.0f / (1.0f + expf(-a.logit_opacities[p]));
-    if (a.S == 1) {
-        const float e = expf(a.log_scales[p]);
-        out_scales[3 * p] = e; out_scales[3 * p + 1] = e; out_scales[3 * p + 2] = e;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 3; i++) out_scales[3 * p + i] = expf(a.log_scales[3 * p + i]);
-    }
+    view_row<false>(a, (size_t)p, (size_t)p, out_means3D, out_unnorm_rot, out_rotations, out_opacities, out_scales);   // hsr_view_row.h
 }
 
 // partials[2 b], partials[2 b + 1]: the holes and the valid-depth pixels workgroup b saw (each below 2^31: N is)

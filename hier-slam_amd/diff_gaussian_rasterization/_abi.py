@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES, SIGNATURES_EXT_MAP_EXPORT and SIGNATURES_EXT_VIEW against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES, SIGNATURES_EXT_MAP_EXPORT, SIGNATURES_EXT_VIEW and SIGNATURES_EXT_REPLAY against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -314,6 +314,22 @@ SIGNATURES_EXT_VIEW = (
                             vp, vp, sz, vp]),
 )
 
+# include/ext/hsr_replay.h: the map as it stood at step t and a view's point cloud; a table of its own like the rest
+SIGNATURES_EXT_REPLAY = (
+    ("hsr_replay_plan_scratch_bytes", sz, [ci, ci]),
+    ("hsr_replay_plan", ci, [ci, ci, vp, vp,
+                             vp, sz, vp]),
+    ("hsr_replay_select_scratch_bytes", sz, [ci]),
+    ("hsr_replay_select", ci, [ci, ci, ci, ci, ci, ci, ci,
+                               vp, vp, vp, vp,
+                               vp, vp, vp, vp,
+                               vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp,
+                               vp, sz, vp]),
+    ("hsr_replay_cloud", ci, [ci, ci, vp, vp, cf, cf, cf, cf,
+                              vp, vp, vp, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -324,7 +340,8 @@ def _load():
     loaded = C.CDLL(LIB_PATH)
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
                                     + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT
-                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT + SIGNATURES_EXT_VIEW):
+                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT + SIGNATURES_EXT_VIEW
+                                    + SIGNATURES_EXT_REPLAY):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

@@ -16,6 +16,8 @@ _SEQUENCE = ("ReplicaSequence", "tree_annotation", "ScanNetSequence", "scannet_c
 _EXPORT = ("export_frame", "jet_colormap", "label_colormap", "tuple_colour_table", "write_png")
 _MAP_EXPORT = ("export_map", "gaussian_tree_labels", "level_prefix_colour_table", "leaf_head_labels", "save_map_ply",
                "save_map_ply_semantic")
+_REPLAY = ("run_w2cs", "ReplayPlan", "replay_rendervars", "replay_view", "view_cloud", "save_cloud_ply", "follow_camera", "camera_centres",
+           "trajectory_lines", "replay_run")
 
 
 def __getattr__(name):
@@ -38,4 +40,7 @@ def __getattr__(name):
     if name in _MAP_EXPORT:      # and the map as PLY records
         from . import map_export
         return getattr(map_export, name)
+    if name in _REPLAY:          # and the replay of a finished run
+        from . import replay
+        return getattr(replay, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -18,6 +18,7 @@ from the device rows this package already has plus two 
         track_frame(frame)     :1808-1904      map_frame(frame)     :1927-2083      add_keyframe(frame)     :2107-2124
         tracking_data(frame)   :1792-1799      densify_data(frame)  :1933-1941      {'im', 'depth', 'cam', 'intrinsics'} at that size
         ingest(time_idx, color_u8, depth_raw, ...)      a frame dict for step() from the raw sensor images (hsr_utils.frames), one launch
+        replay(out_dir, ...)   the run so far as one picture per step, the map as it stood at each (hsr_utils.replay; the viz scripts)
 
 `config` is a dict with the reference's key names (configs/*/*.py): tracking / mapping (num_iters, lrs, loss_weights, sil_thres,
 use_sil_for_loss, use_l1, ignore_outlier_depth_loss; tracking: forward_prop, use_gt_poses, use_depth_loss_thres, depth_loss_thres;
@@ -674,6 +675,17 @@ class SlamSession:
         if self.params is None:
             raise RuntimeError("hsr_utils.slam: export_map before the first frame: there is no map yet")
         return map_export.save_map_ply(path, self.params, **kw)
+
+    def replay(self, out_dir, **kw):
+        """the run so far as one picture per step (and, with cloud=True, one point cloud): hsr_utils.replay.replay_run on the session's
+        own params and variables['timestep'], with its intrinsics and frame size; returns the list of steps written"""
+        from . import replay
+        if self.params is None:
+            raise RuntimeError("hsr_utils.slam: replay before the first frame: there is no map yet")
+        kw.setdefault('semantic', self.flag_use_semantic)
+        kw.setdefault('num_frames', len(self.gt_w2c_all_frames))
+        return replay.replay_run(self.params, out_dir, timestep=self.variables['timestep'], intrinsics=self.intrinsics,
+                                 width=self.cam.image_width, height=self.cam.image_height, **kw)
 
     def step(self, frame):
         """one pass of the frame loop (scripts/hierslam.py:1762-2124) for frame['id'] = the number of frames stepped so far"""
