@@ -157,6 +157,32 @@ bool hsr_bin_plan(int P, int T, size_t scratch_words, HsrBinPlan* plan);   // fa
 int hsr_launch_bin_count(const HsrBinPlan& plan, int P, const int* radii, int tiles_x, int tiles_y, GeomState& g, uint32_t* scratch,
                          uint2* ranges, hipStream_t stream, uint32_t* host_counter = nullptr, uint32_t host_seq = 0);
                          // per-tile counts; produces num_rendered (counters[0]; also {value, seq} into host-mapped memory)
+// Order in which bin_scan_kernel sums the nblk rows of the count table (row b = workgroup b of bin_hist / bin_emit): the k-th row of
+// "all rows with b mod 8 = 0 ascending, then b mod 8 = 1, ... then 7".  With q = nblk / 8 and r = nblk mod 8, class c has q + (c < r)
+// rows; for nblk < 8 it is the identity.  Workgroups are dealt round-robin over the eight XCDs, so a class is what ONE L2 writes: a tile
+// segment becomes eight sub-segments, each filled through one L2 (hsr_preprocess.hip, above bin_hist_kernel).  Speed only: any
+// bijection gives the same sorted lists.
+__host__ __device__ inline int hsr_bin_row_of(int k, int nblk)
+{
+    if (nblk < 8) return k;
+    const int q = nblk >> 3, r = nblk & 7;
+    const int big = r * (q + 1);   // the logical positions of the r classes that hold q + 1 rows
+    if (k < big) {
+        const int c = k / (q + 1);
+        return 8 * (k - c * (q + 1)) + c;
+    }
+    const int m = k - big, c = m / q;
+    return 8 * (m - c * q) + r + c;
+}
+// the row after row b in that order (b is not the last one): hsr_bin_row_of(k + 1) from hsr_bin_row_of(k) without the divisions
+__host__ __device__ inline int hsr_bin_row_next(int b, int nblk) { return b + 8 < nblk ? b + 8 : (b & 7) + 1; }
+// bin_scan_kernel, workgroup w of a grid of n -> its block of 16 tiles (64 bytes of every table row).  Two neighbouring blocks share
+// each 128-byte line; inside a group of sixteen workgroups they go to w and w + 8, which one XCD runs.  The ragged last group keeps w.
+__host__ __device__ inline int hsr_bin_scan_block_of(int w, int n)
+{
+    if ((w | 15) >= n) return w;
+    return (w & ~15) + 2 * (w & 7) + ((w >> 3) & 1);
+}
 int hsr_launch_bin_emit(const HsrBinPlan& plan, int P, const int* radii, int tiles_x, int tiles_y, GeomState& g, const uint32_t* scratch,
                         uint2* ranges, uint64_t* comp, hipStream_t stream, const BinDevRef* ref = nullptr);
                         // tile ranges; (depth, index) composites into the tile segments
