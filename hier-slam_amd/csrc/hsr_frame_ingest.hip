@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_ingest_expr.h"
 #include "../../include/hsr_eval.h"
 #include "../../include/ext/hsr_frame_resample.h"
 #include "../../include/ext/hsr_frame_ingest.h"
@@ -79,12 +80,11 @@ __global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ 
         const double top = a + fx * (b - a);
         const double bot = c + fx * (d - c);
         const double v = top + fy * (bot - top);
-        // float(v) / 255.0f through double: the double quotient of two floats rounds to the correctly rounded fp32 quotient
-        oc[ch * dplane + (size_t)i] = (float)((double)(float)v / 255.0);
+        oc[ch * dplane + (size_t)i] = hsr_ingest_colour((float)v);      // float(v) / 255.0f (hsr_ingest_expr.h)
     }
     // nearest, each image from its own size: products < 2^28; xs <= W_src - 1, ys <= H_src - 1
     const size_t sd = (size_t)((y * src.Hd) / Hd) * src.Wd + (x * src.Wd) / Wd;
-    od[i] = (float)(raw_depth<DT>(depth, sd) / depth_scale);
+    od[i] = hsr_ingest_depth(raw_depth<DT>(depth, sd), depth_scale);
     if (k == 0 && out_labels) {
         const size_t sl = (size_t)((y * src.Hl) / Hd) * src.Wl + (x * src.Wl) / Wd;
         const int id = labels[sl];

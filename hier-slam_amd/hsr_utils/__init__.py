@@ -18,6 +18,7 @@ _MAP_EXPORT = ("export_map", "gaussian_tree_labels", "level_prefix_colour_table"
                "save_map_ply_semantic")
 _REPLAY = ("run_w2cs", "ReplayPlan", "replay_rendervars", "replay_view", "view_cloud", "save_cloud_ply", "follow_camera", "camera_centres",
            "trajectory_lines", "replay_run")
+_CHECKPOINT = ("PackedKeyframe", "pack_keyframe", "unpack_keyframe", "save_checkpoint", "load_checkpoint")
 
 
 def __getattr__(name):
@@ -43,4 +44,7 @@ def __getattr__(name):
     if name in _REPLAY:          # and the replay of a finished run
         from . import replay
         return getattr(replay, name)
+    if name in _CHECKPOINT:      # and the packed keyframe store with a session's checkpoint and resume
+        from . import checkpoint
+        return getattr(checkpoint, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

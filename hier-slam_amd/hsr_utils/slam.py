@@ -12,13 +12,14 @@ from the device rows this package already has plus two 
     render_view(params, w2c, cam, semantic)                                    the map from a given world-to-camera matrix (eval_nvs,
                                                                                utils/eval_helpers.py:1692-1741; the viz scripts)
     is_keyframe(time_idx, num_frames, keyframe_every, gt_w2c=None)             the rule of :2108-2109
-    SlamSession(config, intrinsics, first_frame_w2c, cam)                      the body of the frame loop, :1762-2124:
+    SlamSession(config, intrinsics, first_frame_w2c, cam, *, keyframe_store="raw")      the body of the frame loop, :1762-2124:
         step(frame)            pose seeding, track_frame, map_frame (every map_every frames), add_keyframe, in the reference's order;
                                the first call (frame id 0) builds the map from the frame and maps it without densification
         track_frame(frame)     :1808-1904      map_frame(frame)     :1927-2083      add_keyframe(frame)     :2107-2124
         tracking_data(frame)   :1792-1799      densify_data(frame)  :1933-1941      {'im', 'depth', 'cam', 'intrinsics'} at that size
         ingest(time_idx, color_u8, depth_raw, ...)      a frame dict for step() from the raw sensor images (hsr_utils.frames), one launch
         replay(out_dir, ...)   the run so far as one picture per step, the map as it stood at each (hsr_utils.replay; the viz scripts)
+        save_checkpoint(directory) / load_checkpoint(directory, time_idx, frames=None)      :2128-2133 / :1716-1752 (hsr_utils.checkpoint)
 
 `config` is a dict with the reference's key names (configs/*/*.py): tracking / mapping (num_iters, lrs, loss_weights, sil_thres,
 use_sil_for_loss, use_l1, ignore_outlier_depth_loss; tracking: forward_prop, use_gt_poses, use_depth_loss_thres, depth_loss_thres;
@@ -50,9 +51,18 @@ A frame is a dict: 'id' (its time index), 'im' [3,H,W] in 0..1, 'depth' [1,H,W],
 (relative to frame 0; read by use_gt_poses and by the keyframe rule's validity test), 'semantic_label_gt' [levels (+1 leaf),H,W] and
 the four reduced tensors named above.  A frame dict is never modified.
 
-No dataset code, no logging service, no plotting, no checkpoint resume.  There is no CPU path for anything that renders; the pose seeding,
+SlamSession(..., keyframe_store="packed") keeps every keyframe as 8-/16-bit codes where those reproduce it bit for bit (a frame from
+ingest() at sensor size: 15 instead of 56 bytes per pixel with 5 label planes) and unpacks the members of a mapping window once per
+map_frame; save_checkpoint(directory) / load_checkpoint(directory, time_idx) write and resume a run (hsr_utils.checkpoint: the
+reference's params{t}.npz and keyframe_time_indices{t}.npy, :2128-2133, plus session{t}.npz with the keyframes in that form, the
+bookkeeping, the leaf head's Adam state and the random streams); step() saves when config['save_checkpoints'] is set, every
+config['checkpoint_interval'] frames, into config['workdir'] / config['run_name'].
+
+No dataset code, no logging service, no plotting.  There is no CPU path for anything that renders; the pose seeding,
 the keyframe rule and the config handling are plain torch / Python and run anywhere.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -289,6 +299,11 @@ def normalize_config(config):
         raise KeyError("config['num_semantic_class']")
     if int(cfg['mapping_window_size']) < 2:
         raise ValueError("mapping_window_size counts the last keyframe and the current frame: at least 2")
+    cfg.setdefault('save_checkpoints', False)      # :2128-2133
+    if cfg['save_checkpoints']:
+        for key in ('checkpoint_interval', 'workdir', 'run_name'):
+            if key not in cfg:
+                raise KeyError("config['%s']" % key)
     return cfg
 
 
@@ -343,7 +358,10 @@ class SlamSession:
     `keyframe_time_indices`, `gt_w2c_all_frames`, `optimizer` (the last one built), `last_window` = (selected_time_idx,
     selected_keyframes) of the last mapping step, `num_tracking_iters` of the last tracked frame."""
 
-    def __init__(self, config, intrinsics, first_frame_w2c, cam):
+    def __init__(self, config, intrinsics, first_frame_w2c, cam, *, keyframe_store="raw"):
+        if keyframe_store not in ("raw", "packed"):
+            raise ValueError("hsr_utils.slam: keyframe_store must be \"raw\" or \"packed\", not %r" % (keyframe_store,))
+        self.keyframe_store = keyframe_store
         self.config = normalize_config(config)
         self.intrinsics, self.first_frame_w2c, self.cam = intrinsics, first_frame_w2c, cam
         self.num_frames = int(self.config['num_frames'])
@@ -416,6 +434,12 @@ class SlamSession:
         im, depth = self._level_data(frame)['densify']
         return {'im': im, 'depth': depth, 'cam': self.densify_cam, 'intrinsics': self.densify_intrinsics}
 
+    def _png_depth_scale(self):
+        """config['png_depth_scale'], else config['data']['png_depth_scale'], else None"""
+        cfg = self.config
+        data = cfg.get('data') or {}
+        return cfg['png_depth_scale'] if 'png_depth_scale' in cfg else data.get('png_depth_scale')
+
     def ingest(self, time_idx, color_u8, depth_raw, gt_w2c=None, labels=None, tree_table=None, png_depth_scale=None, leaf_column=False):
         """A frame dict for step() from the raw sensor images (hsr_utils.frames.ingest_frame; basedataset.py:223-227, :248-256,
         replica.py:241-299, scripts/hierslam.py:1777): 'id', 'im' and 'depth' at cam.image_height x cam.image_width, 'gt_w2c' and
@@ -428,13 +452,8 @@ class SlamSession:
         goes through frames.ingest_frame_planes instead: still one launch, each image resampled once per size from its own."""
         from . import frames
         if png_depth_scale is None:
-            cfg = self.config
-            data = cfg.get('data') or {}
-            if 'png_depth_scale' in cfg:
-                png_depth_scale = cfg['png_depth_scale']
-            elif 'png_depth_scale' in data:
-                png_depth_scale = data['png_depth_scale']
-            else:
+            png_depth_scale = self._png_depth_scale()
+            if png_depth_scale is None:
                 raise KeyError("config['data']['png_depth_scale']")
         sizes, uses = [(self.cam.image_height, self.cam.image_width)], {}
         for use, cam in (('tracking', self.tracking_cam), ('densify', self.densify_cam)):
@@ -623,6 +642,10 @@ class SlamSession:
         self.last_window = (list(selected_time_idx), list(selected_keyframes))
         self.optimizer = optimizer = optim.Adam(_param_groups(self.params, mp['lrs']), lr=0.0, eps=1e-15)
         gs_densify = bool(mp['use_gaussian_splatting_densification'])
+        unpacked = {}      # the packed store: each member of the window unpacked once (at most mapping_window_size - 1 launches), dropped on return
+        if self.keyframe_store == "packed":
+            from . import checkpoint
+            unpacked = {pick: checkpoint.unpack_keyframe(self.keyframe_list[pick]['packed']) for pick in set(selected_keyframes) if pick != -1}
         for it in range(int(mp['num_iters'])):
             pick = selected_keyframes[np.random.randint(0, len(selected_keyframes))]
             if pick == -1:
@@ -631,7 +654,10 @@ class SlamSession:
             else:
                 kf = self.keyframe_list[pick]
                 iter_time_idx = kf['id']
-                data = {'im': kf['color'], 'depth': kf['depth'], 'semantic_label_gt': kf.get('label_gt')}
+                if pick in unpacked:
+                    data = dict(zip(('im', 'depth', 'semantic_label_gt'), unpacked[pick]))
+                else:
+                    data = {'im': kf['color'], 'depth': kf['depth'], 'semantic_label_gt': kf.get('label_gt')}
             rv, im, radius, sem, depth, _opac = self._render(iter_time_idx, gaussians_grad=True, camera_grad=False, retain_means2D=gs_densify)
             loss = self._mapping_loss(data, im, sem, depth, it)
             self._note_seen(rv, radius)
@@ -653,10 +679,21 @@ class SlamSession:
         time_idx = int(frame['id'])
         if not is_keyframe(time_idx, self.num_frames, int(self.config['keyframe_every']), frame.get('gt_w2c')):
             return False
-        kf = {'id': time_idx, 'est_w2c': frame_w2c(self.params, time_idx), 'color': frame['im'], 'depth': frame['depth'], 'cam': self.cam,
-              'intrinsics': self.intrinsics}
-        if self.flag_use_semantic:
-            kf['label_gt'] = frame.get('semantic_label_gt')
+        if self.keyframe_store == "packed":
+            # 'packed' in place of 'color' / 'depth' / 'label_gt' (hsr_utils.checkpoint): one launch, no host read; the counts of the
+            # keyframes before this one have long arrived, and reading them lets go of the planes their codes reproduce
+            from . import checkpoint
+            for earlier in self.keyframe_list:
+                earlier['packed'].resolve()
+            labels = frame.get('semantic_label_gt') if self.flag_use_semantic else None
+            kf = {'id': time_idx, 'est_w2c': frame_w2c(self.params, time_idx),
+                  'packed': checkpoint.pack_keyframe(frame['im'], frame['depth'], labels, self._png_depth_scale()), 'cam': self.cam,
+                  'intrinsics': self.intrinsics}
+        else:
+            kf = {'id': time_idx, 'est_w2c': frame_w2c(self.params, time_idx), 'color': frame['im'], 'depth': frame['depth'], 'cam': self.cam,
+                  'intrinsics': self.intrinsics}
+            if self.flag_use_semantic:
+                kf['label_gt'] = frame.get('semantic_label_gt')
         self.keyframe_list.append(kf)
         self.keyframe_time_indices.append(time_idx)
         return True
@@ -703,6 +740,23 @@ class SlamSession:
         if is_mapping_frame(time_idx, int(self.config['map_every'])):
             self.map_frame(frame)
         self.add_keyframe(frame)
+        cfg = self.config
+        if cfg['save_checkpoints'] and time_idx % int(cfg['checkpoint_interval']) == 0:      # :2128-2133
+            self.save_checkpoint(os.path.join(cfg['workdir'], cfg['run_name']), time_idx)
+
+    # -- checkpoint and resume --
+    def save_checkpoint(self, directory, time_idx=None):
+        """params{t}.npz and keyframe_time_indices{t}.npy as the reference writes them (:2128-2133) and session{t}.npz with the rest of
+        the session, into `directory` (hsr_utils.checkpoint.save_checkpoint); t is the last frame stepped.  Returns the three paths."""
+        from . import checkpoint
+        return checkpoint.save_checkpoint(self, directory, time_idx)
+
+    def load_checkpoint(self, directory, time_idx, frames=None):
+        """Resume this freshly constructed session from the checkpoint of frame time_idx in `directory`
+        (hsr_utils.checkpoint.load_checkpoint); returns the id of the frame the next step() takes: time_idx + 1, or time_idx for a
+        checkpoint of the reference's own kind (no session{t}.npz; frames(i) must then supply the frame dicts)."""
+        from . import checkpoint
+        return checkpoint.load_checkpoint(self, directory, time_idx, frames)
 
 
 __all__ = ["initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "is_mapping_frame",
