@@ -1,7 +1,9 @@
 // hsr_densify.hip — silhouette densification of one mapped frame on device (gfx950), SURVEY.md §8(f) rank 3.
 // See include/hsr_densify.h for the reference lines (scripts/hierslam.py:1264-1305, :144-194, :1157).
 //   median : 4 x (select_hist_kernel -> select_pick_kernel): 8-bit radix select, most significant byte first, of the rank
-//            (N-1)/2 element of depth_error's bit patterns (torch.median = lower median);
+//            (N-1)/2 element of depth_error's bit patterns (torch.median = lower median); the first histogram pass also counts
+//            the NaN errors, and with one or more of them the last pick leaves NaN (torch.median's rule), which empties the
+//            depth part of the mask;
 //   mask   : mask_count_kernel — the non-presence mask + one count per 256-pixel block;
 //   scan   : scan_counts_kernel — one workgroup, exclusive scan of the block counts, total -> out_count;
 //   emit   : emit_points_kernel — order-preserving compaction (block offset + wave ballot rank), back-projection, colours,
@@ -14,29 +16,35 @@ namespace {
 
 constexpr int DB = 256;
 
-struct SelectState { unsigned prefix, mask, rank; };   // device scratch: bits fixed so far, their mask, remaining rank
+// device scratch: bits fixed so far, their mask, remaining rank, the number of NaN errors (torch.median: any NaN -> NaN)
+struct SelectState { unsigned prefix, mask, rank, nan; };
 
 __global__ __launch_bounds__(DB) void select_init_kernel(SelectState* st, int N, unsigned* hist)
 {
-    if (threadIdx.x == 0) { st->prefix = 0u; st->mask = 0u; st->rank = (unsigned)((N - 1) / 2); }
+    if (threadIdx.x == 0) { st->prefix = 0u; st->mask = 0u; st->rank = (unsigned)((N - 1) / 2); st->nan = 0u; }
     hist[threadIdx.x] = 0u;
 }
 
 // histogram of byte `shift` among the elements whose already-fixed bits equal the prefix
 __global__ __launch_bounds__(DB) void select_hist_kernel(const float* __restrict__ gt, const float* __restrict__ rd, int N, int shift,
-                                                         const SelectState* __restrict__ st, unsigned* __restrict__ hist)
+                                                         SelectState* __restrict__ st, unsigned* __restrict__ hist)
 {
     __shared__ unsigned s_h[256];
+    __shared__ unsigned s_nan;
     s_h[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) s_nan = 0u;
     __syncthreads();
     const unsigned prefix = st->prefix, mask = st->mask;
     for (int i = blockIdx.x * DB * 8 + threadIdx.x, it = 0; it < 8; it++, i += DB) {
         if (i >= N) break;
-        const unsigned bits = __float_as_uint(hsr_depth_error(gt[i], rd[i]));
+        const float e = hsr_depth_error(gt[i], rd[i]);
+        const unsigned bits = __float_as_uint(e);
         if ((bits & mask) == prefix) atomicAdd(&s_h[(bits >> shift) & 255u], 1u);
+        if (shift == 24 && e != e) atomicAdd(&s_nan, 1u);   // counted once, in the first pass; st->nan is read by the last pick only
     }
     __syncthreads();
     if (s_h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], s_h[threadIdx.x]);   // integer atomics: order-independent
+    if (threadIdx.x == 0 && s_nan) atomicAdd(&st->nan, s_nan);
 }
 
 __global__ __launch_bounds__(DB) void select_pick_kernel(SelectState* st, unsigned* hist, int shift, float* out_median)
@@ -51,10 +59,12 @@ __global__ __launch_bounds__(DB) void select_pick_kernel(SelectState* st, unsign
         if (rank < s_h[d]) break;
         rank -= s_h[d];
     }
-    st->prefix |= d << shift;
+    unsigned prefix = st->prefix | (d << shift);
+    if (shift == 0 && st->nan) prefix = 0x7fc00000u;   // the mask and emit kernels read the median from st->prefix: NaN * factor is NaN
+    st->prefix = prefix;
     st->mask |= 255u << shift;
     st->rank = rank;
-    if (shift == 0 && out_median) *out_median = __uint_as_float(st->prefix);
+    if (shift == 0 && out_median) *out_median = __uint_as_float(prefix);
 }
 
 __device__ __forceinline__ bool non_presence(float sil, float rd, float gt, float sil_thres, float thr)
@@ -124,8 +134,11 @@ __global__ __launch_bounds__(DB) void prune_mask_kernel(int P, int S, const floa
         bool rem = sg < thr;
         if (big > 0.f && lscale) {
             float m = expf(lscale[(size_t)i * S]);
-            for (int c = 1; c < S; c++) m = fmaxf(m, expf(lscale[(size_t)i * S + c]));
-            rem = rem || (m > big);
+            for (int c = 1; c < S; c++) {   // torch's max(dim=1): a NaN column makes the maximum NaN (fmaxf would drop it)
+                const float v = expf(lscale[(size_t)i * S + c]);
+                m = (v > m || v != v) ? v : m;
+            }
+            rem = rem || (m > big);         // NaN > big is false: such a row is not removed for its size
         }
         k = !rem;
         keep[i] = k ? 1 : 0;

@@ -12,7 +12,11 @@
  * (row-major pixel order, exactly what `point_cld[mask]` yields) instead of a global sort for the median, full-frame point
  * clouds, boolean-mask gathers and their temporaries.
  * torch.median's definition is kept: the LOWER median, element (N-1)/2 of the sorted N values (zeros of invalid pixels
- * included), found by a 4-pass radix select on the float bit patterns (non-negative finite values order like unsigned ints).
+ * included), found by a 4-pass radix select on the float bit patterns.  depth_error is |x| * (0 or 1): never negative, never -0,
+ * so the bit patterns of all its values other than NaN, denormals and +inf included, order like unsigned ints.  A NaN error (a NaN
+ * render_depth or gt_depth, or an infinite render_depth over a hole: inf * 0) makes the median NaN, as torch.median does: the first
+ * pass counts the NaN errors and the last one writes NaN if there were any.  50 * NaN is NaN and no error is greater than it, so the
+ * depth part of the mask is then empty and only `silhouette < sil_thres` selects.  out_median reports the same value.
  * The Parameter / optimizer-state concatenation (:1297-1304, utils/slam_external.py:121-137) stays in torch: it is
  * bookkeeping on torch objects.
  *
@@ -60,7 +64,9 @@ typedef struct hsr_row_table {
 size_t hsr_compact_scratch_bytes(int P);
 
 /* out_keep: uint8[P] (1 = keep); out_kept: int[1].  log_scales is [P,S] (S = 1 isotropic, 3 anisotropic);
- * big_world_threshold <= 0 switches the size test off (iter < remove_big_after).  `scratch` afterwards holds the scanned block
+ * big_world_threshold <= 0 switches the size test off (iter < remove_big_after).  Both comparisons are strict and false on a NaN,
+ * and the maximum over the S columns is torch's: NaN if any column is NaN (so a row with a NaN logit, or with a NaN log-scale beside a
+ * large one, is kept, as the reference keeps it).  `scratch` afterwards holds the scanned block
  * counts hsr_compact_append_rows needs: pass the same scratch and keep_is_scanned = 1. */
 int hsr_prune_mask(int P, int S, const float* logit_opacities, const float* log_scales, float removal_opacity_threshold,
                    float big_world_threshold, uint8_t* out_keep, int* out_kept, char* scratch, size_t scratch_bytes, void* stream);

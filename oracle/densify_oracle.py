@@ -14,8 +14,10 @@ def non_presence_points(silhouette, render_depth, gt_depth, color, intrinsics, c
     f = lambda a: np.asarray(a, dtype=dtype)
     sil, rd, gt, col = f(silhouette), f(render_depth), f(gt_depth), f(color)
     H, W = gt.shape
-    derr = np.abs(gt - rd) * (gt > 0)
-    med = np.sort(derr.reshape(-1))[(derr.size - 1) // 2]            # torch.median: the lower median
+    with np.errstate(invalid="ignore"):                              # inf * 0 is the NaN the reference gets too
+        derr = np.abs(gt - rd) * (gt > 0)
+    # torch.median: NaN if any error is NaN, otherwise the lower median (rank (n - 1) // 2)
+    med = dtype(np.nan) if np.isnan(derr).any() else np.sort(derr.reshape(-1))[(derr.size - 1) // 2]
     mask = (sil < dtype(sil_thres)) | ((rd > gt) & (derr > dtype(depth_factor) * med))
     mask = (mask & (gt > 0)).reshape(-1)
     K = f(intrinsics)

@@ -30,11 +30,12 @@ def make_frame(H, W, seed=0, hole=True):
     return sil, rd, gt, col, K, w2c
 
 
-def torch_reference(sil, rd, gt, col, K, w2c, sil_thres):
-    """the reference's expressions on CPU tensors"""
-    sil, rd, gt, col, K, w2c = map(torch.tensor, (sil, rd, gt, col, K, w2c))
+def torch_reference(sil, rd, gt, col, K, w2c, sil_thres, depth_factor=50, full=False):
+    """the reference's expressions on CPU tensors.  depth_factor: the reference's literal 50, or another value at its place.  full: a dict
+    that also holds the median and the threshold as torch computes them (0-dim fp32 tensors: their bits, a NaN as NaN) and the depth error"""
+    sil, rd, gt, col, K, w2c = map(torch.as_tensor, (sil, rd, gt, col, K, w2c))
     depth_error = torch.abs(gt - rd) * (gt > 0)
-    mask = (sil < sil_thres) | ((rd > gt) * (depth_error > 50 * depth_error.median()))
+    mask = (sil < sil_thres) | ((rd > gt) * (depth_error > depth_factor * depth_error.median()))
     mask = mask.reshape(-1) & (gt > 0).reshape(-1)
     H, W = gt.shape
     xg, yg = torch.meshgrid(torch.arange(W).float(), torch.arange(H).float(), indexing='xy')
@@ -44,6 +45,10 @@ def torch_reference(sil, rd, gt, col, K, w2c, sil_thres):
     pts = (torch.inverse(w2c) @ pts4.T).T[:, :3]
     msd = (z / ((K[0][0] + K[1][1]) / 2)) ** 2
     cols = torch.permute(col, (1, 2, 0)).reshape(-1, 3)
+    if full:
+        median = depth_error.median()
+        return {"mask": mask, "median": median, "threshold": depth_factor * median, "depth_error": depth_error, "means3D": pts[mask],
+                "rgb": cols[mask], "mean3_sq_dist": msd[mask], "log_scales": torch.log(torch.sqrt(msd[mask]))}
     return mask.numpy(), float(depth_error.median()), pts[mask].numpy(), cols[mask].numpy(), msd[mask].numpy()
 
 

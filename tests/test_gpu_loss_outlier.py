@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import outlier_ref as R
+from depth_error_cases import CASES, _DEN, _from_errors, _noisy, _small, _with      # noqa: F401  (the builders and the table live there, shared with the densify select's suite)
 from test_gpu_losses import VAL_TOL
 
 pytestmark = pytest.mark.gpu
@@ -28,82 +29,6 @@ SIL_THRES = 0.6
 NAN, INF = float("nan"), float("inf")
 
 
-def _noisy(H, W, seed, holes=0.1, outliers=0.05):
-    """gt depth 0.5..5 m with holes, a rendered depth = gt + Gaussian noise (sigma 1 cm), `outliers` of the pixels 50 times noisier"""
-    g = torch.Generator().manual_seed(seed)
-    gt = 0.5 + 4.5 * torch.rand(H, W, generator=g)
-    noise = 0.01 * torch.randn(H, W, generator=g)
-    noise = torch.where(torch.rand(H, W, generator=g) < outliers, 50 * noise, noise)
-    depth = gt + noise
-    gt = torch.where(torch.rand(H, W, generator=g) < holes, torch.zeros(()), gt)
-    return depth, gt
-
-
-def _from_errors(errors, shape, holes=0, seed=0, hole_depth=1.0):
-    """depth 0 and gt = the given errors (so that e = gt exactly), shuffled, then `holes` pixels of gt = 0 under a depth of hole_depth"""
-    g = torch.Generator().manual_seed(seed)
-    e = torch.as_tensor(errors, dtype=torch.float32)
-    n = shape[0] * shape[1]
-    assert e.numel() + holes == n
-    gt = torch.cat([e, torch.zeros(holes)])
-    depth = torch.cat([torch.zeros(e.numel()), torch.full((holes,), hole_depth)])
-    perm = torch.randperm(n, generator=g)
-    return depth[perm].reshape(shape).contiguous(), gt[perm].reshape(shape).contiguous()
-
-
-def _with(pair, **cells):
-    """a case with single cells replaced: d_IJ = value / g_IJ = value for depth / gt at row I, column J"""
-    depth, gt = pair[0].clone(), pair[1].clone()
-    for key, v in cells.items():
-        t = depth if key[0] == "d" else gt
-        i, j = (int(x) for x in key[2:].split("_"))
-        t[i, j] = v
-    return depth, gt
-
-
-def _small():      # 3 x 5, every pixel valid, errors 0.1 .. 1.5
-    gt = torch.arange(1, 16, dtype=torch.float32).reshape(3, 5) * 0.25 + 1.0
-    return gt - 0.1 * torch.arange(1, 16, dtype=torch.float32).reshape(3, 5), gt
-
-
-_DEN = 2.0 ** -149      # the smallest fp32 denormal
-CASES = {
-    # one pixel: selected; a hole: median 0, nothing is < 0, the mean of nothing is NaN
-    "1x1_valid": lambda: (torch.tensor([[1.5]]), torch.tensor([[2.0]])),
-    "1x1_hole": lambda: (torch.tensor([[1.5]]), torch.tensor([[0.0]])),
-    # e = {1, 20}: the lower median 1 selects one pixel, an upper median would select both; the same on 2 x 2
-    "1x2_lower_median": lambda: (torch.zeros(1, 2), torch.tensor([[1.0, 20.0]])),
-    "2x2_lower_median": lambda: (torch.zeros(2, 2), torch.tensor([[1.0, 20.0], [20.0, 1.0]])),
-    # n = 35, rank 17: 18 zeros reach it (median 0, empty selection); 17 do not (the smallest positive error, 0.05, is the median)
-    "5x7_18_holes": lambda: _from_errors([0.05 + 0.07 * k for k in range(17)], (5, 7), holes=18, seed=1),
-    "5x7_17_holes": lambda: _from_errors([0.05 + 0.07 * k for k in range(18)], (5, 7), holes=17, seed=2),
-    # every valid pixel has the error 0.5 (2.0 - 1.5, exact): all of them are selected
-    "equal_errors": lambda: (torch.full((9, 13), 1.5), torch.where(torch.arange(117).reshape(9, 13) % 4 == 0, 0.0, 2.0)),
-    # keys that differ only in the bits of the last pass (9..0), and only in those of the middle pass (20..10)
-    "32x32_last_pass": lambda: _from_errors([1.0 + k * 2.0 ** -23 for k in range(1024)], (32, 32), seed=3),
-    "32x32_middle_pass": lambda: _from_errors([1.0 + k * 2.0 ** -13 for k in range(1024)], (32, 32), seed=4),
-    # median 0.5, threshold 5.0, one pixel at exactly 5.0: the strict < excludes it
-    "tie_at_threshold": lambda: _from_errors([0.5] * 5 + [5.0, 0.25, 0.25, 7.0], (3, 3), seed=5),
-    # denormal errors (a denormal gt against depth 0): median 311000 * 2^-149, four pixels beyond ten times it
-    "denormal_errors": lambda: _from_errors([(300000 + 1000 * k) * _DEN for k in range(16)] + [m * _DEN for m in (
-        2000000, 2400000, 2800000, 3100000, 3110000, 4000000, 6000000, 8388607)], (4, 6), seed=6),
-    # NaN and inf depth: a NaN error anywhere makes the median NaN and the selection empty; an inf error on a valid pixel only drops out
-    "nan_depth_valid_pixel": lambda: _with(_small(), d_1_2=NAN),
-    "nan_depth_under_hole": lambda: _with(_small(), d_1_2=NAN, g_1_2=0.0),
-    "inf_depth_under_hole": lambda: _with(_small(), d_2_4=INF, g_2_4=0.0),
-    "inf_depth_valid_pixel": lambda: _with(_small(), d_0_3=INF),
-    # a negative gt is a hole: its error is 0 and it is never selected
-    "negative_gt": lambda: _with(_small(), g_0_0=-1.0, g_1_1=-0.5, g_2_2=-3.0, g_2_3=0.0),
-    # tails of a wave and of a workgroup; several workgroups
-    "37x23": lambda: _noisy(37, 23, seed=7),
-    "129x67": lambda: _noisy(129, 67, seed=8),
-    # many workgroups, a non-trivial bin in all three passes
-    "340x600": lambda: _noisy(340, 600, seed=9, holes=0.03),
-    # one partial per 1024 pixels; the finish kernel's 256 threads take a second trip from 257 partials on: H * W > 256 * 1024 = 262 144
-    "513x512": lambda: _noisy(513, 512, seed=10),
-    # the outlier head's grid stops at 512 workgroups and strides from H * W > 512 * 1024 = 524 288 on (the plain head's does not stop)
-    "725x724": lambda: _noisy(725, 724, seed=11),
-}
 FORMS = ["tracking_sil", "tracking_nosil", "mapping"]
 PIXELS_PER_PARTIAL, FINISH_THREADS, OUTLIER_GRID_CAP = 1024, 256, 512
 
