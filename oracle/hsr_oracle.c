@@ -716,6 +716,48 @@ static void gauss_chain(const HsroChain* c, int idx, const real in[9], real* dme
     }
 }
 
+static HsroChain chain_of(const HsroState* s, int D, int M, const float* means3D, const float* shs, const float* scales, float scale_modifier,
+                          const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                          const float* campos, float tan_fovx, float tan_fovy)
+{
+    HsroChain ch;
+    ch.s = s; ch.D = D; ch.M = M; ch.means3D = means3D; ch.shs = shs; ch.scales = scales; ch.rotations = rotations;
+    ch.cov3Ds = cov3D_precomp ? cov3D_precomp : s->cov3D; ch.viewmatrix = viewmatrix; ch.projmatrix = projmatrix; ch.campos = campos;
+    ch.scale_modifier = scale_modifier; ch.tan_fovx = tan_fovx; ch.tan_fovy = tan_fovy;
+    ch.focal_y = s->H / (2.0f * tan_fovy); ch.focal_x = s->W / (2.0f * tan_fovx);   /* rasterizer_impl.cu:393-394, :661-662 */
+    return ch;
+}
+
+/*
+ * The per-Gaussian chain alone (test aid: the reference has no such entry point; hsro_backward runs exactly this on the sums its tile
+ * pass accumulated).  in[P][9]: dL_dmean2D.xy, dL_dconic.{x,y,w}, dL_ddepth, dL_dcolor.rgb per Gaussian, from any source — the sums an
+ * fp32-atomics implementation accumulated, say, so that a comparison of the chain's outputs holds the chain's arithmetic and not the
+ * arrival order of those atomics.  gauss_chain for every Gaussian with radii > 0, zeros for the others; every output is fully
+ * overwritten.  dL_dsh (with shs and M > 0) and dL_dscale / dL_drot (with scales) may be NULL.
+ */
+void hsro_gauss_chain(const HsroState* s, int D, int M, const float* means3D, const float* shs, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                      const float* campos, float tan_fovx, float tan_fovy, const real* in, real* dL_dmean3D, real* dL_dcov3D,
+                      real* dL_dsh, real* dL_dscale, real* dL_drot)
+{
+    const int P = s->P;
+    memset(dL_dmean3D, 0, sizeof(real) * 3 * (size_t)P);
+    memset(dL_dcov3D, 0, sizeof(real) * 6 * (size_t)P);
+    if (dL_dscale) memset(dL_dscale, 0, sizeof(real) * 3 * (size_t)P);
+    if (dL_drot) memset(dL_drot, 0, sizeof(real) * 4 * (size_t)P);
+    if (dL_dsh && M > 0) memset(dL_dsh, 0, sizeof(real) * 3 * (size_t)M * (size_t)P);
+    const HsroChain ch = chain_of(s, D, M, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                  tan_fovx, tan_fovy);
+    const int sr = scales && dL_dscale && dL_drot;
+#pragma omp parallel for schedule(static)
+    for (int idx = 0; idx < P; idx++) {
+        if (!(s->radii[idx] > 0)) continue;
+        gauss_chain(&ch, idx, in + 9 * (size_t)idx, dL_dmean3D + 3 * (size_t)idx, dL_dcov3D + 6 * (size_t)idx,
+                    sr ? dL_dscale + 3 * (size_t)idx : 0, sr ? dL_drot + 4 * (size_t)idx : 0,
+                    (shs && dL_dsh) ? dL_dsh + (size_t)idx * M * 3 : 0);
+    }
+}
+
 /* ---- one pixel of renderCUDA (backward.cu:472-666) / renderCUDA_SEM (backward.cu:669-899) ----
  * Adds the pixel's per-splat terms into rows of NA = 10 + K doubles: mean2D xy, conic xyw, opacity, colour rgb, depth, sem[K].
  * local == NULL: into acc[id] (shared, atomic); else into local[list position - r0] (the tie bounds' private copy). */
@@ -907,7 +949,6 @@ int hsro_backward(const HsroState* s, int D, int M, const float* background, con
     const size_t N = (size_t)W * H;
     const uint32_t gx = (uint32_t)s->tiles_x, gy = (uint32_t)s->tiles_y;
     const size_t Tn = (size_t)gx * gy;
-    const float focal_y = H / (2.0f * tan_fovy), focal_x = W / (2.0f * tan_fovx);
     const float* colors = colors_precomp ? colors_precomp : s->rgb;
     const int NA = 10 + K; /* per-Gaussian accumulators: mean2D xy, conic xyw, opacity, colour rgb, depth, sem[K] */
     size_t Pa = P ? (size_t)P : 1;
@@ -980,26 +1021,21 @@ int hsro_backward(const HsroState* s, int D, int M, const float* background, con
     }
     free(acc);
 
-    memset(dL_dmean3D, 0, sizeof(real) * 3 * (size_t)P);
-    memset(dL_dcov3D, 0, sizeof(real) * 6 * (size_t)P);
-    if (dL_dscale) memset(dL_dscale, 0, sizeof(real) * 3 * (size_t)P);
-    if (dL_drot) memset(dL_drot, 0, sizeof(real) * 4 * (size_t)P);
-    if (dL_dsh && M > 0) memset(dL_dsh, 0, sizeof(real) * 3 * (size_t)M * (size_t)P);
-
-    HsroChain ch;
-    ch.s = s; ch.D = D; ch.M = M; ch.means3D = means3D; ch.shs = shs; ch.scales = scales; ch.rotations = rotations;
-    ch.cov3Ds = cov3D_precomp ? cov3D_precomp : s->cov3D; ch.viewmatrix = viewmatrix; ch.projmatrix = projmatrix; ch.campos = campos;
-    ch.scale_modifier = scale_modifier; ch.focal_x = focal_x; ch.focal_y = focal_y; ch.tan_fovx = tan_fovx; ch.tan_fovy = tan_fovy;
-
-    /* ---- computeCov2DCUDA (backward.cu:144-274) + preprocessCUDA (backward.cu:346-412), per Gaussian ---- */
-#pragma omp parallel for schedule(static)
-    for (int idx = 0; idx < P; idx++) {
-        if (!(s->radii[idx] > 0)) continue;
-        const real in[9] = {dL_dmean2D[3 * idx], dL_dmean2D[3 * idx + 1], dL_dconic[4 * idx], dL_dconic[4 * idx + 1], dL_dconic[4 * idx + 3],
-                            dL_ddepth[idx], dL_dcolor[3 * idx], dL_dcolor[3 * idx + 1], dL_dcolor[3 * idx + 2]};
-        gauss_chain(&ch, idx, in, dL_dmean3D + 3 * (size_t)idx, dL_dcov3D + 6 * (size_t)idx, scales ? dL_dscale + 3 * (size_t)idx : 0,
-                    scales ? dL_drot + 4 * (size_t)idx : 0, (shs && dL_dsh) ? dL_dsh + (size_t)idx * M * 3 : 0);
+    /* ---- computeCov2DCUDA (backward.cu:144-274) + preprocessCUDA (backward.cu:346-412), per Gaussian: the chain on the sums above ---- */
+    real* chain_in = (real*)malloc(sizeof(real) * 9 * Pa);
+    if (!chain_in) return -2;
+    for (int i = 0; i < P; i++) {
+        real* in = chain_in + 9 * (size_t)i;
+        in[0] = dL_dmean2D[3 * i]; in[1] = dL_dmean2D[3 * i + 1];
+        in[2] = dL_dconic[4 * i]; in[3] = dL_dconic[4 * i + 1]; in[4] = dL_dconic[4 * i + 3];
+        in[5] = dL_ddepth[i];
+        in[6] = dL_dcolor[3 * i]; in[7] = dL_dcolor[3 * i + 1]; in[8] = dL_dcolor[3 * i + 2];
     }
+    hsro_gauss_chain(s, D, M, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx,
+                     tan_fovy, chain_in, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+    free(chain_in);
+    const HsroChain ch = chain_of(s, D, M, means3D, shs, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                                  tan_fovx, tan_fovy);
 
     /* ---- tie bounds of the gradients: every flagged decision of every flagged pixel taken the other way ---- */
     if (bounds) {

@@ -27,8 +27,38 @@ def variant_kwargs(sc, variant, extra=None):
     return kw
 
 
+def device_state(geom, binning, img, P, W, H, R):
+    """the fields of the three state buffers of one forward (P > 0) as numpy arrays, carved by the library's own layout"""
+    from diff_gaussian_rasterization import _C
+    lay = _C.state_layout(P, W, H, R)
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+
+    def view(buf, off, dtype, count, shape):
+        nbytes = count * torch.tensor([], dtype=dtype).element_size()
+        base = (-buf.data_ptr()) % 256  # the library aligns the carve to 256 B from the real address
+        return buf[base + off: base + off + nbytes].view(dtype).reshape(shape).cpu().numpy()
+    return dict(
+        num_rendered=R,
+        depths=view(geom, lay["geom_depths"], torch.float32, P, (P,)),
+        means2D=view(geom, lay["geom_means2D"], torch.float32, 2 * P, (P, 2)),
+        conic_opacity=view(geom, lay["geom_conic_opacity"], torch.float32, 4 * P, (P, 4)),
+        cov3D=view(geom, lay["geom_cov3D"], torch.float32, 6 * P, (P, 6)),
+        # the SH colours and their clamp flags: written for visible Gaussians, and only when shs (not colors_precomp) is given
+        rgb=view(geom, lay["geom_rgb"], torch.float32, 3 * P, (P, 3)),
+        clamped=view(geom, lay["geom_clamped"], torch.uint8, 3 * P, (P, 3)),
+        tiles_touched=view(geom, lay["geom_tiles_touched"], torch.int32, P, (P,)).astype(np.uint32),
+        point_offsets=view(geom, lay["geom_point_offsets"], torch.int32, P, (P,)).astype(np.uint32),
+        keys=view(binning, lay["bin_keys"], torch.int64, R, (R,)).astype(np.uint64) if R else np.zeros(0, np.uint64),
+        vals=view(binning, lay["bin_vals"], torch.int32, R, (R,)).astype(np.uint32) if R else np.zeros(0, np.uint32),
+        ranges=view(img, lay["img_ranges"], torch.int32, 2 * T, (T, 2)).astype(np.uint32),
+        final_T=view(img, lay["img_final_T"], torch.float32, W * H, (W * H,)),
+        n_contrib=view(img, lay["img_n_contrib"], torch.int32, W * H, (W * H,)).astype(np.uint32),
+        median_pos=view(img, lay["img_median_pos"], torch.int32, W * H, (W * H,)).astype(np.uint32),
+    )
+
+
 def run_gpu(cam, sc, up, semantic=True, variant="sr", extra=None, dev="cuda:0", want_state=True):
-    from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic, _C
+    from diff_gaussian_rasterization import GaussianRasterizer, GaussianRasterizer_semantic
     dev = torch.device(dev)
     camd = _cam_to(cam, dev)
     kw = variant_kwargs(sc, variant, extra)
@@ -68,31 +98,7 @@ def run_gpu(cam, sc, up, semantic=True, variant="sr", extra=None, dev="cuda:0", 
         grads["semantics_precomp"] = z(sem)
     state = None
     if want_state and P > 0:
-        R = num_rendered
-        H, W = cam["image_height"], cam["image_width"]
-        lay = _C.state_layout(P, W, H, R)
-        geom, binning, img = saved[-3], saved[-2], saved[-1]
-        T = ((W + 15) // 16) * ((H + 15) // 16)
-
-        def view(buf, off, dtype, count, shape):
-            nbytes = count * torch.tensor([], dtype=dtype).element_size()
-            base = (-buf.data_ptr()) % 256  # the library aligns the carve to 256 B from the real address
-            return buf[base + off: base + off + nbytes].view(dtype).reshape(shape).cpu().numpy()
-        state = dict(
-            num_rendered=R,
-            depths=view(geom, lay["geom_depths"], torch.float32, P, (P,)),
-            means2D=view(geom, lay["geom_means2D"], torch.float32, 2 * P, (P, 2)),
-            conic_opacity=view(geom, lay["geom_conic_opacity"], torch.float32, 4 * P, (P, 4)),
-            cov3D=view(geom, lay["geom_cov3D"], torch.float32, 6 * P, (P, 6)),
-            tiles_touched=view(geom, lay["geom_tiles_touched"], torch.int32, P, (P,)).astype(np.uint32),
-            point_offsets=view(geom, lay["geom_point_offsets"], torch.int32, P, (P,)).astype(np.uint32),
-            keys=view(binning, lay["bin_keys"], torch.int64, R, (R,)).astype(np.uint64) if R else np.zeros(0, np.uint64),
-            vals=view(binning, lay["bin_vals"], torch.int32, R, (R,)).astype(np.uint32) if R else np.zeros(0, np.uint32),
-            ranges=view(img, lay["img_ranges"], torch.int32, 2 * T, (T, 2)).astype(np.uint32),
-            final_T=view(img, lay["img_final_T"], torch.float32, W * H, (W * H,)),
-            n_contrib=view(img, lay["img_n_contrib"], torch.int32, W * H, (W * H,)).astype(np.uint32),
-            median_pos=view(img, lay["img_median_pos"], torch.int32, W * H, (W * H,)).astype(np.uint32),
-        )
+        state = device_state(saved[-3], saved[-2], saved[-1], P, cam["image_width"], cam["image_height"], num_rendered)
     return res, grads, state
 
 

@@ -251,5 +251,44 @@ def backward(st, cam, means3D, grads, colors_precomp=None, shs=None, semantics_p
     return o
 
 
+def gauss_chain(st, cam, means3D, sums, shs=None, scales=None, rotations=None, cov3D_precomp=None, colors_precomp=None,
+                semantics_precomp=None, threads=0):
+    """The per-Gaussian chain of the backward alone (hsro_gauss_chain): dL_dconic -> cov2D -> cov3D -> scale / quaternion, mean2D and
+    depth -> mean3D, SH backward, on the forward state `st` (its build decides the arithmetic: float, or double for an "f64" state).
+    sums: the chain's inputs from ANY source — means2D [P,3], conic [P,4], depths [P,1] (or [P]), colors_precomp [P,3] (dL_dcolor; read
+    by the SH path only) — e.g. what a device accumulated with fp32 atomics.  The other keywords are the forward's (variant_kwargs);
+    colors_precomp / semantics_precomp are accepted and ignored.  Returns the keys of backward() that the chain writes: means3D,
+    cov3D_precomp, shs, scales, rotations (zeros for Gaussians with radii <= 0)."""
+    L = lib(st.precision)
+    rt = L.real
+    if threads:
+        L.hsro_set_threads(C.c_int(threads))
+    g = (lambda k: cam[k]) if isinstance(cam, dict) else (lambda k: getattr(cam, k))
+    P = st.P
+    shs_np = _np(shs)
+    M = 0 if shs_np is None or shs_np.size == 0 else shs_np.shape[1]
+    cin = np.zeros((P, 9), rt)
+    cin[:, 0:2] = np.asarray(_np(sums["means2D"]), rt).reshape(P, 3)[:, :2]
+    cin[:, 2:5] = np.asarray(_np(sums["conic"]), rt).reshape(P, 4)[:, [0, 1, 3]]
+    cin[:, 5] = np.asarray(_np(sums["depths"]), rt).reshape(P)
+    cin[:, 6:9] = np.asarray(_np(sums["colors_precomp"]), rt).reshape(P, 3)
+    keep = []
+    def f(a):
+        arr, p = _f(_np(a))
+        keep.append(arr)
+        return p
+    o = dict(means3D=np.zeros((P, 3), rt), cov3D_precomp=np.zeros((P, 6), rt), shs=np.zeros((P, M, 3), rt),
+             scales=np.zeros((P, 3), rt), rotations=np.zeros((P, 4), rt))
+    po = lambda name: o[name].ctypes.data_as(C.c_void_p) if o[name].size else C.c_void_p(0)
+    has_scales = scales is not None and _np(scales).size > 0
+    L.hsro_gauss_chain.restype = None
+    L.hsro_gauss_chain(C.c_void_p(st.h), C.c_int(int(g("sh_degree"))), C.c_int(M), f(means3D), f(shs_np), f(scales),
+                       C.c_float(float(g("scale_modifier"))), f(rotations), f(cov3D_precomp), f(g("viewmatrix")), f(g("projmatrix")),
+                       f(g("campos")), C.c_float(float(g("tanfovx"))), C.c_float(float(g("tanfovy"))),
+                       cin.ctypes.data_as(C.c_void_p) if P else C.c_void_p(0), po("means3D"), po("cov3D_precomp"), po("shs"),
+                       po("scales") if has_scales else C.c_void_p(0), po("rotations") if has_scales else C.c_void_p(0))
+    return o
+
+
 def get_higher_msb(n):
     return int(lib().hsro_get_higher_msb(C.c_uint32(n)))

@@ -9,7 +9,8 @@ Tolerances: harness.assert_close (1e-4, tensor-wide and element-wise) plus the o
 Scenes: kind "slam" — isotropic Gaussians, what a SLAM map holds and what bench.py runs.  With them the conic -> cov3D -> scale chain
 behind the unpack is well-conditioned, so the 1e-4 bar measures what the kernel moved; on needles an entry of that chain sits at 1-3e-4 of
 the bar from one run to the next with the arrival order of the tile kernel's fp32 atomics (harness.FLOOR_FRAC_COV), whatever the unpack
-does.  That chain's arithmetic is not what this file is about: test_gpu_parity.py holds it to the oracle and the truth build."""
+does.  That chain's arithmetic is not what this file is about: test_gpu_gauss_chain.py holds it, bit for bit, to the oracle's chain run on the
+device's own accumulated sums (needles, clamped and culled Gaussians, every input variant), where the arrival order drops out."""
 import os
 import subprocess
 import sys

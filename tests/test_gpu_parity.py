@@ -50,9 +50,9 @@ TIE_BOUNDED = []   # comparisons that needed the oracle's tie bound (reported at
 CONDITIONED = []   # comparisons settled against the truth build: HIP within twice the fp32 noise floor of that gradient (ditto)
 
 
-def _compare_integers(out_g, st_g, out_o, st_o):
+def _compare_integers(out_g, st_g, out_o, st_o, own_cov3D=True):
     """the integer state of one forward, HIP against the oracle, bit for bit: radii, counts, offsets, the sorted lists and tile ranges,
-    and the per-Gaussian fp32 state that feeds them"""
+    and the per-Gaussian fp32 state that feeds them.  own_cov3D: the forward built cov3D from scales and rotations (no cov3D_precomp)"""
     assert np.array_equal(out_g["radii"], out_o["radii"]), "radii"
     assert st_g["num_rendered"] == out_o["num_rendered"], "num_rendered"
     assert np.array_equal(st_g["tiles_touched"], st_o.field("tiles_touched")), "tiles_touched"
@@ -68,13 +68,15 @@ def _compare_integers(out_g, st_g, out_o, st_o):
     assert np.array_equal(st_g["depths"][vis], st_o.field("depths")[vis]), "depths"
     assert np.array_equal(st_g["means2D"][vis], st_o.field("means2D")[vis]), "means2D"
     assert np.array_equal(st_g["conic_opacity"][vis], st_o.field("conic_opacity")[vis]), "conic_opacity"
+    if own_cov3D:   # ... and the state the backward's chain reads again (computeCov3D, forward.cu:118-152): the same expressions, same bits
+        assert np.array_equal(st_g["cov3D"][vis].view(np.uint32), st_o.field("cov3D")[vis].view(np.uint32)), "cov3D"
 
 
 def _compare(cam, sc, up, semantic, variant, extra=None, grad_rtol=1e-4):
     out_g, gr_g, st_g = run_gpu(cam, sc, up, semantic=semantic, variant=variant, extra=extra)
     out_o, gr_o, st_o = run_oracle(cam, sc, up, semantic=semantic, variant=variant, extra=extra)
     # ---- integer outputs: bit-exact ----
-    _compare_integers(out_g, st_g, out_o, st_o)
+    _compare_integers(out_g, st_g, out_o, st_o, own_cov3D=variant != "cov")
     # ---- thresholded integers: budgeted ----
     npix = out_o["color"].shape[1] * out_o["color"].shape[2]
     nmis = int((st_g["n_contrib"] != st_o.field("n_contrib")).sum())
