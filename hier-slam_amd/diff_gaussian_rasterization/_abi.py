@@ -4,7 +4,7 @@ function, and the one way a stream-taking entry point is called.
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
 this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
 time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES, SIGNATURES_EXT_MAP_EXPORT, SIGNATURES_EXT_VIEW, SIGNATURES_EXT_REPLAY and SIGNATURES_EXT_KEYFRAME_PACK against include/ext/ with
+include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES, SIGNATURES_EXT_MAP_EXPORT, SIGNATURES_EXT_VIEW, SIGNATURES_EXT_REPLAY, SIGNATURES_EXT_KEYFRAME_PACK and SIGNATURES_EXT_TSDF against include/ext/ with
 the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
 """
 import ctypes as C
@@ -340,6 +340,20 @@ SIGNATURES_EXT_KEYFRAME_PACK = (
                                  cd, vp, vp, vp, vp]),
 )
 
+# include/ext/hsr_tsdf.h: depth fused into a signed distance volume and its surface; a table of its own like the rest (w2c is a HOST array)
+SIGNATURES_EXT_TSDF = (
+    ("hsr_tsdf_integrate", ci, [ci, ci, ci, cf, cf, cf, cf, cf, cf,
+                                ci, ci, cf, cf, cf, cf, fp,
+                                vp, vp, vp, vp, cf, cf,
+                                vp, vp, vp, vp, vp, vp, vp]),
+    ("hsr_tsdf_count", ci, [ci, ci, ci, vp, vp, vp, vp]),
+    ("hsr_tsdf_faces", ci, [ci, ci, ci, vp, vp, vp, sz, vp,
+                            vp]),
+    ("hsr_tsdf_vertices", ci, [ci, ci, ci, cf, cf, cf, cf, sz, vp,
+                               vp, vp, vp, vp,
+                               vp, vp, vp, vp]),
+)
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -351,7 +365,7 @@ def _load():
     for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
                                     + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT
                                     + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT + SIGNATURES_EXT_VIEW
-                                    + SIGNATURES_EXT_REPLAY + SIGNATURES_EXT_KEYFRAME_PACK):
+                                    + SIGNATURES_EXT_REPLAY + SIGNATURES_EXT_KEYFRAME_PACK + SIGNATURES_EXT_TSDF):
         fn = getattr(loaded, name)
         fn.restype, fn.argtypes = restype, argtypes
     return loaded

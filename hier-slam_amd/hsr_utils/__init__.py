@@ -19,6 +19,7 @@ _MAP_EXPORT = ("export_map", "gaussian_tree_labels", "level_prefix_colour_table"
 _REPLAY = ("run_w2cs", "ReplayPlan", "replay_rendervars", "replay_view", "view_cloud", "save_cloud_ply", "follow_camera", "camera_centres",
            "trajectory_lines", "replay_run")
 _CHECKPOINT = ("PackedKeyframe", "pack_keyframe", "unpack_keyframe", "save_checkpoint", "load_checkpoint")
+_MESH = ("TsdfVolume", "mesh_bounds", "save_mesh_ply", "load_mesh_ply", "mesh_run")
 
 
 def __getattr__(name):
@@ -47,4 +48,7 @@ def __getattr__(name):
     if name in _CHECKPOINT:      # and the packed keyframe store with a session's checkpoint and resume
         from . import checkpoint
         return getattr(checkpoint, name)
+    if name in _MESH:            # and the mesh of a finished run
+        from . import mesh
+        return getattr(mesh, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

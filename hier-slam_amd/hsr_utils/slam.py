@@ -724,6 +724,20 @@ class SlamSession:
         return replay.replay_run(self.params, out_dir, timestep=self.variables['timestep'], intrinsics=self.intrinsics,
                                  width=self.cam.image_width, height=self.cam.image_height, **kw)
 
+    def export_mesh(self, path, **kw):
+        """the run so far as a triangle mesh in a PLY file: hsr_utils.mesh.mesh_run on the session's own params — the map rendered with
+        the session's camera from every `every`-th estimated pose and fused into a signed distance volume (voxel_size= is required) —
+        with its intrinsics, frame size and mapping sil_thres; returns (path, number of vertices, number of faces)"""
+        from . import mesh
+        if self.params is None:
+            raise RuntimeError("hsr_utils.slam: export_mesh before the first frame: there is no map yet")
+        kw.setdefault('semantic', self.flag_use_semantic)
+        kw.setdefault('num_frames', len(self.gt_w2c_all_frames))
+        kw.setdefault('sil_thres', self.config['mapping']['sil_thres'])
+        kw.setdefault('cam', self.cam)
+        kw.setdefault('first_frame_w2c', self.first_frame_w2c)
+        return mesh.mesh_run(self.params, path, intrinsics=self.intrinsics, width=self.cam.image_width, height=self.cam.image_height, **kw)
+
     def step(self, frame):
         """one pass of the frame loop (scripts/hierslam.py:1762-2124) for frame['id'] = the number of frames stepped so far"""
         time_idx = int(frame['id'])
