@@ -2,10 +2,11 @@
 function, and the one way a stream-taking entry point is called.
 
 Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
-this module.  The signature table is written out by hand (nothing parses a header at import: the package does not depend on where include/ sits at run
-time); tests/test_abi.py parses the headers and fails on any entry whose type class differs from its prototype's (SIGNATURES against
-include/hsr_*.h; SIGNATURES_EXT, SIGNATURES_EXT_MAP_INIT, SIGNATURES_EXT_FRAME_RESAMPLE, SIGNATURES_EXT_LOSS_OUTLIER, SIGNATURES_EXT_FRAME_INGEST, SIGNATURES_EXT_FRAME_EXPORT, SIGNATURES_EXT_FRAME_INGEST_PLANES, SIGNATURES_EXT_MAP_EXPORT, SIGNATURES_EXT_VIEW, SIGNATURES_EXT_REPLAY, SIGNATURES_EXT_KEYFRAME_PACK and SIGNATURES_EXT_TSDF against include/ext/ with
-the same checker, each from its extension's own suite).  There is NO fallback path: a missing library is an ImportError.
+this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
+header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
+include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
+header, a name out of the header's order or bound twice, and any entry whose type class differs from its prototype's.  There is NO
+fallback path: a missing library is an ImportError.
 """
 import ctypes as C
 import os
@@ -80,279 +81,269 @@ class hsr_map_export_job(C.Structure):
 
 bp, tk = C.POINTER(hsr_buffer), C.POINTER(hsr_ticket)
 
-# ---- signatures: (name, restype, argtypes), in the order of the headers, broken into lines where the prototype breaks ----------------
-SIGNATURES = (
-    # include/hsr_rasterizer.h
-    ("hsr_required_geometry_bytes", sz, [ci]),
-    ("hsr_required_image_bytes", sz, [ci, ci]),
-    ("hsr_required_binning_bytes", sz, [ci]),
-    ("hsr_backward_scratch_bytes", sz, [ci, ci, ci]),
-    ("hsr_set_backward_mode", ci, [ci]),
-    ("hsr_get_backward_mode", ci, []),
-    ("hsr_plan_backward", ci, [ci, ci, ci, sz, C.POINTER(hsr_backward_plan)]),
-    ("hsr_set_semantic_alpha_mode", ci, [ci]),
-    ("hsr_get_semantic_alpha_mode", ci, []),
-    ("hsr_last_error", cs, []),
-    ("hsr_version", cs, []),
-    ("hsr_mark_visible", ci, [ci, vp, vp, vp,
-                              vp, vp]),
-    ("hsr_forward", ci, [bp, bp, bp,
-                         ci, ci, ci, vp, ci, ci,
-                         vp, vp, vp, vp,
-                         vp, cf, vp, vp,
-                         vp, vp, vp,
-                         cf, cf, ci,
-                         vp, vp, vp, vp, vp,
-                         vp, ci, vp]),
-    ("hsr_forward_semantic", ci, [bp, bp, bp,
-                                  ci, ci, ci, ci, vp, ci, ci,
-                                  vp, vp, vp,
-                                  vp, vp,
-                                  vp, cf, vp, vp,
-                                  vp, vp, vp,
-                                  cf, cf, ci,
-                                  vp, vp, vp, vp,
-                                  vp, vp, ci, vp]),
-    ("hsr_forward_arm_async", ci, [tk]),
-    ("hsr_forward_end", ci, [tk, ci, vp]),
-    ("hsr_backward", ci, [ci, ci, ci, ci, vp, ci, ci,
-                          vp, vp, vp,
-                          vp, cf, vp, vp,
-                          vp, vp, vp,
-                          cf, cf, vp,
-                          vp, vp, vp,
-                          vp, vp, vp,
-                          vp,
-                          vp, vp, vp, vp, vp,
-                          vp, vp, vp, vp, vp,
-                          vp, sz, ci, vp]),
-    ("hsr_backward_semantic", ci, [ci, ci, ci, ci, ci, vp, ci, ci,
-                                   vp, vp, vp,
-                                   vp,
-                                   vp, cf, vp, vp,
-                                   vp, vp, vp,
-                                   cf, cf, vp,
-                                   vp, vp, vp,
-                                   vp, vp, vp,
-                                   vp, vp,
-                                   vp, vp, vp, vp,
-                                   vp, vp,
-                                   vp, vp, vp, vp, vp,
-                                   vp, sz, ci, vp]),
-    ("hsr_get_state_layout", ci, [ci, ci, ci, ci, C.POINTER(hsr_state_layout)]),
-    ("hsr_profile_enable", ci, [ci]),
-    ("hsr_profile_select", ci, [cu]),
-    ("hsr_profile_read", ci, [vp, ci]),
-    ("hsr_stage_name", cs, [ci]),
-    ("hsr_profile_host_wait_ms", cd, [ci]),
-    # include/hsr_frame_prep.h
-    ("hsr_frame_prep_scratch_bytes", sz, [ci]),
-    ("hsr_frame_prep_forward", ci, [ci, ci, ci, ci, vp, vp,
-                                    vp, vp, vp,
-                                    vp, ci, ci, vp, vp,
-                                    vp, vp, vp, vp,
-                                    vp, vp]),
-    ("hsr_frame_prep_backward", ci, [ci, ci, ci, ci, vp, vp,
-                                     vp, vp, vp,
-                                     vp, ci, ci, vp,
-                                     vp, vp, vp,
-                                     vp, vp, vp,
-                                     vp, vp, vp, vp,
-                                     vp, vp, vp, sz, vp]),
-    ("hsr_frame_prep_backward_params", ci, [ci, ci, ci, ci, vp, vp,
-                                            vp, vp, vp,
-                                            vp, ci, ci, vp,
-                                            vp, vp, vp,
-                                            vp, vp, vp,
-                                            vp, vp, vp, vp,
-                                            vp, vp, vp, sz, vp]),
-    # include/hsr_losses.h
-    ("hsr_loss_scratch_bytes", sz, [ci, ci, ci]),
-    ("hsr_loss_l1", ci, [ci, ci, ci, vp, vp, vp, ci, vp,
-                         vp, vp, sz, vp]),
-    ("hsr_loss_tracking_scratch_bytes", sz, [ci, ci]),
-    ("hsr_loss_tracking_value", ci, [ci, ci, ci, vp, vp, vp, vp,
-                                     vp, cf, ci, ci, cf, cf, vp,
-                                     vp, sz, vp]),
-    ("hsr_loss_tracking_grad", ci, [ci, ci, ci, vp, vp, vp, vp,
-                                    vp, cf, ci, cf, cf, vp,
-                                    vp, vp, vp, vp]),
-    ("hsr_loss_ssim", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
-                           sz, vp]),
-    ("hsr_loss_l1_grad", ci, [ci, ci, ci, vp, vp, vp, ci, vp,
-                              vp, vp]),
-    ("hsr_loss_ssim_value", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
-                                 sz, vp]),
-    ("hsr_loss_ssim_grad", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
-                                vp]),
-    ("hsr_loss_tree_ce", ci, [ci, ci, ci, ci, ip, fp, vp,
-                              vp, ci, vp, vp, vp,
-                              sz, vp]),
-    ("hsr_loss_tree_ce_scratch_bytes", sz, [ci, ci]),
-    ("hsr_loss_tree_ce_value", ci, [ci, ci, ci, ci, ip, vp, vp,
-                                    ci, vp, vp, vp, sz,
+# ---- signatures: header (its path under include/) -> (name, restype, argtypes) of each of its functions, in the header's order, -----
+# ---- broken into lines where the prototype breaks ----------------------------------------------------------------------------------
+HEADERS = {
+    "hsr_rasterizer.h": (
+        ("hsr_required_geometry_bytes", sz, [ci]),
+        ("hsr_required_image_bytes", sz, [ci, ci]),
+        ("hsr_required_binning_bytes", sz, [ci]),
+        ("hsr_backward_scratch_bytes", sz, [ci, ci, ci]),
+        ("hsr_set_backward_mode", ci, [ci]),
+        ("hsr_get_backward_mode", ci, []),
+        ("hsr_plan_backward", ci, [ci, ci, ci, sz, C.POINTER(hsr_backward_plan)]),
+        ("hsr_set_semantic_alpha_mode", ci, [ci]),
+        ("hsr_get_semantic_alpha_mode", ci, []),
+        ("hsr_last_error", cs, []),
+        ("hsr_version", cs, []),
+        ("hsr_mark_visible", ci, [ci, vp, vp, vp,
+                                  vp, vp]),
+        ("hsr_forward", ci, [bp, bp, bp,
+                             ci, ci, ci, vp, ci, ci,
+                             vp, vp, vp, vp,
+                             vp, cf, vp, vp,
+                             vp, vp, vp,
+                             cf, cf, ci,
+                             vp, vp, vp, vp, vp,
+                             vp, ci, vp]),
+        ("hsr_forward_semantic", ci, [bp, bp, bp,
+                                      ci, ci, ci, ci, vp, ci, ci,
+                                      vp, vp, vp,
+                                      vp, vp,
+                                      vp, cf, vp, vp,
+                                      vp, vp, vp,
+                                      cf, cf, ci,
+                                      vp, vp, vp, vp,
+                                      vp, vp, ci, vp]),
+        ("hsr_forward_arm_async", ci, [tk]),
+        ("hsr_forward_end", ci, [tk, ci, vp]),
+        ("hsr_backward", ci, [ci, ci, ci, ci, vp, ci, ci,
+                              vp, vp, vp,
+                              vp, cf, vp, vp,
+                              vp, vp, vp,
+                              cf, cf, vp,
+                              vp, vp, vp,
+                              vp, vp, vp,
+                              vp,
+                              vp, vp, vp, vp, vp,
+                              vp, vp, vp, vp, vp,
+                              vp, sz, ci, vp]),
+        ("hsr_backward_semantic", ci, [ci, ci, ci, ci, ci, vp, ci, ci,
+                                       vp, vp, vp,
+                                       vp,
+                                       vp, cf, vp, vp,
+                                       vp, vp, vp,
+                                       cf, cf, vp,
+                                       vp, vp, vp,
+                                       vp, vp, vp,
+                                       vp, vp,
+                                       vp, vp, vp, vp,
+                                       vp, vp,
+                                       vp, vp, vp, vp, vp,
+                                       vp, sz, ci, vp]),
+        ("hsr_get_state_layout", ci, [ci, ci, ci, ci, C.POINTER(hsr_state_layout)]),
+        ("hsr_profile_enable", ci, [ci]),
+        ("hsr_profile_select", ci, [cu]),
+        ("hsr_profile_read", ci, [vp, ci]),
+        ("hsr_stage_name", cs, [ci]),
+        ("hsr_profile_host_wait_ms", cd, [ci]),
+    ),
+    "hsr_frame_prep.h": (
+        ("hsr_frame_prep_scratch_bytes", sz, [ci]),
+        ("hsr_frame_prep_forward", ci, [ci, ci, ci, ci, vp, vp,
+                                        vp, vp, vp,
+                                        vp, ci, ci, vp, vp,
+                                        vp, vp, vp, vp,
+                                        vp, vp]),
+        ("hsr_frame_prep_backward", ci, [ci, ci, ci, ci, vp, vp,
+                                         vp, vp, vp,
+                                         vp, ci, ci, vp,
+                                         vp, vp, vp,
+                                         vp, vp, vp,
+                                         vp, vp, vp, vp,
+                                         vp, vp, vp, sz, vp]),
+        ("hsr_frame_prep_backward_params", ci, [ci, ci, ci, ci, vp, vp,
+                                                vp, vp, vp,
+                                                vp, ci, ci, vp,
+                                                vp, vp, vp,
+                                                vp, vp, vp,
+                                                vp, vp, vp, vp,
+                                                vp, vp, vp, sz, vp]),
+    ),
+    "hsr_losses.h": (
+        ("hsr_loss_scratch_bytes", sz, [ci, ci, ci]),
+        ("hsr_loss_l1", ci, [ci, ci, ci, vp, vp, vp, ci, vp,
+                             vp, vp, sz, vp]),
+        ("hsr_loss_tracking_scratch_bytes", sz, [ci, ci]),
+        ("hsr_loss_tracking_value", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                         vp, cf, ci, ci, cf, cf, vp,
+                                         vp, sz, vp]),
+        ("hsr_loss_tracking_grad", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                        vp, cf, ci, cf, cf, vp,
+                                        vp, vp, vp, vp]),
+        ("hsr_loss_ssim", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
+                               sz, vp]),
+        ("hsr_loss_l1_grad", ci, [ci, ci, ci, vp, vp, vp, ci, vp,
+                                  vp, vp]),
+        ("hsr_loss_ssim_value", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
+                                     sz, vp]),
+        ("hsr_loss_ssim_grad", ci, [ci, ci, ci, vp, vp, vp, vp, vp,
                                     vp]),
-    ("hsr_loss_tree_ce_grad", ci, [ci, ci, ci, ci, ip, fp, vp,
-                                   vp, ci, vp, vp, vp,
-                                   vp, cf, vp, vp]),
-    ("hsr_loss_leaf_mlp_ce", ci, [ci, ci, ci, ci, vp, vp, vp, vp,
-                                  ci, vp, vp, vp, vp, vp,
+        ("hsr_loss_tree_ce", ci, [ci, ci, ci, ci, ip, fp, vp,
+                                  vp, ci, vp, vp, vp,
                                   sz, vp]),
-    # include/hsr_densify.h
-    ("hsr_densify_scratch_bytes", sz, [ci, ci]),
-    ("hsr_densify_frame", ci, [ci, ci, vp, vp, vp, vp,
-                               cf, cf, cf, cf, vp, cf, cf, ci,
-                               vp, vp, vp, vp, vp,
-                               vp, vp, vp, sz, vp]),
-    ("hsr_compact_scratch_bytes", sz, [ci]),
-    ("hsr_prune_mask", ci, [ci, ci, vp, vp, cf,
-                            cf, vp, vp, vp, sz, vp]),
-    ("hsr_compact_append_rows", ci, [ci, vp, ci, ci, C.POINTER(hsr_row_table), ci,
-                                     vp, vp, sz, vp]),
-    # include/hsr_eval.h
-    ("hsr_eval_metrics_scratch_bytes", sz, [ci, ci]),
-    ("hsr_eval_frame_metrics", ci, [ci, ci, vp, vp, vp, vp,
-                                    vp, cf, vp, vp, sz, vp]),
-    ("hsr_eval_labels_flat", ci, [ci, ci, ci, vp, vp, vp]),
-    ("hsr_eval_labels_tree", ci, [ci, ci, ci, ci, ip, vp, vp,
-                                  vp, vp, vp]),
-    ("hsr_eval_leaf_scratch_bytes", sz, [ci]),
-    ("hsr_eval_labels_leaf", ci, [ci, ci, ci, ci, vp, vp, vp, vp,
-                                  vp, sz, vp]),
-    ("hsr_eval_iou_scratch_bytes", sz, [ci, ci]),
-    ("hsr_eval_iou_counts", ci, [ci, ci, vp, vp, ci, vp, vp,
-                                 ci, vp, vp, sz, vp]),
-    ("hsr_eval_frame_miou", ci, [ci, vp, vp, vp]),
-    # include/hsr_optim.h
-    ("hsr_adam_table_entry_bytes", sz, []),
-    ("hsr_adam_step", ci, [ci, C.POINTER(hsr_adam_tensor), vp]),
-    ("hsr_track_keep_best", ci, [ci, ci, vp, vp, vp, vp,
-                                 vp, vp, vp]),
-    # include/hsr_keyframes.h
-    ("hsr_kf_valid_rows", ci, [ci, ci, vp, vp, vp]),
-    ("hsr_kf_sample_scratch_bytes", sz, [ci]),
-    ("hsr_kf_sample_points", ci, [ci, ci, vp, vp, ci, vp, cf, cf,
-                                  cf, cf, vp, vp, vp, vp,
-                                  vp, vp, sz, vp]),
-    ("hsr_kf_round_keys", ci, [ci, vp, vp, vp]),
-    ("hsr_kf_overlap_counts", ci, [ci, vp, vp, ci, vp, vp, ci,
-                                   ci, ci, vp, vp]),
-)
-
-# ---- extensions: headers under include/ext/, outside the counted set of include/hsr_*.h; checked by their own suites ---------------
-SIGNATURES_EXT = (
-    # include/ext/hsr_msssim.h
-    ("hsr_eval_msssim_scratch_bytes", sz, [ci, ci]),
-    ("hsr_eval_msssim", ci, [ci, ci, vp, vp, vp, vp,
-                             cf, vp, vp, sz, vp]),
-)
-
-# include/ext/hsr_map_init.h: a table of its own (SIGNATURES_EXT is pinned to the MS-SSIM header by that header's suite)
-SIGNATURES_EXT_MAP_INIT = (
-    ("hsr_map_init_scratch_bytes", sz, [ci, ci]),
-    ("hsr_map_init_frame", ci, [ci, ci, vp, vp, cf, cf, cf, cf, vp,
-                                cf, ci, ci, vp, vp, vp,
-                                vp, vp, vp, vp,
-                                vp, sz, vp]),
-)
-
-# include/ext/hsr_frame_resample.h: again a table of its own (the two above are pinned by their suites)
-SIGNATURES_EXT_FRAME_RESAMPLE = (
-    ("hsr_frame_resample", ci, [ci, ci, vp, vp, ci, ci, vp, vp,
-                                ci, ci, vp, vp, vp]),
-)
-
-# include/ext/hsr_loss_outlier.h: a table of its own as well (the three above are pinned by their suites)
-SIGNATURES_EXT_LOSS_OUTLIER = (
-    ("hsr_loss_outlier_scratch_bytes", sz, [ci, ci]),
-    ("hsr_loss_outlier_median", ci, [ci, ci, vp, vp, vp, vp, sz,
-                                     vp]),
-    ("hsr_loss_outlier_value", ci, [ci, ci, ci, vp, vp, vp, vp,
-                                    vp, cf, ci, ci, cf, cf, vp,
-                                    vp, vp, sz, vp]),
-    ("hsr_loss_outlier_grad", ci, [ci, ci, ci, vp, vp, vp, vp,
-                                   vp, cf, ci, cf, cf, vp,
-                                   vp, vp, vp, vp, vp]),
-)
-
-# include/ext/hsr_frame_ingest.h: a table of its own too (the four above are pinned by their suites)
-SIGNATURES_EXT_FRAME_INGEST = (
-    ("hsr_frame_ingest", ci, [ci, ci, vp, vp, ci, cd,
-                              vp, ci, vp, ci,
-                              ci, C.POINTER(hsr_ingest_level), vp, vp]),
-)
-
-# include/ext/hsr_frame_export.h: and one more of its own (the five above are pinned by their suites)
-SIGNATURES_EXT_FRAME_EXPORT = (
-    ("hsr_frame_export", ci, [ci, ci, ci, C.POINTER(hsr_export_job), vp]),
-)
-
-# include/ext/hsr_frame_ingest_planes.h: the ingest with a source size per image (SIGNATURES_EXT_FRAME_INGEST is pinned to one name)
-SIGNATURES_EXT_FRAME_INGEST_PLANES = (
-    ("hsr_frame_ingest_planes", ci, [ci, ci, vp,
-                                     ci, ci, vp, ci, cd,
-                                     ci, ci, vp,
-                                     ci, vp, ci, ci,
-                                     ci, C.POINTER(hsr_ingest_level), vp, vp]),
-)
-
-# include/ext/hsr_map_export.h: the map as PLY records; a table of its own like the rest
-SIGNATURES_EXT_MAP_EXPORT = (
-    ("hsr_map_export", ci, [C.POINTER(hsr_map_export_job), vp]),
-)
-
-# include/ext/hsr_view.h: rasterizer inputs from a given world-to-camera matrix and a view's hole counts; a table of its own like the rest
-SIGNATURES_EXT_VIEW = (
-    ("hsr_view_prep", ci, [ci, ci, ci, ci,
-                           vp, vp,
-                           vp, vp,
-                           vp,
-                           vp, vp, vp,
-                           vp, vp, vp]),
-    ("hsr_view_holes_scratch_bytes", sz, [ci, ci]),
-    ("hsr_view_holes", ci, [ci, ci, vp, vp, cf,
-                            vp, vp, sz, vp]),
-)
-
-# include/ext/hsr_replay.h: the map as it stood at step t and a view's point cloud; a table of its own like the rest
-SIGNATURES_EXT_REPLAY = (
-    ("hsr_replay_plan_scratch_bytes", sz, [ci, ci]),
-    ("hsr_replay_plan", ci, [ci, ci, vp, vp,
-                             vp, sz, vp]),
-    ("hsr_replay_select_scratch_bytes", sz, [ci]),
-    ("hsr_replay_select", ci, [ci, ci, ci, ci, ci, ci, ci,
-                               vp, vp, vp, vp,
-                               vp, vp, vp, vp,
-                               vp, vp, vp, vp, vp,
-                               vp, vp, vp, vp,
-                               vp, sz, vp]),
-    ("hsr_replay_cloud", ci, [ci, ci, vp, vp, cf, cf, cf, cf,
-                              vp, vp, vp, vp]),
-)
-
-# include/ext/hsr_keyframe_pack.h: a keyframe's planes as 8-/16-bit codes and back; a table of its own like the rest
-SIGNATURES_EXT_KEYFRAME_PACK = (
-    ("hsr_keyframe_pack_scratch_bytes", sz, [ci, ci, ci]),
-    ("hsr_keyframe_pack", ci, [ci, ci, vp, vp, ci, vp, cd,
-                               vp, vp, vp, vp,
-                               vp, sz, vp]),
-    ("hsr_keyframe_unpack", ci, [ci, ci, vp, vp, ci, vp,
-                                 cd, vp, vp, vp, vp]),
-)
-
-# include/ext/hsr_tsdf.h: depth fused into a signed distance volume and its surface; a table of its own like the rest (w2c is a HOST array)
-SIGNATURES_EXT_TSDF = (
-    ("hsr_tsdf_integrate", ci, [ci, ci, ci, cf, cf, cf, cf, cf, cf,
-                                ci, ci, cf, cf, cf, cf, fp,
-                                vp, vp, vp, vp, cf, cf,
-                                vp, vp, vp, vp, vp, vp, vp]),
-    ("hsr_tsdf_count", ci, [ci, ci, ci, vp, vp, vp, vp]),
-    ("hsr_tsdf_faces", ci, [ci, ci, ci, vp, vp, vp, sz, vp,
-                            vp]),
-    ("hsr_tsdf_vertices", ci, [ci, ci, ci, cf, cf, cf, cf, sz, vp,
-                               vp, vp, vp, vp,
-                               vp, vp, vp, vp]),
-)
+        ("hsr_loss_tree_ce_scratch_bytes", sz, [ci, ci]),
+        ("hsr_loss_tree_ce_value", ci, [ci, ci, ci, ci, ip, vp, vp,
+                                        ci, vp, vp, vp, sz,
+                                        vp]),
+        ("hsr_loss_tree_ce_grad", ci, [ci, ci, ci, ci, ip, fp, vp,
+                                       vp, ci, vp, vp, vp,
+                                       vp, cf, vp, vp]),
+        ("hsr_loss_leaf_mlp_ce", ci, [ci, ci, ci, ci, vp, vp, vp, vp,
+                                      ci, vp, vp, vp, vp, vp,
+                                      sz, vp]),
+    ),
+    "hsr_densify.h": (
+        ("hsr_densify_scratch_bytes", sz, [ci, ci]),
+        ("hsr_densify_frame", ci, [ci, ci, vp, vp, vp, vp,
+                                   cf, cf, cf, cf, vp, cf, cf, ci,
+                                   vp, vp, vp, vp, vp,
+                                   vp, vp, vp, sz, vp]),
+        ("hsr_compact_scratch_bytes", sz, [ci]),
+        ("hsr_prune_mask", ci, [ci, ci, vp, vp, cf,
+                                cf, vp, vp, vp, sz, vp]),
+        ("hsr_compact_append_rows", ci, [ci, vp, ci, ci, C.POINTER(hsr_row_table), ci,
+                                         vp, vp, sz, vp]),
+    ),
+    "hsr_eval.h": (
+        ("hsr_eval_metrics_scratch_bytes", sz, [ci, ci]),
+        ("hsr_eval_frame_metrics", ci, [ci, ci, vp, vp, vp, vp,
+                                        vp, cf, vp, vp, sz, vp]),
+        ("hsr_eval_labels_flat", ci, [ci, ci, ci, vp, vp, vp]),
+        ("hsr_eval_labels_tree", ci, [ci, ci, ci, ci, ip, vp, vp,
+                                      vp, vp, vp]),
+        ("hsr_eval_leaf_scratch_bytes", sz, [ci]),
+        ("hsr_eval_labels_leaf", ci, [ci, ci, ci, ci, vp, vp, vp, vp,
+                                      vp, sz, vp]),
+        ("hsr_eval_iou_scratch_bytes", sz, [ci, ci]),
+        ("hsr_eval_iou_counts", ci, [ci, ci, vp, vp, ci, vp, vp,
+                                     ci, vp, vp, sz, vp]),
+        ("hsr_eval_frame_miou", ci, [ci, vp, vp, vp]),
+    ),
+    "hsr_optim.h": (
+        ("hsr_adam_table_entry_bytes", sz, []),
+        ("hsr_adam_step", ci, [ci, C.POINTER(hsr_adam_tensor), vp]),
+        ("hsr_track_keep_best", ci, [ci, ci, vp, vp, vp, vp,
+                                     vp, vp, vp]),
+    ),
+    "hsr_keyframes.h": (
+        ("hsr_kf_valid_rows", ci, [ci, ci, vp, vp, vp]),
+        ("hsr_kf_sample_scratch_bytes", sz, [ci]),
+        ("hsr_kf_sample_points", ci, [ci, ci, vp, vp, ci, vp, cf, cf,
+                                      cf, cf, vp, vp, vp, vp,
+                                      vp, vp, sz, vp]),
+        ("hsr_kf_round_keys", ci, [ci, vp, vp, vp]),
+        ("hsr_kf_overlap_counts", ci, [ci, vp, vp, ci, vp, vp, ci,
+                                       ci, ci, vp, vp]),
+    ),
+    # ---- extensions: the headers under include/ext/ ------------------------------------------------------------------------------------
+    "ext/hsr_msssim.h": (
+        ("hsr_eval_msssim_scratch_bytes", sz, [ci, ci]),
+        ("hsr_eval_msssim", ci, [ci, ci, vp, vp, vp, vp,
+                                 cf, vp, vp, sz, vp]),
+    ),
+    "ext/hsr_map_init.h": (
+        ("hsr_map_init_scratch_bytes", sz, [ci, ci]),
+        ("hsr_map_init_frame", ci, [ci, ci, vp, vp, cf, cf, cf, cf, vp,
+                                    cf, ci, ci, vp, vp, vp,
+                                    vp, vp, vp, vp,
+                                    vp, sz, vp]),
+    ),
+    "ext/hsr_frame_resample.h": (
+        ("hsr_frame_resample", ci, [ci, ci, vp, vp, ci, ci, vp, vp,
+                                    ci, ci, vp, vp, vp]),
+    ),
+    "ext/hsr_loss_outlier.h": (
+        ("hsr_loss_outlier_scratch_bytes", sz, [ci, ci]),
+        ("hsr_loss_outlier_median", ci, [ci, ci, vp, vp, vp, vp, sz,
+                                         vp]),
+        ("hsr_loss_outlier_value", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                        vp, cf, ci, ci, cf, cf, vp,
+                                        vp, vp, sz, vp]),
+        ("hsr_loss_outlier_grad", ci, [ci, ci, ci, vp, vp, vp, vp,
+                                       vp, cf, ci, cf, cf, vp,
+                                       vp, vp, vp, vp, vp]),
+    ),
+    "ext/hsr_frame_ingest.h": (
+        ("hsr_frame_ingest", ci, [ci, ci, vp, vp, ci, cd,
+                                  vp, ci, vp, ci,
+                                  ci, C.POINTER(hsr_ingest_level), vp, vp]),
+    ),
+    "ext/hsr_frame_export.h": (
+        ("hsr_frame_export", ci, [ci, ci, ci, C.POINTER(hsr_export_job), vp]),
+    ),
+    # the ingest with a source size per image
+    "ext/hsr_frame_ingest_planes.h": (
+        ("hsr_frame_ingest_planes", ci, [ci, ci, vp,
+                                         ci, ci, vp, ci, cd,
+                                         ci, ci, vp,
+                                         ci, vp, ci, ci,
+                                         ci, C.POINTER(hsr_ingest_level), vp, vp]),
+    ),
+    # the map as PLY records
+    "ext/hsr_map_export.h": (
+        ("hsr_map_export", ci, [C.POINTER(hsr_map_export_job), vp]),
+    ),
+    # rasterizer inputs from a given world-to-camera matrix and a view's hole counts
+    "ext/hsr_view.h": (
+        ("hsr_view_prep", ci, [ci, ci, ci, ci,
+                               vp, vp,
+                               vp, vp,
+                               vp,
+                               vp, vp, vp,
+                               vp, vp, vp]),
+        ("hsr_view_holes_scratch_bytes", sz, [ci, ci]),
+        ("hsr_view_holes", ci, [ci, ci, vp, vp, cf,
+                                vp, vp, sz, vp]),
+    ),
+    # the map as it stood at step t and a view's point cloud
+    "ext/hsr_replay.h": (
+        ("hsr_replay_plan_scratch_bytes", sz, [ci, ci]),
+        ("hsr_replay_plan", ci, [ci, ci, vp, vp,
+                                 vp, sz, vp]),
+        ("hsr_replay_select_scratch_bytes", sz, [ci]),
+        ("hsr_replay_select", ci, [ci, ci, ci, ci, ci, ci, ci,
+                                   vp, vp, vp, vp,
+                                   vp, vp, vp, vp,
+                                   vp, vp, vp, vp, vp,
+                                   vp, vp, vp, vp,
+                                   vp, sz, vp]),
+        ("hsr_replay_cloud", ci, [ci, ci, vp, vp, cf, cf, cf, cf,
+                                  vp, vp, vp, vp]),
+    ),
+    # a keyframe's planes as 8-/16-bit codes and back
+    "ext/hsr_keyframe_pack.h": (
+        ("hsr_keyframe_pack_scratch_bytes", sz, [ci, ci, ci]),
+        ("hsr_keyframe_pack", ci, [ci, ci, vp, vp, ci, vp, cd,
+                                   vp, vp, vp, vp,
+                                   vp, sz, vp]),
+        ("hsr_keyframe_unpack", ci, [ci, ci, vp, vp, ci, vp,
+                                     cd, vp, vp, vp, vp]),
+    ),
+    # depth fused into a signed distance volume and its surface (w2c is a HOST array)
+    "ext/hsr_tsdf.h": (
+        ("hsr_tsdf_integrate", ci, [ci, ci, ci, cf, cf, cf, cf, cf, cf,
+                                    ci, ci, cf, cf, cf, cf, fp,
+                                    vp, vp, vp, vp, cf, cf,
+                                    vp, vp, vp, vp, vp, vp, vp]),
+        ("hsr_tsdf_count", ci, [ci, ci, ci, vp, vp, vp, vp]),
+        ("hsr_tsdf_faces", ci, [ci, ci, ci, vp, vp, vp, sz, vp,
+                                vp]),
+        ("hsr_tsdf_vertices", ci, [ci, ci, ci, cf, cf, cf, cf, sz, vp,
+                                   vp, vp, vp, vp,
+                                   vp, vp, vp, vp]),
+    ),
+}
 
 
 def _load():
@@ -362,12 +353,10 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for name, restype, argtypes in (SIGNATURES + SIGNATURES_EXT + SIGNATURES_EXT_MAP_INIT + SIGNATURES_EXT_FRAME_RESAMPLE
-                                    + SIGNATURES_EXT_LOSS_OUTLIER + SIGNATURES_EXT_FRAME_INGEST + SIGNATURES_EXT_FRAME_EXPORT
-                                    + SIGNATURES_EXT_FRAME_INGEST_PLANES + SIGNATURES_EXT_MAP_EXPORT + SIGNATURES_EXT_VIEW
-                                    + SIGNATURES_EXT_REPLAY + SIGNATURES_EXT_KEYFRAME_PACK + SIGNATURES_EXT_TSDF):
-        fn = getattr(loaded, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in HEADERS.values():
+        for name, restype, argtypes in table:
+            fn = getattr(loaded, name)
+            fn.restype, fn.argtypes = restype, argtypes
     return loaded
 
 

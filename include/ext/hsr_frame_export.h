@@ -4,8 +4,8 @@
  * and depth images, :1314-1353 with semantic_label_vis / semantic_label_vis_replica :92-133 for the semantic maps coloured per tree
  * tuple, :1054, :1070, :1335 for the maps coloured per class).  The mirror image of hsr_frame_ingest.h: float maps back to 8-bit
  * interleaved images, all of a frame's pictures in one launch.  An extension under include/ext/: the prototypes under include/hsr_*.h
- * are a counted set (tests/test_abi.py); this one is bound from a table of its own, diff_gaussian_rasterization/_abi.py
- * SIGNATURES_EXT_FRAME_EXPORT.
+ * are a counted set (tests/test_abi.py); this one is bound under its key in diff_gaussian_rasterization/_abi.py
+ * HEADERS.
  *
  * One call is ONE launch for all n_jobs (1 .. HSR_EXPORT_MAX_JOBS) pictures of H x W pixels; the job structs travel by value in the
  * kernel's arguments.  No scratch, no allocation, no host synchronisation.  HSR_ERR_INVALID_ARGUMENT, and nothing launched, for: a

@@ -3,8 +3,8 @@
  * dataset objects do between a decoded image and the frame loop (datasets/gradslam_datasets/basedataset.py:223-227 and
  * scripts/hierslam.py:1777 for the colour image, basedataset.py:248-256 for the depth map, replica.py:241-299 and :369 for the labels),
  * once per size when tracking and densification have sizes of their own (scripts/hierslam.py:1543-1563).  An extension under
- * include/ext/: the prototypes under include/hsr_*.h are a counted set (tests/test_abi.py); this one is bound from a table of its own,
- * diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_FRAME_INGEST.
+ * include/ext/: the prototypes under include/hsr_*.h are a counted set (tests/test_abi.py); this one is bound under its key in
+ * diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * One call is ONE launch: an 8-bit interleaved colour image, a raw depth image and, optionally, a raw class-id image, all at the
  * sensor size Hs x Ws (hsr_frame_ingest_planes.h: the same with a size per image, and a leaf column in the label table), become n_out (1 .. HSR_INGEST_MAX_LEVELS) levels of float32 planar colour in 0..1 and float32 depth in

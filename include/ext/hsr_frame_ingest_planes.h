@@ -5,9 +5,9 @@
  * (basedataset.py:223-227 and scripts/hierslam.py:1777 for the colour image, basedataset.py:248-256 for the depth map,
  * scannet.py:284-339 for the labels; scripts/hierslam.py:1543-1563 for the sizes).  hsr_frame_ingest.h takes one sensor size for all
  * three images; this entry takes one per image and is otherwise that entry: the same kernel runs behind both.  It reuses
- * hsr_ingest_level, HSR_INGEST_DEPTH_* and HSR_INGEST_MAX_LEVELS of hsr_frame_ingest.h.  An extension under include/ext/, bound from a
- * table of its own, diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_FRAME_INGEST_PLANES (the header and the table of
- * hsr_frame_ingest are pinned to that one name by its suite).
+ * hsr_ingest_level, HSR_INGEST_DEPTH_* and HSR_INGEST_MAX_LEVELS of hsr_frame_ingest.h.  An extension under include/ext/, bound under
+ * its key in diff_gaussian_rasterization/_abi.py HEADERS (the header and the table of hsr_frame_ingest are pinned to that one name by
+ * its suite).
  *
  * One call is ONE launch: an 8-bit interleaved colour image [Hc,Wc,3], a raw depth image [Hd,Wd] and, optionally, a raw class-id
  * image [Hl,Wl] become n_out (1 .. HSR_INGEST_MAX_LEVELS) levels of float32 planar colour in 0..1 and float32 depth in metres, plus,

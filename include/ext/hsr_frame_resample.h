@@ -3,7 +3,7 @@
  * reference's second and third dataset objects deliver when tracking or densification run at a resolution of their own
  * (scripts/hierslam.py:1543-1563, :1680-1699, :1792-1799, :1933-1941; datasets/gradslam_datasets/basedataset.py:223-227 for the colour
  * image, :248-252 for the depth map).  An extension under include/ext/: the prototypes under include/hsr_*.h are a counted set
- * (tests/test_abi.py); this one is bound from a table of its own, diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_FRAME_RESAMPLE.
+ * (tests/test_abi.py); this one is bound under its key in diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * RESTATED, NOT PINNED BY cv2: the reference resizes with cv2.resize, which is not available to this project's tests.  Both rules
  * are restated below and checked against two independent float64 restatements (tests/resample_ref.py: torch F.interpolate, and

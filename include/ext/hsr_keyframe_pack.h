@@ -3,8 +3,8 @@
  * float32 depth and int64 label planes as 8-/16-bit codes, with a proof, from the same call, that the codes reproduce the planes bit
  * for bit.  The reference keeps every keyframe as float tensors (scripts/hierslam.py:2107-2124) and its checkpoint re-reads them from
  * the dataset (:1716-1752); a SLAM session that is to be saved and resumed keeps or writes them in this form (hsr_utils/checkpoint.py).
- * An extension under include/ext/: the prototypes under include/hsr_*.h are a counted set (tests/test_abi.py); these are bound from a
- * table of their own, diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_KEYFRAME_PACK.
+ * An extension under include/ext/: the prototypes under include/hsr_*.h are a counted set (tests/test_abi.py); these are bound under
+ * this header's key in diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * Why the codes can be exact: a frame that came through hsr_frame_ingest at sensor size has colour float(v) / 255.0f for an 8-bit v
  * and depth float(double(q) / depth_scale) for a 16-bit q (hsr_frame_ingest.h), and its labels are small non-negative integers.  The

@@ -6,8 +6,8 @@
  *     mask = mask & (curr_data['depth'] > 0)                                                                          :913
  *     mask = mask & ~torch.isnan(depth)                     [& (silhouette > sil_thres) if tracking and use_sil_for_loss]   :916-919
  * with the masked depth and colour terms of :925-935.  An extension under include/ext/: the prototypes under include/hsr_*.h are a
- * counted set (tests/test_abi.py); this one is bound from a table of its own, diff_gaussian_rasterization/_abi.py
- * SIGNATURES_EXT_LOSS_OUTLIER.  HSR_LOSS_SUM / HSR_LOSS_MEAN are those of hsr_losses.h.
+ * counted set (tests/test_abi.py); this one is bound under its key in diff_gaussian_rasterization/_abi.py
+ * HEADERS.  HSR_LOSS_SUM / HSR_LOSS_MEAN are those of hsr_losses.h.
  *
  * ERROR (:911).  e = fabsf(gt - d) * (gt > 0 ? 1.f : 0.f), in fp32, in that order, without contraction (csrc/hsr_loss_masked.hip, which
  * also holds hsr_loss_tracking_* of hsr_losses.h, is compiled with -ffp-contract=off).  NaN and inf travel as in torch: inf * 0 is NaN, and a NaN depth under a hole (gt <= 0) is still a NaN error.

@@ -4,7 +4,7 @@
  * save_ply_semantic :279-327 with transfer_tree_label :208-228 and semantic_label_vis :230-248, save_ply_semantic_multilevel :329-382.
  * hsr_frame_export.h's label rule, tuple table and class table turned on the map itself: the logits are row-major per Gaussian instead
  * of planar, and the output is packed PLY records.  An extension under include/ext/: the prototypes under include/hsr_*.h are a counted
- * set (tests/test_abi.py); this one is bound from a table of its own, diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_MAP_EXPORT.
+ * set (tests/test_abi.py); this one is bound under its key in diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * One call is ONE launch; the job struct travels by value in the kernel's arguments.  No scratch, no allocation, no host
  * synchronisation.  P = 0 succeeds and launches nothing: the checks below hold for it too, except that its pointers may be NULL, as

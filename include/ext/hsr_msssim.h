@@ -2,7 +2,7 @@
  * hsr_msssim.h — C ABI of the multi-scale SSIM of one evaluated frame (libhsr_rast.so): the `ms_ssim(...)` line of the reference's
  * per-frame evaluation (utils/eval_helpers.py:722, :946, :1272; masks :1259-1270), which the reference computes on the host after
  * copying both images there.  An extension of hsr_eval.h, in its own directory: the prototypes under include/hsr_*.h are a counted
- * set (tests/test_abi.py), these two are bound from the second table of diff_gaussian_rasterization/_abi.py (SIGNATURES_EXT).
+ * set (tests/test_abi.py), these two are bound under this header's key in diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * RESTATED, NOT PINNED BY THE REFERENCE'S PACKAGE: the reference calls pytorch_msssim.ms_ssim(data_range=1.0, size_average=True),
  * which is not available to this project's tests; the definition (Wang, Simoncelli, Bovik 2003) and that call's defaults are

@@ -4,8 +4,8 @@
  * final_recon.py do around their rasterizer calls for every step of a run: get_rendervars[_semantic]
  * (online_recon_sem_replica.py:100-158: `params['timestep'] <= curr_timestep`, a boolean index of every per-Gaussian tensor, then the
  * normalize / sigmoid / exp / tile chain) and rgbd2pcd (:220-259).  An extension under include/ext/: the prototypes under
- * include/hsr_*.h are a counted set (tests/test_abi.py); these are bound from a table of their own,
- * diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_REPLAY.
+ * include/hsr_*.h are a counted set (tests/test_abi.py); these are bound under this header's key in
+ * diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * All pointers are DEVICE pointers and contiguous; floats are fp32.  Everything runs on `stream`; nothing synchronises with the host
  * and nothing allocates.  Every refusal returns HSR_ERR_INVALID_ARGUMENT (-1) before any device work, with a message in

@@ -3,8 +3,8 @@
  * distance volume, and the volume's zero surface as a triangle mesh.  The reference has NO mesher — its family fuses the rendered depth
  * of the finished map with Open3D's TSDF integration and takes Open3D's mesh — so nothing here is pinned by reference outputs: every
  * rule below is RESTATED here, and tests/tsdf_ref.py restates it once more in numpy for the tests.  An extension under include/ext/: the
- * prototypes under include/hsr_*.h are a counted set (tests/test_abi.py); these are bound from a table of their own,
- * diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_TSDF.
+ * prototypes under include/hsr_*.h are a counted set (tests/test_abi.py); these are bound under this header's key in
+ * diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * All pointers are DEVICE pointers and contiguous, except `w2c`: a HOST array of 16 floats (row-major world-to-camera, rows 0..2 are
  * read) that is copied into the kernel arguments by value.  Everything runs on `stream`; no entry point allocates or synchronises with

@@ -3,8 +3,8 @@
  * instead of a column of the pose parameters, and the hole count that decides whether such a view is scored.  What the reference's
  * eval_nvs runs per view around its two rasterizer calls (utils/eval_helpers.py:1692-1720 in front, :1726-1738 behind), and what its
  * viz_scripts do before they draw (get_rendervars(params, w2c, ...)).  An extension under include/ext/: the prototypes under
- * include/hsr_*.h are a counted set (tests/test_abi.py); these are bound from a table of their own,
- * diff_gaussian_rasterization/_abi.py SIGNATURES_EXT_VIEW.
+ * include/hsr_*.h are a counted set (tests/test_abi.py); these are bound under this header's key in
+ * diff_gaussian_rasterization/_abi.py HEADERS.
  *
  * All pointers are DEVICE pointers, fp32 (out2: int64) and contiguous.  Everything runs on `stream`; nothing synchronises with the
  * host and nothing allocates.  Errors: return <0 and hsr_last_error() (hsr_rasterizer.h).

@@ -1,6 +1,6 @@
-"""CPU suite: the C-ABI library loads and exports exactly what include/hsr_*.h declare, the ctypes signatures, structures and limits
-of diff_gaussian_rasterization/_abi.py agree with the headers type class by type class, and host-only entry points behave (no compute
-calls: there is no GPU here)."""
+"""CPU suite: the C-ABI library loads and exports exactly what include/hsr_*.h and include/ext/*.h declare, the ctypes signatures,
+structures and limits of diff_gaussian_rasterization/_abi.py agree with the headers type class by type class, and host-only entry
+points behave (no compute calls: there is no GPU here).  A header is named by its path under include/, the key of _abi.HEADERS."""
 import ctypes as C
 import glob
 import os
@@ -10,11 +10,23 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = sorted(glob.glob(os.path.join(ROOT, "include", "hsr_*.h")))    # a glob: the next header is covered without an edit
-N_PROTOTYPES = 64      # asserted as a number: a regex that silently stops matching must not pass
+INCLUDE = os.path.join(ROOT, "include")
+# globs: the next header is covered without an edit
+HEADERS = sorted(os.path.relpath(p, INCLUDE) for p in glob.glob(os.path.join(INCLUDE, "hsr_*.h")))
+ALL_HEADERS = HEADERS + sorted(os.path.relpath(p, INCLUDE).replace(os.sep, "/") for p in glob.glob(os.path.join(INCLUDE, "ext", "*.h")))
+# asserted as numbers: a regex that silently stops matching must not pass
+PROTOTYPE_COUNTS = {
+    "hsr_rasterizer.h": 24, "hsr_frame_prep.h": 4, "hsr_losses.h": 14, "hsr_densify.h": 5, "hsr_eval.h": 9, "hsr_optim.h": 3,
+    "hsr_keyframes.h": 5,
+    "ext/hsr_msssim.h": 2, "ext/hsr_map_init.h": 2, "ext/hsr_frame_resample.h": 1, "ext/hsr_loss_outlier.h": 4,
+    "ext/hsr_frame_ingest.h": 1, "ext/hsr_frame_export.h": 1, "ext/hsr_frame_ingest_planes.h": 1, "ext/hsr_map_export.h": 1,
+    "ext/hsr_view.h": 3, "ext/hsr_replay.h": 5, "ext/hsr_keyframe_pack.h": 3, "ext/hsr_tsdf.h": 4,
+}
+N_PROTOTYPES = 64      # those of include/hsr_*.h
+N_ALL_PROTOTYPES = 92
 
-# what the four older headers declare at least (the newer three are pinned exactly, each in its own suite: test_eval_cpu.py,
-# test_optim_cpu.py, test_keyframes_cpu.py)
+# what the four older headers declare at least (the newer ones are pinned by name, each in its own suite: test_eval_cpu.py,
+# test_optim_cpu.py, test_keyframes_cpu.py and the suites of the headers under include/ext/)
 DECLARED = {
     "hsr_rasterizer.h": {
         "hsr_forward", "hsr_forward_semantic", "hsr_backward", "hsr_backward_semantic", "hsr_mark_visible", "hsr_required_geometry_bytes",
@@ -32,8 +44,9 @@ DECLARED = {
 SCALARS = {"int": "int", "unsigned": "unsigned", "float": "float", "double": "double", "size_t": "size_t"}
 
 
-def _source(path):
-    return re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
+def _source(header):
+    """a header's text without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
 
 
 def _classify(decl, named):
@@ -52,16 +65,28 @@ def _classify(decl, named):
     return SCALARS[words[0]]
 
 
-def _prototypes():
-    """every function prototype of every header: name -> (header file name, class of the return type, [class of each parameter])"""
+def _prototypes(headers=HEADERS):
+    """every function prototype of the given headers, in their order: name -> (header, class of the return type, [class of each
+    parameter])"""
     protos = {}
-    for path in HEADERS:
-        for m in re.finditer(r"^((?:const\s+)?\w+\s*\*?)\s*(hsr_\w+)\s*\(([^;{}()]*)\)\s*;", _source(path), flags=re.M):
+    for header in headers:
+        for m in re.finditer(r"^((?:const\s+)?\w+\s*\*?)\s*(hsr_\w+)\s*\(([^;{}()]*)\)\s*;", _source(header), flags=re.M):
             ret, name, params = m.group(1), m.group(2), m.group(3).strip()
             assert name not in protos, name
             params = [] if params in ("", "void") else [_classify(p, True) for p in params.split(",")]
-            protos[name] = (os.path.basename(path), _classify(ret, False), params)
+            protos[name] = (header, _classify(ret, False), params)
     return protos
+
+
+def _structures(headers=ALL_HEADERS):
+    """every `typedef struct` of the given headers: name -> [field names in order]; an array member `int sizes[16]` is `sizes`"""
+    structs = {}
+    for header in headers:
+        for m in re.finditer(r"typedef struct (hsr_\w+) \{(.*?)\} \1;", _source(header), flags=re.S):
+            assert m.group(1) not in structs, m.group(1)
+            structs[m.group(1)] = [re.search(r"(\w+)\s*(?:\[\w+\])?\s*$", d).group(1)
+                                   for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
+    return structs
 
 
 def _ctype_class(t):
@@ -98,14 +123,40 @@ def check_signature(name, proto):
 
 
 def check_header(header):
-    """every prototype of include/<header> is exported by the library and bound with the header's types; returns their names"""
+    """every prototype of include/<header> is exported by the library and bound with the header's types; returns their names in the
+    header's order"""
     from diff_gaussian_rasterization import _C
-    protos = {n: p for n, p in _prototypes().items() if p[0] == header}
+    protos = _prototypes([header])
     lib = C.CDLL(_C._LIB_PATH)
     for name, proto in protos.items():
         assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
         check_signature(name, proto)
-    return set(protos)
+    return list(protos)
+
+
+@pytest.mark.parametrize("header", ALL_HEADERS)
+def test_header_is_bound_under_its_key(header):
+    """the one header check: the header has a key in _abi.HEADERS whose names are its prototypes in its order (so that a line can be
+    read against its prototype), as many as are pinned; the library exports each and each is bound with the header's type classes
+    (int / unsigned / float / double / size_t / const char* / pointer): ctypes converts silently, so a c_int where the header says
+    float would hand a kernel a wrong value and nothing else would notice"""
+    from diff_gaussian_rasterization import _abi
+    assert header in _abi.HEADERS, "no key %r in _abi.HEADERS" % header
+    names = list(_prototypes([header]))
+    assert header in PROTOTYPE_COUNTS and len(names) == PROTOTYPE_COUNTS[header], (header, len(names))
+    assert [s[0] for s in _abi.HEADERS[header]] == names, header
+    assert check_header(header) == names
+
+
+def test_tables_cover_the_headers_and_bind_every_name_once():
+    """a header without a table fails and a table without a header fails; no function name occurs twice across all tables, whichever
+    two they are in"""
+    from diff_gaussian_rasterization import _abi
+    assert len(ALL_HEADERS) == len(set(ALL_HEADERS)) >= 19
+    assert set(_abi.HEADERS) == set(ALL_HEADERS) == set(PROTOTYPE_COUNTS), set(_abi.HEADERS) ^ set(ALL_HEADERS)
+    names = [s[0] for table in _abi.HEADERS.values() for s in table]
+    assert sorted(names) == sorted(set(names)), sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(names) == len(_prototypes(ALL_HEADERS)) == sum(PROTOTYPE_COUNTS.values()) == N_ALL_PROTOTYPES
 
 
 def test_library_exports_every_declared_symbol():
@@ -120,35 +171,33 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_signatures_match_header():
-    """every prototype has a declared signature whose restype and argtypes agree with it class by class (int / unsigned / float /
-    double / size_t / const char* / pointer): ctypes converts silently, so a c_int where the header says float would hand a kernel a
-    wrong value and nothing else would notice"""
+    """the tables of include/hsr_*.h taken together: every prototype once and nothing else, each header's functions in the header's
+    order, every signature agreeing with its prototype class by class"""
     from diff_gaussian_rasterization import _abi
     protos = _prototypes()
-    table = [s[0] for s in _abi.SIGNATURES]
+    table = [s[0] for header in HEADERS for s in _abi.HEADERS[header]]
     assert sorted(table) == sorted(protos), set(table) ^ set(protos)      # every prototype once, nothing else
-    for path in HEADERS:      # and each header's functions in the header's order, so that a line can be read against its prototype
-        of_header = [n for n, p in protos.items() if p[0] == os.path.basename(path)]
-        assert [n for n in table if n in of_header] == of_header, path
+    for header in HEADERS:
+        of_header = [n for n, p in protos.items() if p[0] == header]
+        assert [n for n in table if n in of_header] == of_header, header
     for name, proto in protos.items():
         check_signature(name, proto)
 
 
 def test_structures_match_header():
-    """the six ctypes structures carry the field names of their typedefs, in order; the Adam entry keeps the library's size"""
+    """the nine ctypes structures carry the field names of their typedefs, in order; the Adam entry keeps the library's size"""
     from diff_gaussian_rasterization import _C, _abi
     from hsr_utils import optim, slam_external
-    src = "\n".join(_source(h) for h in HEADERS)
     checked = set()
-    for m in re.finditer(r"typedef struct (hsr_\w+) \{(.*?)\} \1;", src, flags=re.S):
-        mirror = getattr(_abi, m.group(1), None)
+    for name, fields in _structures(ALL_HEADERS).items():
+        mirror = getattr(_abi, name, None)
         if mirror is None:
+            assert name == "hsr_profile", name      # the one typedef without a mirror
             continue
-        names = [re.search(r"(\w+)\s*$", d).group(1) for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
-        assert names == [f[0] for f in mirror._fields_], m.group(1)
+        assert fields == [f[0] for f in mirror._fields_], name
         checked.add(mirror)
     assert checked == {_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout, _abi.hsr_adam_tensor, _abi.hsr_row_table,
-                       _abi.hsr_backward_plan}
+                       _abi.hsr_backward_plan, _abi.hsr_ingest_level, _abi.hsr_export_job, _abi.hsr_map_export_job}
     assert (_C._HsrBuffer, _C._Ticket, _C._StateLayout) == (_abi.hsr_buffer, _abi.hsr_ticket, _abi.hsr_state_layout)
     assert optim._AdamTensor is _abi.hsr_adam_tensor and slam_external._RowTable is _abi.hsr_row_table
     assert _abi.lib.hsr_adam_table_entry_bytes() == C.sizeof(_abi.hsr_adam_tensor) == 64

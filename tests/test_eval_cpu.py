@@ -129,7 +129,7 @@ def test_tree_lookup_table_missing_and_duplicate():
 def test_eval_abi_exported_and_bound():
     assert {"hsr_eval_frame_metrics", "hsr_eval_labels_flat", "hsr_eval_labels_tree", "hsr_eval_labels_leaf", "hsr_eval_iou_counts",
             "hsr_eval_frame_miou", "hsr_eval_metrics_scratch_bytes", "hsr_eval_leaf_scratch_bytes",
-            "hsr_eval_iou_scratch_bytes"} <= check_header("hsr_eval.h")
+            "hsr_eval_iou_scratch_bytes"} <= set(check_header("hsr_eval.h"))
 
 
 def test_scratch_sizes_host_only():

@@ -1,9 +1,8 @@
-"""CPU suite for the export of an evaluated frame's pictures: the prototype of include/ext/hsr_frame_export.h (exported and bound with
-the header's types: the checker of tests/test_abi.py, pointed at the extension header), its argument checks, the three host-built
+"""CPU suite for the export of an evaluated frame's pictures: the prototype of include/ext/hsr_frame_export.h (its name, type classes
+and job structure; tests/test_abi.py checks that it is exported and bound with the header's types), its argument checks, the three host-built
 colour tables of hsr_utils.export, and the numpy restatement of the header (tests/export_ref.py) against a literal restatement of the
 reference's lines.  Nothing here launches: there is no GPU."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -13,33 +12,22 @@ import torch
 import export_ref as X
 import test_abi
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_frame_export.h")
+EXT_HEADER = "ext/hsr_frame_export.h"
 
 
-def test_frame_export_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert [s[0] for s in _abi.SIGNATURES_EXT_FRAME_EXPORT] == list(protos) == ["hsr_frame_export"]
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, proto in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        test_abi.check_signature(name, proto)
+def test_frame_export_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos) == ["hsr_frame_export"]
     assert protos["hsr_frame_export"][2] == ["int", "int", "int", ("pointer", "hsr_export_job"), ("pointer", "void")]
-    others = set()
-    for table in (_abi.SIGNATURES, _abi.SIGNATURES_EXT, _abi.SIGNATURES_EXT_MAP_INIT, _abi.SIGNATURES_EXT_FRAME_RESAMPLE,
-                  _abi.SIGNATURES_EXT_LOSS_OUTLIER, _abi.SIGNATURES_EXT_FRAME_INGEST):
-        others |= {s[0] for s in table}
-    assert not others & set(protos)
     # the structure carries the field names of its typedef, in order, and the C layout
-    src = test_abi._source(EXT_HEADER)
-    m = re.search(r"typedef struct (hsr_\w+) \{(.*?)\} \1;", src, flags=re.S)
-    names = [re.search(r"(\w+)\s*(?:\[\d+\])?\s*$", d).group(1) for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
-    assert m.group(1) == "hsr_export_job"
-    assert names == [f[0] for f in _abi.hsr_export_job._fields_] == ["kind", "src", "table", "n", "K", "L", "sizes", "lo", "hi", "out"]
+    structs = test_abi._structures([EXT_HEADER])
+    assert list(structs) == ["hsr_export_job"]
+    assert structs["hsr_export_job"] == [f[0] for f in _abi.hsr_export_job._fields_] == ["kind", "src", "table", "n", "K", "L", "sizes", "lo",
+                                                                                         "hi", "out"]
     assert C.sizeof(_abi.hsr_export_job) == 120 and _abi.hsr_export_job.sizes.offset == 36 and _abi.hsr_export_job.out.offset == 112
     from hsr_utils import evaluate, export, slam
-    defines = dict(re.findall(r"^#define\s+(HSR_\w+)\s+(\d+)\s*$", src, flags=re.M))
+    defines = dict(re.findall(r"^#define\s+(HSR_\w+)\s+(\d+)\s*$", test_abi._source(EXT_HEADER), flags=re.M))
     assert export.EXPORT_MAX_JOBS == int(defines["HSR_EXPORT_MAX_JOBS"]) == 8 == len(export.PICTURES)
     assert (export.COLOR, export.DEPTH, export.LABELS, export.LEVELS, export.LOGITS) == tuple(
         int(defines["HSR_EXPORT_" + k]) for k in ("COLOR", "DEPTH", "LABELS", "LEVELS", "LOGITS")) == (0, 1, 2, 3, 4)

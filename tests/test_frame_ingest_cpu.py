@@ -1,5 +1,5 @@
-"""CPU suite for the ingest of raw sensor frames: the prototype of include/ext/hsr_frame_ingest.h (exported and bound with the header's
-types: the checker of tests/test_abi.py, pointed at the extension header), its argument checks, the numpy restatement of the header
+"""CPU suite for the ingest of raw sensor frames: the prototype of include/ext/hsr_frame_ingest.h (its name, type classes and level
+structure; tests/test_abi.py checks that it is exported and bound with the header's types), its argument checks, the numpy restatement of the header
 (tests/ingest_ref.py) against the two independent float64 restatements of tests/resample_ref.py, tree_label_table, the Replica-layout
 reader of hsr_utils.sequence on a directory the test writes, and the argument errors of ingest_frame and SlamSession.ingest that need
 no device.  Nothing here launches: there is no GPU."""
@@ -16,33 +16,22 @@ import ingest_ref as I
 import resample_ref as R
 import test_abi
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_frame_ingest.h")
+EXT_HEADER = "ext/hsr_frame_ingest.h"
 IDS = ["%dx%d-%dx%d" % (s + d) for s, d in R.SIZE_PAIRS]
 
 
-def test_frame_ingest_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert [s[0] for s in _abi.SIGNATURES_EXT_FRAME_INGEST] == list(protos) == ["hsr_frame_ingest"]
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, proto in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        test_abi.check_signature(name, proto)
+def test_frame_ingest_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos) == ["hsr_frame_ingest"]
     assert protos["hsr_frame_ingest"][2][5] == "double" and protos["hsr_frame_ingest"][2][11] == ("pointer", "hsr_ingest_level")
-    others = set()
-    for table in (_abi.SIGNATURES, _abi.SIGNATURES_EXT, _abi.SIGNATURES_EXT_MAP_INIT, _abi.SIGNATURES_EXT_FRAME_RESAMPLE,
-                  _abi.SIGNATURES_EXT_LOSS_OUTLIER):
-        others |= {s[0] for s in table}
-    assert not others & set(protos)
     # the structure carries the field names of its typedef, in order, and the C layout
-    src = test_abi._source(EXT_HEADER)
-    m = re.search(r"typedef struct (hsr_\w+) \{(.*?)\} \1;", src, flags=re.S)
-    names = [re.search(r"(\w+)\s*$", d).group(1) for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
-    assert m.group(1) == "hsr_ingest_level" and names == [f[0] for f in _abi.hsr_ingest_level._fields_] == ["H", "W", "color", "depth"]
+    structs = test_abi._structures([EXT_HEADER])
+    assert list(structs) == ["hsr_ingest_level"]
+    assert structs["hsr_ingest_level"] == [f[0] for f in _abi.hsr_ingest_level._fields_] == ["H", "W", "color", "depth"]
     assert C.sizeof(_abi.hsr_ingest_level) == 24
     from hsr_utils import evaluate, frames, slam
-    defines = dict(re.findall(r"^#define\s+(HSR_\w+)\s+(\d+)\s*$", src, flags=re.M))
+    defines = dict(re.findall(r"^#define\s+(HSR_\w+)\s+(\d+)\s*$", test_abi._source(EXT_HEADER), flags=re.M))
     assert frames.INGEST_MAX_LEVELS == int(defines["HSR_INGEST_MAX_LEVELS"]) == 3
     assert (frames.DEPTH_U16, frames.DEPTH_I32, frames.DEPTH_F32) == tuple(
         int(defines["HSR_INGEST_DEPTH_" + k]) for k in ("U16", "I32", "F32")) == (0, 1, 2)

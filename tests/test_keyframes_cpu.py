@@ -99,7 +99,7 @@ def test_selection_order_is_stable_descending():
 
 def test_keyframes_abi_exported_and_bound():
     assert {"hsr_kf_valid_rows", "hsr_kf_sample_points", "hsr_kf_sample_scratch_bytes", "hsr_kf_round_keys",
-            "hsr_kf_overlap_counts"} == check_header("hsr_keyframes.h")
+            "hsr_kf_overlap_counts"} == set(check_header("hsr_keyframes.h"))
 
 
 def test_argument_validation_without_gpu():

@@ -1,10 +1,9 @@
-"""CPU suite for the device export of the map as PLY records: the prototype of include/ext/hsr_map_export.h (exported and bound with the
-header's types: the checker of tests/test_abi.py, pointed at the extension header), the job structure's layout, every refusal of the
+"""CPU suite for the device export of the map as PLY records: the prototype of include/ext/hsr_map_export.h (its name and type classes;
+tests/test_abi.py checks that it is exported and bound with the header's types), the job structure's layout, every refusal of the
 header, the host-built colour table of the per-level export against a literal restatement of the reference's lines, and the numpy
 restatement of the header (tests/map_export_ref.py) against the host writers hsr_utils.map_io.save_ply / save_ply_semantic, byte for
 byte.  Nothing here launches: there is no GPU."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -14,40 +13,27 @@ import torch
 import map_export_ref as R
 import test_abi
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_map_export.h")
+EXT_HEADER = "ext/hsr_map_export.h"
 FIELDS = ["P", "S", "record", "colour", "means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales", "normals", "colours",
           "labels", "semantic", "table", "n", "K", "L", "sizes", "out", "out_labels"]
 POINTERS = ("means3D", "rgb_colors", "unnorm_rotations", "logit_opacities", "log_scales", "normals", "colours", "labels", "semantic",
             "table", "out", "out_labels")
 
 
-def test_map_export_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert [s[0] for s in _abi.SIGNATURES_EXT_MAP_EXPORT] == list(protos) == ["hsr_map_export"]
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, proto in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        test_abi.check_signature(name, proto)
+def test_map_export_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos) == ["hsr_map_export"]
     assert protos["hsr_map_export"][2] == [("pointer", "hsr_map_export_job"), ("pointer", "void")]
-    others = set()
-    for table in (_abi.SIGNATURES, _abi.SIGNATURES_EXT, _abi.SIGNATURES_EXT_MAP_INIT, _abi.SIGNATURES_EXT_FRAME_RESAMPLE,
-                  _abi.SIGNATURES_EXT_LOSS_OUTLIER, _abi.SIGNATURES_EXT_FRAME_INGEST, _abi.SIGNATURES_EXT_FRAME_EXPORT,
-                  _abi.SIGNATURES_EXT_FRAME_INGEST_PLANES):
-        others |= {s[0] for s in table}
-    assert len(others) > 70 and not others & set(protos)
     # the structure carries the field names of its typedef, in order, and the C layout
-    src = test_abi._source(EXT_HEADER)
-    m = re.search(r"typedef struct (hsr_\w+) \{(.*?)\} \1;", src, flags=re.S)
-    names = [re.search(r"(\w+)\s*(?:\[\d+\])?\s*$", d).group(1) for stmt in m.group(2).split(";") if stmt.strip() for d in stmt.split(",")]
+    structs = test_abi._structures([EXT_HEADER])
     job = _abi.hsr_map_export_job
-    assert m.group(1) == "hsr_map_export_job"
-    assert names == [f[0] for f in job._fields_] == FIELDS
+    assert list(structs) == ["hsr_map_export_job"]
+    assert structs["hsr_map_export_job"] == [f[0] for f in job._fields_] == FIELDS
     assert C.sizeof(job) == 192 and job.means3D.offset == 16 and job.table.offset == 88 and job.n.offset == 96
     assert job.sizes.offset == 108 and job.out.offset == 176 and job.out_labels.offset == 184
     from hsr_utils import evaluate, map_export
-    defines = dict(re.findall(r"^#define\s+(HSR_\w+)\s+(\d+)\s*$", src, flags=re.M))
+    defines = dict(re.findall(r"^#define\s+(HSR_\w+)\s+(\d+)\s*$", test_abi._source(EXT_HEADER), flags=re.M))
     assert map_export.MAP_EXPORT_MAX_P == int(defines["HSR_MAP_EXPORT_MAX_P"]) == (2 ** 31 - 1) // 68
     assert (map_export.RECORD_SH, map_export.RECORD_RGB8, map_export.RECORD_NONE) == tuple(
         int(defines["HSR_MAP_RECORD_" + k]) for k in ("SH", "RGB8", "NONE")) == (0, 1, 2)

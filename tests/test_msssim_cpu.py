@@ -1,13 +1,11 @@
 """CPU suite for the multi-scale SSIM: the checker's two float64 restatements (tests/msssim_ref.py) agree, identical images score
-exactly 1, a pool without the front padding is told apart, and the prototypes of include/ext/hsr_msssim.h are exported and bound
-with the header's types (the checker of tests/test_abi.py, pointed at the extension header).
+exactly 1, a pool without the front padding is told apart, and the prototypes of include/ext/hsr_msssim.h are the two named
+here (tests/test_abi.py checks that they are exported and bound with the header's types).
 
 For the tile suite (tests/test_gpu_msssim_tiles.py) it also holds the conditions on that suite's inputs that need no GPU: the scratch
 size equals the restated layout, the sizes reach every class of last tile and level parity, the explicit-slice maps reproduce the
 float64 reference, and a deliberately wrong restatement (one changed pixel of any level; a pool without the front padding) moves a tile sum past the
 tile budget."""
-import ctypes as C
-import os
 import re
 
 import numpy as np
@@ -18,7 +16,7 @@ import torch.nn.functional as F
 import msssim_ref as R
 import test_abi
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_msssim.h")
+EXT_HEADER = "ext/hsr_msssim.h"
 CASES = R.cases()
 TILE_CASES = R.tile_cases()
 
@@ -59,17 +57,11 @@ def test_floor_pooling_is_told_apart(case):
     assert dist > 1e-3
 
 
-def test_msssim_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert sorted(protos) == sorted(s[0] for s in _abi.SIGNATURES_EXT) == ["hsr_eval_msssim", "hsr_eval_msssim_scratch_bytes"]
-    assert [s[0] for s in _abi.SIGNATURES_EXT] == list(protos)      # in the header's order
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, proto in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        test_abi.check_signature(name, proto)
-    assert not {s[0] for s in _abi.SIGNATURES} & set(protos)
+def test_msssim_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert sorted(protos) == sorted(s[0] for s in _abi.HEADERS[EXT_HEADER]) == ["hsr_eval_msssim", "hsr_eval_msssim_scratch_bytes"]
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos)      # in the header's order
 
 
 def test_python_limits_equal_header_defines():

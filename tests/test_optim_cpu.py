@@ -14,7 +14,7 @@ HEADER = os.path.join(ROOT, "include", "hsr_optim.h")
 
 
 def test_header_prototypes_are_exported_and_bound():
-    assert check_header("hsr_optim.h") == {"hsr_adam_table_entry_bytes", "hsr_adam_step", "hsr_track_keep_best"}
+    assert check_header("hsr_optim.h") == ["hsr_adam_table_entry_bytes", "hsr_adam_step", "hsr_track_keep_best"]
 
 
 def test_table_entry_layout_matches_the_library():

@@ -1,8 +1,7 @@
-"""CPU suite for the replay of a finished run: the prototypes of include/ext/hsr_replay.h (exported and bound with the header's types:
-the checker of tests/test_abi.py, pointed at the extension header), every refusal of the header with dummy pointers, the empty map, the
+"""CPU suite for the replay of a finished run: the prototypes of include/ext/hsr_replay.h (their names and type classes; tests/test_abi.py
+checks that they are exported and bound with the header's types), every refusal of the header with dummy pointers, the empty map, the
 scratch sizes, the pose and trajectory helpers against the reference's expressions, the lazy names and every host argument error.
 Nothing here launches: there is no GPU."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -12,33 +11,22 @@ import torch
 import replay_ref as R
 import test_abi
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_replay.h")
+EXT_HEADER = "ext/hsr_replay.h"
 NAMES = ["hsr_replay_plan_scratch_bytes", "hsr_replay_plan", "hsr_replay_select_scratch_bytes", "hsr_replay_select", "hsr_replay_cloud"]
 FP, VP = ("pointer", "float"), ("pointer", "void")
 
 
-def test_replay_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert [s[0] for s in _abi.SIGNATURES_EXT_REPLAY] == list(protos) == NAMES
+def test_replay_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos) == NAMES
     assert all(n.startswith("hsr_replay_") for n in NAMES)
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, proto in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        test_abi.check_signature(name, proto)
     assert protos["hsr_replay_plan_scratch_bytes"][1:] == ("size_t", ["int", "int"])
     assert protos["hsr_replay_plan"][1:] == ("int", ["int", "int", FP, ("pointer", "int64_t"), ("pointer", "char"), "size_t", VP])
     assert protos["hsr_replay_select_scratch_bytes"][1:] == ("size_t", ["int"])
     assert protos["hsr_replay_select"][1:] == ("int", ["int"] * 7 + [FP] * 8 + [FP] * 7 + [("pointer", "int")] * 2 + [("pointer", "char"), "size_t", VP])
     assert protos["hsr_replay_cloud"][1:] == ("int", ["int", "int", FP, ("pointer", "uint8_t"), "float", "float", "float", "float", FP, FP,
                                                      ("pointer", "uint8_t"), VP])
-    others = set()
-    for table in (_abi.SIGNATURES, _abi.SIGNATURES_EXT, _abi.SIGNATURES_EXT_MAP_INIT, _abi.SIGNATURES_EXT_FRAME_RESAMPLE,
-                  _abi.SIGNATURES_EXT_LOSS_OUTLIER, _abi.SIGNATURES_EXT_FRAME_INGEST, _abi.SIGNATURES_EXT_FRAME_EXPORT,
-                  _abi.SIGNATURES_EXT_FRAME_INGEST_PLANES, _abi.SIGNATURES_EXT_MAP_EXPORT, _abi.SIGNATURES_EXT_VIEW):
-        others |= {s[0] for s in table}
-    assert len(others) > 73 and not others & set(protos)
     from hsr_utils import replay
     assert "#define HSR_REPLAY_MAX_STEPS (1 << 20)" in test_abi._source(EXT_HEADER) and replay.REPLAY_MAX_STEPS == 1 << 20
 

@@ -1,9 +1,8 @@
-"""CPU suite for the ScanNet ingest: the prototype of include/ext/hsr_frame_ingest_planes.h (exported and bound with the header's
-types, the checker of tests/test_abi.py pointed at the extension header), the entry's refusals, composed_label_table against a literal
+"""CPU suite for the ScanNet ingest: the prototype of include/ext/hsr_frame_ingest_planes.h (its name and type classes;
+tests/test_abi.py checks that it is exported and bound with the header's types), the entry's refusals, composed_label_table against a literal
 restatement of the reference's loops of masked assignments (tests/ingest_planes_ref.py), the two tsv readers and ScanNetSequence on
 files the tests write, the argument errors of ingest_frame_planes, and the routing of SlamSession.ingest between the two ingest
 functions.  Nothing here launches: there is no GPU."""
-import ctypes as C
 import inspect
 import os
 
@@ -15,25 +14,16 @@ import ingest_planes_ref as P
 import ingest_ref as I
 import test_abi
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_frame_ingest_planes.h")
+EXT_HEADER = "ext/hsr_frame_ingest_planes.h"
 NAME = "hsr_frame_ingest_planes"
 
 
-def test_frame_ingest_planes_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert [s[0] for s in _abi.SIGNATURES_EXT_FRAME_INGEST_PLANES] == list(protos) == [NAME]
-    lib = C.CDLL(_C._LIB_PATH)
-    assert hasattr(lib, NAME), "libhsr_rast.so does not export %s" % NAME
-    test_abi.check_signature(NAME, protos[NAME])
+def test_frame_ingest_planes_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos) == [NAME]
     params = protos[NAME][2]
     assert len(params) == 19 and params[7] == "double" and params[16] == ("pointer", "hsr_ingest_level") and params[14] == "int"
-    others = set()
-    for table in (_abi.SIGNATURES, _abi.SIGNATURES_EXT, _abi.SIGNATURES_EXT_MAP_INIT, _abi.SIGNATURES_EXT_FRAME_RESAMPLE,
-                  _abi.SIGNATURES_EXT_LOSS_OUTLIER, _abi.SIGNATURES_EXT_FRAME_INGEST, _abi.SIGNATURES_EXT_FRAME_EXPORT):
-        others |= {s[0] for s in table}
-    assert not others & set(protos)
     # the header reuses the structure and the defines of hsr_frame_ingest.h and declares none of its own
     src = test_abi._source(EXT_HEADER)
     assert '#include "hsr_frame_ingest.h"' in src and "typedef" not in src and "#define HSR_INGEST" not in src

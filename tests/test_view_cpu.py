@@ -1,8 +1,7 @@
-"""CPU suite for the novel-view path: the prototypes of include/ext/hsr_view.h (exported and bound with the header's types: the checker of
-tests/test_abi.py, pointed at the extension header), every refusal of the header, the quaternion rule against build_rotation, the host
+"""CPU suite for the novel-view path: the prototypes of include/ext/hsr_view.h (their names and type classes; tests/test_abi.py checks
+that they are exported and bound with the header's types), every refusal of the header, the quaternion rule against build_rotation, the host
 validity rule against torch's own expression, the Replica-V2 reader on a directory of tiny PNGs, and the argument errors of
 render_view / evaluate_novel_views.  Nothing here launches: there is no GPU."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -12,31 +11,20 @@ import torch
 import test_abi
 import view_ref as R
 
-EXT_HEADER = os.path.join(test_abi.ROOT, "include", "ext", "hsr_view.h")
+EXT_HEADER = "ext/hsr_view.h"
 NAMES = ["hsr_view_prep", "hsr_view_holes_scratch_bytes", "hsr_view_holes"]
 
 
-def test_view_abi_exported_and_bound(monkeypatch):
-    from diff_gaussian_rasterization import _C, _abi
-    monkeypatch.setattr(test_abi, "HEADERS", [EXT_HEADER])
-    protos = test_abi._prototypes()
-    assert [s[0] for s in _abi.SIGNATURES_EXT_VIEW] == list(protos) == NAMES
-    lib = C.CDLL(_C._LIB_PATH)
-    for name, proto in protos.items():
-        assert hasattr(lib, name), "libhsr_rast.so does not export %s" % name
-        test_abi.check_signature(name, proto)
+def test_view_abi_exported_and_bound():
+    from diff_gaussian_rasterization import _abi
+    protos = test_abi._prototypes([EXT_HEADER])
+    assert [s[0] for s in _abi.HEADERS[EXT_HEADER]] == list(protos) == NAMES
     assert protos["hsr_view_prep"][1] == "int" and protos["hsr_view_prep"][2] == ["int"] * 4 + [("pointer", "float")] * 10 + [("pointer", "void")]
     assert protos["hsr_view_holes_scratch_bytes"][1:] == ("size_t", ["int", "int"])
     assert protos["hsr_view_holes"][2] == ["int", "int", ("pointer", "float"), ("pointer", "float"), "float", ("pointer", "int64_t"),
                                            ("pointer", "char"), "size_t", ("pointer", "void")]
-    others = set()
-    for table in (_abi.SIGNATURES, _abi.SIGNATURES_EXT, _abi.SIGNATURES_EXT_MAP_INIT, _abi.SIGNATURES_EXT_FRAME_RESAMPLE,
-                  _abi.SIGNATURES_EXT_LOSS_OUTLIER, _abi.SIGNATURES_EXT_FRAME_INGEST, _abi.SIGNATURES_EXT_FRAME_EXPORT,
-                  _abi.SIGNATURES_EXT_FRAME_INGEST_PLANES, _abi.SIGNATURES_EXT_MAP_EXPORT):
-        others |= {s[0] for s in table}
-    assert len(others) > 70 and not others & set(protos)
     from hsr_utils import slam_helpers
-    src = test_abi._source(os.path.join(test_abi.ROOT, "include", "hsr_frame_prep.h"))
+    src = test_abi._source("hsr_frame_prep.h")
     assert "#define HSR_PREP_ROT_PARAMS 0" in src and "#define HSR_PREP_ROT_TRANSFORMED 1" in src
     assert (slam_helpers.ROT_PARAMS, slam_helpers.ROT_TRANSFORMED) == (R.ROT_PARAMS, R.ROT_TRANSFORMED) == (0, 1)
 
