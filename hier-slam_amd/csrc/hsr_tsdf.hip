@@ -14,6 +14,7 @@
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_project.h"
 #include "../../include/ext/hsr_tsdf.h"
 
 namespace {
@@ -46,14 +47,8 @@ __device__ __forceinline__ bool project(const Grid& g, const View& c, int i, int
                                         const float* __restrict__ opacity, float& sdf, int& pix)
 {
     const float px = g.ox + g.h * (float)i, py = g.oy + g.h * (float)j, pz = g.oz + g.h * (float)k;
-    const float xc = ((c.m[0] * px + c.m[1] * py) + c.m[2] * pz) + c.m[3];
-    const float yc = ((c.m[4] * px + c.m[5] * py) + c.m[6] * pz) + c.m[7];
-    const float zc = ((c.m[8] * px + c.m[9] * py) + c.m[10] * pz) + c.m[11];
-    if (!(zc > 0.f)) return false;
-    const float u = c.fx * (xc / zc) + c.cx, v = c.fy * (yc / zc) + c.cy;
-    const float fu = floorf(u + 0.5f), fv = floorf(v + 0.5f);
-    if (!(fu >= 0.f && fu < (float)c.W && fv >= 0.f && fv < (float)c.H)) return false;      // in float: a NaN or 1e30 never reaches (int)
-    pix = (int)fv * c.W + (int)fu;                                                              // < 2^28: both sides <= 16384
+    float zc;
+    if (!hsr_project_pixel(c.m, c.fx, c.fy, c.cx, c.cy, c.H, c.W, px, py, pz, zc, pix)) return false;      // hsr_project.h
     const float d = depth[pix];
     if (!(d > 0.f && d < INFINITY)) return false;
     if (c.depth_max > 0.f && d > c.depth_max) return false;

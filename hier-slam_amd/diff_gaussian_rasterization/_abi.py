@@ -1,8 +1,8 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h and include/ext/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules import from
-this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
+Everything under include/hsr_*.h, include/ext/ and include/eval/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
+import from this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
 header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
 include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
 header, a name out of the header's order or bound twice, and any entry whose type class differs from its prototype's.  There is NO
@@ -345,6 +345,24 @@ HEADERS = {
     ),
 }
 
+# ---- the headers under include/eval/, a second table of the same shape: HEADERS above is a counted set (tests/test_abi.py), and the
+# ---- suite of each header here checks it with the same helpers (tests/test_mesh_eval_cpu.py) ----------------------------------------
+EVAL_HEADERS = {
+    # a run's mesh against a ground-truth mesh: areas, surface samples, seen vertices, exact nearest neighbours (w2c is a HOST array;
+    # the seed is a 64-bit word)
+    "eval/hsr_mesh_eval.h": (
+        ("hsr_mesh_areas", ci, [ci, ci, vp, vp, vp, vp]),
+        ("hsr_mesh_sample", ci, [ci, ci, ci, sz, vp, vp, vp,
+                                 vp, vp, vp, vp, vp]),
+        ("hsr_mesh_seen", ci, [ci, vp, ci, ci, cf, cf, cf, cf, fp,
+                               vp, cf, vp, vp]),
+        ("hsr_nn_cells", ci, [ci, ci, ci, cf, cf, cf, cf, ci, vp, vp, vp]),
+        ("hsr_nn_pack", ci, [ci, vp, vp, vp, vp]),
+        ("hsr_nn_query", ci, [ci, ci, ci, cf, cf, cf, cf, ci, vp, vp,
+                              ci, vp, vp, vp, vp]),
+    ),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -353,7 +371,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for table in HEADERS.values():
+    for table in list(HEADERS.values()) + list(EVAL_HEADERS.values()):
         for name, restype, argtypes in table:
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -20,6 +20,8 @@ _REPLAY = ("run_w2cs", "ReplayPlan", "replay_rendervars", "replay_view", "view_c
            "trajectory_lines", "replay_run")
 _CHECKPOINT = ("PackedKeyframe", "pack_keyframe", "unpack_keyframe", "save_checkpoint", "load_checkpoint")
 _MESH = ("TsdfVolume", "mesh_bounds", "save_mesh_ply", "load_mesh_ply", "mesh_run")
+_MESH_EVAL = ("face_areas", "sample_mesh", "NearestGrid", "seen_vertices", "cull_mesh", "distance_metrics", "label_metrics", "mesh_metrics",
+              "evaluate_mesh_run")
 
 
 def __getattr__(name):
@@ -51,4 +53,7 @@ def __getattr__(name):
     if name in _MESH:            # and the mesh of a finished run
         from . import mesh
         return getattr(mesh, name)
+    if name in _MESH_EVAL:       # and that mesh scored against a ground-truth mesh
+        from . import mesh_eval
+        return getattr(mesh_eval, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

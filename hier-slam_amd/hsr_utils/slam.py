@@ -738,6 +738,21 @@ class SlamSession:
         kw.setdefault('first_frame_w2c', self.first_frame_w2c)
         return mesh.mesh_run(self.params, path, intrinsics=self.intrinsics, width=self.cam.image_width, height=self.cam.image_height, **kw)
 
+    def evaluate_mesh(self, gt_ply, **kw):
+        """the run so far scored against the ground-truth mesh of its scene: hsr_utils.mesh_eval.evaluate_mesh_run on the session's own
+        params — export_mesh's mesh (voxel_size= is required), the ground truth culled to what the estimated poses saw — with the
+        session's camera, intrinsics, frame size and mapping sil_thres; returns the dictionary of mesh_metrics and the mesh sizes"""
+        from . import mesh_eval
+        if self.params is None:
+            raise RuntimeError("hsr_utils.slam: evaluate_mesh before the first frame: there is no map yet")
+        kw.setdefault('semantic', self.flag_use_semantic)
+        kw.setdefault('num_frames', len(self.gt_w2c_all_frames))
+        kw.setdefault('sil_thres', self.config['mapping']['sil_thres'])
+        kw.setdefault('cam', self.cam)
+        kw.setdefault('first_frame_w2c', self.first_frame_w2c)
+        return mesh_eval.evaluate_mesh_run(self.params, gt_ply, intrinsics=self.intrinsics, width=self.cam.image_width,
+                                           height=self.cam.image_height, **kw)
+
     def step(self, frame):
         """one pass of the frame loop (scripts/hierslam.py:1762-2124) for frame['id'] = the number of frames stepped so far"""
         time_idx = int(frame['id'])

@@ -1,0 +1,54 @@
+#!/usr/bin/env python3
+"""Scores the mesh of a finished run against the ground-truth mesh of its scene, on the device (hsr_utils.mesh_eval.evaluate_mesh_run;
+include/eval/hsr_mesh_eval.h states the rules): the run is meshed as tools/mesh_run.py meshes it, the ground truth is culled to the
+vertices the estimated poses saw, both surfaces are sampled, and every sample's exact nearest neighbour on the other side gives accuracy,
+completion, their ratios at the threshold, the F-score and, with --semantic, the 3D mIoU of the labels transferred by nearest neighbour.
+
+    python tools/eval_mesh.py PARAMS_NPZ GT_PLY [--voxel-size S] [--every N] [--threshold T] [--semantic] [--out JSON]
+
+PARAMS_NPZ is the params.npz of a run (hsr_utils.map_io.save_params after finalize_params).  GT_PLY is a mesh in the layout
+hsr_utils.mesh.save_mesh_ply writes (vertex x y z [red green blue] [label], triangular faces), in the run's world frame.  One JSON
+object on stdout, and in --out when given; distances are in metres.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "hier-slam_amd"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("params_npz")
+    ap.add_argument("gt_ply")
+    ap.add_argument("--voxel-size", type=float, default=0.02, help="metres between the sample points of the run's mesh")
+    ap.add_argument("--every", type=int, default=5, help="every N-th estimated pose is meshed and culls the ground truth")
+    ap.add_argument("--threshold", type=float, default=0.05, help="metres: the ratios' distance and the culling's depth slack")
+    ap.add_argument("--samples", type=int, default=200000, help="points drawn on each surface")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--semantic", action="store_true", help="mesh through the semantic rasterizer and score the labels too")
+    ap.add_argument("--classes", type=int, default=None, help="number of classes (default: one more than the largest label)")
+    ap.add_argument("--no-cull", action="store_true", help="score against the whole ground-truth mesh")
+    ap.add_argument("--sil-thres", type=float, default=0.5)
+    ap.add_argument("--out", default=None, help="also write the JSON object here")
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("eval_mesh.py needs a GPU")
+    from hsr_utils import map_io, mesh_eval
+    params = map_io.load_params(a.params_npz, device="cuda")
+    got = mesh_eval.evaluate_mesh_run(params, a.gt_ply, voxel_size=a.voxel_size, every=a.every, threshold=a.threshold, n_samples=a.samples,
+                                      seed=a.seed, semantic=a.semantic, num_classes=a.classes, sil_thres=a.sil_thres, cull=not a.no_cull)
+    result = {k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in got.items()}
+    result.update(threshold=a.threshold, samples=a.samples, voxel_size=a.voxel_size, every=a.every)
+    line = json.dumps(result)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
