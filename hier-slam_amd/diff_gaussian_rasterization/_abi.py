@@ -1,7 +1,7 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h, include/ext/ and include/eval/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
+Everything under include/hsr_*.h, include/ext/, include/eval/ and include/recon/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
 import from this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
 header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
 include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
@@ -363,6 +363,17 @@ EVAL_HEADERS = {
     ),
 }
 
+# ---- the headers under include/recon/, a third table of the same shape: EVAL_HEADERS above is a counted set too
+# ---- (tests/test_mesh_eval_cpu.py); tests/test_mesh_depth_cpu.py checks this one with the same helpers ------------------------------
+RECON_HEADERS = {
+    # the depth image of a triangle mesh from one view (w2c is a HOST array)
+    "recon/hsr_mesh_depth.h": (
+        ("hsr_mesh_depth_scratch_bytes", sz, [ci, ci, ci]),
+        ("hsr_mesh_depth", ci, [ci, ci, vp, vp, ci, ci, cf, cf, cf, cf,
+                                fp, cf, vp, sz, vp, vp, vp]),
+    ),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -371,7 +382,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for table in list(HEADERS.values()) + list(EVAL_HEADERS.values()):
+    for table in list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()):
         for name, restype, argtypes in table:
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -22,6 +22,7 @@ _CHECKPOINT = ("PackedKeyframe", "pack_keyframe", "unpack_keyframe", "save_check
 _MESH = ("TsdfVolume", "mesh_bounds", "save_mesh_ply", "load_mesh_ply", "mesh_run")
 _MESH_EVAL = ("face_areas", "sample_mesh", "NearestGrid", "seen_vertices", "cull_mesh", "distance_metrics", "label_metrics", "mesh_metrics",
               "evaluate_mesh_run")
+_MESH_DEPTH = ("MeshDepthRenderer", "render_mesh_depth", "virtual_views", "mesh_depth_l1")
 
 
 def __getattr__(name):
@@ -56,4 +57,7 @@ def __getattr__(name):
     if name in _MESH_EVAL:       # and that mesh scored against a ground-truth mesh
         from . import mesh_eval
         return getattr(mesh_eval, name)
+    if name in _MESH_DEPTH:      # and both meshes as depth images from views the sensor never took
+        from . import mesh_depth
+        return getattr(mesh_depth, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

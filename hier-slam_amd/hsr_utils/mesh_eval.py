@@ -9,7 +9,8 @@ mesh evaluation, so the rules are this project's own and the header states each 
     seen_vertices(vertices, w2cs, intrinsics, H, W, depths=None, eps=0.0)      ONE hsr_mesh_seen per view
     cull_mesh(vertices, faces, seen, *per_vertex)              plain torch
     mesh_metrics(rec, gt, n_samples=200000, threshold=0.05, seed=0, num_classes=None)
-    evaluate_mesh_run(params, gt_ply, voxel_size=, every=5, ...)    mesh_run's mesh, the culled ground truth, mesh_metrics
+    evaluate_mesh_run(params, gt_ply, voxel_size=, every=5, ...)    mesh_run's mesh, the culled ground truth, mesh_metrics; with
+                                                               depth_views=N also mesh_depth.mesh_depth_l1 from N virtual views
 
 There is no CPU path for anything that launches; cull_mesh is plain torch and runs anywhere.
 """
@@ -278,7 +279,7 @@ def mesh_metrics(rec, gt, n_samples=200000, threshold=0.05, seed=0, num_classes=
 # ---- a run --------------------------------------------------------------------------------------------------------------------------------
 def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_samples=200000, seed=0, semantic=False, num_classes=None,
                       sil_thres=0.5, cull=True, keep_mesh=None, intrinsics=None, width=None, height=None, num_frames=None, cam=None,
-                      first_frame_w2c=None, near=0.01, far=100, **mesh_kw):
+                      first_frame_w2c=None, near=0.01, far=100, depth_views=0, depth_seed=0, depth_size=None, **mesh_kw):
     """The mesh of a finished run scored against the ground-truth mesh of its scene.  mesh.mesh_run(params, voxel_size=, every=,
     semantic=, ...) makes the run's mesh (kept at keep_mesh when that is a path); gt_ply is read with mesh.load_mesh_ply; with cull=True
     the ground truth is culled to the vertices seen from every `every`-th estimated pose — in the image, and no deeper than the map's
@@ -286,7 +287,10 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
     threshold, seed, num_classes) scores the two; labels count with semantic=True when the ground truth carries them.  params,
     intrinsics, width, height, num_frames, cam, first_frame_w2c, near and far are mesh_run's, as is every other keyword (label_mode,
     depth_max, bounds, ...).  Returns mesh_metrics' dictionary plus the integers rec_vertices, rec_faces, gt_vertices, gt_faces,
-    gt_vertices_seen and gt_faces_kept."""
+    gt_vertices_seen and gt_faces_kept.  With depth_views = N > 0 the (culled) ground truth and the run's mesh are also rendered to depth
+    from N views the sensor never took — mesh_depth.virtual_views(the poses that were meshed, the culled ground truth's vertices, N,
+    depth_seed) — at depth_size = (H, W), or the run's own size, with the intrinsics scaled per axis, and mesh_depth.mesh_depth_l1 adds
+    depth_l1, depth_l1_covered, depth_gt_cover, depth_rec_cover (floats) and depth_views; with the default 0 no key is added."""
     from . import mesh, slam
     from .camera import setup_camera
     from .replay import run_w2cs
@@ -303,7 +307,10 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
     gv, gf, gl = _mesh(gt_v, gt_f, gt_l if use_labels else None, device=dev)
     counts = dict(rec_vertices=len(rec_v), rec_faces=len(rec_f), gt_vertices=len(gt_v), gt_faces=len(gt_f), gt_vertices_seen=len(gt_v),
                   gt_faces_kept=len(gt_f))
-    if cull:
+    depth_views = int(depth_views)
+    if depth_views < 0:
+        raise ValueError("hsr_utils.mesh_eval: depth_views must be >= 0 (got %d)" % depth_views)
+    if cull or depth_views:
         # the views of mesh_run: the same camera, the same poses, the same silhouette
         k = np.asarray(_host(params['intrinsics'] if intrinsics is None else intrinsics), dtype=np.float32)[:3, :3]
         w = int(_host(params['org_width'])) if width is None else int(width)
@@ -318,6 +325,7 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
         if not np.array_equal(first, np.eye(4, dtype=np.float32)):
             views = np.stack([first @ m for m in views])
         steps = list(range(0, T, int(every)))
+    if cull:
         depths = []
         with torch.no_grad():
             for t in steps:
@@ -331,6 +339,15 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
     rec = _mesh(rec_v, rec_f, rec_l if use_labels else None, device=dev)
     out = mesh_metrics(rec, (gv, gf, gl), n_samples=n_samples, threshold=threshold, seed=seed, num_classes=num_classes)
     out.update(counts)
+    if depth_views:
+        from . import mesh_depth
+        from .camera import scale_intrinsics
+        dh, dw = (h, w) if depth_size is None else (int(depth_size[0]), int(depth_size[1]))
+        dk = scale_intrinsics(k, dh / h, dw / w)
+        virtual = mesh_depth.virtual_views(views[steps], gv, depth_views, depth_seed)
+        l1 = mesh_depth.mesh_depth_l1(rec[:2], (gv, gf), virtual, dk, dh, dw, near=near)
+        out.update(depth_l1=l1["depth_l1"], depth_l1_covered=l1["depth_l1_covered"], depth_gt_cover=l1["gt_cover"],
+                   depth_rec_cover=l1["rec_cover"], depth_views=depth_views)
     return out
 
 

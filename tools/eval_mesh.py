@@ -5,10 +5,13 @@ vertices the estimated poses saw, both surfaces are sampled, and every sample's 
 completion, their ratios at the threshold, the F-score and, with --semantic, the 3D mIoU of the labels transferred by nearest neighbour.
 
     python tools/eval_mesh.py PARAMS_NPZ GT_PLY [--voxel-size S] [--every N] [--threshold T] [--semantic] [--out JSON]
+                              [--depth-views N [--depth-seed S] [--depth-size H W]]
 
 PARAMS_NPZ is the params.npz of a run (hsr_utils.map_io.save_params after finalize_params).  GT_PLY is a mesh in the layout
 hsr_utils.mesh.save_mesh_ply writes (vertex x y z [red green blue] [label], triangular faces), in the run's world frame.  One JSON
-object on stdout, and in --out when given; distances are in metres.
+object on stdout, and in --out when given; distances are in metres.  With --depth-views N both meshes are also rendered to depth from N
+views the sensor never took (hsr_utils.mesh_depth; include/recon/hsr_mesh_depth.h) and depth_l1, depth_l1_covered, depth_gt_cover,
+depth_rec_cover and depth_views join the object; without it the object is what it was.
 """
 import argparse
 import json
@@ -32,6 +35,9 @@ def main():
     ap.add_argument("--classes", type=int, default=None, help="number of classes (default: one more than the largest label)")
     ap.add_argument("--no-cull", action="store_true", help="score against the whole ground-truth mesh")
     ap.add_argument("--sil-thres", type=float, default=0.5)
+    ap.add_argument("--depth-views", type=int, default=0, help="also report Depth L1 of the two meshes from N virtual views")
+    ap.add_argument("--depth-seed", type=int, default=0)
+    ap.add_argument("--depth-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="size of the depth images (default: the run's)")
     ap.add_argument("--out", default=None, help="also write the JSON object here")
     a = ap.parse_args()
     import torch
@@ -40,7 +46,8 @@ def main():
     from hsr_utils import map_io, mesh_eval
     params = map_io.load_params(a.params_npz, device="cuda")
     got = mesh_eval.evaluate_mesh_run(params, a.gt_ply, voxel_size=a.voxel_size, every=a.every, threshold=a.threshold, n_samples=a.samples,
-                                      seed=a.seed, semantic=a.semantic, num_classes=a.classes, sil_thres=a.sil_thres, cull=not a.no_cull)
+                                      seed=a.seed, semantic=a.semantic, num_classes=a.classes, sil_thres=a.sil_thres, cull=not a.no_cull, depth_views=a.depth_views,
+                                      depth_seed=a.depth_seed, depth_size=a.depth_size)
     result = {k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in got.items()}
     result.update(threshold=a.threshold, samples=a.samples, voxel_size=a.voxel_size, every=a.every)
     line = json.dumps(result)
