@@ -11,6 +11,8 @@
 // in scratch -> one-block finish in double, fixed order, so the result is reproducible bit for bit.
 // Compiled with -ffp-contract=off: the forward then evaluates exactly the expression tree of the oracle
 // (oracle/frame_prep_oracle.py), which matters because out_means3D feeds the rasterizer's integer decisions.
+#include <cstdint>
+
 #include "hsr_common.h"
 #include "hsr_block.h"
 #include "hsr_quat.h"
@@ -68,6 +70,42 @@ struct PrepArgs {
     const float *means3D, *unnorm_rotations, *logit_opacities, *log_scales, *cam_unnorm_rots, *cam_trans, *w2c;
 };
 
+// A quaternion row ([P,4] arrays: 16 bytes per Gaussian).  A16: the array's base is 16-byte aligned, so every row is, and the row
+// moves as one float4; otherwise (a gradient written into a slice of a communication bucket that starts at any float) as four
+// floats — the same bits either way.  The host picks the instantiation per launch from the pointers it was given (rows16).
+// (What the four floats become is the compiler's business: it knows them float-aligned and no more, and for gfx950 it merges them into
+// one multi-dword access, which needs dword alignment only — as it does with the 12-byte rows of every [P,3] array here.  The float4
+// cast, in contrast, promises 16 bytes.)
+template <bool A16>
+__device__ __forceinline__ float4 load_row4(const float* base, int p)
+{
+    if constexpr (A16) {
+        return reinterpret_cast<const float4*>(base)[p];
+    } else {
+        const float* r = base + 4 * (size_t)p;
+        return make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
+template <bool A16>
+__device__ __forceinline__ void store_row4(float* base, int p, float4 v)
+{
+    if constexpr (A16) {
+        reinterpret_cast<float4*>(base)[p] = v;
+    } else {
+        float* r = base + 4 * (size_t)p;
+        r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+    }
+}
+
+// true if every given pointer (NULL: not given) is 16-byte aligned
+template <typename... Ptr>
+bool rows16(Ptr... ptrs)
+{
+    return (((reinterpret_cast<uintptr_t>(ptrs)) % 16 == 0) && ...);
+}
+
+template <bool A16>
 __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_forward_kernel(PrepArgs a, float* __restrict__ out_means3D,
                                                                        float* __restrict__ out_unnorm_rot,
                                                                        float* __restrict__ out_rotations,
@@ -82,11 +120,11 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_forward_kernel(PrepArgs
 #pragma unroll
     for (int i = 0; i < 3; i++) m[i] = ((x0 * ps.R[3 * i] + x1 * ps.R[3 * i + 1]) + x2 * ps.R[3 * i + 2]) + ps.t[i] * 1.0f;
     out_means3D[3 * p] = m[0]; out_means3D[3 * p + 1] = m[1]; out_means3D[3 * p + 2] = m[2];
-    const float4 u = reinterpret_cast<const float4*>(a.unnorm_rotations)[p];
+    const float4 u = load_row4<A16>(a.unnorm_rotations, p);
     float4 tr = u;
     if (a.transform_rots) tr = hsr_quat_mult(ps.q, hsr_normalize4(u));
-    if (out_unnorm_rot) reinterpret_cast<float4*>(out_unnorm_rot)[p] = tr;
-    reinterpret_cast<float4*>(out_rotations)[p] = hsr_normalize4(a.rot_source == HSR_PREP_ROT_PARAMS ? u : tr);
+    if (out_unnorm_rot) store_row4<A16>(out_unnorm_rot, p, tr);
+    store_row4<A16>(out_rotations, p, hsr_normalize4(a.rot_source == HSR_PREP_ROT_PARAMS ? u : tr));
     out_opacities[p] = 1.0f / (1.0f + expf(-a.logit_opacities[p]));
     if (a.S == 1) {
         const float e = expf(a.log_scales[p]);
@@ -101,6 +139,7 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_forward_kernel(PrepArgs
     }
 }
 
+template <bool A16>
 __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_backward_kernel(
     PrepArgs a, const float* __restrict__ g_means, const float* __restrict__ g_unnorm, const float* __restrict__ g_rot,
     const float* __restrict__ g_opac, const float* __restrict__ g_scales, const float* __restrict__ g_sil, float* __restrict__ d_means3D,
@@ -136,10 +175,18 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_backward_kernel(
             for (int j = 0; j < 3; j++) sums[3 + 3 * i + j] += g[i] * x[j];
         }
         // rotations
-        const float4 u = reinterpret_cast<const float4*>(a.unnorm_rotations)[p];
+        const float4 u = load_row4<A16>(a.unnorm_rotations, p);
         const float4 zero4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        const float4 gr = g_rot ? reinterpret_cast<const float4*>(g_rot)[p] : zero4;
-        float4 gtr = g_unnorm ? reinterpret_cast<const float4*>(g_unnorm)[p] : zero4;
+        float4 gr, gtr;
+        // A16 spelled out, here and at the store below: through load_row4 / store_row4 the compiler turns these conditional loads into
+        // other instructions, and the aligned instantiation is to stay the code the kernel was before it became a template
+        if constexpr (A16) {
+            gr = g_rot ? reinterpret_cast<const float4*>(g_rot)[p] : zero4;
+            gtr = g_unnorm ? reinterpret_cast<const float4*>(g_unnorm)[p] : zero4;
+        } else {
+            gr = g_rot ? load_row4<false>(g_rot, p) : zero4;
+            gtr = g_unnorm ? load_row4<false>(g_unnorm, p) : zero4;
+        }
         float4 gu = zero4;
         float4 un = zero4;
         if (a.transform_rots) un = hsr_normalize4(u);
@@ -164,7 +211,10 @@ __global__ __launch_bounds__(PREP_BLOCK) void frame_prep_backward_kernel(
         } else {
             gu.x += gtr.x; gu.y += gtr.y; gu.z += gtr.z; gu.w += gtr.w;
         }
-        if (d_unnorm) reinterpret_cast<float4*>(d_unnorm)[p] = gu;
+        if (d_unnorm) {
+            if constexpr (A16) reinterpret_cast<float4*>(d_unnorm)[p] = gu;
+            else store_row4<false>(d_unnorm, p, gu);
+        }
         if (d_logit) {
             const float s = 1.0f / (1.0f + expf(-a.logit_opacities[p]));
             d_logit[p] = (g_opac ? g_opac[p] : 0.0f) * s * (1.0f - s);
@@ -292,9 +342,10 @@ extern "C" int hsr_frame_prep_forward(int P, int S, int transform_rots, int rot_
     }
     PrepArgs a{P, S, transform_rots != 0, rot_source, num_frames, time_idx, means3D, unnorm_rotations, logit_opacities, log_scales,
                cam_unnorm_rots, cam_trans, w2c};
-    frame_prep_forward_kernel<<<(P + PREP_BLOCK - 1) / PREP_BLOCK, PREP_BLOCK, 0, stream>>>(a, out_means3D, out_unnorm_rot,
-                                                                                          out_rotations, out_opacities, out_scales,
-                                                                                          out_depth_sil);
+    const auto kernel = rows16(unnorm_rotations, out_unnorm_rot, out_rotations) ? frame_prep_forward_kernel<true>
+                                                                                 : frame_prep_forward_kernel<false>;
+    kernel<<<(P + PREP_BLOCK - 1) / PREP_BLOCK, PREP_BLOCK, 0, stream>>>(a, out_means3D, out_unnorm_rot, out_rotations, out_opacities,
+                                                                         out_scales, out_depth_sil);
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
@@ -325,10 +376,12 @@ int frame_prep_backward_impl(int P, int S, int transform_rots, int rot_source, c
     const int per_block = PREP_BLOCK * PREP_BWD_ITEMS;
     const int nblocks = P > 0 ? (int)(((size_t)P + per_block - 1) / per_block) : 0;
     if (nblocks > 0) {
-        frame_prep_backward_kernel<<<nblocks, PREP_BLOCK, 0, stream>>>(a, dL_dout_means3D, dL_dout_unnorm_rot, dL_dout_rotations,
-                                                                       dL_dout_opacities, dL_dout_scales, dL_dout_depth_sil,
-                                                                       dL_dmeans3D, dL_dunnorm_rotations, dL_dlogit_opacities,
-                                                                       dL_dlog_scales, partials);
+        const auto kernel = rows16(unnorm_rotations, dL_dout_unnorm_rot, dL_dout_rotations, dL_dunnorm_rotations)
+                                ? frame_prep_backward_kernel<true>
+                                : frame_prep_backward_kernel<false>;
+        kernel<<<nblocks, PREP_BLOCK, 0, stream>>>(a, dL_dout_means3D, dL_dout_unnorm_rot, dL_dout_rotations, dL_dout_opacities,
+                                                   dL_dout_scales, dL_dout_depth_sil, dL_dmeans3D, dL_dunnorm_rotations,
+                                                   dL_dlogit_opacities, dL_dlog_scales, partials);
         HSR_HIP_CHECK(hipGetLastError());
     }
     if (dL_dcam_unnorm_rot || dL_dcam_tran) {

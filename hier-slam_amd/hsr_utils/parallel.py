@@ -138,18 +138,23 @@ class GradientExchange:
       allocates its own output, and autograd adds it INTO the leaf's `.grad` in place — which is the bucket's slice, because
       AccumulateGrad adopted the first producer's view instead of copying it.  After the last backward every `leaf.grad` is a slice
       of the bucket holding the sum over this rank's keyframes, and submit() starts the all-reduce on the bucket as it stands.
-      (A leaf whose `.grad` is not the bucket's slice at submit() — a gradient assigned by hand — is copied into its slot;
-      stats() counts both.)
+      (A leaf whose `.grad` is not the bucket's slice at submit() — a gradient assigned by hand — is copied into its slot, a leaf
+      without a gradient — a rank that rendered no keyframe in the step — has its slot zeroed; stats() counts both.)
     * **Visibility-sparse.**  A keyframe sees part of the map: rows of Gaussians with radii <= 0 in EVERY keyframe of EVERY rank
       are exact zeros everywhere — provided every gradient came from the rasterizer.  add_keyframe(radii) ORs the byte mask
       radii > 0 into the rank's mask; submit() all-reduces (max) the mask and exchanges only the rows of the union: gather into
       a compact buffer, ONE all-reduce, scatter back.  The result equals the dense all-reduce — bit for bit with two ranks, up to
-      the order of the ring's fp32 additions with more.  The mask carries one more byte, "a gradient of this rank did not come
-      from the sink" (another producer — a regulariser on the scales, say — whose rows need not be zero outside the union): if any
-      rank sets it, every rank exchanges the bucket whole in that step.  When the union covers more than `dense_above` of the
-      rows the bucket also goes whole — and after `probe_after` such steps in a row the mask itself (a P-byte all-reduce, a
-      nonzero() and the host wait for both) is only exchanged every `probe_every`-th step until a probe finds the union sparse
-      again.  Every rank takes these decisions from the same all-reduced bytes.  A step in which a keyframe gave no radii is dense.
+      the order of the ring's fp32 additions with more.  The mask carries two more bytes.  "Foreign": this rank's bucket holds a
+      value that is not zero (NaN included, -0.0 not) in a row outside its own mask — another producer (a regulariser on the
+      scales, say, in any keyframe's loss, in a backward of its own, or added to `.grad` in place) whose rows the union need not
+      cover; local_foreign_flag() reads it off the bucket itself, on the device, and a gradient assigned by hand sets it too.
+      "No radii": a keyframe of this rank called add_keyframe(None).  If any rank sets either byte, every rank exchanges the
+      bucket whole in that step.  When the union covers more than `dense_above` of the rows the bucket also goes whole — and
+      after `probe_after` such steps in a row the mask itself (a P-byte all-reduce, the read of the bucket for the foreign byte,
+      a nonzero() and the host wait for them) is only exchanged every `probe_every`-th step until a probe finds the union sparse
+      again.  Whether a mask is exchanged at all, and everything decided after it, depends on nothing but `sparse`, the world size
+      and bytes every rank holds alike (the all-reduced mask and the history of earlier ones): a rank that rendered no keyframe
+      (shard_keyframes of a window shorter than the world) or has no radii joins the same collectives with a mask of zeros.
     * **depth.**  1 (default): reduced(step) waits for the exchange submit() started — the gradients an optimizer step may use.
       depth = 2 is the "stale gradients" pipeline: two buckets, a bucket is waited for only when it is handed out again, so the
       exchange of step i overlaps the renders of step i + 1 — legitimate only for a caller that applies the gradients of step i
@@ -174,8 +179,9 @@ class GradientExchange:
         self.step_index, self.cur = 0, None
         self.probe_after, self.probe_every = int(probe_after), int(probe_every)
         self._dense_run = 0        # consecutive steps whose union was dense (or that skipped the probe while in a dense run)
-        self._vis = None           # this rank's visibility mask of the current step: uint8 [P + 1] (last byte: foreign-gradient flag)
+        self._vis = None           # this rank's visibility mask of the current step: uint8 [P + 2] (two flag bytes: foreign gradient, no radii)
         self._vis_complete = True  # every keyframe of the step gave its radii
+        self._keyframes = 0
         self._handed = set()
         self._prev_sink = None
         self._sink_installed = False
@@ -238,8 +244,8 @@ class GradientExchange:
             return
         m = (radii > 0)
         if self._vis is None:
-            self._vis = torch.zeros(self.P + 1, dtype=torch.uint8, device=radii.device)
-        self._vis[:self.P] |= m.to(torch.uint8)
+            self._vis = torch.zeros(self.P + 2, dtype=torch.uint8, device=self.device)
+        self._vis[:self.P] |= m.to(device=self.device, dtype=torch.uint8)
 
     def abort(self):
         """leaves a step without exchanging (an exception between begin_step and submit): the previous gradient sink is restored"""
@@ -272,6 +278,26 @@ class GradientExchange:
         """exchange the visibility mask in this step?  Always, until `probe_after` dense steps in a row; then every `probe_every`-th"""
         return self._dense_run < self.probe_after or (self._dense_run - self.probe_after) % self.probe_every == 0
 
+    def local_foreign_flag(self):
+        """Between begin_step() and submit(): does this rank's bucket of the step hold anything outside the rows its keyframes saw
+        so far?  A 0-dim bool tensor on the bucket's device, True if any row whose byte of the rank's visibility mask is 0 has an
+        element that is not zero — NaN is not zero, -0.0 is.  Such a value cannot have come from the rasterizer, so the rows of the
+        visible union need not cover it.  Without a keyframe every row is outside.  One read of the bucket, device ops only: nothing
+        here waits for the device, and no process group is needed.  (submit() calls it after it has zeroed the slots of leaves that
+        got no gradient; before that such a slot still holds what the bucket's previous step left there.)"""
+        if self.cur is None:
+            raise RuntimeError("local_foreign_flag: no step is open (call it between begin_step() and submit())")
+        return self._foreign_flag(self.buckets[self.cur])
+
+    def _foreign_flag(self, bucket):
+        rows = torch.zeros(self.P, dtype=torch.bool, device=bucket.flat.device)
+        for v, n in zip(bucket.views, bucket.sizes):
+            if n:
+                rows |= (v.reshape(self.P, n // self.P) != 0).any(dim=1)
+        if self._vis is not None:
+            rows &= self._vis[:self.P] == 0
+        return rows.any()
+
     def submit(self, radii=None):
         """call after the step's last backward(): starts the exchange of the accumulated gradients; returns the bucket index"""
         if radii is not None:
@@ -294,32 +320,38 @@ class GradientExchange:
         self.cur = None
         self.step_index += 1
         self._stats["steps"] += 1
-        self._stats["keyframes"] += max(1, getattr(self, "_keyframes", 1))
+        self._stats["keyframes"] += self._keyframes
         world = self._world()
         dense_bytes = bucket.flat.numel() * bucket.flat.element_size()
         self._stats["bytes_dense_equivalent"] += dense_bytes
         if world == 1:
             return b
         idx = None
-        have_mask = self.sparse and self._vis is not None and self._vis_complete
-        if have_mask:
+        # Which collectives this step runs may depend only on what every rank holds alike: `sparse`, the world size and _dense_run,
+        # which changes below by the all-reduced bytes alone.  What this rank rendered (nothing at all, a keyframe without radii) only
+        # changes the bytes it contributes.
+        if self.sparse:
             if self._probe_now():
-                m = self._vis
-                m[self.P] = 1 if foreign else 0
-                dist.all_reduce(m, op=dist.ReduceOp.MAX, group=self.group)     # the rows ANY rank saw in ANY of its keyframes + the flag
+                m = self._vis if self._vis is not None else torch.zeros(self.P + 2, dtype=torch.uint8, device=self.device)
+                if foreign:
+                    m[self.P] = 1
+                elif self._vis_complete:    # without radii the step is dense anyway: the bucket need not be read
+                    m[self.P:self.P + 1].copy_(self._foreign_flag(bucket).reshape(1))
+                m[self.P + 1] = 0 if self._vis_complete else 1
+                dist.all_reduce(m, op=dist.ReduceOp.MAX, group=self.group)     # the rows ANY rank saw in ANY of its keyframes + the flags
                 self._stats["mask_bytes"] += int(m.numel())
                 self._stats["masks_exchanged"] += 1
-                any_foreign = bool(m[self.P].item())
-                if any_foreign:
+                flags = int((m[self.P] + 2 * m[self.P + 1]).item())             # the step's one wait for the device
+                if flags & 1:
                     self._stats["foreign_dense_steps"] += 1
-                else:
+                if flags == 0:
                     idx = m[:self.P].nonzero(as_tuple=False).flatten()
                     if idx.numel() > self.dense_above * self.P:
                         idx = None
                         self._dense_run += 1
                     else:
                         self._dense_run = 0
-            elif self._dense_run >= self.probe_after:
+            else:
                 self._dense_run += 1      # a skipped probe inside a dense run: stays dense
         self._vis = None
         if idx is None:

@@ -23,6 +23,11 @@
  * `cam_unnorm_rots` is [1, 4, num_frames] and `cam_trans` [1, 3, num_frames] exactly as the reference stores
  * them (scripts/hierslam.py:394-395): element (c, t) sits at c*num_frames + t.
  *
+ * Alignment: any float (4-byte) alignment, for every pointer.  The quaternion rows ([P,4]: unnorm_rotations, out_unnorm_rot,
+ * out_rotations forward; unnorm_rotations, dL_dout_unnorm_rot, dL_dout_rotations, dL_dunnorm_rotations backward) move as one
+ * 16-byte access each where all of those given to the call are 16-byte aligned, and as four floats otherwise (an output that
+ * is a slice of a larger buffer, say); the choice is made per launch and the results are the same bits either way.
+ *
  * Errors: return <0 and hsr_last_error() (declared in hsr_rasterizer.h).  P == 0 is legal (pose gradients
  * come out zero).  No torch types, no allocation inside the library.
  */

@@ -14,7 +14,8 @@ import torch.multiprocessing as mp
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _keyframe_grads(rank):
+def _keyframe(rank, behind_frac=0.0):
+    """the oracle's gradients and radii of keyframe `rank`: the same Gaussians seen from a camera of its own"""
     for p in (os.path.join(ROOT, "hier-slam_amd"), os.path.join(ROOT, "tests")):
         if p not in sys.path:
             sys.path.insert(0, p)
@@ -22,14 +23,19 @@ def _keyframe_grads(rank):
     from harness import run_oracle
     from hsr_utils.camera import replica_intrinsics, setup_camera_tensors
     W, H, P, K = 48, 32, 120, 4
-    cam, sc, up = scenes.build(W, H, P, K, seed=1, kind="aniso", scale_mult=3.0, tilt=False, grad_seed=10 + rank)
+    cam, sc, up = scenes.build(W, H, P, K, seed=1, kind="aniso", scale_mult=3.0, tilt=False, grad_seed=10 + rank, behind_frac=behind_frac)
     w2c = np.eye(4)
     w2c[0, 3] = 0.02 * rank  # a different keyframe per rank, same Gaussians
     cam2 = setup_camera_tensors(W, H, replica_intrinsics(W, H), w2c)
-    _, gr, st = run_oracle(cam2, sc, up, semantic=True, threads=1)
+    out, gr, st = run_oracle(cam2, sc, up, semantic=True, threads=1)
     st.free()
     names = ("means3D", "colors_precomp", "semantics_precomp", "opacities", "scales", "rotations")
-    return names, [torch.tensor(gr[n]) for n in names]
+    return names, [torch.tensor(gr[n]) for n in names], torch.tensor(np.asarray(out["radii"]).astype(np.int32))
+
+
+def _keyframe_grads(rank):
+    names, grads, _ = _keyframe(rank)
+    return names, grads
 
 
 def _worker(rank, world, port, q):
@@ -79,26 +85,36 @@ def _worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
+_TOY_NAMES = {3: ("raster.means3D", "raster.semantics_precomp", "raster.opacities"),
+              6: tuple("raster." + n for n in ("means3D", "colors_precomp", "semantics_precomp", "opacities", "scales", "rotations"))}
+
+
 class _ToyRender(torch.autograd.Function):
     """stands in for the rasterizer's autograd node on the CPU: its backward takes its gradient outputs from the gradient sink
-    exactly as diff_gaussian_rasterization/_C.py does (a fresh allocation when no sink is installed)"""
+    exactly as diff_gaussian_rasterization/_C.py does (a fresh allocation when no sink is installed).  apply(*leaves, *gradients):
+    three leaves or all six of the rasterizer (_TOY_NAMES), and the gradient the backward is to produce for each"""
 
     @staticmethod
-    def forward(ctx, a, b, c, ga, gb, gc):
-        ctx.save_for_backward(ga, gb, gc)
-        return (a * 0).sum() + (b * 0).sum() + (c * 0).sum()
+    def forward(ctx, *args):
+        n = len(args) // 2
+        assert n in _TOY_NAMES and len(args) == 2 * n
+        ctx.save_for_backward(*args[n:])
+        out = (args[0] * 0).sum()
+        for a in args[1:n]:
+            out = out + (a * 0).sum()
+        return out
 
     @staticmethod
     def backward(ctx, g):
         from diff_gaussian_rasterization import _C
         outs = []
-        for name, src in zip(("raster.means3D", "raster.semantics_precomp", "raster.opacities"), ctx.saved_tensors):
+        for name, src in zip(_TOY_NAMES[len(ctx.saved_tensors)], ctx.saved_tensors):
             t = _C._from_sink(name, tuple(src.shape), src.device)
             if t is None:
                 t = torch.empty_like(src)
             t.copy_(src)                      # the kernel overwrites every row (zeros for the Gaussians it did not see)
             outs.append(t)
-        return outs[0], outs[1], outs[2], None, None, None
+        return tuple(outs) + (None,) * len(outs)
 
 
 def _exchange_checks(rank, world):
@@ -352,3 +368,372 @@ def test_bench_rank_cpu_sets_do_not_collide():
     assert bench.choose_cpus(0, 1, range(128), l3, None, start_cpu=13) == frozenset(range(8, 16))
     assert bench.choose_cpus(0, 1, range(128), lambda c: {c}, None, start_cpu=13) is None
     assert bench.parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
+
+
+# ---- GradientExchange where the ranks do NOT do the same thing: windows shorter than the world (a rank without a keyframe), a keyframe
+# without radii, gradients that did not come from the rasterizer.  Every exchange decision has to come from bytes all ranks share; a rank
+# that decides from its own state enters another collective than its peers, which gloo reports by aborting (and RCCL by hanging).  So every
+# case below runs its ranks as spawned CPU processes over gloo, compares each step with allreduce_gradients on the same per-rank sums,
+# and the parent asserts on the exit codes. ----
+def _rank_main(rank, world, port, check, kw):
+    import datetime
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    for p in (os.path.join(ROOT, "hier-slam_amd"), os.path.join(ROOT, "tests")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=100))
+    globals()[check](rank, world, **kw)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def _run_ranks(check, world, **kw):
+    """`check(rank, world, **kw)` on `world` spawned gloo ranks; a rank that fails an assertion, aborts in a mismatched collective or is
+    still running at the time limit shows in the exit codes"""
+    ctx = mp.get_context("spawn")
+    port = _bench().free_port()
+    procs = [ctx.Process(target=_rank_main, args=(r, world, port, check, kw)) for r in range(world)]
+    try:
+        for p in procs:
+            p.start()
+        procs[0].join(timeout=240)
+        for p in procs[1:]:
+            p.join(timeout=120)
+        codes = [p.exitcode for p in procs]
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.kill()
+                p.join()
+    assert codes == [0] * world, "the ranks of %s exited with %s (None: still running at the time limit)" % (check, codes)
+
+
+TOY_P = 200
+
+
+def _toy_leaves():
+    return {"raster.means3D": torch.zeros(TOY_P, 3, requires_grad=True), "raster.semantics_precomp": torch.zeros(TOY_P, 5, requires_grad=True),
+            "raster.opacities": torch.zeros(TOY_P, 1, requires_grad=True)}
+
+
+def _toy_keyframe(leaves, step, kf, integer, lo=None, width=20):
+    """keyframe `kf` of step `step`, the same whichever rank renders it: it sees `width` rows (a seeded place unless `lo` is given) and
+    its gradients are zero everywhere else, as the rasterizer's are.  integer: small integers in fp32, whose sums are exact in any order"""
+    gen = torch.Generator().manual_seed(1000 * step + kf + 1)
+    if lo is None:
+        lo = int(torch.randint(0, TOY_P - width, (1,), generator=gen))
+    radii = torch.zeros(TOY_P, dtype=torch.int32)
+    radii[lo:lo + width] = 1 + kf
+    grads = []
+    for t in leaves.values():
+        g = torch.randint(-8, 9, t.shape, generator=gen).float() if integer else torch.randn(t.shape, generator=gen)
+        g[radii <= 0] = 0.0
+        grads.append(g)
+    return radii, grads
+
+
+def _toy_step(ex, leaves, frames, no_radii=(), reg_in=None, reg_after=None, add_after=None):
+    """One step of this rank: begin_step, a _ToyRender forward and backward per frame ((radii, gradients); the frames listed in
+    `no_radii` call add_keyframe(None)), submit.  Other producers, each a coefficient c standing for the gradient c of sum(c * leaf) on
+    EVERY row: reg_in = (k, c) adds it to the loss of frame k, reg_after = c runs it as a backward of its own after the last frame,
+    add_after = c adds it to .grad in place.  Returns the rank's own sums, formed by the same fp32 additions in the same order."""
+    ts = list(leaves.values())
+    local = [torch.zeros_like(t) for t in ts]
+    ex.begin_step()
+    for k, (radii, grads) in enumerate(frames):
+        ex.add_keyframe(None if k in no_radii else radii)
+        loss = _ToyRender.apply(*ts, *grads)
+        c = reg_in[1] if reg_in is not None and reg_in[0] == k else None
+        if c is not None:
+            loss = loss + sum((t * c).sum() for t in ts)
+        loss.backward()
+        for acc, g in zip(local, grads):
+            acc += g if c is None else g + c          # autograd sums a leaf's two gradients of one backward before it accumulates
+    if reg_after is not None:
+        sum((t * reg_after).sum() for t in ts).backward()
+        for acc in local:
+            acc += reg_after
+    if add_after is not None:
+        for t, acc in zip(ts, local):
+            t.grad.add_(torch.full_like(t, add_after))
+            acc += add_after
+    if frames:
+        for i, t in enumerate(ts):                    # adopted by the first backward and never replaced: nothing to pack
+            assert t.grad.data_ptr() == ex.buckets[ex.cur].views[i].data_ptr(), "gradient %d is no longer the bucket's slice" % i
+    ex.submit()
+    return local
+
+
+def _dense_reference(ref_leaves, local, average=False):
+    from hsr_utils.parallel import allreduce_gradients
+    for r, acc in zip(ref_leaves, local):
+        r.grad = acc.clone()
+    allreduce_gradients(ref_leaves, average=average)
+    return [r.grad.clone() for r in ref_leaves]
+
+
+def _shared_counts(ex, world):
+    """the counters that follow from the exchange decisions: gathered, and the same on every rank"""
+    st = ex.stats()
+    mine = {k: st[k] for k in ("masks_exchanged", "sparse_steps", "foreign_dense_steps")}
+    got = [None] * world
+    dist.all_gather_object(got, mine)
+    assert all(g == got[0] for g in got), "the ranks took different decisions: %s" % (got,)
+    return mine
+
+
+UNEVEN_WINDOWS = (1, 0, 2, 1, 3, 4, 7, 1, 0, 2, 1)     # keyframes in the window, step by step: 0, 1, 2, 3, 4 and 7, short ones more than once
+
+
+def _deal(window, rank, step, world):
+    """shard_keyframes, with the ranks' places rotated from step to step so that it is not always the last ranks that go without"""
+    from hsr_utils.parallel import shard_keyframes
+    return shard_keyframes(window, (rank + step) % world, world)
+
+
+def _check_uneven_windows(rank, world, depth):
+    from hsr_utils.parallel import GradientExchange
+    integer = world > 2             # three ranks: the ring's order of additions must not matter, so the sums are made exact
+    leaves = _toy_leaves()
+    ex = GradientExchange(leaves, "cpu", depth=depth, sparse=True, dense_above=0.9)
+    ref_leaves = [torch.zeros_like(t).requires_grad_(True) for t in leaves.values()]
+    kept, without, keyframes = {}, [], 0
+
+    def compare(s):
+        dense, serial, bound = kept.pop(s)
+        for v, e, t, b in zip(ex.reduced(s), dense, serial, bound):
+            assert torch.equal(v, e), "step %d: the sparse exchange differs from the dense all-reduce of the same sums" % s
+            if integer:
+                assert torch.equal(v.double(), t), "step %d: not the serial sum over the window" % s
+            else:   # n <= 7 fp32 additions in another order than the serial float64 sum: (n - 1) 2^-24 sum |terms| (8 > n - 1)
+                assert bool(((v.double() - t).abs() <= 8 * 2.0 ** -24 * b).all()), "step %d: not the serial sum over the window" % s
+
+    for s, length in enumerate(UNEVEN_WINDOWS):
+        window = list(range(length))
+        mine = _deal(window, rank, s, world)
+        without.append(frozenset(r for r in range(world) if not _deal(window, r, s, world)))
+        if depth > 1 and s >= depth:
+            compare(s - depth)                      # its bucket is about to be reused: read first
+        local = _toy_step(ex, leaves, [_toy_keyframe(leaves, s, kf, integer) for kf in mine])
+        keyframes += len(mine)
+        serial = [torch.zeros(t.shape, dtype=torch.float64) for t in leaves.values()]
+        bound = [torch.zeros(t.shape, dtype=torch.float64) for t in leaves.values()]
+        for kf in window:
+            for acc, b, g in zip(serial, bound, _toy_keyframe(leaves, s, kf, integer)[1]):
+                acc += g.double()
+                b += g.double().abs()
+        kept[s] = (_dense_reference(ref_leaves, local), serial, bound)
+        counts = _shared_counts(ex, world)
+        # at most 7 x 20 of 200 rows: every step probes, finds the union sparse and has no foreign gradient
+        assert counts == dict(masks_exchanged=s + 1, sparse_steps=s + 1, foreign_dense_steps=0), (s, counts)
+        if depth == 1:
+            compare(s)
+    for s in sorted(kept):
+        compare(s)
+    ex.drain()
+    assert all(w is None for w in ex.pending)
+    st = ex.stats()
+    assert st["keyframes"] == keyframes and st["steps"] == len(UNEVEN_WINDOWS), st
+    assert st["copied_tensors"] == 3 * sum(1 for s, length in enumerate(UNEVEN_WINDOWS) if not _deal(list(range(length)), rank, s, world)), st
+    assert st["bytes_exchanged"] < st["bytes_dense_equivalent"]
+    # what this case is for: steps in which some ranks, but not all, go without a keyframe — and not always the same ranks
+    some = {w for w in without if 0 < len(w) < world}
+    assert len(some) >= 2 and frozenset(range(world)) in without and frozenset() in without, without
+
+
+@pytest.mark.parametrize("world,depth", [(2, 1), (3, 1), (2, 2), (3, 2)])
+def test_exchange_with_windows_shorter_than_the_world(world, depth):
+    """Windows of 0, 1, 2, 3, 4 and 7 keyframes dealt by shard_keyframes to 2 and 3 ranks over consecutive steps: the ranks that render
+    nothing change from step to step and still enter the same collectives as the others.  depth = 2: the same with two buckets, each
+    step's bucket read before it is reused and nothing left pending after drain().  At the parent commit a rank without a keyframe skipped
+    the mask all-reduce its peer entered, and the ranks ended with exit codes [-6, 1]."""
+    _run_ranks("_check_uneven_windows", world, depth=depth)
+
+
+def _check_missing_radii(rank, world):
+    from hsr_utils.parallel import GradientExchange
+    leaves = _toy_leaves()
+    ex = GradientExchange(leaves, "cpu", sparse=True, dense_above=0.9)
+    ref_leaves = [torch.zeros_like(t).requires_grad_(True) for t in leaves.values()]
+    dense_bytes = ex.buckets[0].flat.numel() * 4
+    # step -> (keyframes of rank 0, keyframes of rank 1, (rank, frame) that gives no radii); in step 3 the other rank has no keyframe at all
+    plan = [(1, 1, None), (1, 2, (1, 1)), (2, 1, None), (1, 0, (0, 0)), (1, 1, None)]
+    for s, (n0, n1, missing) in enumerate(plan):
+        n = (n0, n1)[rank]
+        frames = [_toy_keyframe(leaves, s, 2 * k + rank, False) for k in range(n)]
+        before = ex.stats()
+        local = _toy_step(ex, leaves, frames, no_radii=(missing[1],) if missing is not None and missing[0] == rank else ())
+        after, counts = ex.stats(), _shared_counts(ex, world)
+        for v, e in zip(ex.reduced(s), _dense_reference(ref_leaves, local)):
+            assert torch.equal(v, e), s
+        assert counts["masks_exchanged"] == s + 1 and counts["foreign_dense_steps"] == 0, (s, counts)
+        if missing is None:        # sparse before and sparse again right after
+            assert after["sparse_steps"] - before["sparse_steps"] == 1 and after["bytes_exchanged"] - before["bytes_exchanged"] < dense_bytes, s
+        else:                      # EVERY rank exchanges the bucket whole, not only the one without radii
+            assert after["sparse_steps"] == before["sparse_steps"] and after["bytes_exchanged"] - before["bytes_exchanged"] == dense_bytes, s
+
+
+def test_exchange_when_one_keyframe_gives_no_radii():
+    """add_keyframe(None) on one rank for one of its keyframes: that step is exchanged whole by every rank — the flag travels with the
+    mask — and the next one is sparse again"""
+    _run_ranks("_check_missing_radii", 2)
+
+
+FOREIGN_KINDS = {"regulariser_in_the_loss_of_keyframe_2_of_3": dict(reg_in=1), "separate_backward_after_the_last_keyframe": dict(reg_after=True),
+                 "added_to_grad_in_place_after_adoption": dict(add_after=True)}
+
+
+def _check_foreign(rank, world, kind):
+    from hsr_utils.parallel import GradientExchange
+    leaves = _toy_leaves()
+    ex = GradientExchange(leaves, "cpu", sparse=True, dense_above=0.9)
+    ref_leaves = [torch.zeros_like(t).requires_grad_(True) for t in leaves.values()]
+    s = 0
+    for producers in ((0,), (0, 1)):                      # the other producer on one rank only, then on both
+        c = float(rank + 1) if rank in producers else None
+        extra = {}
+        if c is not None:
+            extra = {k: ((v, c) if k == "reg_in" else c) for k, v in FOREIGN_KINDS[kind].items()}
+        # three keyframes per rank, all inside rows 0..19: rows 20.. are seen by nobody, and only the other producer writes them
+        frames = [_toy_keyframe(leaves, s, 3 * rank + k, True, lo=3 * k + rank, width=10) for k in range(3)]
+        before = ex.stats()
+        local = _toy_step(ex, leaves, frames, **extra)
+        after, counts = ex.stats(), _shared_counts(ex, world)
+        outside = float(sum(r + 1 for r in producers))
+        for v, e in zip(ex.reduced(s), _dense_reference(ref_leaves, local)):
+            assert torch.equal(v[20:], torch.full_like(v[20:], outside)), \
+                "row 50 holds %s, the regularisers of ranks %s sum to %s" % (v[50].tolist(), producers, outside)
+            assert torch.equal(v, e)
+        assert after["foreign_dense_steps"] - before["foreign_dense_steps"] == 1 and after["sparse_steps"] == before["sparse_steps"], (before, after)
+        assert after["zero_copy_tensors"] - before["zero_copy_tensors"] == 3 and after["copied_tensors"] == before["copied_tensors"], (before, after)
+        s += 1
+        # and a step without it is sparse again
+        local = _toy_step(ex, leaves, [_toy_keyframe(leaves, s, 3 * rank + k, True, lo=3 * k + rank, width=10) for k in range(3)])
+        counts = _shared_counts(ex, world)
+        for v, e in zip(ex.reduced(s), _dense_reference(ref_leaves, local)):
+            assert torch.equal(v, e) and not bool(v[20:].any())
+        assert counts["sparse_steps"] == (s + 1) // 2 and counts["foreign_dense_steps"] == (s + 1) // 2, (s, counts)
+        s += 1
+
+
+@pytest.mark.parametrize("kind", list(FOREIGN_KINDS))
+def test_exchange_with_a_gradient_that_is_not_the_rasterizers(kind):
+    """A producer whose gradient is not zero outside the visible union, contributing AFTER the first backward's view was adopted — so
+    `.grad` is still the bucket's slice and no pointer tells: the step must go dense on every rank (foreign_dense_steps + 1), the rows no
+    keyframe saw must hold the summed regulariser, and nothing may be copied.  At the parent commit the keyframe-2 regulariser of one
+    rank left row 50 of the reduced gradient at 1.0 on that rank and 0.0 on the other, with foreign_dense_steps == 0."""
+    _run_ranks("_check_foreign", 2, kind=kind)
+
+
+def _check_probe_schedule(rank, world):
+    from hsr_utils.parallel import GradientExchange
+    leaves = _toy_leaves()
+    ex = GradientExchange(leaves, "cpu", depth=1, sparse=True, dense_above=0.5, probe_after=2, probe_every=3)
+    ref_leaves = [torch.zeros_like(t).requires_grad_(True) for t in leaves.values()]
+    without = {1: 1, 3: 1, 4: 0, 6: 1, 7: 0, 10: 0}       # step -> the rank that has no keyframe in it
+    # steps 0..9: every keyframe sees all rows.  _dense_run 0, 1: probed; from 2 on every third step: 2, 5, 8.  From step 10 on a keyframe sees
+    # 40 rows, but step 10 is no probe: still dense; the probe of step 11 finds the union sparse, and the run is over.
+    probes = [1, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5, 6, 7]
+    sparse = [0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 2]
+    for s in range(13):
+        frames = [] if without.get(s) == rank else [_toy_keyframe(leaves, s, rank, False, lo=0, width=TOY_P if s < 10 else 40)]
+        local = _toy_step(ex, leaves, frames)
+        counts = _shared_counts(ex, world)
+        assert counts == dict(masks_exchanged=probes[s], sparse_steps=sparse[s], foreign_dense_steps=0), (s, counts)
+        for v, e in zip(ex.reduced(s), _dense_reference(ref_leaves, local)):
+            assert torch.equal(v, e), s
+
+
+def test_probe_schedule_is_the_same_on_a_rank_without_a_keyframe():
+    """probe_after = 2, probe_every = 3 through a dense stretch in which one rank or the other has no keyframe in some steps: _dense_run
+    moves by the all-reduced bytes alone, so every rank probes in the same steps — masks_exchanged, gathered step by step"""
+    _run_ranks("_check_probe_schedule", 2)
+
+
+def _check_sparse_average(rank, world):
+    from hsr_utils.parallel import GradientExchange
+    leaves = _toy_leaves()
+    ex = GradientExchange(leaves, "cpu", sparse=True, dense_above=0.9, average=True)
+    ref_leaves = [torch.zeros_like(t).requires_grad_(True) for t in leaves.values()]
+    for s, length in enumerate((3, 1, 0, 2, 1)):
+        mine = _deal(list(range(length)), rank, s, world)
+        local = _toy_step(ex, leaves, [_toy_keyframe(leaves, s, kf, False) for kf in mine])
+        for v, e in zip(ex.reduced(s), _dense_reference(ref_leaves, local, average=True)):
+            assert torch.equal(v, e), s
+        assert _shared_counts(ex, world)["sparse_steps"] == s + 1
+
+
+def test_sparse_exchange_with_average_equals_the_dense_mean():
+    _run_ranks("_check_sparse_average", 2)
+
+
+def _check_real_gradients(rank, world):
+    from hsr_utils.parallel import GradientExchange
+    names, grads, radii = _keyframe(rank, behind_frac=0.3)      # part of the map behind both cameras
+    P = int(radii.numel())
+    for n, g in zip(names, grads):
+        assert not bool(g[radii <= 0].any()), "%s: a Gaussian the keyframe did not see has a gradient" % n
+    seen = [None] * world
+    dist.all_gather_object(seen, (radii > 0).tolist())
+    union = int(torch.tensor(seen).any(dim=0).sum())
+    assert 0 < union < 0.9 * P and int((radii > 0).sum()) > 0, (union, P)
+    leaves = {"raster." + n: torch.zeros_like(g).requires_grad_(True) for n, g in zip(names, grads)}
+    ex = GradientExchange(leaves, "cpu", sparse=True, dense_above=0.9)
+    ex.begin_step()
+    ex.add_keyframe(radii)
+    _ToyRender.apply(*leaves.values(), *grads).backward()
+    ex.submit()
+    ref_leaves = [torch.zeros_like(g).requires_grad_(True) for g in grads]
+    for n, v, e in zip(names, ex.reduced(0), _dense_reference(ref_leaves, grads)):
+        assert torch.equal(v, e), n
+    st = ex.stats()
+    assert st["sparse_steps"] == 1 and st["union_rows"] == union and st["foreign_dense_steps"] == 0 and st["zero_copy_tensors"] == 6, st
+
+
+def test_sparse_exchange_of_the_oracles_gradients_with_its_own_radii():
+    """the two oracle keyframes (different cameras, 30 % of the map behind them) with the oracle's radii as the visibility: every row with
+    radii <= 0 is exactly zero in all six gradients, the union is smaller than P, and the sparse exchange equals the dense sum bit for bit"""
+    _run_ranks("_check_real_gradients", 2)
+
+
+def test_local_foreign_flag_reads_the_bucket_not_the_pointers():
+    """one rank, no process group: the flag is a device scalar, true where a row outside the rank's own mask holds anything but zero —
+    NaN counts, -0.0 does not — and without a keyframe every row is outside"""
+    sys.path.insert(0, os.path.join(ROOT, "hier-slam_amd"))
+    from hsr_utils.parallel import GradientExchange
+    leaves = _toy_leaves()
+    ex = GradientExchange(leaves, "cpu", sparse=True)
+    with pytest.raises(RuntimeError):
+        ex.local_foreign_flag()                                   # no step is open
+    radii, grads = _toy_keyframe(leaves, 0, 0, False, lo=10, width=20)
+    try:
+        ex.begin_step()
+        ex.add_keyframe(radii)
+        _ToyRender.apply(*leaves.values(), *grads).backward()
+        flag = ex.local_foreign_flag()
+        assert isinstance(flag, torch.Tensor) and flag.dim() == 0 and flag.dtype == torch.bool and not bool(flag)
+        sem = leaves["raster.semantics_precomp"].grad
+        assert sem.data_ptr() == ex.buckets[0].views[1].data_ptr()
+        sem[150, 3] = -0.0
+        assert not bool(ex.local_foreign_flag())
+        sem[15, 3] = float("nan")                                  # inside the mask: the rasterizer's own business
+        assert not bool(ex.local_foreign_flag())
+        sem[150, 3] = float("nan")
+        assert bool(ex.local_foreign_flag())
+        sem[150, 3] = 0.0
+        leaves["raster.opacities"].grad[TOY_P - 1, 0] = 1e-30      # the last row of the last tensor
+        assert bool(ex.local_foreign_flag())
+        ex.submit()
+        ex.begin_step()                                            # no keyframe: nothing is visible
+        assert ex.stats()["keyframes"] == 1
+        for t in leaves.values():
+            t.grad = torch.zeros_like(t)
+        ex.submit()
+        assert ex.stats()["keyframes"] == 1 and ex.stats()["steps"] == 2    # a step without a keyframe counts none
+        ex.begin_step()
+        ex.buckets[0].flat.zero_()
+        assert not bool(ex.local_foreign_flag())
+        ex.buckets[0].flat[7] = 2.0
+        assert bool(ex.local_foreign_flag())
+    finally:
+        ex.abort()
