@@ -17,8 +17,9 @@
 //   * each 16-lane group of a wave owns a 4x4 sub-block and walks a compacted per-sub-block list built at
 //     staging time from the splats' alpha>=1/255 regions (subblock_mask, hsr_tile_common.h), so splats that
 //     cannot touch the sub-block cost it nothing; the wave iterates to the longest of its four lists (a shorter
-//     group visits a dummy entry of opacity 0 meanwhile: no validity predicate in the loop), and a
-//     visit that no lane accepts costs only the alpha test (wave ballot).  A wave whose 64 pixels are all
+//     group visits a dummy entry of opacity 0 meanwhile: no validity predicate in the loop).  In the wide-tree
+//     kernels a visit that no lane accepts costs only the alpha test (wave ballot); the kernels up to 32 channels
+//     run one block per visit, staged by hand, without that branch.  A wave whose 64 pixels are all
 //     terminated stops blending but keeps staging.
 //   * records are staged pre-scaled (log2(e) and the -0.5 folded into the conic) so alpha costs one
 //     v_exp_f32 and a handful of FMAs: the kernel is VALU-issue bound, not HBM bound.
@@ -160,6 +161,10 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     // it never contributes) and a feature row of zeros, written once per workgroup.  A group pads its list with it up to the wave's
     // iteration count, so the blend loop visits a real staged entry on every trip and carries no "is this visit mine" predicate.
     constexpr int NSLOT = BATCH + (QS ? 0 : 1);
+    // ALPHA_AHEAD: the per-lane kernels' visit loop computes an entry's alpha a trip ahead of its blend.  Only at K = 16, where it is what
+    // keeps the instantiation at the 24 bytes of scratch it had (28 without) and costs nothing; at K = 26 it gains nothing and at K = 0 it
+    // loses 2 us (EXPERIMENTS.md §10n).
+    constexpr bool ALPHA_AHEAD = KC == 16;
     static_assert(NSLOT <= 256, "list entries are bytes");
     __shared__ float4 s_rec[NSLOT * 2];
     __shared__ float4 s_row[NSLOT * (RW / 4)];
@@ -505,48 +510,80 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
             // or the dummy — so nothing in it asks whether the visit counts; a lane that does not contribute multiplies by w = 0.
             // The median crossing and the last contributor are recorded as the entry's SLOT in registers that hold "list position -
             // (start + 1)" for the length of the batch (negative: set in an earlier batch, or never), and are turned back after it.
+            //
+            // The loop is staged by hand (EXPERIMENTS.md §10n): one block per trip, in which the LDS reads of three trips are in flight.
+            // Trip k computes its alpha from the record the trip before asked for, decides from it and the running T, requests the list byte
+            // of trip k + 2, the record of trip k + 1 and the first rows of its own entry, blends those rows, requests the rest and blends
+            // them (ALPHA_AHEAD: the alpha of trip k + 1 is computed in trip k, while the rows are in flight, and handed over).  There is no
+            // branch round a trip in which no lane contributes (2 % of the trips at the headline workload): with it hipcc keeps two paths
+            // apart and the staging gains nothing.  The look-ahead reads up to list[m + 1], which pad_sublist has filled with the dummy;
+            // nothing staged here survives the batch.  The per-pixel arithmetic is what it was, operation for operation.
             const int base1 = start + 1;
             int last_rel = (int)last_contributor - base1, med_rel = (int)median_at - base1;
-            int j = (int)list[0];
-            for (int k = 0; k < m; k++) {
-                const int j_next = (int)list[k + 1];   // list[m] is padding too
-                const float4 g = s_rec[2 * j];
-                const float4 h4 = s_rec[2 * j + 1];
-                const float2 co = make_float2(h4.x, h4.y);
+            auto alpha_of = [&](const float4& g, const float2& co, float& alpha) -> bool {   // the part of a trip that does not depend on T
                 const float dx = g.x - pfx, dy = g.y - pfy;
                 const float power2 = fmaf(co.x, dy * dy, fmaf(g.w, dx * dy, g.z * (dx * dx)));
-                const float alpha = fminf(0.99f, co.y * __builtin_amdgcn_exp2f(power2));
-                const bool reach = power2 <= 0.0f && alpha >= 1.0f / 255.0f;
+                alpha = fminf(0.99f, co.y * __builtin_amdgcn_exp2f(power2));
+                return power2 <= 0.0f && alpha >= 1.0f / 255.0f;
+            };
+            auto read_rec = [&](int slot, float4& g, float2& co) {
+                g = s_rec[2 * slot];
+                co = *reinterpret_cast<const float2*>(&s_rec[2 * slot + 1]);
+            };
+            constexpr int NQ = RW / 4;
+            // 16-byte row reads of the first request group (K = 26: three, then four; the second group lands in the registers of the first
+            // and of the trip's temporaries, which is what lets the next record be in flight at 128 registers)
+            constexpr int Q1 = NQ > 4 ? (NQ - 1) / 2 : NQ;
+            int j = (int)list[0], j1 = (int)list[1];
+            float4 g;
+            float2 co;
+            read_rec(j, g, co);
+            float alpha = 0.f;
+            bool reach = false;
+            if constexpr (ALPHA_AHEAD) reach = alpha_of(g, co, alpha);
+            for (int k = 0; k < m; k++) {
+                if constexpr (!ALPHA_AHEAD) reach = alpha_of(g, co, alpha);
+                // decide: the instructions of a trip that wait for the previous one's T
                 const float test_T = T * (1.0f - alpha);
                 const bool low = test_T < 0.0001f;
                 const bool contrib = reach && !low;   // never on a finished pixel: its test_T is 0
                 const float w = contrib ? alpha * T : 0.f;
-                // no lane contributes (2 % of the trips at the headline workload): the rows are not read.  The test is one scalar branch on
-                // the mask the select above already has; a lane that finishes here still has its T cleared.
-                if (__ballot(contrib) == 0ull) {
-                    T = reach ? 0.0f : T;
-                    j = j_next;
-                    continue;
-                }
+                // request
+                const int j2 = (int)list[k + 2];
+                read_rec(j1, g, co);
+                const float4* row = &s_row[j * NQ];
+                float4 f[NQ];
+                float2 rg = make_float2(0.f, 0.f);
+                if (BASE) rg = reinterpret_cast<const float2*>(&s_rec[2 * j + 1])[1];
+#pragma unroll
+                for (int q = 0; q < Q1; q++) f[q] = row[q];
+                float alpha_n = 0.f;
+                bool reach_n = false;
+                if constexpr (ALPHA_AHEAD) reach_n = alpha_of(g, co, alpha_n);
+                // blend
                 if (BASE) {
-                    C0 = fmaf(h4.z, w, C0);
-                    C1 = fmaf(h4.w, w, C1);
+                    C0 = fmaf(rg.x, w, C0);
+                    C1 = fmaf(rg.y, w, C1);
                     if (MASK) Mm += w;
                 }
-                {
-                    const float4* row = &s_row[j * (RW / 4)];
+                auto blend = [&](int q) {
+                    const float fv[4] = {f[q].x, f[q].y, f[q].z, f[q].w};
 #pragma unroll
-                    for (int q = 0; q < RW / 4; q++) {
-                        const float4 f = row[q];
-                        const float fv[4] = {f.x, f.y, f.z, f.w};
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            const int c = 4 * q + i;
-                            if (c < KC) S[c < KC ? c : 0] = fmaf(fv[i], w, S[c < KC ? c : 0]);
-                            else if (BASE && c == KC) C2 = fmaf(fv[i], w, C2);
-                            else if (BASE && c == KC + 1) Dd = fmaf(fv[i], w, Dd);
-                        }
+                    for (int i = 0; i < 4; i++) {
+                        const int c = 4 * q + i;
+                        if (c < KC) S[c < KC ? c : 0] = fmaf(fv[i], w, S[c < KC ? c : 0]);
+                        else if (BASE && c == KC) C2 = fmaf(fv[i], w, C2);
+                        else if (BASE && c == KC + 1) Dd = fmaf(fv[i], w, Dd);
                     }
+                };
+#pragma unroll
+                for (int q = 0; q < Q1; q++) blend(q);
+                if constexpr (Q1 < NQ) {
+                    __builtin_amdgcn_sched_barrier(0);   // the second group is requested behind the first group's FMAs, not hoisted above them
+#pragma unroll
+                    for (int q = Q1; q < NQ; q++) f[q] = row[q];
+#pragma unroll
+                    for (int q = Q1; q < NQ; q++) blend(q);
                 }
                 // T_out moves only when the lane contributes, so "contributes, T > 0.5 before, < 0.5 after" needs no third term
                 const float T_was = T_out;
@@ -554,7 +591,12 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
                 if (BASE) med_rel = (T_was > 0.5f && T_out < 0.5f) ? j : med_rel;
                 last_rel = contrib ? j : last_rel;
                 T = reach ? (low ? 0.0f : test_T) : T;   // contributes: goes on; finishes (again): 0
-                j = j_next;
+                if constexpr (ALPHA_AHEAD) {
+                    alpha = alpha_n;
+                    reach = reach_n;
+                }
+                j = j1;
+                j1 = j2;
 #ifdef HSR_TRACE
                 tr_iters++;
 #endif

@@ -240,12 +240,13 @@ __device__ __forceinline__ int flatten_sublist(int sb, int lane, uint8_t* s_list
 }
 
 // Forward visit loop without a validity predicate: a wave runs m = the longest of its four groups' lists trips, and a shorter group
-// fills its list up to and including index m (the loop reads one entry ahead) with `dummy`, the slot of a staged entry of opacity 0.
-// m <= 240 entries per batch < HSR_SUB_LSTRIDE, so the padding stays inside the group's own list.  Call after flatten_sublist.
+// fills its list up to and including index m + 1 (the loop reads the list two entries ahead) with `dummy`, the
+// slot of a staged entry of opacity 0.  m <= 240 entries per batch, so m + 1 < HSR_SUB_LSTRIDE and the padding stays inside the group's own
+// list.  Call after flatten_sublist.
 __device__ __forceinline__ void pad_sublist(int sb, int lane, uint8_t* s_list, int total, int m, int dummy)
 {
     uint8_t* list = s_list + sb * HSR_SUB_LSTRIDE;
-    for (int p = total + (lane & 15); p <= m; p += 16) list[p] = (uint8_t)dummy;
+    for (int p = total + (lane & 15); p <= m + 1; p += 16) list[p] = (uint8_t)dummy;
 }
 
 // ---- packed per-Gaussian gradient row (backward, default accumulation mode) ----
