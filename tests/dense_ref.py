@@ -143,8 +143,11 @@ def dense_render(cam, p, point_list, ranges, semantic=True, sem_alpha_exact=Fals
             out_o[y0:y1, x0:x1] = Op
             out_mask[y0:y1, x0:x1] = Mk
             n_contrib[y0:y1, x0:x1] = ncon
+    # the per-Gaussian forward state as formed above (view depth, pixel centre, conic): what the oracle keeps in depths, means2D and
+    # conic_opacity[:, :3], for the tests that pin that state under general cameras (tests/test_oracle_cameras.py)
+    state = dict(depths=tz.detach(), means2D=torch.stack([px, py], 1).detach(), conic=conic.detach())
     return dict(color=out_c, semantic=out_s, depth=out_d[None], median=out_m[None], opacity=out_o[None],
-                mask=out_mask[None], final_T=out_T, n_contrib=n_contrib)
+                mask=out_mask[None], final_T=out_T, n_contrib=n_contrib, state=state)
 
 
 def dense_loss_and_grads(cam, scene, grads, point_list, ranges, semantic=True, use_cov3d=False, sem_alpha_exact=False):

@@ -2,7 +2,7 @@
 Gaussian at every branch of that code.  tests/test_gauss_chain_cpu.py holds every directed Gaussian to the regime it is named for on the
 oracle's forward state; tests/test_gpu_gauss_chain.py runs every case on the device.
 
-    CASES            name -> builder of a Case; the directed scene in seven variants, then three random scenes
+    CASES            name -> builder of a Case; the directed scene in seven variants, then five random scenes (two of them under general cameras)
     directed_info()  name of a directed Gaussian -> its index in the directed scene, its group and the regime it is meant for
     prefix(n)        the first n Gaussians of the directed scene
 
@@ -232,7 +232,9 @@ def prefix(n):
     return directed(n=n)
 
 
-def _random(Wr, Hr, seed, scale_mult, off_centre=False, sh_degree=None):
+def _random(Wr, Hr, seed, scale_mult, off_centre=False, sh_degree=None, camera=None):
+    """camera: a name of scenes.CAMERAS, in place of the turn about y"""
+    assert camera is None or not off_centre
     if off_centre:      # the intrinsics of test_off_centre_principal_point_and_unequal_focal_lengths, at this size
         from hsr_utils.camera import setup_camera_tensors
         from hsr_utils.synthetic import make_scene, make_upstream_grads
@@ -242,7 +244,8 @@ def _random(Wr, Hr, seed, scale_mult, off_centre=False, sh_degree=None):
         sc = make_scene(P, Wr, Hr, K, k, seed=seed, kind="aniso", scale_mult=scale_mult, w2c=w2c)
         up = {n: v * float(Wr * Hr) for n, v in make_upstream_grads(Wr, Hr, K, seed=1).items()}
     else:
-        cam, sc, up = scenes.build(Wr, Hr, P, K, seed=seed, kind="aniso", scale_mult=scale_mult)
+        cam, sc, up = scenes.build(Wr, Hr, P, K, seed=seed, kind="aniso", scale_mult=scale_mult,
+                                   w2c=None if camera is None else scenes.CAMERAS[camera])
     extra = None
     if sh_degree is not None:
         cam = dict(cam, sh_degree=int(sh_degree))
@@ -261,4 +264,7 @@ CASES = {
     "random_64x48_x2": lambda: _random(64, 48, 51, 2.0),
     "random_100x70_x40": lambda: _random(100, 70, 52, 40.0),
     "random_100x70_off_centre_sh3": lambda: _random(100, 70, 53, 2.0, off_centre=True, sh_degree=3),
+    # general cameras: every entry of the view matrix that the chain reads is live (tests/test_gpu_cameras.py)
+    "random_64x48_x2_skew23": lambda: _random(64, 48, 54, 2.0, camera="skew23"),
+    "random_100x70_x2_skew140_sh3": lambda: _random(100, 70, 55, 2.0, sh_degree=3, camera="skew140"),
 }

@@ -175,6 +175,35 @@ def tilted_plane(seed=0, n=9):
     return vertices, np.array(faces, np.int32)
 
 
+def place(vertices, w2c):
+    """camera-space vertices -> float32 world-space vertices that w2c maps back to them (to rounding): the scene placed with the inverse
+    camera, so that it stays in view whatever the camera"""
+    m = np.asarray(w2c, np.float64)
+    return ((np.asarray(vertices, np.float64) - m[:3, 3]) @ m[:3, :3]).astype(F32)
+
+
+def random_faces(seed, k, H, W, n=160):
+    """(vertices float32 [3n,3], faces int32 [n,3]) in camera coordinates: n triangles at depths of 0.6 to 4 around pixel centres spread over
+    the image and a margin around it, from a pixel or two across to a third of the image, both windings; two have one corner pushed
+    behind the camera"""
+    rng = np.random.default_rng(seed)
+    k = np.asarray(k, np.float64)
+    vertices, faces = [], []
+    for i in range(n):
+        u, v, z = rng.uniform(-6, W + 6), rng.uniform(-6, H + 6), rng.uniform(0.6, 4.0)
+        size = float(rng.choice([1.2, 3.0, 8.0, W / 3.0]))
+        tri = []
+        for j in range(3):
+            du, dv = rng.uniform(-size, size, 2)
+            zz = z + rng.uniform(-0.3, 0.3)
+            if i in (57, 121) and j == 2:
+                zz = -0.4
+            tri.append([(u + du - k[0][2]) / k[0][0] * zz, (v + dv - k[1][2]) / k[1][1] * zz, zz])
+        vertices += tri
+        faces.append([3 * i, 3 * i + 1, 3 * i + 2] if rng.random() < 0.5 else [3 * i, 3 * i + 2, 3 * i + 1])
+    return np.array(vertices, F32), np.array(faces, np.int32)
+
+
 def plane_truth():
     """(t float64 [H,W], inner bool [H,W]): the depth at which the ray of every pixel centre of the plane scene meets the analytic
     plane, and whether that point lies within |x|, |y| < 3.6: inside the mesh whatever the jitter of its border (at most 0.3 from 4)"""

@@ -15,10 +15,41 @@ def tilted_w2c(angle=0.2, t=(0.1, -0.05, 0.2)):
     return w2c
 
 
+def rodrigues_w2c(axis, degrees, t):
+    """w2c [4,4] float64: the rotation by `degrees` about `axis` (Rodrigues' formula) and the translation t"""
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    th = np.deg2rad(degrees)
+    Kx = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    w2c = np.eye(4)
+    w2c[:3, :3] = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * (Kx @ Kx)
+    w2c[:3, 3] = t
+    return w2c
+
+
+# General cameras.  tilted_w2c is a turn about y: R01 = R10 = R12 = R21 = 0 and R11 = 1, so in the kernels' column-major viewmatrix vm[1],
+# vm[4], vm[6], vm[9] are 0 and vm[5] is 1 (projmatrix [1], [4], [7], [9] are 0 too) — an index or transposition error in the y row or
+# column of any projection multiplies a zero or swaps two zeros, and y = 1 * y + t however the sum is associated.  These four are the
+# cameras under which no view-matrix entry the kernels read is 0 or 1 in all cases (tests/test_oracle_cameras.py holds them to that):
+#   skew23    every entry non-trivial, a small angle (the matrix tests/test_gpu_view.py calls "tilted")
+#   skew140   every entry large (the smallest |R entry| is 0.108), negative diagonal
+#   roll90    x and y exchanged exactly: a transposed index becomes a sign or axis error
+#   pitch17   the complement of the y-turn: R12 and R21 are live, the x row is trivial
+CAMERAS = {
+    "skew23": rodrigues_w2c((0.9, 0.2, -0.1), 23.0, (0.3, -0.2, 0.5)),
+    "skew140": rodrigues_w2c((0.3, -0.8, 0.5), 140.0, (-0.4, 0.1, 0.6)),
+    "roll90": rodrigues_w2c((0.0, 0.0, 1.0), 90.0, (0.1, 0.2, -0.1)),
+    "pitch17": rodrigues_w2c((1.0, 0.0, 0.0), -17.0, (0.0, 0.3, 0.2)),
+}
+
+
 def build(W, H, P, K, seed=0, kind="aniso", scale_mult=2.0, tilt=True, bg=(0.0, 0.0, 0.0), behind_frac=0.0, grad_seed=1,
-          grad_scale=None):
+          grad_scale=None, w2c=None):
+    """w2c: a camera (one of CAMERAS, or any 4x4) in place of the y-turn, for the camera tensors and for placing the scene"""
     k = replica_intrinsics(W, H)
-    w2c = tilted_w2c() if tilt else np.eye(4)
+    if w2c is not None:
+        w2c, tilt = np.asarray(w2c, np.float64), True
+    else:
+        w2c = tilted_w2c() if tilt else np.eye(4)
     cam = setup_camera_tensors(W, H, k, w2c)
     cam["bg"] = torch.tensor(bg, dtype=torch.float32)
     sc = make_scene(P, W, H, K, k, seed=seed, kind=kind, scale_mult=scale_mult, w2c=w2c if tilt else None,

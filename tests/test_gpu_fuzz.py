@@ -100,6 +100,45 @@ def test_random_configuration_variants(name, cfg):
     _compare(cam, sc, up, semantic, variant, extra)
 
 
+# Both generators above look through scenes.tilted_w2c, a turn about the y axis, under which the view matrix's vm[1], vm[4], vm[6], vm[9]
+# are 0 and vm[5] is 1 (tests/test_gpu_cameras.py).  A third generator — separate again, so that the named cases of the first two keep their
+# seeds — draws what _cases draws, plus a camera: a rotation about a random axis (normalised N(0, 1)^3) by U(0, 80) degrees and a
+# translation from U(-0.5, 0.5)^3.
+def _cases_v3(n=16, seed=7313):
+    g = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        W, H = int(g.integers(17, 200)), int(g.integers(17, 150))
+        P = int(g.choice([1, 7, 63, 300, 1200, 2500]))
+        semantic = bool(g.random() < 0.8)
+        K = int(g.choice([0, 1, 3, 11, 16, 26, 27, 28, 31, 40, 52, 53, 74, 90])) if semantic else 0
+        kind = str(g.choice(["slam", "aniso"]))
+        sm = float(g.choice([0.3, 1.0, 3.0, 12.0, 60.0]))
+        bg = tuple(float(x) for x in g.choice([0.0, 1.0, 0.3], size=3))
+        behind = float(g.choice([0.0, 0.0, 0.3]))
+        axis = tuple(float(x) for x in g.standard_normal(3))
+        angle = float(g.uniform(0.0, 80.0))
+        t = tuple(float(x) for x in g.uniform(-0.5, 0.5, 3))
+        out.append(("v3_%02d_%dx%d_P%d_K%d_%s_x%g_turn%.0f" % (i, W, H, P, K, kind, sm, angle),
+                    (W, H, P, K, kind, sm, semantic, "sr", bg, behind, axis, angle, t)))
+    return out
+
+
+CASES_V3 = _cases_v3(int(os.environ.get("HSR_FUZZ_CASES_V3", "16")), int(os.environ.get("HSR_FUZZ_SEED_V3", "7313")))
+
+
+def build_v3(name, cfg):
+    W, H, P, K, kind, sm, semantic, variant, bg, behind, axis, angle, t = cfg
+    cam, sc, up = scenes.build(W, H, P, K, seed=zlib.crc32(name.encode()) % 1000, kind=kind, scale_mult=sm, bg=bg, behind_frac=behind,
+                               w2c=scenes.rodrigues_w2c(axis, angle, t))
+    return cam, sc, up, semantic, variant, None
+
+
+@pytest.mark.parametrize("name,cfg", CASES_V3, ids=[c[0] for c in CASES_V3])
+def test_random_configuration_under_a_random_camera(name, cfg):
+    _compare(*build_v3(name, cfg))
+
+
 # the legacy accumulation mode (no scratch: atomics straight into the reference's six arrays) runs the all-VALU quadrant-list backward
 # (hsr_render_bwd.hip) since round 3: every third case of the default list through it
 @pytest.mark.parametrize("name,cfg", CASES[::3], ids=[c[0] for c in CASES[::3]])

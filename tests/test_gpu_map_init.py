@@ -8,7 +8,7 @@ means go through torch's matmul, whose accumulation order and contraction are th
 distance from a float64 restatement on the same inputs is held to twice the fp32 restatement's own distance from it.  Every figure is printed.
 
 Shapes: 1x1; 7x5; 64x48 with 30 % zero or negative depth; 37x23 (851 pixels: four 256-pixel blocks, the last one partial); 515x511 (1028
-blocks: the single-workgroup scan takes two blocks per thread); all-invalid depth; capacity < M; S = 1 and 3; identity and tilted c2w."""
+blocks: the single-workgroup scan takes two blocks per thread); all-invalid depth; capacity < M; S = 1 and 3; identity, tilted and general c2w."""
 import numpy as np
 import pytest
 import torch
@@ -23,14 +23,20 @@ CASES = [("1x1",          1,   1,   1, 0.0,     True),
          ("64x48_holes",  64,  48,  1, 0.3,     True),
          ("37x23",        37,  23,  3, 0.1,     True),
          ("515x511",      515, 511, 1, 0.3,     True),
-         ("all_invalid",  9,   31,  1, 1.0,     True)]
+         ("all_invalid",  9,   31,  1, 1.0,     True),
+         # general cameras (scenes.CAMERAS): under a turn about y, c2w[0][1], [1][0], [1][2], [2][1] are 0 and c2w[1][1] is 1
+         ("skew23",       37,  23,  3, 0.1,     "skew23"),
+         ("skew140",      64,  48,  1, 0.3,     "skew140"),
+         ("roll90",       37,  23,  1, 0.1,     "roll90"),
+         ("pitch17",      7,   5,   3, 0.0,     "pitch17")]
 
 
 def _w2c(tilted):
+    """False: the identity; True: the turn about y; a name: that camera of scenes.CAMERAS"""
     if not tilted:
         return torch.eye(4)
     import scenes
-    return torch.tensor(np.asarray(scenes.tilted_w2c())).float()
+    return torch.tensor(np.asarray(scenes.tilted_w2c() if tilted is True else scenes.CAMERAS[tilted])).float()
 
 
 def _frame(H, W, invalid, seed):

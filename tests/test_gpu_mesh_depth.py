@@ -114,6 +114,40 @@ def test_tilted_plane_equals_the_restatement_and_has_no_hole():
     assert (np.abs(depth[inner] - truth[inner]) / truth[inner]).max() <= 4 * 2.87e-6      # tests/test_mesh_depth_cpu.py measures the figure
 
 
+CAMERAS = ["skew23", "skew140", "roll90", "pitch17"]      # scenes.CAMERAS: every entry of the rotation that hsr_camera_point reads is live
+
+
+@pytest.mark.parametrize("camera", CAMERAS)
+def test_tilted_plane_under_general_cameras(camera):
+    """the plane placed with the inverse camera and rendered through the camera: m01, m10, m12, m21 of hsr_camera_point are 0 and m11 is 1
+    under the identity and under a turn about y, here none is"""
+    import scenes
+    w2c = scenes.CAMERAS[camera]
+    for seed in (0, 1):
+        vertices, faces = R.tilted_plane(seed)
+        depth, face = check(R.place(vertices, w2c), faces, w2c, R.PLANE_K, R.PLANE_H, R.PLANE_W)
+        truth, inner = R.plane_truth()
+        assert (face[inner] >= 0).all() and len(np.unique(face[face >= 0])) > 60
+        if seed == 0:
+            assert (np.abs(depth[inner] - truth[inner]) / truth[inner]).max() <= 4 * 2.87e-6      # as tests/test_mesh_depth_cpu.py holds the restatement
+
+
+@pytest.mark.parametrize("camera", CAMERAS)
+def test_random_faces_under_general_cameras(camera):
+    """160 random faces on both sides of the split, two across the camera's plane, both windings (tests/test_mesh_depth_cpu.py holds the
+    scene to that), placed with the inverse camera; and an odd image size through intrinsics with fx != fy"""
+    import scenes
+    w2c = scenes.CAMERAS[camera]
+    vertices, faces = R.random_faces(3, R.PLANE_K, R.PLANE_H, R.PLANE_W)
+    boxes = []
+    depth, face = check(R.place(vertices, w2c), faces, w2c, R.PLANE_K, R.PLANE_H, R.PLANE_W, boxes=boxes)
+    assert min(b for b in boxes if b) <= R.SMALL_BOX < max(boxes) and len(np.unique(face[face >= 0])) > 40
+    k = np.array([[19.0, 0, 17.25], [0, 23.0, 20.5], [0, 0, 1]])
+    vertices, faces = R.random_faces(4, k, 43, 37)
+    depth, face = check(R.place(vertices, w2c), faces, w2c, k, 43, 37)
+    assert len(np.unique(face[face >= 0])) > 30
+
+
 @pytest.mark.parametrize("bad", [[0, 1, -1], [0, 1, 5], [0, 1, 3], [0, 1, 4], [0, 1, 1]], ids=["index-1", "indexV", "nan", "inf", "det0"])
 def test_a_face_that_takes_no_part_beside_a_good_one(bad):
     v = np.concatenate([TRIANGLE, np.array([[0, 0, NAN], [INF, 0, 2]], np.float32)])
@@ -224,12 +258,13 @@ def test_no_faces_and_two_views_on_one_scratch():
     renderer = mesh_depth.MeshDepthRenderer(dev(vertices, torch.float32), dev(faces, torch.int32), R.PLANE_H, R.PLANE_W)
     away = np.eye(4)
     away[:3, 3] = [30.0, 0, 0]      # the plane is out of sight
-    views = [EYE, scenes.tilted_w2c(), away, EYE]
+    views = [EYE, scenes.tilted_w2c(), away, EYE] + [scenes.CAMERAS[n] for n in CAMERAS]
     got = [renderer.render(m, R.PLANE_K) for m in views]      # nothing is read between the calls
     for m, (d, f) in zip(views, got):
         want = R.render(vertices, faces, m, R.PLANE_K, R.PLANE_H, R.PLANE_W)
         assert np.array_equal(bits(d.cpu().numpy()), bits(want[0])) and np.array_equal(f.cpu().numpy(), want[1])
     assert (got[2][1] == -1).all() and (got[0][1] >= 0).sum() > 3000 and not torch.equal(got[0][1], got[1][1])
+    assert sum(int((f >= 0).sum()) > 500 for _d, f in got[4:]) >= 3      # the general cameras see the plane too (skew140 looks away from it)
     with pytest.raises(ValueError, match="near must be finite and positive"):
         renderer.render(EYE, R.PLANE_K, near=0.0)
     with pytest.raises(RuntimeError, match=r"w2c must be \[4,4\]"):

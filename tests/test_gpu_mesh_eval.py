@@ -194,6 +194,21 @@ def test_seen_accumulates_over_views_and_clears_nothing():
     assert np.array_equal(device_seen(pts, [np.eye(4)], depths[:1], 0.02), first)
     assert np.array_equal(device_seen(pts, [np.eye(4), tilted], depths, 0.02), both)
     assert np.array_equal(device_seen(pts, [np.eye(4), tilted]), R.seen(pts, tilted, K, SH, SW, out=R.seen(pts, np.eye(4), K, SH, SW)))
+    # general cameras as further views (scenes.CAMERAS: every entry of the rotation that hsr_camera_point reads is live), each with a depth
+    # image of its own, on top of the two above
+    cams = [m.astype(np.float32) for m in scenes.CAMERAS.values()]
+    more = [g.uniform(0.5, 2.5, (SH, SW)).astype(np.float32) for _ in cams]
+    want, plain, grew = both.copy(), R.seen(pts, tilted, K, SH, SW, out=R.seen(pts, np.eye(4), K, SH, SW)), 0
+    for m, d in zip(cams, more):
+        alone = R.seen(pts, m, K, SH, SW, d, 0.02)
+        assert np.array_equal(device_seen(pts, [m], [d], 0.02), alone)
+        before = int(want.sum())
+        want = R.seen(pts, m, K, SH, SW, d, 0.02, out=want)
+        plain = R.seen(pts, m, K, SH, SW, out=plain)
+        grew += int(want.sum()) > before
+    assert grew >= 2 and (want >= both).all() and want.sum() < 300
+    assert np.array_equal(device_seen(pts, [np.eye(4), tilted] + cams, depths + more, 0.02), want)
+    assert np.array_equal(device_seen(pts, [np.eye(4), tilted] + cams), plain)
 
 
 # ---- metrics ------------------------------------------------------------------------------------------------------------------------------

@@ -130,6 +130,52 @@ def test_restatement_against_float64_on_the_tilted_plane():
     assert len(np.unique(face[hit])) > 60      # the image is made of many faces, not of one
 
 
+def general_cameras():
+    import scenes
+    return scenes.CAMERAS
+
+
+@pytest.mark.parametrize("camera", ["skew23", "skew140", "roll90", "pitch17"])
+def test_restatement_against_float64_under_general_cameras(camera):
+    """The identity and a turn about y leave m01, m10, m12, m21 of camera_points at 0 and m11 at 1.  The plane scene placed with the inverse
+    of each general camera (every entry of the rotation live) and rendered through that camera: the float32 rule against float64 on the same
+    float32 inputs, by the criteria of the test above.  Measured (largest relative depth error; pixels left out of the face comparison):
+    skew23 1.6e-6, 3; skew140 3.2e-6, 3; roll90 2.8e-6, 3; pitch17 2.7e-6, 3 — within four times the identity scene's 2.87e-6, which holds unchanged."""
+    w2c = general_cameras()[camera]
+    vertices, faces = R.tilted_plane(0)
+    world = R.place(vertices, w2c)
+    assert np.abs(R.camera_points(world, w2c, np.float64) - vertices).max() < 5e-6      # back where they were, to the rounding of the placement
+    depth, face = R.render(world, faces, w2c, R.PLANE_K, R.PLANE_H, R.PLANE_W)
+    depth64, face64, margin = R.render64(world, faces, w2c, R.PLANE_K, R.PLANE_H, R.PLANE_W)
+    hit, hit64 = face >= 0, face64 >= 0
+    truth, inner = R.plane_truth()
+    assert hit[inner].all()      # no hole
+    both = hit & hit64
+    assert both.sum() >= 3000 and (hit ^ hit64).sum() <= 0.01 * both.sum()
+    rel = np.abs(depth[both].astype(np.float64) - depth64[both]) / depth64[both]
+    sure = both & (np.abs(margin) > 1e-4)
+    print("%s: largest relative depth error against float64 %.3e; left out of the face comparison %d of %d" % (camera, rel.max(), (both & ~sure).sum(), both.sum()))
+    assert rel.max() <= 4 * 2.87e-6
+    assert (np.abs(depth[inner] - truth[inner]) / truth[inner]).max() <= 4 * 2.87e-6
+    assert (both & ~sure).sum() <= 0.05 * both.sum() and np.array_equal(face[sure], face64[sure])
+    assert len(np.unique(face[hit])) > 60
+
+
+@pytest.mark.parametrize("camera", ["skew23", "skew140", "roll90", "pitch17"])
+def test_random_faces_scene_takes_both_paths_under_every_camera(camera):
+    """the scene tests/test_gpu_mesh_depth.py renders under the general cameras holds what it is meant to: boxes on both sides of SMALL_BOX,
+    faces across the camera's plane (whole-image boxes), both windings, and an image made of many faces"""
+    w2c = general_cameras()[camera]
+    k, H, W = R.PLANE_K, R.PLANE_H, R.PLANE_W
+    vertices, faces = R.random_faces(3, k, H, W)
+    boxes = []
+    depth, face = R.render(R.place(vertices, w2c), faces, w2c, k, H, W, boxes=boxes)
+    boxes = np.array(boxes)
+    assert (boxes == 0).sum() > 0 and ((boxes > 0) & (boxes <= R.SMALL_BOX)).sum() > 40 and ((boxes > R.SMALL_BOX) & (boxes < H * W)).sum() > 20
+    assert (boxes == H * W).sum() >= 2
+    assert len(np.unique(face[face >= 0])) > 40 and (face >= 0).mean() > 0.5
+
+
 def test_restatement_edges():
     k = np.array([[8.0, 0, 3.5], [0, 8.0, 2.5], [0, 0, 1]])
     v = np.array([[-1, -1, 2], [1, -1, 2], [0, 1, 2], [0, 0, NAN], [INF, 0, 2]], np.float32)
