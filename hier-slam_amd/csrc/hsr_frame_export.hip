@@ -7,13 +7,15 @@
 //                      stores per picture; the last H * W % 4 pixels go one at a time through the V = 1 path.  V = 1: a lane takes one
 //                      pixel and stores three bytes, for calls with a src off 16 bytes or an out off 4.
 // A plane of H * W % 4 != 0 floats puts the next plane off 16 bytes: the 16-byte accesses are declared 4-byte (8-byte for int64)
-// aligned, which global memory takes at any dword.  Streaming, bound by bytes: a 1200x680 frame with K = 26 logits and 4 levels reads
-// 85 MB per LOGITS picture and writes 2.4 MB per picture; nothing is reused across lanes, so nothing is staged in LDS.  The LOGITS
-// labels (hsr_tree.h's rule) read each plane of a level once for the maximum and once for the sum (the second read hits the caches).
-// Compiled with -ffp-contract=off: no rule of the header has a fused multiply-add.
+// aligned, which global memory takes at any dword (hsr_lane_io.h: the vector types and hsr_load<V>).  Streaming, bound by bytes: a
+// 1200x680 frame with K = 26 logits and 4 levels reads 85 MB per LOGITS picture and writes 2.4 MB per picture; nothing is reused
+// across lanes, so nothing is staged in LDS.  The LOGITS labels (hsr_tree.h's rule) read each plane of a level once for the maximum
+// and once for the sum (the second read hits the caches).  Compiled with -ffp-contract=off: no rule of the header has a fused
+// multiply-add.
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_lane_io.h"
 #include "hsr_tree.h"
 #include "../../include/hsr_eval.h"
 #include "../../include/ext/hsr_frame_resample.h"
@@ -26,35 +28,6 @@ constexpr int XB = 256;
 struct Jobs {
     hsr_export_job j[HSR_EXPORT_MAX_JOBS];
 };
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef int i4 __attribute__((ext_vector_type(4)));
-typedef long long l2 __attribute__((ext_vector_type(2)));
-typedef f4 f4_a4 __attribute__((aligned(4)));
-typedef i4 i4_a4 __attribute__((aligned(4)));
-typedef l2 l2_a8 __attribute__((aligned(8)));
-
-template <int V> __device__ __forceinline__ void load(const float* __restrict__ p, float (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const float* __restrict__ p, float (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const float* __restrict__ p, float (&v)[4])
-{
-    const f4 t = *reinterpret_cast<const f4_a4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <int V> __device__ __forceinline__ void load(const int* __restrict__ p, int (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const int* __restrict__ p, int (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const int* __restrict__ p, int (&v)[4])
-{
-    const i4 t = *reinterpret_cast<const i4_a4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <int V> __device__ __forceinline__ void load(const long long* __restrict__ p, long long (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const long long* __restrict__ p, long long (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const long long* __restrict__ p, long long (&v)[4])
-{
-    const l2 a = reinterpret_cast<const l2_a8*>(p)[0], b = reinterpret_cast<const l2_a8*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
 
 // V pixels from flat index i on: V = 4 packs the 12 bytes into three dwords (out is 4-byte aligned and i a multiple of 4)
 template <int V> __device__ __forceinline__ void store(uint8_t* __restrict__ out, size_t i, const unsigned (&r)[V], const unsigned (&g)[V],
@@ -89,8 +62,6 @@ __device__ __forceinline__ void lookup(const uint8_t* __restrict__ table, const 
     }
 }
 
-__device__ __forceinline__ float clamp01(float x) { return x > 0.f ? (x < 1.f ? x : 1.f) : 0.f; }      // a NaN fails x > 0
-
 // V pixels of picture `job` from flat index i on; N = H * W
 template <int V>
 __device__ __forceinline__ void export_pixels(const hsr_export_job& job, size_t i, size_t N)
@@ -101,27 +72,27 @@ __device__ __forceinline__ void export_pixels(const hsr_export_job& job, size_t 
     if (job.kind == HSR_EXPORT_COLOR) {
         const float* __restrict__ src = static_cast<const float*>(job.src) + i;
         float x[3][V];
-        load<V>(src, x[0]);
-        load<V>(src + N, x[1]);
-        load<V>(src + 2 * N, x[2]);
+        hsr_load<V>(src, x[0]);
+        hsr_load<V>(src + N, x[1]);
+        hsr_load<V>(src + 2 * N, x[2]);
 #pragma unroll
         for (int v = 0; v < V; v++) {
-            r[v] = (unsigned)rintf(clamp01(x[0][v]) * 255.0f);      // rintf: to nearest, halves to even
-            g[v] = (unsigned)rintf(clamp01(x[1][v]) * 255.0f);
-            b[v] = (unsigned)rintf(clamp01(x[2][v]) * 255.0f);
+            r[v] = (unsigned)hsr_colour_code(x[0][v]);
+            g[v] = (unsigned)hsr_colour_code(x[1][v]);
+            b[v] = (unsigned)hsr_colour_code(x[2][v]);
         }
     } else if (job.kind == HSR_EXPORT_DEPTH) {
         float d[V];
-        load<V>(static_cast<const float*>(job.src) + i, d);
+        hsr_load<V>(static_cast<const float*>(job.src) + i, d);
         const float lo = job.lo, range = job.hi - job.lo;
 #pragma unroll
         for (int v = 0; v < V; v++) {
-            idx[v] = (int)(clamp01((d[v] - lo) / range) * 255.0f);
+            idx[v] = (int)(hsr_clamp01((d[v] - lo) / range) * 255.0f);
             ok[v] = true;
         }
         lookup<V>(job.table, idx, ok, r, g, b);
     } else if (job.kind == HSR_EXPORT_LABELS) {
-        load<V>(static_cast<const int*>(job.src) + i, idx);
+        hsr_load<V>(static_cast<const int*>(job.src) + i, idx);
 #pragma unroll
         for (int v = 0; v < V; v++) ok[v] = idx[v] >= 0 && idx[v] < job.n;
         lookup<V>(job.table, idx, ok, r, g, b);
@@ -132,7 +103,7 @@ __device__ __forceinline__ void export_pixels(const hsr_export_job& job, size_t 
             const long long* __restrict__ src = static_cast<const long long*>(job.src) + i;
             for (int l = 0; l < job.L; l++) {
                 long long lab[V];
-                load<V>(src + (size_t)l * N, lab);
+                hsr_load<V>(src + (size_t)l * N, lab);
                 const int size = job.sizes[l];
 #pragma unroll
                 for (int v = 0; v < V; v++) {
@@ -147,7 +118,7 @@ __device__ __forceinline__ void export_pixels(const hsr_export_job& job, size_t 
                 int lab[V];
                 const int size = job.sizes[l];
                 const float* __restrict__ x = src + (size_t)begin * N;      // hsr_tree.h's rule on V pixels: a 16-byte load per plane
-                hsr_softmax_argmax<V>([&](int k, float (&t)[V]) { load<V>(x + (size_t)k * N, t); },
+                hsr_softmax_argmax<V>([&](int k, float (&t)[V]) { hsr_load<V>(x + (size_t)k * N, t); },
                                       [&](int k, int v) { return x[(size_t)k * N + v]; }, size, lab);
 #pragma unroll
                 for (int v = 0; v < V; v++) idx[v] = idx[v] * size + lab[v];
@@ -226,7 +197,7 @@ extern "C" int hsr_frame_export(int H, int W, int n_jobs, const hsr_export_job* 
                 return HSR_ERR_INVALID_ARGUMENT;
             }
         }
-        vec = vec && (uintptr_t)j.src % 16 == 0 && (uintptr_t)j.out % 4 == 0;
+        vec = vec && hsr_aligned(j.src, 16) && hsr_aligned(j.out, 4);
         kj.j[k] = j;
     }
     const long long N = (long long)H * W;      // <= 2^28

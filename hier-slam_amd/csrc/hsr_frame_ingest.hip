@@ -31,16 +31,6 @@ struct Sources {
     int Hc, Wc, Hd, Wd, Hl, Wl;
 };
 
-// the left tap, the right one and the weight of the right one along one axis: destination index i of nd from ns source samples
-__device__ __forceinline__ void taps(int i, int ns, int nd, int& i0, int& i1, double& f)
-{
-    int n = (2 * i + 1) * ns - nd;      // <= (2 * 16383 + 1) * 16384 < 2^30
-    n = n > 0 ? n : 0;
-    i0 = n / (2 * nd);
-    f = (double)(n - i0 * 2 * nd) / (double)(2 * nd);
-    i1 = i0 + 1 < ns ? i0 + 1 : ns - 1;
-}
-
 template <int DT>
 __device__ __forceinline__ double raw_depth(const void* __restrict__ p, size_t i)
 {
@@ -68,8 +58,8 @@ __global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ 
     const int y = (int)(i / Wd), x = (int)(i - (long long)y * Wd);      // i < Hd * Wd
     int x0, x1, y0, y1;
     double fx, fy;
-    taps(x, src.Wc, Wd, x0, x1, fx);
-    taps(y, src.Hc, Hd, y0, y1, fy);
+    hsr_taps(x, src.Wc, Wd, x0, x1, fx);      // hsr_ingest_expr.h, in double
+    hsr_taps(y, src.Hc, Hd, y0, y1, fy);
     const size_t dplane = (size_t)Hd * Wd;
     const uint8_t* __restrict__ r0 = color + (size_t)y0 * src.Wc * 3;
     const uint8_t* __restrict__ r1 = color + (size_t)y1 * src.Wc * 3;
@@ -96,8 +86,6 @@ __global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ 
     }
 }
 
-bool side_ok(int v) { return v >= 1 && v <= HSR_RESAMPLE_MAX_SIDE; }
-
 // the checks and the launch of both entries; `planes`: hsr_frame_ingest_planes (the messages name the entry and its arguments)
 int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_raw, int depth_type, double depth_scale,
            const int* labels, int num_levels, const int* table, int n_ids, int leaf_column,
@@ -108,8 +96,9 @@ int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_
         hsr_set_error("%s: n_out must be 1..%d with a host array of that many levels; got %d", who, HSR_INGEST_MAX_LEVELS, n_out);
         return HSR_ERR_INVALID_ARGUMENT;
     }
-    bool sides = side_ok(src.Hc) && side_ok(src.Wc) && side_ok(src.Hd) && side_ok(src.Wd) && (!labels || (side_ok(src.Hl) && side_ok(src.Wl)));
-    for (int k = 0; k < n_out; k++) sides = sides && side_ok(levels[k].H) && side_ok(levels[k].W);
+    bool sides = hsr_side_ok(src.Hc) && hsr_side_ok(src.Wc) && hsr_side_ok(src.Hd) && hsr_side_ok(src.Wd) &&
+                 (!labels || (hsr_side_ok(src.Hl) && hsr_side_ok(src.Wl)));
+    for (int k = 0; k < n_out; k++) sides = sides && hsr_side_ok(levels[k].H) && hsr_side_ok(levels[k].W);
     if (!sides) {
         if (planes)
             hsr_set_error("frame_ingest_planes: sides must be 1..%d: colour %dx%d, depth %dx%d, labels %dx%d (checked when given), "

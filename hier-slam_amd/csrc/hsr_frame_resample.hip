@@ -6,6 +6,7 @@
 // the three lerps are evaluated as the header writes them, so that equal sizes copy and the result is comparable with a plain fp32
 // restatement.
 #include "hsr_common.h"
+#include "hsr_ingest_expr.h"
 #include "../../include/ext/hsr_frame_resample.h"
 
 namespace {
@@ -13,16 +14,6 @@ namespace {
 constexpr int RB = 256;
 
 struct Level { int H, W; float* color; float* depth; };
-
-// the left tap and the weight of the right one along one axis: destination index i of nd from ns source samples (header, COLOUR)
-__device__ __forceinline__ void taps(int i, int ns, int nd, int& i0, int& i1, float& f)
-{
-    int n = (2 * i + 1) * ns - nd;      // <= (2 * 16383 + 1) * 16384 < 2^30
-    n = n > 0 ? n : 0;
-    i0 = n / (2 * nd);
-    f = (float)(n - i0 * 2 * nd) / (float)(2 * nd);
-    i1 = i0 + 1 < ns ? i0 + 1 : ns - 1;
-}
 
 __global__ __launch_bounds__(RB) void resample_kernel(const float* __restrict__ color, const uint32_t* __restrict__ depth, int H, int W,
                                                       Level l0, Level l1, long long n0, long long n_all)
@@ -37,8 +28,8 @@ __global__ __launch_bounds__(RB) void resample_kernel(const float* __restrict__ 
     const int y = (int)(i / Wd), x = (int)(i - (long long)y * Wd);      // i < Hd * Wd
     int x0, x1, y0, y1;
     float fx, fy;
-    taps(x, W, Wd, x0, x1, fx);
-    taps(y, H, Hd, y0, y1, fy);
+    hsr_taps(x, W, Wd, x0, x1, fx);      // hsr_ingest_expr.h, in float
+    hsr_taps(y, H, Hd, y0, y1, fy);
     const size_t plane = (size_t)H * W, dplane = (size_t)Hd * Wd;
     const size_t r0 = (size_t)y0 * W, r1 = (size_t)y1 * W;
 #pragma unroll
@@ -53,15 +44,13 @@ __global__ __launch_bounds__(RB) void resample_kernel(const float* __restrict__ 
     od[i] = depth[(size_t)ys * W + xs];
 }
 
-bool side_ok(int v) { return v >= 1 && v <= HSR_RESAMPLE_MAX_SIDE; }
-
 }  // namespace
 
 extern "C" int hsr_frame_resample(int H, int W, const float* color, const float* depth, int H0, int W0, float* out_color0,
                                   float* out_depth0, int H1, int W1, float* out_color1, float* out_depth1, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!side_ok(H) || !side_ok(W) || !side_ok(H0) || !side_ok(W0) || (H1 != 0 && (!side_ok(H1) || !side_ok(W1)))) {
+    if (!hsr_side_ok(H) || !hsr_side_ok(W) || !hsr_side_ok(H0) || !hsr_side_ok(W0) || (H1 != 0 && (!hsr_side_ok(H1) || !hsr_side_ok(W1)))) {
         hsr_set_error("frame_resample: sides must be 1..%d (H1 == 0 skips level 1): source %dx%d, level 0 %dx%d, level 1 %dx%d",
                       HSR_RESAMPLE_MAX_SIDE, H, W, H0, W0, H1, W1);
         return HSR_ERR_INVALID_ARGUMENT;

@@ -9,13 +9,14 @@
 //   unpack_kernel<V> : the same indexing, the other way.
 // A plane of N % 4 != 0 values puts the next plane off the vector's natural alignment: the vector accesses are declared with the
 // element's alignment (4 for float, 8 for int64, 1 for the colour codes, 2 for the 16-bit codes) and the compiler picks an access
-// global memory takes at that alignment.  Streaming, bound by bytes: a 1200x680 keyframe with 5 label planes reads 45.7 MB and writes
-// 12.2 MB; nothing is reused across lanes, so nothing is staged in LDS.  Compiled with -ffp-contract=off: the rules have one product
-// each and no sum next to it; the flag keeps them as written.
+// global memory takes at that alignment (hsr_lane_io.h: the vector types, hsr_load<V> and hsr_store<V>).  Streaming, bound by bytes:
+// a 1200x680 keyframe with 5 label planes reads 45.7 MB and writes 12.2 MB; nothing is reused across lanes, so nothing is staged in
+// LDS.  Compiled with -ffp-contract=off: the rules have one product each and no sum next to it; the flag keeps them as written.
 #include <math.h>
 
 #include "hsr_common.h"
 #include "hsr_block.h"
+#include "hsr_lane_io.h"
 #include "hsr_ingest_expr.h"
 #include "../../include/hsr_eval.h"
 #include "../../include/ext/hsr_frame_resample.h"
@@ -29,14 +30,6 @@ namespace {
 constexpr int PB = 256;
 constexpr int PER_BLOCK = 4 * PB;      // values of one plane per workgroup, in both paths
 constexpr int COLOUR_PLANES = 3, DEPTH_PLANE = 3, FIRST_LABEL_PLANE = 4;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef long long l2 __attribute__((ext_vector_type(2)));
-typedef unsigned short h4 __attribute__((ext_vector_type(4)));
-typedef f4 f4_a4 __attribute__((aligned(4)));
-typedef l2 l2_a8 __attribute__((aligned(8)));
-typedef h4 h4_a2 __attribute__((aligned(2)));
-typedef unsigned u32_a1 __attribute__((aligned(1)));
 
 struct PackArgs {
     long long N;
@@ -86,68 +79,6 @@ __device__ __forceinline__ unsigned label_code(long long l, unsigned& bad)
     return (unsigned)(l < 0 ? 0 : (l > 65535 ? 65535 : l));
 }
 
-// ---- V values of one plane from flat index i on ----
-template <int V> __device__ __forceinline__ void load(const float* __restrict__ p, float (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const float* __restrict__ p, float (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const float* __restrict__ p, float (&v)[4])
-{
-    const f4 t = *reinterpret_cast<const f4_a4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-template <int V> __device__ __forceinline__ void load(const long long* __restrict__ p, long long (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const long long* __restrict__ p, long long (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const long long* __restrict__ p, long long (&v)[4])
-{
-    const l2 a = reinterpret_cast<const l2_a8*>(p)[0], b = reinterpret_cast<const l2_a8*>(p)[1];
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y;
-}
-template <int V> __device__ __forceinline__ void load(const uint8_t* __restrict__ p, unsigned (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const uint8_t* __restrict__ p, unsigned (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const uint8_t* __restrict__ p, unsigned (&v)[4])
-{
-    const unsigned t = *reinterpret_cast<const u32_a1*>(p);
-    v[0] = t & 255u; v[1] = (t >> 8) & 255u; v[2] = (t >> 16) & 255u; v[3] = t >> 24;
-}
-template <int V> __device__ __forceinline__ void load(const uint16_t* __restrict__ p, unsigned (&v)[V]);
-template <> __device__ __forceinline__ void load<1>(const uint16_t* __restrict__ p, unsigned (&v)[1]) { v[0] = *p; }
-template <> __device__ __forceinline__ void load<4>(const uint16_t* __restrict__ p, unsigned (&v)[4])
-{
-    const h4 t = *reinterpret_cast<const h4_a2*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-}
-
-template <int V> __device__ __forceinline__ void store(uint8_t* __restrict__ p, const unsigned (&v)[V]);
-template <> __device__ __forceinline__ void store<1>(uint8_t* __restrict__ p, const unsigned (&v)[1]) { *p = (uint8_t)v[0]; }
-template <> __device__ __forceinline__ void store<4>(uint8_t* __restrict__ p, const unsigned (&v)[4])
-{
-    *reinterpret_cast<u32_a1*>(p) = v[0] | v[1] << 8 | v[2] << 16 | v[3] << 24;      // every code is below 256
-}
-template <int V> __device__ __forceinline__ void store(uint16_t* __restrict__ p, const unsigned (&v)[V]);
-template <> __device__ __forceinline__ void store<1>(uint16_t* __restrict__ p, const unsigned (&v)[1]) { *p = (uint16_t)v[0]; }
-template <> __device__ __forceinline__ void store<4>(uint16_t* __restrict__ p, const unsigned (&v)[4])
-{
-    h4 t;
-    t.x = (unsigned short)v[0]; t.y = (unsigned short)v[1]; t.z = (unsigned short)v[2]; t.w = (unsigned short)v[3];
-    *reinterpret_cast<h4_a2*>(p) = t;
-}
-template <int V> __device__ __forceinline__ void store(float* __restrict__ p, const float (&v)[V]);
-template <> __device__ __forceinline__ void store<1>(float* __restrict__ p, const float (&v)[1]) { *p = v[0]; }
-template <> __device__ __forceinline__ void store<4>(float* __restrict__ p, const float (&v)[4])
-{
-    f4 t;
-    t.x = v[0]; t.y = v[1]; t.z = v[2]; t.w = v[3];
-    *reinterpret_cast<f4_a4*>(p) = t;
-}
-template <int V> __device__ __forceinline__ void store(long long* __restrict__ p, const unsigned (&v)[V]);
-template <> __device__ __forceinline__ void store<1>(long long* __restrict__ p, const unsigned (&v)[1]) { *p = (long long)v[0]; }
-template <> __device__ __forceinline__ void store<4>(long long* __restrict__ p, const unsigned (&v)[4])
-{
-    l2 a, b;
-    a.x = (long long)v[0]; a.y = (long long)v[1]; b.x = (long long)v[2]; b.y = (long long)v[3];
-    reinterpret_cast<l2_a8*>(p)[0] = a;
-    reinterpret_cast<l2_a8*>(p)[1] = b;
-}
-
 // `plane` is uniform over the workgroup; at = plane * N + i, the flat index into the group's first plane
 template <int V>
 __device__ __forceinline__ void pack_values(const PackArgs& a, int plane, size_t i, unsigned& bad)
@@ -156,23 +87,23 @@ __device__ __forceinline__ void pack_values(const PackArgs& a, int plane, size_t
     if (plane < COLOUR_PLANES) {
         const size_t at = (size_t)plane * (size_t)a.N + i;
         float c[V];
-        load<V>(a.color + at, c);
+        hsr_load<V>(a.color + at, c);
 #pragma unroll
         for (int v = 0; v < V; v++) code[v] = colour_code(c[v], bad);
-        store<V>(a.out_color + at, code);
+        hsr_store<V>(a.out_color + at, code);
     } else if (plane == DEPTH_PLANE) {
         float d[V];
-        load<V>(a.depth + i, d);
+        hsr_load<V>(a.depth + i, d);
 #pragma unroll
         for (int v = 0; v < V; v++) code[v] = depth_code(d[v], a.depth_scale, bad);
-        store<V>(a.out_depth + i, code);
+        hsr_store<V>(a.out_depth + i, code);
     } else {
         const size_t at = (size_t)(plane - FIRST_LABEL_PLANE) * (size_t)a.N + i;
         long long l[V];
-        load<V>(a.labels + at, l);
+        hsr_load<V>(a.labels + at, l);
 #pragma unroll
         for (int v = 0; v < V; v++) code[v] = label_code(l[v], bad);
-        store<V>(a.out_labels + at, code);
+        hsr_store<V>(a.out_labels + at, code);
     }
 }
 
@@ -183,19 +114,19 @@ __device__ __forceinline__ void unpack_values(const UnpackArgs& a, int plane, si
     float x[V];
     if (plane < COLOUR_PLANES) {
         const size_t at = (size_t)plane * (size_t)a.N + i;
-        load<V>(a.color + at, code);
+        hsr_load<V>(a.color + at, code);
 #pragma unroll
         for (int v = 0; v < V; v++) x[v] = hsr_ingest_colour((float)code[v]);
-        store<V>(a.out_color + at, x);
+        hsr_store<V>(a.out_color + at, x);
     } else if (plane == DEPTH_PLANE) {
-        load<V>(a.depth + i, code);
+        hsr_load<V>(a.depth + i, code);
 #pragma unroll
         for (int v = 0; v < V; v++) x[v] = hsr_ingest_depth((double)code[v], a.depth_scale);
-        store<V>(a.out_depth + i, x);
+        hsr_store<V>(a.out_depth + i, x);
     } else {
         const size_t at = (size_t)(plane - FIRST_LABEL_PLANE) * (size_t)a.N + i;
-        load<V>(a.labels + at, code);
-        store<V>(a.out_labels + at, code);
+        hsr_load<V>(a.labels + at, code);
+        hsr_store<V>(a.out_labels + at, code);
     }
 }
 
@@ -279,8 +210,6 @@ __global__ __launch_bounds__(PB) void unpack_kernel(UnpackArgs a)
 
 unsigned blocks_x(int H, int W) { return (unsigned)(((size_t)H * W + PER_BLOCK - 1) / PER_BLOCK); }      // <= 2^18
 
-bool aligned_to(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }      // NULL is aligned
-
 // the checks both entries share; `wide`: the float / int64 side, `codes`: the 8-/16-bit side of each group
 int check(const char* who, int H, int W, int L, double depth_scale, const void* wide_color, const void* code_color, const void* wide_depth,
           const void* code_depth, const void* wide_labels, const void* code_labels, bool packing)
@@ -321,8 +250,8 @@ int check(const char* who, int H, int W, int L, double depth_scale, const void* 
 bool vector_path(const void* wide_color, const void* code_color, const void* wide_depth, const void* code_depth, const void* wide_labels,
                  const void* code_labels)
 {
-    return aligned_to(wide_color, 16) && aligned_to(wide_depth, 16) && aligned_to(wide_labels, 16) && aligned_to(code_color, 4) &&
-           aligned_to(code_depth, 8) && aligned_to(code_labels, 8);
+    return hsr_aligned(wide_color, 16) && hsr_aligned(wide_depth, 16) && hsr_aligned(wide_labels, 16) && hsr_aligned(code_color, 4) &&
+           hsr_aligned(code_depth, 8) && hsr_aligned(code_labels, 8);
 }
 
 }  // namespace
@@ -345,7 +274,7 @@ extern "C" int hsr_keyframe_pack(int H, int W, const float* color, const float* 
         return HSR_ERR_INVALID_ARGUMENT;
     }
     const size_t need = hsr_keyframe_pack_scratch_bytes(H, W, L);
-    if (!scratch || scratch_bytes < need || !aligned_to(scratch, 4)) {
+    if (!scratch || scratch_bytes < need || !hsr_aligned(scratch, 4)) {
         hsr_set_error("keyframe_pack: scratch too small: %zu bytes needed, %zu given (or NULL, or not 4-byte aligned)", need, scratch_bytes);
         return HSR_ERR_INVALID_ARGUMENT;
     }

@@ -9,13 +9,14 @@
 //            its 256 destination rows in LDS and walks its 256 * K source floats with the lanes along the flat index, so reads are
 //            coalesced and writes are wherever neighbours are both selected (a row per lane would stride the lanes by 4 K bytes).
 //   cloud  : cloud_kernel<V> — hsr_block.h's back-projection per pixel; V = 4: a lane owns four pixels, 60 record bytes = 15 aligned
-//            dwords and 12 floats of points; V = 1 for the tail and for records off a dword.
+//            dwords and 12 floats of points (hsr_lane_io.h's vector types); V = 1 for the tail and for records off a dword.
 // Compiled with -ffp-contract=off: the select's outputs must equal hsr_view_prep's bit for bit and the cloud's chain is pinned against
 // a float32 restatement that rounds every operation once.
 #include <math.h>
 
 #include "hsr_common.h"
 #include "hsr_block.h"
+#include "hsr_lane_io.h"
 #include "hsr_view_row.h"
 #include "../../include/ext/hsr_replay.h"
 
@@ -116,9 +117,6 @@ __global__ __launch_bounds__(RB) void select_emit_kernel(ViewArgs a, int K, floa
 }
 
 // ---- cloud -----------------------------------------------------------------------------------------------------------------------------
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef f4 f4_a4 __attribute__((aligned(4)));
-
 // `bytes` bytes of v (little-endian) at byte offset `at` of the packed dwords w (zero before the first call): constant offsets after unrolling
 template <int WORDS>
 __device__ __forceinline__ void put(unsigned (&w)[WORDS], int at, unsigned v, int bytes)
@@ -146,10 +144,10 @@ __device__ __forceinline__ void cloud_pixels(size_t i, int W, const float* __res
         if (V == 4) {
 #pragma unroll
             for (int q = 0; q < 3; q++) {
-                f4 t;
+                hsr_f4 t;
                 t.x = pts[(4 * q) / 3][(4 * q) % 3]; t.y = pts[(4 * q + 1) / 3][(4 * q + 1) % 3];
                 t.z = pts[(4 * q + 2) / 3][(4 * q + 2) % 3]; t.w = pts[(4 * q + 3) / 3][(4 * q + 3) % 3];
-                reinterpret_cast<f4_a4*>(op)[q] = t;
+                reinterpret_cast<hsr_f4_a4*>(op)[q] = t;
             }
         } else {
             op[0] = pts[0][0]; op[1] = pts[0][1]; op[2] = pts[0][2];
@@ -201,7 +199,7 @@ size_t select_blocks(int P) { return ((size_t)(P > 0 ? P : 1) + RB - 1) / RB; }
 // the replay's own scratch check: a refusal like the rest (HSR_ERR_INVALID_ARGUMENT), not hsr_check_scratch's BUFFER_TOO_SMALL
 bool bad_scratch(const char* who, const char* scratch, size_t have, size_t need)
 {
-    if (scratch && have >= need && (reinterpret_cast<uintptr_t>(scratch) & 3) == 0) return false;
+    if (scratch && have >= need && hsr_aligned(scratch, 4)) return false;
     hsr_set_error("%s: scratch too small: %zu bytes needed, %zu given (or NULL, or not 4-byte aligned)", who, need, have);
     return true;
 }
@@ -307,7 +305,7 @@ extern "C" int hsr_replay_cloud(int H, int W, const float* depth, const uint8_t*
     }
     const long long N = (long long)H * W;
     const hsr_pinhole f{fx, fy, cx, cy};
-    if ((reinterpret_cast<uintptr_t>(out_records) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_points) & 3) == 0)
+    if (hsr_aligned(out_records, 4) && hsr_aligned(out_points, 4))
         cloud_kernel<4><<<(unsigned)(((N + 3) / 4 + RB - 1) / RB), RB, 0, stream>>>(N, W, depth, picture, f, c2w, out_points, out_records);
     else
         cloud_kernel<1><<<(unsigned)((N + RB - 1) / RB), RB, 0, stream>>>(N, W, depth, picture, f, c2w, out_points, out_records);

@@ -5,7 +5,8 @@
 //               consecutive lin (consecutive x), projects them first and touches the state only where one of the four is updated: 16-byte
 //               loads and stores of tsdf / weight (and cweight, the three colour planes, best, label where the band |sdf| <= trunc is
 //               hit), so a wave moves whole lines and the points outside the view cost no volume traffic at all.  V = 1 with equal
-//               results for X * Y * Z % 4 != 0 (the colour planes then start off a 16-byte boundary) and for unaligned state.
+//               results for X * Y * Z % 4 != 0 (the colour planes then start off a 16-byte boundary) and for unaligned state: one
+//               body on hsr_lane_io.h's hsr_load<V> / hsr_store<V>.
 //   count     : count_kernel — a cube per lane: eight weights and signs, the triangle count of its six tetrahedra.
 //   faces     : faces_kernel — the same walk, writing edge keys at the cube's offset.  Both read each point eight times; the lines are
 //               shared by neighbouring lanes and rows, and the pass runs once per mesh, not once per view.
@@ -14,15 +15,13 @@
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_lane_io.h"
 #include "hsr_project.h"
 #include "../../include/ext/hsr_tsdf.h"
 
 namespace {
 
 constexpr int TB = 256;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef int i4 __attribute__((ext_vector_type(4)));
 
 struct Grid {
     int X, Y, Z;
@@ -86,62 +85,51 @@ __global__ __launch_bounds__(TB) void integrate_kernel(Grid g, View c, long long
         }
     }
     if (!any) return;
-    if (V == 4) {
-        f4 t = *reinterpret_cast<const f4*>(s.tsdf + base), w = *reinterpret_cast<const f4*>(s.weight + base);
+    // one body for both widths on hsr_lane_io.h's accessors: whatever a lane loads it stores back, changed where the point is updated
+    float t[V], w[V];
+    hsr_load<V>(s.tsdf + base, t);
+    hsr_load<V>(s.weight + base, w);
 #pragma unroll
-        for (int v = 0; v < 4; v++) {
-            if (!hit[v]) continue;
-            t[v] = running_mean(t[v], w[v], fminf(1.f, sdf[v] / c.trunc));
-            w[v] = fminf(w[v] + 1.f, c.max_weight);
+    for (int v = 0; v < V; v++) {
+        if (!hit[v]) continue;
+        t[v] = running_mean(t[v], w[v], fminf(1.f, sdf[v] / c.trunc));
+        w[v] = fminf(w[v] + 1.f, c.max_weight);
+    }
+    hsr_store<V>(s.tsdf + base, t);
+    hsr_store<V>(s.weight + base, w);
+    if (!any_band) return;
+    if (image) {
+        const long long HW = (long long)c.H * c.W;
+        float cw[V];
+        hsr_load<V>(s.cweight + base, cw);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            float col[V];
+            hsr_load<V>(s.color + ch * N + base, col);
+#pragma unroll
+            for (int v = 0; v < V; v++)
+                if (hit[v] && fabsf(sdf[v]) <= c.trunc) col[v] = running_mean(col[v], cw[v], image[ch * HW + pix[v]]);
+            hsr_store<V>(s.color + ch * N + base, col);
         }
-        *reinterpret_cast<f4*>(s.tsdf + base) = t;
-        *reinterpret_cast<f4*>(s.weight + base) = w;
-        if (!any_band) return;
-        if (image) {
-            const long long HW = (long long)c.H * c.W;
-            f4 cw = *reinterpret_cast<const f4*>(s.cweight + base);
 #pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                f4 col = *reinterpret_cast<const f4*>(s.color + ch * N + base);
+        for (int v = 0; v < V; v++)
+            if (hit[v] && fabsf(sdf[v]) <= c.trunc) cw[v] = fminf(cw[v] + 1.f, c.max_weight);
+        hsr_store<V>(s.cweight + base, cw);
+    }
+    if (labels) {
+        float b[V];
+        int l[V];
+        hsr_load<V>(s.best + base, b);
+        hsr_load<V>(s.label + base, l);
 #pragma unroll
-                for (int v = 0; v < 4; v++)
-                    if (hit[v] && fabsf(sdf[v]) <= c.trunc) col[v] = running_mean(col[v], cw[v], image[ch * HW + pix[v]]);
-                *reinterpret_cast<f4*>(s.color + ch * N + base) = col;
+        for (int v = 0; v < V; v++) {
+            if (hit[v] && fabsf(sdf[v]) <= c.trunc && fabsf(sdf[v]) < b[v]) {
+                b[v] = fabsf(sdf[v]);
+                l[v] = (int)labels[pix[v]];
             }
-#pragma unroll
-            for (int v = 0; v < 4; v++)
-                if (hit[v] && fabsf(sdf[v]) <= c.trunc) cw[v] = fminf(cw[v] + 1.f, c.max_weight);
-            *reinterpret_cast<f4*>(s.cweight + base) = cw;
         }
-        if (labels) {
-            f4 b = *reinterpret_cast<const f4*>(s.best + base);
-            i4 l = *reinterpret_cast<const i4*>(s.label + base);
-#pragma unroll
-            for (int v = 0; v < 4; v++) {
-                if (hit[v] && fabsf(sdf[v]) <= c.trunc && fabsf(sdf[v]) < b[v]) {
-                    b[v] = fabsf(sdf[v]);
-                    l[v] = (int)labels[pix[v]];
-                }
-            }
-            *reinterpret_cast<f4*>(s.best + base) = b;
-            *reinterpret_cast<i4*>(s.label + base) = l;
-        }
-    } else {
-        const float w = s.weight[base];
-        s.tsdf[base] = running_mean(s.tsdf[base], w, fminf(1.f, sdf[0] / c.trunc));
-        s.weight[base] = fminf(w + 1.f, c.max_weight);
-        if (!any_band) return;
-        if (image) {
-            const long long HW = (long long)c.H * c.W;
-            const float cw = s.cweight[base];
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) s.color[ch * N + base] = running_mean(s.color[ch * N + base], cw, image[ch * HW + pix[0]]);
-            s.cweight[base] = fminf(cw + 1.f, c.max_weight);
-        }
-        if (labels && fabsf(sdf[0]) < s.best[base]) {
-            s.best[base] = fabsf(sdf[0]);
-            s.label[base] = (int)labels[pix[0]];
-        }
+        hsr_store<V>(s.best + base, b);
+        hsr_store<V>(s.label + base, l);
     }
 }
 
@@ -271,8 +259,6 @@ __global__ __launch_bounds__(TB) void faces_kernel(int X, int Y, int Z, long lon
     }
 }
 
-__device__ __forceinline__ float clamp01(float x) { return x > 0.f ? (x < 1.f ? x : 1.f) : 0.f; }      // a NaN fails x > 0
-
 __global__ __launch_bounds__(TB) void vertices_kernel(Grid g, long long N, long long V, const long long* __restrict__ keys,
                                                       const float* __restrict__ tsdf, const float* __restrict__ color,
                                                       const float* __restrict__ cweight, const int* __restrict__ label,
@@ -303,7 +289,7 @@ __global__ __launch_bounds__(TB) void vertices_kernel(Grid g, long long N, long 
         for (int c = 0; c < 3; c++) {
             const float c0 = color[c * N + lo], c1 = color[c * N + hi];
             const float mix = has0 && has1 ? c0 + t * (c1 - c0) : (has0 ? c0 : (has1 ? c1 : 0.5f));
-            out_rgb[3 * v + c] = (uint8_t)rintf(clamp01(mix) * 255.0f);      // rintf: to nearest, halves to even
+            out_rgb[3 * v + c] = (uint8_t)hsr_colour_code(mix);
         }
     }
     if (out_labels) out_labels[v] = fabsf(s0) <= fabsf(s1) ? label[lo] : label[hi];
@@ -325,8 +311,6 @@ bool bad_grid(const char* who, int X, int Y, int Z, long long& N)
     hsr_set_error("%s: invalid volume X=%d Y=%d Z=%d (every side >= 1, X*Y*Z <= 2^31-1)", who, X, Y, Z);
     return true;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 unsigned blocks_for(long long items) { return (unsigned)((items + TB - 1) / TB); }
 
@@ -369,8 +353,8 @@ extern "C" int hsr_tsdf_integrate(int X, int Y, int Z, float ox, float oy, float
     c.sil_thres = sil_thres; c.depth_max = depth_max; c.trunc = trunc; c.max_weight = max_weight;
     State s{tsdf, weight, color, cweight, best, label};
     const long long* lab = reinterpret_cast<const long long*>(labels);
-    const bool wide = N % 4 == 0 && aligned16(tsdf) && aligned16(weight) && aligned16(color) && aligned16(cweight) && aligned16(best)
-                      && aligned16(label);
+    const bool wide = N % 4 == 0 && hsr_aligned(tsdf, 16) && hsr_aligned(weight, 16) && hsr_aligned(color, 16) && hsr_aligned(cweight, 16)
+                      && hsr_aligned(best, 16) && hsr_aligned(label, 16);
     if (wide)
         integrate_kernel<4><<<blocks_for(N / 4), TB, 0, stream>>>(g, c, N, depth, image, lab, opacity, s);
     else
