@@ -16,8 +16,11 @@
 //     point_list -> record global round trips hide behind compute instead of serialising the tile.
 //   * each 16-lane group of a wave owns a 4x4 sub-block and walks a compacted per-sub-block list built at
 //     staging time from the splats' alpha>=1/255 regions (subblock_mask, hsr_tile_common.h), so splats that
-//     cannot touch the sub-block cost it nothing; the wave iterates to the longest of its four lists (a shorter
-//     group visits a dummy entry of opacity 0 meanwhile: no validity predicate in the loop).  In the wide-tree
+//     cannot touch the sub-block cost it nothing; the wave iterates to the longest of its four lists.  In the per-lane kernels
+//     (K <= 26, the 32-channel chunks) the group is EIGHT lanes on a 4x2 half-block — the upper or the lower two pixel rows of the
+//     sub-block, which is where the lane mapping has lanes 0-7 and 8-15 of a 16-lane group — and the wave builds the eight lists of
+//     its own quadrant from 32-bit half masks (build_half_lists): 60 instead of 68 trips per tile and wave at the headline workload; a
+//     shorter group visits a dummy entry of opacity 0 meanwhile: no validity predicate in the loop.  In the wide-tree
 //     kernels a visit that no lane accepts costs only the alpha test (wave ballot); the kernels up to 32 channels
 //     run one block per visit, staged by hand, without that branch.  A wave whose 64 pixels are all
 //     terminated stops blending but keeps staging.
@@ -138,7 +141,11 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     //     48 channels: K = 48 0.278 -> 0.263 ms, K = 64 0.366 -> 0.354, K = 74 0.364 -> 0.351, 1920x1080 / 2M / K = 74 1.260 -> 1.215;
     //     the 80-channel instantiation fits 136.
     //   * beyond 80 channels (PF): two workgroups per CU, 144 up to 112 channels, 128 x (32 + 4 KC + 8) B < 80 KB at 128.
-    constexpr int BATCH = KC <= 32 ? (KC > 26 ? 200 : 240)
+    //   * the per-lane kernels (no PF) keep thirty-two half-block lists and the batch's half masks where the others keep sixteen lists: 5 KB
+    //     more.  K = 26: 224 entries (two batches still cover the headline's longest tile list, 448); K = 16: 212 (five workgroups per
+    //     CU: 32 000 B each at the LDS's 1 280-byte allocation step); K = 0 and the 32-channel chunk (three workgroups per CU by its registers)
+    //     have the room for what they had.
+    constexpr int BATCH = KC <= 32 ? (PF ? 200 : (KC > 26 ? 200 : (KC == 0 ? 240 : (KC == 16 ? 212 : 224))))
                                    : (KC <= 48 ? 152 : ((KC <= 64 || KC == 74) ? 144 : (KC <= 80 ? 136 : (KC <= 112 ? 144 : 128))));
     static_assert(KC <= 32 || PF, "batch sizes beyond 32 channels assume the touched rows (PF)");
     // per staged splat: a 32-byte record { x, y, A, B | C, opacity, r, g } (pre-scaled conic, see hsr_tile_common.h) — all the
@@ -168,8 +175,13 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
     static_assert(NSLOT <= 256, "list entries are bytes");
     __shared__ float4 s_rec[NSLOT * 2];
     __shared__ float4 s_row[NSLOT * (RW / 4)];
-    __shared__ uint8_t s_sublist[16 * HSR_SUB_LSTRIDE];
-    __shared__ uint8_t s_subcnt[4][16];
+    // lists of batch slots: sixteen sub-block lists in four cross-wave segments each (QS), or thirty-two half-block lists, eight to a wave
+    // and built by that wave from the staged half masks (hsr_tile_common.h)
+    constexpr int HLS = hsr_half_lstride(BATCH);
+    static_assert(QS || BATCH + 3 <= HLS, "a list holds a batch, the two entries read ahead and the byte nothing reads");
+    __shared__ __attribute__((aligned(16))) uint8_t s_sublist[QS ? 16 * HSR_SUB_LSTRIDE : 32 * HLS];
+    __shared__ uint8_t s_subcnt[QS ? 4 : 1][16];
+    __shared__ uint32_t s_hmask[QS ? 1 : BATCH];
     __shared__ int s_wdone[4];
 
     const int tile = hsr_block_tile(blockIdx.x, hsr_num_tiles(a.W, a.H));
@@ -338,7 +350,11 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
         if constexpr (PIPE) settle_staging();   // the one wait of a batch for its gathers
         uint32_t mask16 = 0u;
         if (t < cnt) {
-            mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0);
+            if constexpr (QS) {
+                mask16 = subblock_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0);
+            } else {   // the same sixteen bits, and under each the halves that are reached
+                s_hmask[t] = subblock_half_mask(p_xy.x, p_xy.y, p_co.x, p_co.y, p_co.z, p_co.w, tile_x0, tile_y0, mask16);
+            }
             if constexpr (PIPE) masks_g[range.x + start + t] = mask16;
             else a.masks[range.x + start + t] = mask16;   // the backward stages the same entries: it reads the mask instead of deriving it again
             s_rec[2 * t] = make_float4(p_xy.x, p_xy.y, (-0.5f * HSR_LOG2E) * p_co.x, -HSR_LOG2E * p_co.y);
@@ -405,7 +421,7 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
         }
         const long long tp0 = TRF_NOW();
         (void)tp0;
-        publish_subblock_lists(mask16, t, s_sublist, s_subcnt);
+        if constexpr (QS) publish_subblock_lists(mask16, t, s_sublist, s_subcnt);
         TRF_ADD(tr_pub, tp0);
         TRF_ADD(tr_stage, ts0);
         const long long tb1 = TRF_NOW();
@@ -422,18 +438,22 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
         }
         if (wave_done) continue;
 
-        // four lists per wave, one per 16-lane group; the wave iterates to the longest of them
+        // QS: four lists per wave, one per 16-lane group; the per-lane kernels: eight, one per 8-lane group (a 4x2 half-block), padded with
+        // the dummy entry.  The wave iterates to the longest of them.
         const int lane = t & 63, sb = wv * 4 + (lane >> 4);
-        const int total = flatten_sublist(sb, lane, s_sublist, s_subcnt);
-        const int m = __builtin_amdgcn_readfirstlane(max(max(__builtin_amdgcn_readlane(total, 0), __builtin_amdgcn_readlane(total, 16)),
-                                                         max(__builtin_amdgcn_readlane(total, 32), __builtin_amdgcn_readlane(total, 48))));
-        const uint8_t* list = s_sublist + sb * HSR_SUB_LSTRIDE;
+        int total, m;
+        const uint8_t* list;
         if constexpr (QS) {
+            total = flatten_sublist(sb, lane, s_sublist, s_subcnt);
+            m = __builtin_amdgcn_readfirstlane(max(max(__builtin_amdgcn_readlane(total, 0), __builtin_amdgcn_readlane(total, 16)),
+                                                   max(__builtin_amdgcn_readlane(total, 32), __builtin_amdgcn_readlane(total, 48))));
+            list = s_sublist + sb * HSR_SUB_LSTRIDE;
             // a group past the end of its list keeps re-reading its last entry, with weight 0 (an empty list is given the always
             // staged slot 0 as its only entry): an unconditional clamped read instead of a masked one
             if (total == 0 && (lane & 15) == 0) s_sublist[sb * HSR_SUB_LSTRIDE] = 0;
         } else {
-            pad_sublist(sb, lane, s_sublist, total, m, BATCH);
+            total = build_half_lists<HLS>(wv, lane, cnt, BATCH, s_hmask, s_sublist, m);
+            list = s_sublist + (wv * 8 + (lane >> 3)) * HLS;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -516,7 +536,7 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
             // of trip k + 2, the record of trip k + 1 and the first rows of its own entry, blends those rows, requests the rest and blends
             // them (ALPHA_AHEAD: the alpha of trip k + 1 is computed in trip k, while the rows are in flight, and handed over).  There is no
             // branch round a trip in which no lane contributes (2 % of the trips at the headline workload): with it hipcc keeps two paths
-            // apart and the staging gains nothing.  The look-ahead reads up to list[m + 1], which pad_sublist has filled with the dummy;
+            // apart and the staging gains nothing.  The look-ahead reads up to list[m + 1], which build_half_lists has filled with the dummy;
             // nothing staged here survives the batch.  The per-pixel arithmetic is what it was, operation for operation.
             const int base1 = start + 1;
             int last_rel = (int)last_contributor - base1, med_rel = (int)median_at - base1;
@@ -645,7 +665,7 @@ __global__ void __launch_bounds__(256, KC <= 26 ? (KC == 16 ? 5 : 4) : (PF ? (KC
             o[2] = tr_bar; o[3] = tr_stage; o[4] = tr_blend;  // inside workgroup barriers / staging work / blend loops
             o[5] = (unsigned long long)(clock64() - tr_t2);   // epilogue (output stores)
             o[6] = tr_iters;
-            o[7] = tr_pub;                                    // of the staging work: publishing the sixteen sub-block lists
+            o[7] = tr_pub;                                    // of the staging work: publishing the sixteen sub-block lists (wide trees only)
         }
     }
 #endif

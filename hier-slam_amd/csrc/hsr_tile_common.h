@@ -154,14 +154,19 @@ __device__ __forceinline__ TileGeom tile_geom_sub(int tile, int W, int H, int t)
 // per-pixel test in the blend loop stays exact, so a block kept in vain costs time, never accuracy; a block dropped wrongly
 // would cost accuracy — the parity and fuzz suites compare every pixel with the oracle).  ~25 live registers: it is inlined
 // into the staging phase of kernels that sit at the 128-register step.
-__device__ __forceinline__ uint32_t subblock_mask(float x, float y, float cx, float cy, float cz, float opacity, float tile_x0,
-                                                  float tile_y0)
+template <bool HALVES>
+__device__ __forceinline__ uint32_t subblock_masks(float x, float y, float cx, float cy, float cz, float opacity, float tile_x0, float tile_y0,
+                                                   uint32_t& halves)
 {
+    halves = 0u;
     const float t255 = 255.0f * opacity;
     if (!(t255 >= 1.0f)) return 0u;
     const float tau = 2.0f * __logf(t255) * 1.002f + 0.02f;
     const float det = cx * cz - cy * cy;
-    if (!(det > 0.0f) || !(cx > 0.0f) || !(cz > 0.0f)) return 0xFFFFu;
+    if (!(det > 0.0f) || !(cx > 0.0f) || !(cz > 0.0f)) {
+        halves = 0xFFFFFFFFu;
+        return 0xFFFFu;
+    }
     const float inv_det = 1.0f / det, inv_a = 1.0f / cx;
     const float hx = sqrtf(tau * cz * inv_det), hy = sqrtf(tau * cx * inv_det) * 1.001f + 0.02f;   // half extents of E
     const float dyp = -(cy / cz) * hx;                  // dy of E's rightmost point; its leftmost point sits at -dyp
@@ -181,9 +186,114 @@ __device__ __forceinline__ uint32_t subblock_mask(float x, float y, float cx, fl
 #pragma unroll
         for (int c = 0; c < 4; c++)   // the sub-block's dx interval is [rx - (4c + 3), rx - 4c]
             rb |= (uint32_t)((rx - (4.0f * c + 3.0f)) <= xmax && (rx - 4.0f * c) >= xmin) << (4 * (c >> 1) + (c & 1));
-        if (lo <= hi) m |= rb << (8 * (r >> 1) + 2 * (r & 1));
+        if (lo <= hi) {
+            const uint32_t row = rb << (8 * (r >> 1) + 2 * (r & 1));
+            m |= row;
+            if constexpr (HALVES) {
+                // the slabs of the row's upper two pixel rows, dy in [ry_hi - 1, ry_hi], and of its lower two, [ry_hi - 3, ry_hi - 2]
+                if (fmaxf(ry_hi - 1.0f, -hy) <= hi) halves |= row;
+                if (lo <= fminf(ry_hi - 2.0f, hy)) halves |= row << 16;
+            }
+        }
     }
     return m;
+}
+__device__ __forceinline__ uint32_t subblock_mask(float x, float y, float cx, float cy, float cz, float opacity, float tile_x0,
+                                                  float tile_y0)
+{
+    uint32_t halves;
+    return subblock_masks<false>(x, y, cx, cy, cz, opacity, tile_x0, tile_y0, halves);
+}
+
+// ---- 4x2 half-blocks (hsr_render_fwd.hip, the per-lane kernels' visit loop) ----
+// Under tile_geom_sub's lane mapping lanes 0..7 of a 16-lane group hold pixel rows 0 and 1 of the 4x4 sub-block and lanes 8..15 rows 2 and 3:
+// every EIGHT-lane group of a wave is a 4x2 HALF-BLOCK, half (b, h) of the tile (b: the sub-block's bit in subblock_mask, h = 1: the lower
+// two rows), eight to a wave.  The forward's visit loop costs a wave as many trips as its longest list, and eight lists of half-blocks
+// are shorter than four of sub-blocks (tests/sim_half_groups.py: 68 -> 60 trips per tile and wave at the headline workload).
+//
+// subblock_half_mask returns subblock_mask's 16 bits in `mask16` — one body (subblock_masks above), so bit for bit the mask the backward
+// is given — and, for every bit that is set, which of the sub-block's halves the alpha >= 1/255 region can reach: bit 16 h + b of the
+// result (the upper halves in subblock_mask's own layout, the lower halves sixteen bits above them).  The rule for a half is the
+// sub-block's own for the columns and E's extent in y for the rows: the half's slab of two pixel rows must meet [ry - hy, ry + hy].  A
+// bit of mask16 with neither half bit: the region crosses the 4x4 slab between its pixel rows 1 and 2 and holds no pixel centre; no
+// group visits it.  A degenerate conic reaches every half, as it reaches every sub-block.
+// (E's dx interval over the half's own slab — the sub-block's rule applied to two rows, on hardware square roots — was built and measured
+// too: 56.6 instead of 60.1 trips, but 73 instead of 14 instructions more per row of sub-blocks and staged entry, and the step came out
+// 0.6 % slower than with this rule: EXPERIMENTS.md §10o.)
+__device__ __forceinline__ uint32_t subblock_half_mask(float x, float y, float cx, float cy, float cz, float opacity, float tile_x0,
+                                                       float tile_y0, uint32_t& mask16)
+{
+    uint32_t halves;
+    mask16 = subblock_masks<true>(x, y, cx, cy, cz, opacity, tile_x0, tile_y0, halves);
+    return halves;
+}
+
+// Bytes of a half-block's list for batches of `batch` entries: the batch, the two entries the visit loop reads ahead, one byte more that
+// nothing reads (build_half_lists sends there what a list does not take), and a length in 4-byte words that is ODD, so that the eight
+// lists of a wave start in eight different banks.
+__host__ __device__ constexpr int hsr_half_lstride(int batch) { return 4 * (((batch + 3 + 3) / 4) | 1); }
+
+// Inclusive prefix sums over the 64 lanes of a wave (row shifts, then the two cross-row broadcasts of gfx9's DPP) of two words, step by
+// step in turn; a word may hold FOUR counters, one per byte, if no byte's total passes 255.
+__device__ __forceinline__ void hsr_wave_scan_bytes2(uint32_t& a, uint32_t& b)
+{
+#define HSR_SCAN_STEP(CTRL, ROWS)                                                      \
+    a += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, CTRL, ROWS, 0xf, false);     \
+    b += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, CTRL, ROWS, 0xf, false);
+    HSR_SCAN_STEP(0x111, 0xf)   // row_shr:1
+    HSR_SCAN_STEP(0x112, 0xf)   // row_shr:2
+    HSR_SCAN_STEP(0x114, 0xf)   // row_shr:4
+    HSR_SCAN_STEP(0x118, 0xf)   // row_shr:8
+    HSR_SCAN_STEP(0x142, 0xa)   // row_bcast:15 into rows 1 and 3
+    HSR_SCAN_STEP(0x143, 0xc)   // row_bcast:31 into rows 2 and 3
+#undef HSR_SCAN_STEP
+}
+
+// The eight half-block lists of wave `wv`, built by the wave itself from the batch's staged masks (s_hmask[slot]: subblock_half_mask of the
+// entry in the slot, written by the staging lanes in front of the workgroup barrier that precedes this call; the wave reads bits 4 wv ..
+// 4 wv + 3 of each half-word, the eight halves of its own quadrant; group g = lane >> 3 is half (4 wv + (g >> 1), g & 1)).  No other wave
+// reads or writes these lists, so nothing here needs a cross-wave prefix or a barrier, and a wave that has nothing left to blend does
+// not build them.  The lists are first filled with `dummy` — the slot of the staged entry of opacity 0 — sixteen bytes a lane at a time
+// (LDS operations of one wave execute in order), then written front to back in slot order, 64 slots a round: behind its last entry every
+// list holds the dummy for as far as it goes, which is what the visit loop reads while a longer list of the wave is walked and what its
+// look-ahead of two entries reads.  A round ranks its 64 slots in all eight lists with two prefix sums: the four upper halves' bits are
+// spread to the four bytes of one word, the lower halves' to another, and a list's length (at most a batch: under 256) rides in the
+// same byte, so a slot's place in four lists is one addition; where a list does not take the slot the place is replaced, in the same word, by
+// the list's last byte, which nothing reads: eight unconditional byte stores instead of eight under a lane mask of their own.  Returns this lane's group's list length; `longest`: the longest of the
+// eight, wave-uniform.
+template <int LSTRIDE>
+__device__ __forceinline__ int build_half_lists(int wv, int lane, int cnt, int dummy, const uint32_t* s_hmask, uint8_t* s_list, int& longest)
+{
+    static_assert(LSTRIDE % 4 == 0 && (8 * LSTRIDE) % 16 == 0, "the fill moves 16 bytes at a time");
+    static_assert(LSTRIDE <= 256, "a place in a list is a byte");
+    uint8_t* const base = s_list + wv * 8 * LSTRIDE;
+    const uint32_t d4 = 0x01010101u * (uint32_t)dummy;
+    for (int i = lane; i < 8 * LSTRIDE / 16; i += 64) reinterpret_cast<uint4*>(base)[i] = make_uint4(d4, d4, d4, d4);
+    uint32_t len[2] = {0u, 0u};   // byte j of len[h]: the length of the list of group 2 j + h
+    for (int s0 = 0; s0 < cnt; s0 += 64) {
+        const int slot = s0 + lane;
+        const uint32_t w = slot < cnt ? s_hmask[slot] >> (4 * wv) : 0u;
+        // (both prefix sums first: their DPP steps interleave, and neither waits for the other's stores)
+        uint32_t on[2], incl[2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) on[h] = (((w >> (16 * h)) & 15u) * 0x00204081u) & 0x01010101u;   // bit j -> bit 8 j
+#pragma unroll
+        for (int h = 0; h < 2; h++) incl[h] = on[h];
+        hsr_wave_scan_bytes2(incl[0], incl[1]);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const uint32_t take = on[h] * 255u;   // 0xff in the bytes of the lists that take the slot
+            const uint32_t at = ((len[h] + incl[h] - on[h]) & take) | (~take & (0x01010101u * (uint32_t)(LSTRIDE - 1)));
+#pragma unroll
+            for (int j = 0; j < 4; j++) base[(2 * j + h) * LSTRIDE + ((at >> (8 * j)) & 255u)] = (uint8_t)slot;
+            len[h] += (uint32_t)__builtin_amdgcn_readlane((int)incl[h], 63);
+        }
+    }
+    const int g = lane >> 3;
+    longest = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) longest = max(longest, (int)((len[k & 1] >> (8 * (k >> 1))) & 255u));
+    return (int)(((g & 1 ? len[1] : len[0]) >> (8 * (g >> 1))) & 255u);
 }
 
 // quadrant mask (bit q = wave q) from the exact sub-block test: a quadrant is visited iff one of its four sub-blocks is
@@ -237,16 +347,6 @@ __device__ __forceinline__ int flatten_sublist(int sb, int lane, uint8_t* s_list
     }
     __builtin_amdgcn_wave_barrier();
     return total;
-}
-
-// Forward visit loop without a validity predicate: a wave runs m = the longest of its four groups' lists trips, and a shorter group
-// fills its list up to and including index m + 1 (the loop reads the list two entries ahead) with `dummy`, the
-// slot of a staged entry of opacity 0.  m <= 240 entries per batch, so m + 1 < HSR_SUB_LSTRIDE and the padding stays inside the group's own
-// list.  Call after flatten_sublist.
-__device__ __forceinline__ void pad_sublist(int sb, int lane, uint8_t* s_list, int total, int m, int dummy)
-{
-    uint8_t* list = s_list + sb * HSR_SUB_LSTRIDE;
-    for (int p = total + (lane & 15); p <= m + 1; p += 16) list[p] = (uint8_t)dummy;
 }
 
 // ---- packed per-Gaussian gradient row (backward, default accumulation mode) ----
