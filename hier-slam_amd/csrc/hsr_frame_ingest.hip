@@ -1,11 +1,15 @@
 // hsr_frame_ingest.hip — device ingest of one raw sensor frame to one, two or three sizes (gfx950), DESIGN.md §7 row 8.
 // See include/ext/hsr_frame_ingest.h for the three rules, step by step, and the reference lines (basedataset.py:223-227, :248-256,
 // replica.py:241-299, scripts/hierslam.py:1777), and include/ext/hsr_frame_ingest_planes.h for the same rules with a source size per
-// image and a leaf column in the label table (scannet.py:284-339).  ONE kernel runs behind both entries: hsr_frame_ingest passes the
-// sensor size three times and leaf_column = 0.
+// image and a leaf column in the label table (scannet.py:284-339), and include/sensor/hsr_frame_undistort.h for hsr_frame_ingest with the
+// colour image undistorted on the way (basedataset.py:306-309).  ONE kernel runs behind all three entries: hsr_frame_ingest passes the
+// sensor size three times and leaf_column = 0; hsr_frame_ingest_undistort does the same and sets the compile-time flag UND, with which
+// a colour tap is a value of the undistorted image U at that pixel instead of the 8-bit pixel.
 //   ingest_kernel : one thread per destination pixel over the concatenated pixel ranges of the levels (level 0's pixels first): the
 //                   three colour channels bilinearly in float64 from four interleaved 8-bit taps, then / 255; the depth from one raw
 //                   source word divided by the scale; at level 0 the L + 1 int64 label planes from one raw id and its table row.
+//                   With UND each of the four taps is U: the pixel's source coordinates in float64, quantised to 1/32 pixel, and the
+//                   exact integer blend of four 8-bit taps that are 0 outside the image (one tap at a level of the sensor's size).
 // Memory-bound and small (a 1200x680 frame to itself and two 600x340 levels reads 8 MB and writes 20 MB with 5-level labels); no
 // reuse worth staging in LDS.  Compiled with -ffp-contract=off: the three float64 lerps are evaluated as the header writes them.
 #include <math.h>
@@ -16,6 +20,7 @@
 #include "../../include/ext/hsr_frame_resample.h"
 #include "../../include/ext/hsr_frame_ingest.h"
 #include "../../include/ext/hsr_frame_ingest_planes.h"
+#include "../../include/sensor/hsr_frame_undistort.h"
 
 namespace {
 
@@ -39,12 +44,43 @@ __device__ __forceinline__ double raw_depth(const void* __restrict__ p, size_t i
     return (double)static_cast<const float*>(p)[i];
 }
 
+// where the undistorted pixel (u, v) reads the 8-bit image: the tap (sy, sx), the weights ax, ay / 32 of the taps after it
+// (include/sensor/hsr_frame_undistort.h, U); !ok: a NaN coordinate, the pixel is 0
+struct Und {
+    int sx, sy, ax, ay;
+    bool ok;
+};
+
+__device__ __forceinline__ Und und_at(int u, int v, const hsr_lens& lens)
+{
+    double us, vs;
+    hsr_undistort_source(u, v, lens, us, vs);      // hsr_ingest_expr.h, in double
+    Und t;
+    const bool okx = hsr_undistort_step(us, t.sx, t.ax), oky = hsr_undistort_step(vs, t.sy, t.ay);
+    t.ok = okx && oky;
+    return t;
+}
+
+// U[v][u][ch] of the pixel `t` was made for: an exact integer below 2^18 over 1024; a tap outside the image is 0 and is not read
+__device__ __forceinline__ double und_value(const uint8_t* __restrict__ color, int Hc, int Wc, const Und& t, int ch)
+{
+    if (!t.ok) return 0.0;
+    const bool x0 = t.sx >= 0 && t.sx < Wc, x1 = t.sx + 1 >= 0 && t.sx + 1 < Wc;      // |sx|, |sy| <= 2^25
+    const bool y0 = t.sy >= 0 && t.sy < Hc, y1 = t.sy + 1 >= 0 && t.sy + 1 < Hc;
+    const uint8_t* __restrict__ p = color + ((long long)t.sy * Wc + t.sx) * 3 + ch;      // followed only where the tap is inside
+    const int a = y0 && x0 ? p[0] : 0, b = y0 && x1 ? p[3] : 0;
+    const int c = y1 && x0 ? p[(size_t)Wc * 3] : 0, d = y1 && x1 ? p[(size_t)Wc * 3 + 3] : 0;
+    const int n = a * (32 - t.ax) * (32 - t.ay) + b * t.ax * (32 - t.ay) + c * (32 - t.ax) * t.ay + d * t.ax * t.ay;
+    return (double)n / 1024.0;
+}
+
 // table: int32 [n_ids, L + leaf], leaf 0 or 1; n_ids 0 without a table (no id is then "known" and the table is not read)
-template <int DT>
+// UND: a colour tap is U at that pixel (lens: the sensor's camera and coefficients), else the 8-bit pixel (lens is not read)
+template <int DT, bool UND>
 __global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ color, const void* __restrict__ depth, Sources src,
                                                     double depth_scale, const int* __restrict__ labels, int L, int leaf,
                                                     const int* __restrict__ table, int n_ids, Levels lv, long long n_all,
-                                                    long long* __restrict__ out_labels)
+                                                    long long* __restrict__ out_labels, hsr_lens lens)
 {
     long long i = (long long)blockIdx.x * IB + threadIdx.x;
     if (i >= n_all) return;
@@ -61,16 +97,35 @@ __global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ 
     hsr_taps(x, src.Wc, Wd, x0, x1, fx);      // hsr_ingest_expr.h, in double
     hsr_taps(y, src.Hc, Hd, y0, y1, fy);
     const size_t dplane = (size_t)Hd * Wd;
-    const uint8_t* __restrict__ r0 = color + (size_t)y0 * src.Wc * 3;
-    const uint8_t* __restrict__ r1 = color + (size_t)y1 * src.Wc * 3;
-    const size_t c0 = (size_t)x0 * 3, c1 = (size_t)x1 * 3;
+    if constexpr (!UND) {
+        const uint8_t* __restrict__ r0 = color + (size_t)y0 * src.Wc * 3;
+        const uint8_t* __restrict__ r1 = color + (size_t)y1 * src.Wc * 3;
+        const size_t c0 = (size_t)x0 * 3, c1 = (size_t)x1 * 3;
 #pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const double a = (double)r0[c0 + ch], b = (double)r0[c1 + ch], c = (double)r1[c0 + ch], d = (double)r1[c1 + ch];
-        const double top = a + fx * (b - a);
-        const double bot = c + fx * (d - c);
-        const double v = top + fy * (bot - top);
-        oc[ch * dplane + (size_t)i] = hsr_ingest_colour((float)v);      // float(v) / 255.0f (hsr_ingest_expr.h)
+        for (int ch = 0; ch < 3; ch++) {
+            const double a = (double)r0[c0 + ch], b = (double)r0[c1 + ch], c = (double)r1[c0 + ch], d = (double)r1[c1 + ch];
+            const double top = a + fx * (b - a);
+            const double bot = c + fx * (d - c);
+            const double v = top + fy * (bot - top);
+            oc[ch * dplane + (size_t)i] = hsr_ingest_colour((float)v);      // float(v) / 255.0f (hsr_ingest_expr.h)
+        }
+    } else if (Hd == src.Hc && Wd == src.Wc) {
+        // a level of the sensor's size: x0 = x, y0 = y and both weights are 0, so v = a + 0 * (b - a) is a bit for bit; one tap
+        const Und ta = und_at(x, y, lens);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++)
+            oc[ch * dplane + (size_t)i] = hsr_ingest_colour((float)und_value(color, src.Hc, src.Wc, ta, ch));
+    } else {
+        const Und ta = und_at(x0, y0, lens), tb = und_at(x1, y0, lens), tc = und_at(x0, y1, lens), td = und_at(x1, y1, lens);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) {
+            const double a = und_value(color, src.Hc, src.Wc, ta, ch), b = und_value(color, src.Hc, src.Wc, tb, ch);
+            const double c = und_value(color, src.Hc, src.Wc, tc, ch), d = und_value(color, src.Hc, src.Wc, td, ch);
+            const double top = a + fx * (b - a);
+            const double bot = c + fx * (d - c);
+            const double v = top + fy * (bot - top);
+            oc[ch * dplane + (size_t)i] = hsr_ingest_colour((float)v);
+        }
     }
     // nearest, each image from its own size: products < 2^28; xs <= W_src - 1, ys <= H_src - 1
     const size_t sd = (size_t)((y * src.Hd) / Hd) * src.Wd + (x * src.Wd) / Wd;
@@ -86,12 +141,13 @@ __global__ __launch_bounds__(IB) void ingest_kernel(const uint8_t* __restrict__ 
     }
 }
 
-// the checks and the launch of both entries; `planes`: hsr_frame_ingest_planes (the messages name the entry and its arguments)
-int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_raw, int depth_type, double depth_scale,
+// the checks and the launch of the three entries; `planes`: hsr_frame_ingest_planes (the messages name the entry and its arguments);
+// `lens`: hsr_frame_ingest_undistort, else NULL
+int ingest(bool planes, const hsr_lens* lens, Sources src, const uint8_t* color_u8, const void* depth_raw, int depth_type, double depth_scale,
            const int* labels, int num_levels, const int* table, int n_ids, int leaf_column,
            int n_out, const hsr_ingest_level* levels, int64_t* out_labels, hipStream_t stream)
 {
-    const char* who = planes ? "frame_ingest_planes" : "frame_ingest";
+    const char* who = planes ? "frame_ingest_planes" : lens ? "frame_ingest_undistort" : "frame_ingest";
     if (n_out < 1 || n_out > HSR_INGEST_MAX_LEVELS || !levels) {
         hsr_set_error("%s: n_out must be 1..%d with a host array of that many levels; got %d", who, HSR_INGEST_MAX_LEVELS, n_out);
         return HSR_ERR_INVALID_ARGUMENT;
@@ -105,7 +161,7 @@ int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_
                           "level 0 %dx%d (of %d levels)", HSR_RESAMPLE_MAX_SIDE, src.Hc, src.Wc, src.Hd, src.Wd, src.Hl, src.Wl,
                           levels[0].H, levels[0].W, n_out);
         else
-            hsr_set_error("frame_ingest: sides must be 1..%d: sensor %dx%d, level 0 %dx%d (of %d levels)", HSR_RESAMPLE_MAX_SIDE, src.Hc,
+            hsr_set_error("%s: sides must be 1..%d: sensor %dx%d, level 0 %dx%d (of %d levels)", who, HSR_RESAMPLE_MAX_SIDE, src.Hc,
                           src.Wc, levels[0].H, levels[0].W, n_out);
         return HSR_ERR_INVALID_ARGUMENT;
     }
@@ -124,8 +180,8 @@ int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_
                           "label_table of n_ids >= 1 rows; got %d levels, leaf_column %d, n_ids %d", HSR_EVAL_MAX_LEVELS, num_levels,
                           leaf_column, n_ids);
         else
-            hsr_set_error("frame_ingest: num_levels must be 0..%d, and with num_levels > 0 a tree_table of n_ids >= 1 rows; got %d levels, "
-                          "n_ids %d", HSR_EVAL_MAX_LEVELS, num_levels, n_ids);
+            hsr_set_error("%s: num_levels must be 0..%d, and with num_levels > 0 a tree_table of n_ids >= 1 rows; got %d levels, "
+                          "n_ids %d", who, HSR_EVAL_MAX_LEVELS, num_levels, n_ids);
         return HSR_ERR_INVALID_ARGUMENT;
     }
     bool null = !color_u8 || !depth_raw || ((labels == nullptr) != (out_labels == nullptr));
@@ -133,6 +189,18 @@ int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_
     if (null) {
         hsr_set_error("%s: NULL color_u8 / depth_raw, a NULL output of a requested level, or labels without out_labels (or the reverse)", who);
         return HSR_ERR_INVALID_ARGUMENT;
+    }
+    if (lens) {
+        if (!isfinite(lens->fx) || !isfinite(lens->fy) || lens->fx == 0.0 || lens->fy == 0.0) {
+            hsr_set_error("%s: fx and fy must be finite and non-zero; got %g, %g", who, lens->fx, lens->fy);
+            return HSR_ERR_INVALID_ARGUMENT;
+        }
+        if (!isfinite(lens->cx) || !isfinite(lens->cy) || !isfinite(lens->k1) || !isfinite(lens->k2) || !isfinite(lens->p1) ||
+            !isfinite(lens->p2) || !isfinite(lens->k3)) {
+            hsr_set_error("%s: cx, cy and the coefficients k1, k2, p1, p2, k3 must be finite; got %g, %g and %g, %g, %g, %g, %g", who,
+                          lens->cx, lens->cy, lens->k1, lens->k2, lens->p1, lens->p2, lens->k3);
+            return HSR_ERR_INVALID_ARGUMENT;
+        }
     }
     if (!labels) src.Hl = src.Wl = 1;      // not read by the kernel; never a side it was not checked for
     Levels lv{};
@@ -149,12 +217,18 @@ int ingest(bool planes, Sources src, const uint8_t* color_u8, const void* depth_
     const unsigned nblk = (unsigned)((n_all + IB - 1) / IB);
     long long* ol = reinterpret_cast<long long*>(out_labels);
     const int n_ids_k = has_table ? n_ids : 0;      // without a table no id is "known"
-#define HSR_INGEST_LAUNCH(DT) \
-    ingest_kernel<DT><<<nblk, IB, 0, stream>>>(color_u8, depth_raw, src, depth_scale, labels, num_levels, leaf_column, table, n_ids_k, lv, n_all, ol)
+    const hsr_lens lens_k = lens ? *lens : hsr_lens{};      // read by the UND instantiations only
+#define HSR_INGEST_ARGS color_u8, depth_raw, src, depth_scale, labels, num_levels, leaf_column, table, n_ids_k, lv, n_all, ol, lens_k
+#define HSR_INGEST_LAUNCH(DT)                                                        \
+    do {                                                                             \
+        if (lens) ingest_kernel<DT, true><<<nblk, IB, 0, stream>>>(HSR_INGEST_ARGS); \
+        else ingest_kernel<DT, false><<<nblk, IB, 0, stream>>>(HSR_INGEST_ARGS);     \
+    } while (0)
     if (depth_type == HSR_INGEST_DEPTH_U16) HSR_INGEST_LAUNCH(HSR_INGEST_DEPTH_U16);
     else if (depth_type == HSR_INGEST_DEPTH_I32) HSR_INGEST_LAUNCH(HSR_INGEST_DEPTH_I32);
     else HSR_INGEST_LAUNCH(HSR_INGEST_DEPTH_F32);
 #undef HSR_INGEST_LAUNCH
+#undef HSR_INGEST_ARGS
     HSR_HIP_CHECK(hipGetLastError());
     return HSR_OK;
 }
@@ -165,7 +239,7 @@ extern "C" int hsr_frame_ingest(int Hs, int Ws, const uint8_t* color_u8, const v
                                 const int* labels, int num_levels, const int* tree_table, int n_ids,
                                 int n_out, const hsr_ingest_level* levels, int64_t* out_labels, void* stream_)
 {
-    return ingest(false, Sources{Hs, Ws, Hs, Ws, Hs, Ws}, color_u8, depth_raw, depth_type, depth_scale, labels, num_levels, tree_table, n_ids,
+    return ingest(false, nullptr, Sources{Hs, Ws, Hs, Ws, Hs, Ws}, color_u8, depth_raw, depth_type, depth_scale, labels, num_levels, tree_table, n_ids,
                   0, n_out, levels, out_labels, (hipStream_t)stream_);
 }
 
@@ -175,6 +249,17 @@ extern "C" int hsr_frame_ingest_planes(int Hc, int Wc, const uint8_t* color_u8,
                                        int num_levels, const int* label_table, int n_ids, int leaf_column,
                                        int n_out, const hsr_ingest_level* levels, int64_t* out_labels, void* stream_)
 {
-    return ingest(true, Sources{Hc, Wc, Hd, Wd, Hl, Wl}, color_u8, depth_raw, depth_type, depth_scale, labels, num_levels, label_table, n_ids,
+    return ingest(true, nullptr, Sources{Hc, Wc, Hd, Wd, Hl, Wl}, color_u8, depth_raw, depth_type, depth_scale, labels, num_levels, label_table, n_ids,
                   leaf_column, n_out, levels, out_labels, (hipStream_t)stream_);
+}
+
+extern "C" int hsr_frame_ingest_undistort(int Hs, int Ws, const uint8_t* color_u8, const void* depth_raw, int depth_type, double depth_scale,
+                                          const int* labels, int num_levels, const int* tree_table, int n_ids,
+                                          double fx, double fy, double cx, double cy,
+                                          double k1, double k2, double p1, double p2, double k3,
+                                          int n_out, const hsr_ingest_level* levels, int64_t* out_labels, void* stream_)
+{
+    const hsr_lens lens{fx, fy, cx, cy, k1, k2, p1, p2, k3};
+    return ingest(false, &lens, Sources{Hs, Ws, Hs, Ws, Hs, Ws}, color_u8, depth_raw, depth_type, depth_scale, labels, num_levels, tree_table,
+                  n_ids, 0, n_out, levels, out_labels, (hipStream_t)stream_);
 }

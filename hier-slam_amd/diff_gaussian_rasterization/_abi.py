@@ -1,7 +1,7 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h, include/ext/, include/eval/ and include/recon/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
+Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/ and include/sensor/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
 import from this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
 header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
 include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
@@ -374,6 +374,19 @@ RECON_HEADERS = {
     ),
 }
 
+# ---- the headers under include/sensor/, a fourth table of the same shape: RECON_HEADERS above is a counted set too
+# ---- (tests/test_mesh_depth_cpu.py); tests/test_frame_undistort_cpu.py checks this one with the same helpers -------------------------
+SENSOR_HEADERS = {
+    # the ingest with the colour image undistorted on the way: the camera of the sensor image and five coefficients, all double
+    "sensor/hsr_frame_undistort.h": (
+        ("hsr_frame_ingest_undistort", ci, [ci, ci, vp, vp, ci, cd,
+                                            vp, ci, vp, ci,
+                                            cd, cd, cd, cd,
+                                            cd, cd, cd, cd, cd,
+                                            ci, C.POINTER(hsr_ingest_level), vp, vp]),
+    ),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -382,7 +395,7 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for table in list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()):
+    for table in list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()) + list(SENSOR_HEADERS.values()):
         for name, restype, argtypes in table:
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes

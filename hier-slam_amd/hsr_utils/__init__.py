@@ -10,9 +10,9 @@ from .synthetic import make_scene, make_upstream_grads  # noqa: F401
 _KEYFRAMES = ("keyframe_selection_overlap", "overlap_counts", "KeyframePoses", "mapping_window")
 _SLAM = ("initialize_first_timestep", "initialize_camera_pose", "update_poses", "matrix_to_quaternion", "is_keyframe", "SlamSession",
          "resample_frame", "render_view")
-_FRAMES = ("tree_label_table", "ingest_frame", "ingest_frame_planes", "composed_label_table")
+_FRAMES = ("tree_label_table", "ingest_frame", "ingest_frame_planes", "composed_label_table", "ingest_frame_undistort")
 _SEQUENCE = ("ReplicaSequence", "tree_annotation", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation",
-             "ReplicaV2Sequence")
+             "ReplicaV2Sequence", "TUMSequence")
 _EXPORT = ("export_frame", "jet_colormap", "label_colormap", "tuple_colour_table", "write_png")
 _MAP_EXPORT = ("export_map", "gaussian_tree_labels", "level_prefix_colour_table", "leaf_head_labels", "save_map_ply",
                "save_map_ply_semantic")

@@ -6,6 +6,9 @@ depth map, replica.py:241-299 and :369 for the labels).
     tree_label_table(label_mapping_tree, num_levels, device)      the class-id -> level-labels table the ingest reads
     ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_table=None)
                                                                   ONE launch: every size's colour and depth, level 0's label planes
+    ingest_frame_undistort(color_u8, depth_raw, sizes, png_depth_scale, camera, distortion, labels=None, tree_table=None)
+                                                                  the same, the colour image undistorted inside that launch
+                                                                  (include/sensor/hsr_frame_undistort.h, basedataset.py:306-309)
 
 There is no CPU path for the computation; host inputs are copied to the device once each.  hsr_utils.sequence reads a Replica-layout
 directory into the raw arrays ingest_frame takes; SlamSession.ingest (hsr_utils.slam) builds a frame dict for step() from them.
@@ -69,7 +72,7 @@ def _as_tensor(x, what):
     raise RuntimeError("hsr_utils.frames: %s must be a torch tensor or a numpy array, not %s" % (what, type(x).__name__))
 
 
-def ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_table=None):
+def ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_table=None, _lens=None):
     """hsr_frame_ingest on one raw sensor frame: returns ([(color_i [3,h,w], depth_i [1,h,w]), ...] for the one to three (h, w) of
     `sizes`, labels_out | None).  color_u8 is uint8 [Hs,Ws,3] as decoders deliver it; depth_raw [Hs,Ws] is uint16 (or int16 bits,
     read as uint16), int32 or float32, in sensor units of 1 / png_depth_scale metres; labels, when given, is a [Hs,Ws] class-id image
@@ -77,7 +80,8 @@ def ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_
     [n_ids, L], tree_label_table; None: flat classes, L = 0), then the id itself.  Colour is float32 in 0..1, bilinear in float64 on
     the 8-bit values; depth float32 metres, nearest (include/ext/hsr_frame_ingest.h states every step).  Inputs may be device tensors,
     host tensors or numpy arrays: each host input is copied to the device once (the device of the first device tensor among the
-    inputs, else the current one).  One launch, no host synchronisation; there is no CPU path for the computation."""
+    inputs, else the current one).  One launch, no host synchronisation; there is no CPU path for the computation.
+    (_lens: the nine doubles ingest_frame_undistort has checked; the call then goes to hsr_frame_ingest_undistort.)"""
     color, depth = _as_tensor(color_u8, "color_u8"), _as_tensor(depth_raw, "depth_raw")
     lab = None if labels is None else _as_tensor(labels, "labels")
     if color.dtype != torch.uint8 or color.dim() != 3 or color.shape[2] != 3:
@@ -127,10 +131,45 @@ def ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=None, tree_
     out = [(torch.empty((3, h, w), dtype=torch.float32, device=dev), torch.empty((1, h, w), dtype=torch.float32, device=dev)) for h, w in sizes]
     levels = (_abi.hsr_ingest_level * len(sizes))(*[_abi.hsr_ingest_level(h, w, c.data_ptr(), d.data_ptr()) for (h, w), (c, d) in zip(sizes, out)])
     labels_out = None if lab is None else torch.empty((L + 1,) + sizes[0], dtype=torch.int64, device=dev)
-    _abi.call(_lib.hsr_frame_ingest, "hsr_frame_ingest", dev, Hs, Ws, color.data_ptr(), depth.data_ptr(), depth_type, scale,
-              None if lab is None else lab.data_ptr(), L, None if tree_table is None else tree_table.data_ptr(),
-              0 if tree_table is None else int(tree_table.shape[0]), len(sizes), levels, None if labels_out is None else labels_out.data_ptr())
+    head = (Hs, Ws, color.data_ptr(), depth.data_ptr(), depth_type, scale, None if lab is None else lab.data_ptr(), L,
+            None if tree_table is None else tree_table.data_ptr(), 0 if tree_table is None else int(tree_table.shape[0]))
+    tail = (len(sizes), levels, None if labels_out is None else labels_out.data_ptr())
+    if _lens is None:
+        _abi.call(_lib.hsr_frame_ingest, "hsr_frame_ingest", dev, *head, *tail)
+    else:
+        _abi.call(_lib.hsr_frame_ingest_undistort, "hsr_frame_ingest_undistort", dev, *head, *_lens, *tail)
     return out, labels_out
+
+
+def ingest_frame_undistort(color_u8, depth_raw, sizes, png_depth_scale, camera, distortion, labels=None, tree_table=None):
+    """hsr_frame_ingest_undistort: ingest_frame with the colour image undistorted inside the same single launch (the reference's
+    cv2.undistort(color, K, distortion) on the colour image only, basedataset.py:306-309).  camera = (fx, fy, cx, cy) of the SENSOR
+    image, in its pixels; distortion holds 4 or 5 Brown-Conrady coefficients in OpenCV's order (k1, k2, p1, p2[, k3]); with 4, k3 is 0.
+    More than 5 is a ValueError: the rational and thin-prism terms are not built.  Everything else — the inputs taken, the checks, the
+    depth and label rules, the returned ([(color_i [3,h,w], depth_i [1,h,w]), ...], labels_out | None) — is ingest_frame's.  Colour at
+    every size is ingest_frame's bilinear rule on the undistorted sensor image, whose pixels are 1/32-pixel bilinear samples of the
+    8-bit image with a border of 0 (include/sensor/hsr_frame_undistort.h states every step, and how a reduced size differs from the
+    reference's resize-then-undistort).  One launch, no host synchronisation; there is no CPU path for the computation."""
+    try:
+        cam = [float(v) for v in camera]
+    except TypeError:
+        cam = []
+    if len(cam) != 4:
+        raise ValueError("hsr_utils.frames: ingest_frame_undistort: camera must be (fx, fy, cx, cy) of the sensor image; got %r" % (camera,))
+    if torch.is_tensor(distortion):
+        distortion = distortion.detach().cpu().reshape(-1).tolist()
+    coeff = [float(v) for v in np.asarray(distortion, dtype=np.float64).reshape(-1)]
+    if len(coeff) > 5:
+        raise ValueError("hsr_utils.frames: ingest_frame_undistort takes 4 or 5 distortion coefficients (k1, k2, p1, p2[, k3]); got %d: "
+                         "the rational (k4, k5, k6) and thin-prism (s1..s4) terms are not built" % len(coeff))
+    if len(coeff) < 4:
+        raise ValueError("hsr_utils.frames: ingest_frame_undistort takes 4 or 5 distortion coefficients (k1, k2, p1, p2[, k3]); got %d" % len(coeff))
+    coeff = coeff + [0.0] * (5 - len(coeff))
+    if not (math.isfinite(cam[0]) and math.isfinite(cam[1]) and cam[0] != 0.0 and cam[1] != 0.0):
+        raise ValueError("hsr_utils.frames: ingest_frame_undistort: fx and fy must be finite and non-zero; got %r, %r" % (cam[0], cam[1]))
+    if not all(math.isfinite(v) for v in cam[2:] + coeff):
+        raise ValueError("hsr_utils.frames: ingest_frame_undistort: cx, cy and the coefficients must be finite; got %r and %r" % (cam[2:], coeff))
+    return ingest_frame(color_u8, depth_raw, sizes, png_depth_scale, labels=labels, tree_table=tree_table, _lens=tuple(cam + coeff))
 
 
 def _int_keys(mapping, what):
@@ -259,4 +298,4 @@ def ingest_frame_planes(color_u8, depth_raw, sizes, png_depth_scale, labels=None
     return out, labels_out
 
 
-__all__ = ["tree_label_table", "ingest_frame", "composed_label_table", "ingest_frame_planes"]
+__all__ = ["tree_label_table", "ingest_frame", "composed_label_table", "ingest_frame_planes", "ingest_frame_undistort"]

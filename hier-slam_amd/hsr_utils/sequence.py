@@ -36,7 +36,17 @@ and the ScanNet layout of datasets/gradslam_datasets/scannet.py (:404-418, :114)
     scannet_class_mapping(tsv_path, column=4) -> {raw id: NYU40 id}
     scannet_tree_annotation(tsv_path, num_levels, key_column) -> (label_mapping_tree, num_semantic)
 
-Other datasets, undistortion, cropping, image pyramids and embeddings are not read.
+and the TUM RGB-D layout of datasets/gradslam_datasets/tum.py (:44-158), whose colour and depth images and poses are three lists with
+timestamps of their own, and whose colour image is distorted (hsr_utils.frames.ingest_frame_undistort; the calibration is the
+caller's, as the camera is for every reader here):
+
+    <basedir>/<sequence>/rgb.txt, depth.txt          one "timestamp path" line per image, the path relative to the sequence
+    <basedir>/<sequence>/groundtruth.txt             one "timestamp tx ty tz qx qy qz qw" line per pose; else pose.txt, the same
+
+    TUMSequence(basedir, sequence, start=0, end=-1, stride=1, max_dt=0.08, frame_rate=32)
+        len(seq), seq[i] -> (color uint8 [H,W,3], depth uint16 [H,W], None, gt_w2c float32 [4,4])
+
+Other datasets, cropping, image pyramids and embeddings are not read.
 """
 import csv
 import glob
@@ -180,6 +190,103 @@ class ReplicaV2Sequence(ReplicaSequence):
         self._first_inv = np.linalg.inv(self.c2w[0])
 
 
+def _tum_list(path, columns):
+    """the lines of a TUM list file that do not start with '#', split at blanks: [[cell, ...], ...], each of at least `columns` cells"""
+    rows = []
+    with open(path) as f:
+        for n, line in enumerate(f.read().splitlines()):
+            if not line.strip() or line.lstrip().startswith("#"):
+                continue
+            cells = line.split()
+            if len(cells) < columns:
+                raise RuntimeError("hsr_utils.sequence: %s line %d has %d cells, not %d" % (path, n + 1, len(cells), columns))
+            rows.append(cells)
+    if not rows:
+        raise RuntimeError("hsr_utils.sequence: %s lists nothing" % path)
+    return rows
+
+
+def quaternion_c2w(values):
+    """float64 [4,4] camera-to-world matrix of one TUM pose (tx, ty, tz, qx, qy, qz, qw): the quaternion, scalar LAST, is normalised
+    first, as scipy's Rotation.from_quat does for the reference (tum.py:69-76)"""
+    tx, ty, tz, x, y, z, w = (float(v) for v in values)
+    norm = np.sqrt(x * x + y * y + z * z + w * w)
+    if not np.isfinite(norm) or norm == 0.0:
+        raise RuntimeError("hsr_utils.sequence: a pose's quaternion (%r, %r, %r, %r) has no direction" % (x, y, z, w))
+    x, y, z, w = x / norm, y / norm, z / norm, w / norm
+    pose = np.eye(4, dtype=np.float64)
+    pose[:3, :3] = [[x * x - y * y - z * z + w * w, 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)],
+                    [2.0 * (x * y + z * w), -x * x + y * y - z * z + w * w, 2.0 * (y * z - x * w)],
+                    [2.0 * (x * z - y * w), 2.0 * (y * z + x * w), -x * x - y * y + z * z + w * w]]
+    pose[:3, 3] = (tx, ty, tz)
+    return pose
+
+
+class TUMSequence(ReplicaSequence):
+    """The retained frames [start:end:stride] of one TUM RGB-D sequence, as the reference's TUMDataset reads it
+    (datasets/gradslam_datasets/tum.py:44-158):
+
+      lists        rgb.txt, depth.txt and groundtruth.txt (pose.txt when there is no groundtruth.txt); a line that starts with '#' is
+                   ignored (the reference's np.loadtxt drops them too, and its skiprows=1 on the pose list drops one more comment line
+                   of the dataset's three);
+      association  for each colour timestamp t, in the order of rgb.txt, the depth line and the pose line whose timestamps are
+                   nearest to t (the first of equally near ones); the triple is kept when BOTH are closer than max_dt seconds
+                   (|dt| < max_dt; tum.py:50-67);
+      thinning     the first triple is kept; every other one when its colour timestamp is more than 1 / frame_rate seconds after
+                   that of the last KEPT triple (tum.py:101-106; frame_rate is the reference's constant 32);
+      poses        t tx ty tz qx qy qz qw, camera to world, the quaternion normalised (quaternion_c2w: plain numpy).
+
+    [start:end:stride] is then taken of the thinned list, with ReplicaSequence's rules and errors; `retained_inds` indexes that list
+    and `associations` holds the (colour line, depth line, pose line) of every retained frame.  seq[i] returns raw host arrays: colour
+    uint8 [H,W,3], depth uint16 [H,W] (TUM's png_depth_scale is 5000), None for the labels, which this layout does not have, and
+    gt_w2c float32 [4,4] relative to the first RETAINED frame: inverse(inverse(c2w_first) @ c2w_i) in float64, as the other readers
+    (the reference rounds each pose to float32 first, tum.py:155).  The calibration, distortion included, is the caller's:
+    SlamSession.ingest(..., undistort=(fx, fy, cx, cy, coefficients))."""
+
+    def __init__(self, basedir, sequence, start=0, end=-1, stride=1, max_dt=0.08, frame_rate=32):
+        start, end, stride = int(start), int(end), int(stride)
+        _check_range(start, end, stride)
+        max_dt, frame_rate = float(max_dt), float(frame_rate)
+        if not max_dt > 0.0 or not frame_rate > 0.0:
+            raise ValueError("hsr_utils.sequence: max_dt and frame_rate must be positive; got %r, %r" % (max_dt, frame_rate))
+        self.input_folder = os.path.join(basedir, sequence)
+        for name in ("rgb.txt", "depth.txt"):
+            if not os.path.isfile(os.path.join(self.input_folder, name)):
+                raise RuntimeError("hsr_utils.sequence: %s has no %s" % (self.input_folder, name))
+        self.pose_path = next((p for p in (os.path.join(self.input_folder, n) for n in ("groundtruth.txt", "pose.txt")) if os.path.isfile(p)), None)
+        if self.pose_path is None:
+            raise RuntimeError("hsr_utils.sequence: %s has neither groundtruth.txt nor pose.txt" % self.input_folder)
+        images = _tum_list(os.path.join(self.input_folder, "rgb.txt"), 2)
+        depths = _tum_list(os.path.join(self.input_folder, "depth.txt"), 2)
+        poses = _tum_list(self.pose_path, 8)
+        t_image = np.array([float(r[0]) for r in images], dtype=np.float64)
+        t_depth = np.array([float(r[0]) for r in depths], dtype=np.float64)
+        t_pose = np.array([float(r[0]) for r in poses], dtype=np.float64)
+        triples = []
+        for i, t in enumerate(t_image):
+            j, k = int(np.argmin(np.abs(t_depth - t))), int(np.argmin(np.abs(t_pose - t)))
+            if abs(t_depth[j] - t) < max_dt and abs(t_pose[k] - t) < max_dt:
+                triples.append((i, j, k))
+        if not triples:
+            raise RuntimeError("hsr_utils.sequence: %s: no colour image has a depth image and a pose within %g s" % (self.input_folder, max_dt))
+        kept = [triples[0]]
+        for triple in triples[1:]:
+            if t_image[triple[0]] - t_image[kept[-1][0]] > 1.0 / frame_rate:
+                kept.append(triple)
+        stop = len(kept) if end == -1 else end
+        pick = slice(start, stop, stride)
+        self.associations = kept[pick]
+        self.retained_inds = list(range(len(kept)))[pick]
+        if not self.associations:
+            raise RuntimeError("hsr_utils.sequence: no frame of %d left by start=%d, end=%d, stride=%d" % (len(kept), start, end, stride))
+        self.color_paths = [os.path.join(self.input_folder, images[i][1]) for i, _j, _k in self.associations]
+        self.depth_paths = [os.path.join(self.input_folder, depths[j][1]) for _i, j, _k in self.associations]
+        self.semantic_paths = None
+        self.timestamps = [float(t_image[i]) for i, _j, _k in self.associations]
+        self.c2w = [quaternion_c2w(poses[k][1:8]) for _i, _j, k in self.associations]
+        self._first_inv = np.linalg.inv(self.c2w[0])
+
+
 def tree_annotation(path, num_levels):
     """info_semantic_tree.json as the reference reads it (replica.py:630-691 with :144-147).  The file is a dict whose keys are
     "<class id>_<class name>" and whose values list, level by level from the root, one {"<level label>": "<name>"} dict per level
@@ -244,7 +351,7 @@ class ScanNetSequence:
     returned as float32.  ScanNet marks a frame whose pose was lost with a matrix of -inf: a pose file that holds a non-finite number
     gives its frame a gt_w2c full of NaN, and SlamSession.step keeps such a frame out of the keyframes, as the reference's check at
     scripts/hierslam.py:2108-2109 does.  A non-finite FIRST retained pose (every other pose is relative to it) is a RuntimeError
-    naming the file.  Undistortion, pyramids and embeddings are not read."""
+    naming the file.  Pyramids and embeddings are not read."""
 
     def __init__(self, basedir, sequence, start=0, end=-1, stride=1, labels=True):
         start, end, stride = int(start), int(end), int(stride)
@@ -350,4 +457,5 @@ def scannet_tree_annotation(tsv_path, num_levels, key_column):
     return tree, num_semantic
 
 
-__all__ = ["ReplicaSequence", "ReplicaV2Sequence", "tree_annotation", "numeric_order", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation"]
+__all__ = ["ReplicaSequence", "ReplicaV2Sequence", "tree_annotation", "numeric_order", "ScanNetSequence", "scannet_class_mapping", "scannet_tree_annotation",
+           "TUMSequence"]

@@ -440,7 +440,8 @@ class SlamSession:
         data = cfg.get('data') or {}
         return cfg['png_depth_scale'] if 'png_depth_scale' in cfg else data.get('png_depth_scale')
 
-    def ingest(self, time_idx, color_u8, depth_raw, gt_w2c=None, labels=None, tree_table=None, png_depth_scale=None, leaf_column=False):
+    def ingest(self, time_idx, color_u8, depth_raw, gt_w2c=None, labels=None, tree_table=None, png_depth_scale=None, undistort=None,
+               leaf_column=False):
         """A frame dict for step() from the raw sensor images (hsr_utils.frames.ingest_frame; basedataset.py:223-227, :248-256,
         replica.py:241-299, scripts/hierslam.py:1777): 'id', 'im' and 'depth' at cam.image_height x cam.image_width, 'gt_w2c' and
         'semantic_label_gt' (int64 [levels + 1, H, W]; tree_table: frames.tree_label_table, None for flat classes) where given, and
@@ -449,7 +450,10 @@ class SlamSession:
         png_depth_scale defaults to config['data']['png_depth_scale'] (or the same key at the top level); a KeyError without either.
         A depth or label image of another size than the colour image (a ScanNet frame: 968x1296 colour and labels, 480x640 depth), or
         leaf_column=True (tree_table: frames.composed_label_table, whose last column becomes the last label plane: scannet.py:284-339),
-        goes through frames.ingest_frame_planes instead: still one launch, each image resampled once per size from its own."""
+        goes through frames.ingest_frame_planes instead: still one launch, each image resampled once per size from its own.
+        undistort=(fx, fy, cx, cy, coefficients) of the SENSOR image (a TUM RGB-D frame; coefficients: 4 or 5, OpenCV's order) goes
+        through frames.ingest_frame_undistort: the colour image is undistorted inside the same launch, depth and labels are not
+        (basedataset.py:306-309), and the frame dict has the same keys.  It does not combine with the planes route: a ValueError."""
         from . import frames
         if png_depth_scale is None:
             png_depth_scale = self._png_depth_scale()
@@ -467,7 +471,17 @@ class SlamSession:
         def own_size(image):
             other = tuple(getattr(image, 'shape', ()))
             return len(other) == 2 and other != shape
-        if leaf_column or own_size(depth_raw) or own_size(labels):
+        if undistort is not None:
+            if leaf_column or own_size(depth_raw) or own_size(labels):
+                raise ValueError("hsr_utils.slam: ingest: undistort does not combine with the planes route (leaf_column=True, or a depth or "
+                                 "label image of another size than the colour image): hsr_frame_ingest_undistort takes one sensor size")
+            try:
+                fx, fy, cx, cy, coefficients = undistort
+            except (TypeError, ValueError):
+                raise ValueError("hsr_utils.slam: ingest: undistort must be (fx, fy, cx, cy, coefficients) of the sensor image")
+            levels, labels_out = frames.ingest_frame_undistort(color_u8, depth_raw, sizes, png_depth_scale, (fx, fy, cx, cy), coefficients,
+                                                               labels=labels, tree_table=tree_table)
+        elif leaf_column or own_size(depth_raw) or own_size(labels):
             levels, labels_out = frames.ingest_frame_planes(color_u8, depth_raw, sizes, png_depth_scale, labels=labels, label_table=tree_table,
                                                             leaf_column=leaf_column)
         else:
