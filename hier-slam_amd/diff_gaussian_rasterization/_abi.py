@@ -1,7 +1,7 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/ and include/sensor/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
+Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/, include/sensor/ and include/surface/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
 import from this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
 header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
 include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
@@ -387,6 +387,18 @@ SENSOR_HEADERS = {
     ),
 }
 
+# ---- the headers under include/surface/, a fifth table of the same shape: SENSOR_HEADERS above is a counted set too
+# ---- (tests/test_frame_undistort_cpu.py); tests/test_mesh_clean_cpu.py checks this one with the same helpers ---------------------------
+SURFACE_HEADERS = {
+    # the connected components of a mesh and the faces and vertices of the kept ones (out_counts is three 64-bit words on the device)
+    "surface/hsr_mesh_clean.h": (
+        ("hsr_mesh_components", ci, [ci, ci, vp, vp, vp, vp]),
+        ("hsr_mesh_select_scratch_bytes", sz, [ci, ci]),
+        ("hsr_mesh_select", ci, [ci, ci, vp, vp, vp, vp, vp,
+                                 vp, vp, sz, vp]),
+    ),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -395,7 +407,8 @@ def _load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C hier-slam_amd/csrc`. "
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
-    for table in list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()) + list(SENSOR_HEADERS.values()):
+    for table in (list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()) + list(SENSOR_HEADERS.values())
+                  + list(SURFACE_HEADERS.values())):
         for name, restype, argtypes in table:
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes

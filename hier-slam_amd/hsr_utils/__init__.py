@@ -23,6 +23,7 @@ _MESH = ("TsdfVolume", "mesh_bounds", "save_mesh_ply", "load_mesh_ply", "mesh_ru
 _MESH_EVAL = ("face_areas", "sample_mesh", "NearestGrid", "seen_vertices", "cull_mesh", "distance_metrics", "label_metrics", "mesh_metrics",
               "evaluate_mesh_run")
 _MESH_DEPTH = ("MeshDepthRenderer", "render_mesh_depth", "virtual_views", "mesh_depth_l1")
+_MESH_CLEAN = ("mesh_components", "component_keep", "clean_mesh")
 
 
 def __getattr__(name):
@@ -60,4 +61,7 @@ def __getattr__(name):
     if name in _MESH_DEPTH:      # and both meshes as depth images from views the sensor never took
         from . import mesh_depth
         return getattr(mesh_depth, name)
+    if name in _MESH_CLEAN:      # and the run's mesh without its small disconnected pieces
+        from . import mesh_clean
+        return getattr(mesh_clean, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -8,7 +8,8 @@ project's own and the header states each of them.
         .extract()     hsr_tsdf_count, torch.cumsum, ONE host read (the triangle count), hsr_tsdf_faces, torch.unique, hsr_tsdf_vertices
     mesh_bounds(params, pad, voxel_size, max_voxels=2**28)    (origin, dims) of the padded box of the finite means3D
     save_mesh_ply(path, vertices, faces, rgb=None, labels=None), load_mesh_ply(path)
-    mesh_run(params, out_path, voxel_size=, every=5, semantic=False, ...)    render every `every`-th pose, fuse, extract, save
+    mesh_run(params, out_path, voxel_size=, every=5, semantic=False, ...)    render every `every`-th pose, fuse, extract, save; with
+        min_component_faces=, min_component_ratio= or largest_component= the small components are dropped first (mesh_clean.py)
 
 There is no CPU path for anything that launches; the bounds and the file helpers are plain torch / numpy and run anywhere.
 """
@@ -242,7 +243,8 @@ def load_mesh_ply(path):
 # ---- a run --------------------------------------------------------------------------------------------------------------------------------
 def mesh_run(params, out_path, *, voxel_size, every=5, semantic=False, label_mode="flat", sil_thres=0.5, depth_max=0.0, bounds=None,
              intrinsics=None, width=None, height=None, num_frames=None, cam=None, first_frame_w2c=None, pad=None, trunc=None, max_weight=64.0,
-             max_voxels=DEFAULT_MAX_VOXELS, near=0.01, far=100, level_sizes=None, tree_table=None, mlp=None):
+             max_voxels=DEFAULT_MAX_VOXELS, near=0.01, far=100, level_sizes=None, tree_table=None, mlp=None, min_component_faces=0,
+             min_component_ratio=0.0, largest_component=False):
     """The mesh of a finished run as a PLY file.  For every `every`-th step t the finished map `params` is rendered from the estimated
     pose of frame t (slam.render_params, without gradients) and the view is fused into a TsdfVolume: depth and colour where the final
     opacity exceeds sil_thres and, with semantic=True (the semantic rasterizer), the class plane of evaluate.semantic_labels(mode
@@ -250,7 +252,10 @@ def mesh_run(params, out_path, *, voxel_size, every=5, semantic=False, label_mod
     back inside the loop.  params is the dictionary of a finished run (map_io.load_params(path, device)); intrinsics, width, height,
     num_frames and first_frame_w2c default to its 'intrinsics', 'org_width', 'org_height', the number of pose columns and 'w2c' (else
     the identity); cam is the camera to render with (default: setup_camera of those).  bounds = (origin, dims) of the volume, default
-    mesh_bounds(params, pad, voxel_size, max_voxels) with pad = trunc.  Returns (path, number of vertices, number of faces)."""
+    mesh_bounds(params, pad, voxel_size, max_voxels) with pad = trunc.  min_component_faces, min_component_ratio and largest_component
+    are mesh_clean.clean_mesh's min_faces, min_ratio and largest: with one of them set, the small disconnected pieces of the mesh are
+    dropped on the device between extract and save; with all three at their defaults clean_mesh is not called and the file is what it
+    always was.  Returns (path, number of vertices, number of faces)."""
     from . import evaluate, slam
     from .camera import setup_camera
     from .replay import run_w2cs
@@ -289,6 +294,10 @@ def mesh_run(params, out_path, *, voxel_size, every=5, semantic=False, label_mod
                 labels = (labels[0] if label_mode == "tree" else labels).to(torch.int64)
             vol.integrate(depth, views[t], k, color=im, labels=labels, opacity=opac, sil_thres=sil_thres, depth_max=depth_max)
     vertices, faces, rgb, labels = vol.extract()
+    if int(min_component_faces) != 0 or float(min_component_ratio) != 0.0 or largest_component:
+        from . import mesh_clean
+        vertices, faces, rgb, labels = mesh_clean.clean_mesh(vertices, faces, rgb, labels, min_faces=min_component_faces,
+                                                             min_ratio=min_component_ratio, largest=bool(largest_component))
     save_mesh_ply(out_path, vertices, faces, rgb, labels)
     return out_path, int(vertices.shape[0]), int(faces.shape[0])
 

@@ -6,12 +6,14 @@ completion, their ratios at the threshold, the F-score and, with --semantic, the
 
     python tools/eval_mesh.py PARAMS_NPZ GT_PLY [--voxel-size S] [--every N] [--threshold T] [--semantic] [--out JSON]
                               [--depth-views N [--depth-seed S] [--depth-size H W]]
+                              [--min-component-faces N] [--min-component-ratio R] [--largest-component]
 
 PARAMS_NPZ is the params.npz of a run (hsr_utils.map_io.save_params after finalize_params).  GT_PLY is a mesh in the layout
 hsr_utils.mesh.save_mesh_ply writes (vertex x y z [red green blue] [label], triangular faces), in the run's world frame.  One JSON
 object on stdout, and in --out when given; distances are in metres.  With --depth-views N both meshes are also rendered to depth from N
 views the sensor never took (hsr_utils.mesh_depth; include/recon/hsr_mesh_depth.h) and depth_l1, depth_l1_covered, depth_gt_cover,
-depth_rec_cover and depth_views join the object; without it the object is what it was.
+depth_rec_cover and depth_views join the object; without it the object is what it was.  The component options are those of
+tools/mesh_run.py: the run's mesh loses its small disconnected pieces before it is scored (hsr_utils.mesh_clean).
 """
 import argparse
 import json
@@ -39,6 +41,9 @@ def main():
     ap.add_argument("--depth-seed", type=int, default=0)
     ap.add_argument("--depth-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="size of the depth images (default: the run's)")
     ap.add_argument("--out", default=None, help="also write the JSON object here")
+    ap.add_argument("--min-component-faces", type=int, default=0, help="drop connected components of fewer faces than this")
+    ap.add_argument("--min-component-ratio", type=float, default=0.0, help="drop components of fewer faces than this part of the largest one's")
+    ap.add_argument("--largest-component", action="store_true", help="keep the connected component of the most faces only")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -47,7 +52,8 @@ def main():
     params = map_io.load_params(a.params_npz, device="cuda")
     got = mesh_eval.evaluate_mesh_run(params, a.gt_ply, voxel_size=a.voxel_size, every=a.every, threshold=a.threshold, n_samples=a.samples,
                                       seed=a.seed, semantic=a.semantic, num_classes=a.classes, sil_thres=a.sil_thres, cull=not a.no_cull, depth_views=a.depth_views,
-                                      depth_seed=a.depth_seed, depth_size=a.depth_size)
+                                      depth_seed=a.depth_seed, depth_size=a.depth_size, min_component_faces=a.min_component_faces,
+                                      min_component_ratio=a.min_component_ratio, largest_component=a.largest_component)
     result = {k: (v.tolist() if isinstance(v, torch.Tensor) else v) for k, v in got.items()}
     result.update(threshold=a.threshold, samples=a.samples, voxel_size=a.voxel_size, every=a.every)
     line = json.dumps(result)
