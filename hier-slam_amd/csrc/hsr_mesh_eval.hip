@@ -11,24 +11,19 @@
 //            stand in the same or neighbouring cells: they walk the same rows of the grid, the cell_start words and the packed
 //            candidates they load are the same lines, and their ring counts — the one divergent loop bound — agree.  A row of the grid
 //            (fixed j, k) is contiguous in the packed order, so a ring costs two cell_start loads per row and then one 16-byte load per
-//            candidate.  No LDS, no cross-lane traffic; the kernel is a latency-bound gather that lives on occupancy.
+//            candidate.  No LDS, no cross-lane traffic; the kernel is a latency-bound gather that lives on occupancy.  The grid, a
+//            point's cell, the scan of a row and the ring walk itself are in hsr_nn_grid.h, which hsr_mesh_align.hip includes too.
 // Compiled with -ffp-contract=off: every output is pinned bit for bit against a numpy restatement that rounds every operation once.
 #include <math.h>
 
 #include "hsr_common.h"
+#include "hsr_nn_grid.h"
 #include "hsr_project.h"
 #include "../../include/eval/hsr_mesh_eval.h"
 
 namespace {
 
 constexpr int TB = 256;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-struct Grid {
-    int X, Y, Z;
-    float ox, oy, oz, c;
-};
 
 struct View {
     float m[12];      // rows 0..2 of the world-to-camera matrix
@@ -130,12 +125,6 @@ __global__ __launch_bounds__(TB) void seen_kernel(View c, int V, const float* __
 }
 
 // ---- the grid ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cell_axis(float p, float o, float c, int n)
-{
-    const float f = floorf((p - o) / c);
-    return f >= (float)n ? n - 1 : (f > 0.f ? (int)f : 0);      // a NaN fails both comparisons: 0
-}
-
 __global__ __launch_bounds__(TB) void cells_kernel(Grid g, int M, const float* __restrict__ points, int* __restrict__ out_cell)
 {
     const int m = blockIdx.x * TB + threadIdx.x;
@@ -161,85 +150,19 @@ __global__ __launch_bounds__(TB) void pack_kernel(int M, const float* __restrict
     out_packed[m] = e;
 }
 
-struct Best {
-    float d2;
-    int index;
-};
-
-// the packed points of cells a..b of one row (consecutive numbers) against the query
-__device__ __forceinline__ void scan_cells(int a, int b, int M, const int* __restrict__ cell_start, const f4* __restrict__ packed, float qx,
-                                           float qy, float qz, Best& best)
-{
-    int begin = cell_start[a], end = cell_start[b + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > M ? M : end;
-    for (int m = begin; m < end; m++) {
-        const f4 p = packed[m];
-        const float dx = qx - p[0], dy = qy - p[1], dz = qz - p[2];
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        const int index = __float_as_int(p[3]);
-        if (d2 < best.d2 || (d2 == best.d2 && index < best.index)) {      // a NaN fails both
-            best.d2 = d2;
-            best.index = index;
-        }
-    }
-}
-
 __global__ __launch_bounds__(TB) void query_kernel(Grid g, int M, const int* __restrict__ cell_start, const f4* __restrict__ packed, int N,
                                                    const float* __restrict__ queries, float* __restrict__ out_d2, int* __restrict__ out_index)
 {
     const int n = blockIdx.x * TB + threadIdx.x;
     if (n >= N) return;
     const float qx = queries[3 * (size_t)n], qy = queries[3 * (size_t)n + 1], qz = queries[3 * (size_t)n + 2];
-    Best best{INFINITY, 0x7fffffff};
-    if (fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY) {      // else every d2 is +inf or a NaN: nothing to search
-        const int qi = cell_axis(qx, g.ox, g.c, g.X), qj = cell_axis(qy, g.oy, g.c, g.Y), qk = cell_axis(qz, g.oz, g.c, g.Z);
-        for (int r = 0;; r++) {
-            const int i0 = max(qi - r, 0), i1 = min(qi + r, g.X - 1);
-            const int j0 = max(qj - r, 0), j1 = min(qj + r, g.Y - 1);
-            const int k0 = max(qk - r, 0), k1 = min(qk + r, g.Z - 1);
-            for (int k = k0; k <= k1; k++) {
-                const bool k_face = k == qk - r || k == qk + r;
-                for (int j = j0; j <= j1; j++) {
-                    const int row = (k * g.Y + j) * g.X;
-                    if (k_face || j == qj - r || j == qj + r) {
-                        scan_cells(row + i0, row + i1, M, cell_start, packed, qx, qy, qz, best);      // a row of the ring's shell
-                    } else {                                                                            // inside it: the two end cells
-                        if (qi - r >= 0) scan_cells(row + qi - r, row + qi - r, M, cell_start, packed, qx, qy, qz, best);
-                        if (qi + r < g.X) scan_cells(row + qi + r, row + qi + r, M, cell_start, packed, qx, qy, qz, best);
-                    }
-                }
-            }
-            if (r >= 1) {
-                const float t = ((float)r - 0.015625f) * g.c;
-                if (best.d2 <= t * t) break;
-            }
-            if (i0 == 0 && j0 == 0 && k0 == 0 && i1 == g.X - 1 && j1 == g.Y - 1 && k1 == g.Z - 1) break;      // the ring covered the grid
-        }
-    }
+    Best best{INFINITY, 0x7fffffff, 0};
+    if (fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY)      // else every d2 is +inf or a NaN: nothing to search
+        best = ring_walk<false>(g, M, cell_start, packed, qx, qy, qz, 0.f);      // hsr_nn_grid.h
     const bool won = best.d2 < INFINITY;
     out_d2[n] = won ? best.d2 : INFINITY;
     out_index[n] = won ? best.index : -1;
 }
-
-bool finite_positive(float x) { return isfinite(x) && x > 0.f; }
-
-bool bad_grid(const char* who, int X, int Y, int Z, float ox, float oy, float oz, float c)
-{
-    const bool sides = X >= 1 && Y >= 1 && Z >= 1 && X <= HSR_NN_MAX_SIDE && Y <= HSR_NN_MAX_SIDE && Z <= HSR_NN_MAX_SIDE;
-    if (!sides || (long long)X * Y * Z > (long long)HSR_NN_MAX_CELLS) {
-        hsr_set_error("%s: invalid grid X=%d Y=%d Z=%d (every side 1..%d, X*Y*Z <= 2^24)", who, X, Y, Z, HSR_NN_MAX_SIDE);
-        return true;
-    }
-    if (!finite_positive(c) || !isfinite(ox) || !isfinite(oy) || !isfinite(oz)) {
-        hsr_set_error("%s: the cell size must be finite and positive and the origin finite; got %g and (%g, %g, %g)", who, (double)c, (double)ox,
-                      (double)oy, (double)oz);
-        return true;
-    }
-    return false;
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 unsigned blocks_for(int items) { return (unsigned)(((long long)items + TB - 1) / TB); }
 

@@ -1,7 +1,7 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/, include/sensor/ and include/surface/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
+Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/, include/sensor/, include/surface/ and include/align/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
 import from this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
 header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
 include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
@@ -399,6 +399,18 @@ SURFACE_HEADERS = {
     ),
 }
 
+# ---- the headers under include/align/, a sixth table of the same shape: SURFACE_HEADERS above is a counted set too
+# ---- (tests/test_mesh_clean_cpu.py); tests/test_mesh_align_cpu.py checks this one with the same helpers ---------------------------------
+ALIGN_HEADERS = {
+    # one pass of point-to-point ICP against the grid of hsr_nn_query (transform is a HOST array of 12 floats; out_sums is 17 float64)
+    "align/hsr_mesh_align.h": (
+        ("hsr_icp_scratch_bytes", sz, [ci]),
+        ("hsr_icp_step", ci, [ci, ci, ci, cf, cf, cf, cf, ci, vp, vp,
+                              ci, vp, fp, cf, vp, vp,
+                              vp, vp, sz, vp]),
+    ),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -408,7 +420,7 @@ def _load():
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
     for table in (list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()) + list(SENSOR_HEADERS.values())
-                  + list(SURFACE_HEADERS.values())):
+                  + list(SURFACE_HEADERS.values()) + list(ALIGN_HEADERS.values())):
         for name, restype, argtypes in table:
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -24,6 +24,7 @@ _MESH_EVAL = ("face_areas", "sample_mesh", "NearestGrid", "seen_vertices", "cull
               "evaluate_mesh_run")
 _MESH_DEPTH = ("MeshDepthRenderer", "render_mesh_depth", "virtual_views", "mesh_depth_l1")
 _MESH_CLEAN = ("mesh_components", "component_keep", "clean_mesh")
+_MESH_ALIGN = ("rigid_from_sums", "icp_step", "icp", "trajectory_alignment", "transform_points", "align_mesh")
 
 
 def __getattr__(name):
@@ -64,4 +65,7 @@ def __getattr__(name):
     if name in _MESH_CLEAN:      # and the run's mesh without its small disconnected pieces
         from . import mesh_clean
         return getattr(mesh_clean, name)
+    if name in _MESH_ALIGN:      # and that mesh registered to the ground truth before it is scored
+        from . import mesh_align
+        return getattr(mesh_align, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

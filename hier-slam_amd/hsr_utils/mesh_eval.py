@@ -10,7 +10,8 @@ mesh evaluation, so the rules are this project's own and the header states each 
     cull_mesh(vertices, faces, seen, *per_vertex)              plain torch
     mesh_metrics(rec, gt, n_samples=200000, threshold=0.05, seed=0, num_classes=None)
     evaluate_mesh_run(params, gt_ply, voxel_size=, every=5, ...)    mesh_run's mesh, the culled ground truth, mesh_metrics; with
-                                                               depth_views=N also mesh_depth.mesh_depth_l1 from N virtual views
+                                                               depth_views=N also mesh_depth.mesh_depth_l1 from N virtual views, and with
+                                                               align="icp" | "trajectory" the run's mesh registered first (mesh_align)
 
 There is no CPU path for anything that launches; cull_mesh is plain torch and runs anywhere.
 """
@@ -279,7 +280,8 @@ def mesh_metrics(rec, gt, n_samples=200000, threshold=0.05, seed=0, num_classes=
 # ---- a run --------------------------------------------------------------------------------------------------------------------------------
 def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_samples=200000, seed=0, semantic=False, num_classes=None,
                       sil_thres=0.5, cull=True, keep_mesh=None, intrinsics=None, width=None, height=None, num_frames=None, cam=None,
-                      first_frame_w2c=None, near=0.01, far=100, depth_views=0, depth_seed=0, depth_size=None, **mesh_kw):
+                      first_frame_w2c=None, near=0.01, far=100, depth_views=0, depth_seed=0, depth_size=None, align=None, align_max_dist=0.1,
+                      align_iterations=30, gt_w2cs=None, **mesh_kw):
     """The mesh of a finished run scored against the ground-truth mesh of its scene.  mesh.mesh_run(params, voxel_size=, every=,
     semantic=, ...) makes the run's mesh (kept at keep_mesh when that is a path); gt_ply is read with mesh.load_mesh_ply; with cull=True
     the ground truth is culled to the vertices seen from every `every`-th estimated pose — in the image, and no deeper than the map's
@@ -290,7 +292,17 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
     gt_vertices_seen and gt_faces_kept.  With depth_views = N > 0 the (culled) ground truth and the run's mesh are also rendered to depth
     from N views the sensor never took — mesh_depth.virtual_views(the poses that were meshed, the culled ground truth's vertices, N,
     depth_seed) — at depth_size = (H, W), or the run's own size, with the intrinsics scaled per axis, and mesh_depth.mesh_depth_l1 adds
-    depth_l1, depth_l1_covered, depth_gt_cover, depth_rec_cover (floats) and depth_views; with the default 0 no key is added."""
+    depth_l1, depth_l1_covered, depth_gt_cover, depth_rec_cover (floats) and depth_views; with the default 0 no key is added.
+    align registers the run's mesh to the ground truth (mesh_align; include/align/hsr_mesh_align.h)
+    AFTER the cull (which keeps using the estimated poses) and BEFORE mesh_metrics and Depth L1, which then see the aligned vertices:
+    "icp" is mesh_align.align_mesh(the run's mesh, the culled ground truth, n_samples, seed, max_dist=align_max_dist,
+    max_iterations=align_iterations) and "trajectory" applies mesh_align.trajectory_alignment(gt_w2cs, the run's poses), which needs
+    gt_w2cs [T,4,4] world-to-camera; either adds align, align_transform (a nested list, estimate's world -> ground truth's) and, for
+    "icp" only, align_fitness, align_rmse and align_iterations.  With the default None nothing is called and no key is added."""
+    if align not in (None, "icp", "trajectory"):
+        raise ValueError("hsr_utils.mesh_eval: align must be None, \"icp\" or \"trajectory\" (got %r)" % (align,))
+    if align == "trajectory" and gt_w2cs is None:
+        raise ValueError("hsr_utils.mesh_eval: align=\"trajectory\" needs gt_w2cs, the ground-truth world-to-camera matrices")
     from . import mesh, slam
     from .camera import setup_camera
     from .replay import run_w2cs
@@ -310,7 +322,7 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
     depth_views = int(depth_views)
     if depth_views < 0:
         raise ValueError("hsr_utils.mesh_eval: depth_views must be >= 0 (got %d)" % depth_views)
-    if cull or depth_views:
+    if cull or depth_views or align == "trajectory":
         # the views of mesh_run: the same camera, the same poses, the same silhouette
         k = np.asarray(_host(params['intrinsics'] if intrinsics is None else intrinsics), dtype=np.float32)[:3, :3]
         w = int(_host(params['org_width'])) if width is None else int(width)
@@ -337,8 +349,22 @@ def evaluate_mesh_run(params, gt_ply, *, voxel_size, every=5, threshold=0.05, n_
         if gf.shape[0] == 0:
             raise ValueError("hsr_utils.mesh_eval: the cameras saw no face of %s" % gt_ply)
     rec = _mesh(rec_v, rec_f, rec_l if use_labels else None, device=dev)
+    aligned = {}
+    if align is not None:
+        from . import mesh_align
+        if align == "icp":
+            moved, icp = mesh_align.align_mesh(rec, (gv, gf), n_samples=n_samples, seed=seed, max_dist=align_max_dist,
+                                               max_iterations=align_iterations)
+            transform = icp["transform"]
+            aligned.update(align_fitness=icp["fitness"], align_rmse=icp["inlier_rmse"], align_iterations=icp["iterations"])
+        else:
+            transform = mesh_align.trajectory_alignment(gt_w2cs, views)
+            moved = mesh_align.transform_points(rec[0], transform)
+        rec = (moved,) + tuple(rec[1:])
+        aligned.update(align=align, align_transform=transform.tolist())
     out = mesh_metrics(rec, (gv, gf, gl), n_samples=n_samples, threshold=threshold, seed=seed, num_classes=num_classes)
     out.update(counts)
+    out.update(aligned)
     if depth_views:
         from . import mesh_depth
         from .camera import scale_intrinsics
