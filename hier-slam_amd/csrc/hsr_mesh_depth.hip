@@ -1,7 +1,7 @@
 // hsr_mesh_depth.hip — the depth image of a triangle mesh from one view (gfx950): include/recon/hsr_mesh_depth.h states the rule, and
 // the rule alone defines the result; this file only divides the work.
-//   setup   : setup_kernel — a face per lane: three gathered vertices into camera space (hsr_project.h), the three crosses, det, the
-//             box.  A face whose box holds at most HSR_MESH_DEPTH_SMALL_BOX pixels is rasterized right there by its lane (a ground-truth
+//   setup   : setup_kernel — a face per lane: three gathered vertices into camera space, the three crosses, det, the box
+//             (hsr_mesh_face.h, shared with hsr_mesh_shade.hip).  A face whose box holds at most HSR_MESH_DEPTH_SMALL_BOX pixels is rasterized right there by its lane (a ground-truth
 //             mesh is a million faces of a pixel or less: a box of 9 to 16 pixels).  A larger face is appended to the list in the
 //             scratch: one atomic add per wave on the counter, the order in the list does not matter.
 //   sweep   : sweep_kernel — a fixed grid of SWEEP_X x SWEEP_Y workgroups, so that no host read of the count is needed: workgroup
@@ -17,7 +17,7 @@
 #include <math.h>
 
 #include "hsr_common.h"
-#include "hsr_project.h"
+#include "hsr_mesh_face.h"
 #include "../../include/recon/hsr_mesh_depth.h"
 
 namespace {
@@ -27,62 +27,6 @@ constexpr int SWEEP_X = 128;      // workgroups across the list of large faces
 constexpr int SWEEP_Y = 16;       // workgroups across one face's box: 2048 in all, eight per CU
 
 typedef unsigned long long u64;
-
-struct View {
-    float m[12];      // rows 0..2 of the world-to-camera matrix
-    float fx, fy, cx, cy, near;
-    int H, W;
-};
-
-struct Face {
-    float nA[3], nB[3], nC[3], det;
-    int x0, x1, y0, y1;      // the box, inclusive
-};
-
-__device__ __forceinline__ void cross(const float* P, const float* Q, float* out)
-{
-    out[0] = P[1] * Q[2] - P[2] * Q[1];
-    out[1] = P[2] * Q[0] - P[0] * Q[2];
-    out[2] = P[0] * Q[1] - P[1] * Q[0];
-}
-
-__device__ __forceinline__ bool finite3(const float* p) { return fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY; }
-
-// the face f of the header: false when it takes no part or its box is empty
-__device__ __forceinline__ bool make_face(const View& c, int V, const float* __restrict__ vertices, const int* __restrict__ faces, int f, Face& out)
-{
-    const int ia = faces[3 * (size_t)f], ib = faces[3 * (size_t)f + 1], ic = faces[3 * (size_t)f + 2];
-    if (!((unsigned)ia < (unsigned)V && (unsigned)ib < (unsigned)V && (unsigned)ic < (unsigned)V)) return false;
-    float A[3], B[3], C[3];
-    const float* a = vertices + 3 * (size_t)ia;
-    const float* b = vertices + 3 * (size_t)ib;
-    const float* d = vertices + 3 * (size_t)ic;
-    hsr_camera_point(c.m, a[0], a[1], a[2], A[0], A[1], A[2]);
-    hsr_camera_point(c.m, b[0], b[1], b[2], B[0], B[1], B[2]);
-    hsr_camera_point(c.m, d[0], d[1], d[2], C[0], C[1], C[2]);
-    if (!(finite3(A) && finite3(B) && finite3(C))) return false;
-    cross(B, C, out.nA);
-    cross(C, A, out.nB);
-    cross(A, B, out.nC);
-    if (!(finite3(out.nA) && finite3(out.nB) && finite3(out.nC))) return false;
-    out.det = (A[0] * out.nA[0] + A[1] * out.nA[1]) + A[2] * out.nA[2];
-    if (!(fabsf(out.det) < INFINITY) || out.det == 0.f) return false;
-    if (A[2] < c.near && B[2] < c.near && C[2] < c.near) return false;      // wholly nearer than near, or behind the camera
-    if (A[2] < c.near || B[2] < c.near || C[2] < c.near) {
-        out.x0 = 0; out.x1 = c.W - 1; out.y0 = 0; out.y1 = c.H - 1;
-        return true;
-    }
-    const float uA = c.fx * (A[0] / A[2]) + c.cx, uB = c.fx * (B[0] / B[2]) + c.cx, uC = c.fx * (C[0] / C[2]) + c.cx;
-    const float vA = c.fy * (A[1] / A[2]) + c.cy, vB = c.fy * (B[1] / B[2]) + c.cy, vC = c.fy * (C[1] / C[2]) + c.cy;
-    float x0 = floorf(fminf(fminf(uA, uB), uC)) - 1.f, x1 = ceilf(fmaxf(fmaxf(uA, uB), uC)) + 1.f;
-    float y0 = floorf(fminf(fminf(vA, vB), vC)) - 1.f, y1 = ceilf(fmaxf(fmaxf(vA, vB), vC)) + 1.f;
-    const float xe = (float)(c.W - 1), ye = (float)(c.H - 1);
-    if (!(x1 >= 0.f && x0 <= xe && y1 >= 0.f && y0 <= ye)) return false;      // empty (u and v are never NaN: see the header)
-    x0 = fmaxf(x0, 0.f); x1 = fminf(x1, xe);
-    y0 = fmaxf(y0, 0.f); y1 = fminf(y1, ye);                                  // in float: an infinite bound never reaches (int)
-    out.x0 = (int)x0; out.x1 = (int)x1; out.y0 = (int)y0; out.y1 = (int)y1;
-    return true;
-}
 
 // the hit test of the header at pixel (x, y) and the pixel's minimum
 __device__ __forceinline__ void test_pixel(const View& c, const Face& t, int f, int x, int y, u64* __restrict__ keys)

@@ -1,7 +1,7 @@
 """The C ABI of libhsr_rast.so as ctypes sees it: the library handle, the structures of the headers, the signature of every exported
 function, and the one way a stream-taking entry point is called.
 
-Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/, include/sensor/, include/surface/ and include/align/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
+Everything under include/hsr_*.h, include/ext/, include/eval/, include/recon/, include/sensor/, include/surface/, include/align/ and include/shade/ is declared HERE and nowhere else; `_C.py` and the hsr_utils modules
 import from this module.  One rule: HEADERS maps each header, by its path under include/, to the signatures of that header's functions, in the
 header's order.  The entries are written out by hand (nothing parses a header at import: the package does not depend on where
 include/ sits at run time); tests/test_abi.py parses every header on disk and fails on a header without a key, a key without a
@@ -77,6 +77,12 @@ class hsr_map_export_job(C.Structure):
     _fields_ = [("P", ci), ("S", ci), ("record", ci), ("colour", ci), ("means3D", vp), ("rgb_colors", vp), ("unnorm_rotations", vp),
                 ("logit_opacities", vp), ("log_scales", vp), ("normals", vp), ("colours", vp), ("labels", vp), ("semantic", vp),
                 ("table", vp), ("n", ci), ("K", ci), ("L", ci), ("sizes", ci * 16), ("out", vp), ("out_labels", vp)]
+
+
+class hsr_shade_job(C.Structure):
+    """one picture of hsr_mesh_shade (include/shade/hsr_mesh_shade.h)"""
+    _fields_ = [("kind", ci), ("lit", ci), ("normals", vp), ("attr", vp), ("table", vp), ("n", ci), ("lo", cf), ("hi", cf), ("ambient", cf),
+                ("albedo", cf * 3), ("background", C.c_uint8 * 4), ("out", vp)]
 
 
 bp, tk = C.POINTER(hsr_buffer), C.POINTER(hsr_ticket)
@@ -411,6 +417,19 @@ ALIGN_HEADERS = {
     ),
 }
 
+# ---- the headers under include/shade/, a seventh table of the same shape: ALIGN_HEADERS above is a counted set too
+# ---- (tests/test_mesh_align_cpu.py); tests/test_mesh_view_cpu.py checks this one with the same helpers -----------------------------------
+SHADE_HEADERS = {
+    # vertex normals and the pictures of a mesh from one view (w2c and jobs are HOST arrays)
+    "shade/hsr_mesh_shade.h": (
+        ("hsr_mesh_normals_scratch_bytes", sz, [ci]),
+        ("hsr_mesh_normals", ci, [ci, ci, vp, vp, vp, sz, vp,
+                                  vp]),
+        ("hsr_mesh_shade", ci, [ci, ci, vp, vp, ci, ci, cf, cf, cf, cf,
+                                fp, vp, ci, C.POINTER(hsr_shade_job), vp]),
+    ),
+}
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -420,7 +439,7 @@ def _load():
             "There is no CPU fallback." % LIB_PATH)
     loaded = C.CDLL(LIB_PATH)
     for table in (list(HEADERS.values()) + list(EVAL_HEADERS.values()) + list(RECON_HEADERS.values()) + list(SENSOR_HEADERS.values())
-                  + list(SURFACE_HEADERS.values()) + list(ALIGN_HEADERS.values())):
+                  + list(SURFACE_HEADERS.values()) + list(ALIGN_HEADERS.values()) + list(SHADE_HEADERS.values())):
         for name, restype, argtypes in table:
             fn = getattr(loaded, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -25,6 +25,7 @@ _MESH_EVAL = ("face_areas", "sample_mesh", "NearestGrid", "seen_vertices", "cull
 _MESH_DEPTH = ("MeshDepthRenderer", "render_mesh_depth", "virtual_views", "mesh_depth_l1")
 _MESH_CLEAN = ("mesh_components", "component_keep", "clean_mesh")
 _MESH_ALIGN = ("rigid_from_sums", "icp_step", "icp", "trajectory_alignment", "transform_points", "align_mesh")
+_MESH_VIEW = ("vertex_normals", "MeshRenderer", "vertex_errors", "orbit_views", "render_mesh_views", "render_mesh_run")
 
 
 def __getattr__(name):
@@ -68,4 +69,7 @@ def __getattr__(name):
     if name in _MESH_ALIGN:      # and that mesh registered to the ground truth before it is scored
         from . import mesh_align
         return getattr(mesh_align, name)
+    if name in _MESH_VIEW:       # and pictures of either mesh without a window
+        from . import mesh_view
+        return getattr(mesh_view, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

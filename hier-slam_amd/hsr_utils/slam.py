@@ -767,6 +767,29 @@ class SlamSession:
         return mesh_eval.evaluate_mesh_run(self.params, gt_ply, intrinsics=self.intrinsics, width=self.cam.image_width,
                                            height=self.cam.image_height, **kw)
 
+    def render_mesh(self, out_dir, **kw):
+        """pictures of the run's mesh so far, without a window: hsr_utils.mesh_view.render_mesh_run on the session's own params, with its
+        intrinsics, frame size and first_frame_w2c, into out_dir.  mesh= is (vertices, faces[, rgb[, labels]]) or the path of a PLY that
+        export_mesh wrote; without it export_mesh(out_dir/mesh.ply, voxel_size=...) makes one first (voxel_size= is then required, and
+        mesh_every= is its `every`).  Every other keyword is render_mesh_run's (every, orbit, pictures, gt, size, ...).  Returns the
+        list of the PNG paths."""
+        from . import mesh, mesh_view
+        if self.params is None:
+            raise RuntimeError("hsr_utils.slam: render_mesh before the first frame: there is no map yet")
+        given = kw.pop('mesh', None)
+        voxel_size, mesh_every = kw.pop('voxel_size', None), kw.pop('mesh_every', 5)
+        if given is None:
+            if voxel_size is None:
+                raise ValueError("hsr_utils.slam: render_mesh needs mesh= or voxel_size= to make one")
+            os.makedirs(out_dir, exist_ok=True)
+            given = self.export_mesh(os.path.join(out_dir, "mesh.ply"), voxel_size=voxel_size, every=mesh_every)[0]
+        if isinstance(given, (str, os.PathLike)):
+            given = mesh.load_mesh_ply(given)
+        kw.setdefault('num_frames', len(self.gt_w2c_all_frames))
+        kw.setdefault('first_frame_w2c', self.first_frame_w2c)
+        return mesh_view.render_mesh_run(self.params, given, out_dir, intrinsics=self.intrinsics, width=self.cam.image_width,
+                                         height=self.cam.image_height, **kw)
+
     def step(self, frame):
         """one pass of the frame loop (scripts/hierslam.py:1762-2124) for frame['id'] = the number of frames stepped so far"""
         time_idx = int(frame['id'])
